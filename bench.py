@@ -176,7 +176,12 @@ def main():
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the live rocprofv3 --pmc passes for roofline.traffic (use the committed profile instead); "
                          "required when this command itself runs under rocprofv3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, pixels, parameter gradients, "
+                         "parameters after the Adam update) as DIR/<name>.npy, float32, at most 64 MB in all (e.g. bench_outputs/)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -250,18 +255,19 @@ def main():
     def step(i, timed=False):
         opt.zero_grad(set_to_none=True)
         if fused:       # forward + MSE + backward in one pass per ray chunk (afx_train_step_mse)
-            loss, _ = train_step_mse(model, projection_spec(poses[i], W, H, focal, S, near, far), targets[i],
-                                     n_global=n_global)
+            loss, pixels = train_step_mse(model, projection_spec(poses[i], W, H, focal, S, near, far), targets[i],
+                                          n_global=n_global)
         else:
             out = render_projection(model, poses[i], W, H, focal, S, near, far)
-            loss = ((out.rgb_map - targets[i]) ** 2).sum() / n_global
+            pixels = out.rgb_map
+            loss = ((pixels - targets[i]) ** 2).sum() / n_global
             loss.backward()
         if timed:
             t_adam.begin()
         opt.step()
         if timed:
             t_adam.end()
-        return loss
+        return loss, pixels
 
     # the backward workspace is allocated before any timing (also with --warmup 0): a 128 GiB hipMalloc is setup, not a step
     from nerf_for_angiography_amd import _lib as afx_lib
@@ -279,7 +285,7 @@ def main():
     t0 = time.perf_counter()
     ev0.record()
     for i in range(args.steps):
-        loss = step(args.warmup + i, timed=True)
+        loss, pixels = step(args.warmup + i, timed=True)
     ev1.record()
     torch.cuda.synchronize()
     if world > 1:
@@ -293,6 +299,13 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the gradient check and the CPU leg below overwrite the gradients and reload the weights
+        named = {"loss": loss, "pixels": pixels}
+        named.update({f"grad.{k}": p.grad for k, p in model.named_parameters() if p.grad is not None})
+        named.update({f"param.{k}": p for k, p in model.named_parameters()})
+        dumped = dump_outputs(args.dump_outputs, named)
 
     samples_per_step = W * H * S
     value = world * samples_per_step * args.steps / elapsed
@@ -358,6 +371,8 @@ def main():
                          "rays_per_step_per_gpu": W * H, "parallelism": f"ray-batch dp{world}"},
               "ms_per_step_hip_events": round(hip_ms / args.steps, 2),
               "final_loss": round(float(loss) * (world if fused else 1), 6), "roofline": roofline}
+    if dumped is not None:
+        result["dump_outputs"] = dumped
 
     if world > 1:
         if fused:
@@ -415,6 +430,27 @@ def main():
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, named):
+    """Write each tensor of `named` as out_dir/<name>.npy (float64 stays float64, everything else float32).  When they exceed
+    DUMP_BYTES in all, every array is cut to the same fraction of its elements, flattened: the sorted flat indices
+    torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k], the same elements in every run with the same arguments."""
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in named.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, (DUMP_BYTES - 4096 * len(arrays)) / total)
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for k, a in arrays.items():
+        if frac < 1.0:
+            idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(0))[:max(1, int(a.size * frac))].sort().values
+            a = a.reshape(-1)[idx.numpy()]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        written += a.nbytes
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written, "sampled": frac < 1.0}
 
 
 def usable_cpus():

@@ -424,6 +424,9 @@ def _dp_flat_grad(m, o, d, tgt, n_global):
 
 
 def _dp_worker(rank, world, port, q):
+    # the ranks are CPU processes on any machine: on a GPU host init_from_env would otherwise pick cuda:<rank>, which does
+    # not exist for rank 1 on a one-GPU host
+    torch.cuda.is_available = lambda: False
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     import torch.distributed as dist
@@ -478,10 +481,16 @@ def test_two_rank_gloo_grad_sync_and_sharding():
     procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    res = sorted(q.get(timeout=180) for _ in procs)
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    try:
+        res = sorted(q.get(timeout=180) for _ in procs)
+        for p in procs:
+            p.join(60)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:          # a rank that failed leaves the other blocked in a collective: do not outlive the test
+            if p.is_alive():
+                p.kill()
+                p.join()
     (r0, w0, g0, u0, s0, c0, d0, x0), (r1, w1, g1, u1, s1, c1, d1, x1) = res
     assert x0 == (37, True, [1.5] * 4, 19) and x1 == (37, True, [1.5] * 4, 18)      # default n_global / global_mse / local-mean mode
     assert d0 and d1                               # the sharded density grid equals the single-process grid on both ranks

@@ -82,7 +82,11 @@ def test_g5_render(golden, rk, zk):
     g = golden("g5_render")
     rgb, dep, w, ent, (sig, _) = orc.render_volume_density(T(g["raw_" + rk]), T(g["d"]), T(g[zk]))
     for name, got in (("rgb", rgb), ("depth", dep), ("weights", w), ("entropy", ent), ("sigma", sig)):
-        np.testing.assert_allclose(got.numpy(), g[f"{rk}_{zk}_{name}"], rtol=2e-6, atol=1e-30, err_msg=name)
+        # weights = (1 - a_i) * prod_{j<i} a_j over 32 float32 exp() results: the fixture holds the capturing host's exp
+        # rounding, and torch's exp (MKL VML) takes a different code path per host CPU.  One ulp per factor of the
+        # product is 31 * 2^-23 = 3.7e-6 relative (measured 2.7e-6 on a tail weight when MKL runs its SSE4.2 path)
+        rtol = 4e-6 if name == "weights" else 2e-6
+        np.testing.assert_allclose(got.numpy(), g[f"{rk}_{zk}_{name}"], rtol=rtol, atol=1e-30, err_msg=name)
     if rk == "m3":      # the 1e10 tail makes the projection exactly 0
         assert float(rgb.abs().max()) == 0.0
     if rk == "m40":
