@@ -11,8 +11,11 @@
  *     afx_last_error() gives a thread-local message.  Nothing throws or exits.
  *   - the CALLER owns every buffer (parameters, gradients, outputs, prepared
  *     weights, workspace).  The library allocates nothing on the device and
- *     holds only immutable descriptors => calls are hipGraph-capturable.
- *   - all calls are asynchronous on the stream passed in; no hidden syncs.
+ *     holds only immutable descriptors => calls are hipGraph-capturable, with
+ *     two exceptions: afx_march_train_step_mse reads two sizes back (it polls),
+ *     and afx_profile_read synchronises.  The grid iteration's capturable form
+ *     is afx_march_train_step_mse_capturable.
+ *   - all other calls are asynchronous on the stream passed in.
  *   - results are deterministic: no floating-point atomics anywhere.
  */
 #ifndef AFX_H
@@ -332,7 +335,8 @@ int afx_march_compact(const uint8_t* keep, const int64_t* offsets_in, const int6
  * afx_mlp_infer at the candidates' mid-points + afx_march_visibility (the reference's alpha_fn + nerfacc's render_visibility),
  * afx_march_compact / afx_pack_groups, afx_train_step_packed_mse - the same entry points in the same order, so the results are those of
  * the call-by-call sequence bit for bit.  (At the reference's batch the GPU is busy for 0.27 ms of an iteration; the ~30 launches cost more
- * when a Python loop issues them.)  Two host read-backs inside (sizes are data), so the call is NOT graph-capturable.  Every array
+ * when a Python loop issues them.)  Two host read-backs inside (sizes are data: the host polls a mapped mailbox, or with AFX_MAILBOX=0
+ * copies and synchronises), so the call is NOT graph-capturable - see afx_march_train_step_mse_capturable below.  Every array
  * between the steps lives in `workspace`; when it is too small the call returns AFX_E_WORKSPACE with `workspace_needed` set (nothing the
  * caller owns has been written) - grow and call again.  n_kept == 0 on return: no sample survived, pixel / grad_flat untouched (the
  * reference skips the optimizer step, :293). */
@@ -348,6 +352,20 @@ typedef struct afx_march_train_args {
   size_t workspace_needed;                     /* out, with AFX_E_WORKSPACE */
 } afx_march_train_args;
 int afx_march_train_step_mse(afx_ctx* ctx, int prec, const void* prepared, afx_march_train_args* args, void* stream);
+
+/* The same iteration with its sizes kept on the device: no host read-back, synchronisation or allocation, so the call can be captured
+ * into a HIP graph and replayed.  Same entry-point sequence and arguments as afx_march_train_step_mse (f16s8 only; the march needs a far
+ * plane) and the same results bit for bit: every buffer is carved for the worst case - every step of every ray occupied, the bound
+ * afx_march_max_steps gives - every launch is sized for it, and the kernels bound their work by the counts the offsets kernels leave on the
+ * device.  Out (device memory, written by the call's kernels): counts_dev[3] = (n_candidates, n_kept, n_groups); skip_dev[1] = 1.0f when
+ * nothing survived the march (pixel and grad_flat are then untouched), else 0.0f - usable as an optimizer's found-inf flag.  The
+ * host-side n_candidates / n_kept / n_groups of `args` are not written.  The workspace must hold afx_march_train_workspace_bytes(ctx, prec,
+ * n_rays, afx_march_max_steps(&args->march)) bytes (else AFX_E_WORKSPACE with workspace_needed set); a worst case beyond the one-chunk
+ * sample limit of the packed step (2^32 / width group-padded samples) is refused with AFX_E_INVALID. */
+int64_t afx_march_max_steps(const afx_march_args* args);      /* >= the steps k_march_count can give any ray; -1: error */
+int64_t afx_march_train_workspace_bytes(const afx_ctx* ctx, int prec, int64_t n_rays, int64_t max_steps_per_ray);      /* -1: error */
+int afx_march_train_step_mse_capturable(afx_ctx* ctx, int prec, const void* prepared, afx_march_train_args* args, int64_t* counts_dev,
+                                        float* skip_dev, void* stream);
 
 /* Indices of the k largest of keys[n] (ties: lowest index first), written in ASCENDING INDEX order - the selection step of the
  * weighted ray sampler (the batch of nerf/nerf_helpers.py:137-150 is a set; its order carries no meaning).  Radix select:
@@ -385,7 +403,7 @@ int afx_set_encoding_grad(afx_ctx* ctx, const float* params, float* d_enc_aux);
 
 /* Measurement aid (bench.py's roofline leg): when enabled, every launch of the three MFMA kernels is
  * bracketed by HIP events recorded on the launch stream.  afx_profile_read blocks on those events
- * (the only call in this library that synchronises), returns the summed device time and the launch
+ * (it synchronises), returns the summed device time and the launch
  * count for one kernel kind, and forgets them. */
 enum { AFX_K_CHAIN_FWD = 0, AFX_K_CHAIN_BWD = 1, AFX_K_WGRAD = 2 };
 int afx_profile_enable(afx_ctx* ctx, int on);

@@ -597,8 +597,10 @@ static int launch_wgrad8_t(afx_ctx* c, const WgradArgs& w, const ReduceArgs& rd,
 // backward pointers; `head` bytes at the start of the workspace are already in use (dod).
 // `split` (fused MSE step whose rays straddle tiles): the chain runs as PHASE 1, per-ray finish (pixel, dL/d(optical depth)), PHASE 2 -
 // a.dod / a.od_part / a.target / a.pixel / a.inv_n are set by the caller; chunks hold whole rays.
+// `dsz` (capacity launch, afx_march_train_step_mse_capturable): a.n_total is the capacity and the device-resident size block (SZ_* slots) bounds
+// the work of every kernel; the launches are those of the capacity, which must fit one chunk.
 static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws, size_t ws_bytes, float* grad_flat, hipStream_t st,
-                        bool split = false, int64_t n_rays = 0, const int64_t* goff = nullptr) {
+                        bool split = false, int64_t n_rays = 0, const int64_t* goff = nullptr, const int64_t* dsz = nullptr) {
   const int F = c->d.width, N = c->d.n_hidden;
   if (c->d.act != AFX_ACT_RELU && prec != AFX_PREC_F32)
     return fail(AFX_E_INVALID, "backward: tanh / sine models train in the exact-fp32 kernels only (AFX_PREC_F32); the 16-bit kernels are forward-only for them");
@@ -686,6 +688,8 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
   }
   a.stash_rows = (int64_t)rows;
   a.debug = 0;
+  if (dsz && (chunk < tiles || nbuf != 1)) return fail(AFX_E_WORKSPACE, "capturable training step: the capacity must fit one chunk");
+  a.n_dev = dsz ? dsz + SZ_NTOTAL : nullptr;
   // encoded inputs, 16-bit kernels: the inputs are stashed in 16-bit chunk-major form and the first layer's weight gradient (and the
   // fourier coefficients' gradient, afx_set_encoding_grad) is contracted on the matrix pipe by k_wgrad_bf16
   const bool enc16 = b16 && c->d.enc != AFX_ENC_NONE;
@@ -718,7 +722,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
       const int gpr = a.s_pad / GROUP;
       if (goff)
         hipLaunchKernelGGL(k_finish_mse_packed, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, (const float*)a.od_part, goff, n_rays, a.target,
-                           a.inv_n, a.pixel, (float*)a.dod);
+                           a.inv_n, a.pixel, (float*)a.dod, (const int64_t*)a.n_dev);
       else
         hipLaunchKernelGGL(k_finish_mse, dim3((unsigned)((ray1 - ray0 + 255) / 256)), dim3(256), 0, st, (const float*)a.od_part + ray0 * gpr, gpr,
                            ray1 - ray0, a.target + ray0, a.inv_n, a.pixel + ray0, (float*)a.dod + ray0);
@@ -749,6 +753,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     w.gmax = a.gmax; w.stash_esz = (int)esz; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = enc16 ? 1 : 0; w.coef_cols = a.coef_cols;
     w.dod = split ? a.dod : nullptr; w.gpr = a.s_pad / GROUP; w.group0 = t0 * (TILE / GROUP); w.group_ray = goff ? a.group_ray : nullptr;
     w.n_groups_valid = goff ? a.n_total / GROUP : n_rays * (int64_t)(a.s_pad / GROUP);
+    w.dsz = dsz;
     ReduceArgs rd = {};
     rd.partial = partial; rd.partial2 = partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = k0ld; rd.n_splits = splits;
     rd.grad = grad_flat; rd.hidden_only = b16 ? 1 : 0; rd.partial_s = partial_s;
@@ -757,6 +762,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     rd.n_small = (int)std::min<int64_t>(kSmallBlocks, std::max<int64_t>(64, (w.rows / GROUP + 3) / 4));
     rd.gmax = a.gmax; rd.scale_shift = s8 ? AFX_S8_JSHIFT : 0; rd.layer0_mfma = enc16 ? 1 : 0;
     rd.w0 = c->coef_params; rd.d_coef = c->d_coef; rd.coef_cols = a.coef_cols;
+    rd.dsz = dsz;
     if (!b16) rc = F == 64 ? launch_wgrad_t<64>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad_t<128>(c, w, rd, N, ws_st) : launch_wgrad_t<256>(c, w, rd, N, ws_st));
     else if (s8) rc = F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, ws_st) : launch_wgrad8_t<256>(c, w, rd, N, ws_st));
     else if (h16) rc = F == 64 ? launch_wgrad16_t<64, true>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad16_t<128, true>(c, w, rd, N, ws_st) : launch_wgrad16_t<256, true>(c, w, rd, N, ws_st));
@@ -835,10 +841,22 @@ extern "C" int afx_pack_groups(const int64_t* offsets, const int64_t* group_offs
   return AFX_OK;
 }
 
+static int packed_step(afx_ctx* c, int prec, const void* prepared, const float* origins, const float* dirs, int64_t n_rays,
+                       const int64_t* group_offsets, const int32_t* group_ray, int64_t n_groups, const float* ts_pad,
+                       const float* te_pad, const float* target, float inv_n, float* pixel, float* grad_flat,
+                       void* workspace, size_t workspace_bytes, void* stream, const int64_t* dsz);
 extern "C" int afx_train_step_packed_mse(afx_ctx* c, int prec, const void* prepared, const float* origins, const float* dirs, int64_t n_rays,
                                          const int64_t* group_offsets, const int32_t* group_ray, int64_t n_groups, const float* ts_pad,
                                          const float* te_pad, const float* target, float inv_n, float* pixel, float* grad_flat,
                                          void* workspace, size_t workspace_bytes, void* stream) {
+  return packed_step(c, prec, prepared, origins, dirs, n_rays, group_offsets, group_ray, n_groups, ts_pad, te_pad, target, inv_n, pixel, grad_flat,
+                     workspace, workspace_bytes, stream, nullptr);
+}
+// (dsz: capacity launch - n_groups is the capacity, the device-resident sizes bound the work; see run_backward)
+static int packed_step(afx_ctx* c, int prec, const void* prepared, const float* origins, const float* dirs, int64_t n_rays,
+                       const int64_t* group_offsets, const int32_t* group_ray, int64_t n_groups, const float* ts_pad,
+                       const float* te_pad, const float* target, float inv_n, float* pixel, float* grad_flat,
+                       void* workspace, size_t workspace_bytes, void* stream, const int64_t* dsz) {
   if (!c || !prepared || !origins || !dirs || !group_offsets || !target || !pixel || !grad_flat || !workspace)
     return fail(AFX_E_INVALID, "afx_train_step_packed_mse: null argument");
   if (n_rays <= 0) return AFX_OK;
@@ -864,7 +882,7 @@ extern "C" int afx_train_step_packed_mse(afx_ctx* c, int prec, const void* prepa
   a.n_samples = GROUP; a.s_pad = GROUP; a.n_total = n_groups * GROUP;
   a.fused = 1; a.target = target; a.pixel = pixel; a.inv_n = inv_n;
   a.dod = dod; a.od_part = od_part;
-  return run_backward(c, prec, a, dod_bytes + od_bytes, (char*)workspace, workspace_bytes, grad_flat, st, true, n_rays, group_offsets);
+  return run_backward(c, prec, a, dod_bytes + od_bytes, (char*)workspace, workspace_bytes, grad_flat, st, true, n_rays, group_offsets, dsz);
 }
 
 // ---- hierarchical training step with coarse re-use
@@ -1441,4 +1459,126 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
   if ((rc = afx_pack_groups(off2, goff, R, ts2, te2, tsp, tep, gray, stream))) return rc;
   return afx_train_step_packed_mse(c, prec, prepared, m.origins, m.dirs, R, goff, gray, ng, tsp, tep, t->target, t->inv_n, t->pixel, t->grad_flat,
                                    ws + off, t->workspace_bytes - off, stream);
+}
+
+// ---- the same iteration with device-resident sizes (afx_march_train_step_mse_capturable): every buffer is carved for the worst case the march
+// arguments allow, every launch is sized for it, and the kernels bound their work by the counts the offsets kernels leave on the device.
+// Bound of k_march_count's steps per ray: the steps of a ray with t_min = lo = max(0, near) and t_max = far, counted exactly (the kernel's
+// fp32 expressions).  Every ray has t_min >= lo and t_max <= far, and the step mid-points are non-decreasing in t_min and k (fp32 addition and
+// multiplication are monotone), so a step whose mid-point lies before the ray's t_max has one before `far` on the bounding lattice too: no ray
+// has more steps.  (Separate statements: no contraction into an fma.)
+static float march_mid(float t_min, float dt, int64_t k) {
+  volatile float kd = (float)k * dt;
+  volatile float ts = t_min + kd;
+  volatile float te2 = ts + dt;
+  volatile float sum = ts + te2;
+  return sum * 0.5f;
+}
+extern "C" int64_t afx_march_max_steps(const afx_march_args* m) {
+  if (!m || !(m->step > 0.f)) { fail(AFX_E_INVALID, "afx_march_max_steps: need args with step > 0"); return -1; }
+  if (!m->has_far) { fail(AFX_E_INVALID, "afx_march_max_steps: the bound needs a far plane"); return -1; }
+  const float lo = m->has_near ? std::max(0.f, m->near_plane) : 0.f, far = m->far_plane, dt = m->step;
+  if (!(far > lo)) return 0;
+  volatile float span = far - lo;
+  const float q = std::ceil(span / dt);
+  if (!(q < 2.0e9f)) { fail(AFX_E_INVALID, "afx_march_max_steps: more than 2e9 steps per ray"); return -1; }
+  int64_t n = (int64_t)q;
+  while (n > 0 && !(march_mid(lo, dt, n - 1) < far)) --n;
+  while (march_mid(lo, dt, n) < far) ++n;
+  return n;
+}
+
+struct CapLayout {
+  size_t o_counts, o_offsets, o_totals, o_counts2, o_off2, o_goff, o_dsz;
+  size_t o_ri, o_ts, o_te, o_pts, o_raw, o_keep, o_ri2, o_ts2, o_te2, o_tsp, o_tep, o_gray, o_step;
+  size_t total;
+  int64_t n_cap, g_cap;      // candidates (= kept samples) and 32-sample groups of the worst case: every step of every ray occupied
+};
+static int cap_layout(const afx_ctx* c, int prec, int64_t R, int64_t S, CapLayout& L, const char* who) {
+  if (R <= 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays > 0 and max_steps_per_ray >= 0", who);
+  L.n_cap = R * S;
+  L.g_cap = R * ((S + GROUP - 1) / GROUP);
+  // the packed step runs as ONE chunk, and a chunk's 8-bit layer plane stays below 4 GiB (run_backward): at most 2^32 / width samples
+  const int64_t max_samples = (int64_t)(((uint64_t)1 << 32) / ((uint64_t)256 * c->d.width)) * 256;
+  if (L.g_cap * GROUP > max_samples || L.n_cap > ((int64_t)1 << 31) - 256)
+    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed the capturable step's sample limit (%lld group-padded samples at width %d, one "
+                "chunk of the packed step); use afx_march_train_step_mse or fewer rays per step", who, (long long)R, (long long)S,
+                (long long)max_samples, c->d.width);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
+  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(4 * 8);
+  L.o_counts2 = take((size_t)R * 4); L.o_off2 = take((size_t)(R + 1) * 8); L.o_goff = take((size_t)(R + 1) * 8); L.o_dsz = take(SZ_COUNT * 8);
+  const size_t n = (size_t)std::max<int64_t>(L.n_cap, 1), g = (size_t)std::max<int64_t>(L.g_cap, 1);
+  L.o_ri = take(n * 4); L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_pts = take(n * 12); L.o_raw = take(n * 4); L.o_keep = take(n);
+  L.o_ri2 = take(n * 4); L.o_ts2 = take(n * 4); L.o_te2 = take(n * 4);
+  L.o_tsp = take(g * 32 * 4); L.o_tep = take(g * 32 * 4); L.o_gray = take(g * 4);
+  L.o_step = off;
+  // the packed step: dL/d(optical depth) per ray and optical-depth partials per group (packed_step's head), then run_backward's fixed part and
+  // one chunk of the 8-bit stash over every tile of the capacity
+  const size_t tiles = (g * 32 + 255) / 256;
+  L.total = off + rup64((size_t)R * 4, 256) + rup64(g * 4, 256) + bwd_layout(c, prec, 0).fixed_bytes + tiles * per_tile_s8(c) + 1024;
+  return AFX_OK;
+}
+
+extern "C" int64_t afx_march_train_workspace_bytes(const afx_ctx* c, int prec, int64_t n_rays, int64_t max_steps_per_ray) {
+  if (!c) { fail(AFX_E_INVALID, "afx_march_train_workspace_bytes: null ctx"); return -1; }
+  if (prec != AFX_PREC_F16S8) { fail(AFX_E_INVALID, "afx_march_train_workspace_bytes: AFX_PREC_F16S8 only"); return -1; }
+  CapLayout L;
+  if (cap_layout(c, prec, n_rays, max_steps_per_ray, L, "afx_march_train_workspace_bytes")) return -1;
+  return (int64_t)L.total;
+}
+
+extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const void* prepared, afx_march_train_args* t, int64_t* counts_dev,
+                                                   float* skip_dev, void* stream) {
+  const char* who = "afx_march_train_step_mse_capturable";
+  if (!c || !prepared || !t || !counts_dev || !skip_dev) return fail(AFX_E_INVALID, "%s: null argument", who);
+  t->workspace_needed = 0;
+  const afx_march_args& m = t->march;
+  const int64_t R = m.n_rays;
+  if (R <= 0) return fail(AFX_E_INVALID, "%s: n_rays must be > 0", who);
+  if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "%s: AFX_PREC_F16S8 only", who);
+  const int64_t S = afx_march_max_steps(&m);
+  if (S < 0) return AFX_E_INVALID;
+  CapLayout L;
+  if (int rc = cap_layout(c, prec, R, S, L, who)) return rc;
+  if (L.total > t->workspace_bytes) {
+    t->workspace_needed = L.total;
+    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_train_workspace_bytes)", who, t->workspace_bytes, L.total);
+  }
+  if (int rc = check_dev(c, who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)t->workspace;
+  int32_t *counts = (int32_t*)(ws + L.o_counts), *counts2 = (int32_t*)(ws + L.o_counts2);
+  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals), *off2 = (int64_t*)(ws + L.o_off2),
+          *goff = (int64_t*)(ws + L.o_goff), *dsz = (int64_t*)(ws + L.o_dsz);
+  int32_t *ri = (int32_t*)(ws + L.o_ri), *ri2 = (int32_t*)(ws + L.o_ri2), *gray = (int32_t*)(ws + L.o_gray);
+  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *pts = (float*)(ws + L.o_pts), *raw = (float*)(ws + L.o_raw);
+  float *ts2 = (float*)(ws + L.o_ts2), *te2 = (float*)(ws + L.o_te2), *tsp = (float*)(ws + L.o_tsp), *tep = (float*)(ws + L.o_tep);
+  uint8_t* keep = (uint8_t*)(ws + L.o_keep);
+  int rc;
+  // 1. candidates (totals[0]: their count, on the device only)
+  if ((rc = afx_march_count(&m, counts, stream))) return rc;
+  if ((rc = afx_ray_offsets(counts, R, offsets, nullptr, totals, stream))) return rc;
+  if ((rc = afx_march_write(&m, offsets, ri, ts, te, pts, stream))) return rc;
+  // 2. alpha pass over the capacity, bounded by totals[0], + render_visibility
+  if (L.n_cap > 0) {
+    ChainArgs a = {};
+    fill_model(c, prec, false, prepared, a);
+    a.tile0 = 0; a.tile1 = (int)((L.n_cap + fwd_tile(prec) - 1) / fwd_tile(prec)); a.n_total = L.n_cap; a.mode = 0;
+    a.pts = pts; a.out = raw; a.apply_sigmoid = 0; a.n_dev = totals;
+    if ((rc = launch_chain(c, prec, false, a, st))) return rc;
+  }
+  if ((rc = afx_march_visibility(raw, 0, ts, te, offsets, R, t->early_stop_eps, t->alpha_thre, keep, counts2, stream))) return rc;
+  if ((rc = afx_ray_offsets(counts2, R, off2, goff, totals + 2, stream))) return rc;
+  // 3. the sizes of the rest, the caller's counters and skip flag
+  hipLaunchKernelGGL(k_grid_step_sizes, dim3(1), dim3(64), 0, st, (const int64_t*)totals, bwd_tile(prec), c->n_cu / c->d.n_hidden, kSplits,
+                     kSmallBlocks, counts_dev, skip_dev, dsz);
+  HIPCHK(hipGetLastError());
+  // 4. compaction, group-aligned copy, fused training step over the capacity (nothing kept: every kernel of the step exits, pixel and
+  //    grad_flat stay untouched)
+  if ((rc = afx_march_compact(keep, offsets, off2, R, ts, te, ri2, ts2, te2, stream))) return rc;
+  if ((rc = afx_pack_groups(off2, goff, R, ts2, te2, tsp, tep, gray, stream))) return rc;
+  return packed_step(c, prec, prepared, m.origins, m.dirs, R, goff, gray, std::max<int64_t>(L.g_cap, 1), tsp, tep, t->target, t->inv_n, t->pixel,
+                     t->grad_flat, ws + L.o_step, t->workspace_bytes - L.o_step, stream, dsz);
 }

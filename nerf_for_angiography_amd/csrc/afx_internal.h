@@ -106,6 +106,9 @@ struct ChainArgs {
   // split phases of the 8-bit-stash training kernel (rays that straddle workgroup tiles)
   char* masks;              // [tiles of the chunk][(N+1) x NT x 512 x u16]: the ReLU-mask LDS image of each tile (PHASE 1 writes, PHASE 2 reads)
   float* gpart;             // [rows] g' = dt sigma (1 - sigma) of each sample (PHASE 1 writes, PHASE 2 reads)
+  // device-resident sample count (afx_march_train_step_mse_capturable): null = n_total / tile1 are the work range (every other caller).
+  // Otherwise the launch is sized for the capacity n_total / tile1 and the kernel bounds its work by min(*n_dev, n_total) samples.
+  const int64_t* n_dev;
 };
 
 struct WgradArgs {
@@ -139,6 +142,9 @@ struct WgradArgs {
   int32_t gpr;              // 32-sample groups per ray (s_pad / 32)
   int64_t group0;           // global index of the chunk's first group
   int64_t n_groups_valid;   // groups that belong to a ray (the chunk's last tile may be padded with dead groups beyond them)
+  const int64_t* dsz;       // device-resident sizes (SZ_* slots; afx_march_train_step_mse_capturable) or null: rows / n_splits / rows_per_split /
+                            // n_groups_valid above and the record count (gridDim.x) are the work range.  Otherwise the launch is sized for the capacity
+                            // and the kernels take the sizes from dsz: workgroups beyond the device counts exit without writing
 };
 
 struct ReduceArgs {
@@ -155,6 +161,11 @@ struct ReduceArgs {
   const float* w0;          // k_reduce_coef: the first layer's fp32 weights [F, k0]
   float* d_coef;            // k_reduce_coef: d loss / d fourier coefficients [coef_cols], accumulated into
   int32_t coef_cols;
+  const int64_t* dsz;       // device-resident sizes (as WgradArgs::dsz) or null: n_splits / n_small above; dsz[SZ_ROWS] == 0: nothing to add
 };
+
+// Slots of the device-resident size block of afx_march_train_step_mse_capturable (k_grid_step_sizes writes them from the offsets kernels'
+// totals with the formulas run_backward applies on the host, so the capturable step sums in the same order as the one-call step)
+enum { SZ_NTOTAL = 0, SZ_ROWS = 1, SZ_SPLITS = 2, SZ_RPS = 3, SZ_SMALL = 4, SZ_GROUPS = 5, SZ_COUNT = 8 };
 
 }  // namespace afx

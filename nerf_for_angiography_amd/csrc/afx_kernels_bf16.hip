@@ -286,7 +286,14 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
   const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // provably wave-uniform: scalar branches, no exec masking
   const int N = a.n_hidden;
-  if (a.tile0 + (int)blockIdx.x >= a.tile1) return;
+  // work range: the host's (a.n_total, a.tile1), or - capacity launch (a.n_dev) - the device-resident count, bounded by them (uniform branch)
+  int64_t n_total = a.n_total;
+  int tile1 = a.tile1;
+  if (a.n_dev) {
+    n_total = min(n_total, *a.n_dev);
+    tile1 = min(tile1, (int)((n_total + TS - 1) / TS));
+  }
+  if (a.tile0 + (int)blockIdx.x >= tile1) return;
 
   // A step covers TPS consecutive 32-row output tiles of one layer: one barrier and one LDS-DMA batch per step.
 #ifdef AFX_STAMP
@@ -324,7 +331,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
   // Request cursor: runs PD steps ahead of the compute, across tile boundaries, until every step of this
   // workgroup's tiles has been requested.
   const int steps_per_tile = P2 ? SPL * N : SPL * (N + 1) + ((BWD && !P1) ? SPL * N : 0);
-  int to_issue = ((a.tile1 - a.tile0 - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x) * steps_per_tile;
+  int to_issue = ((tile1 - a.tile0 - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x) * steps_per_tile;
   int cpos = 0;                           // position of the next requested step inside its tile
   uint32_t wslot = 0, rslot = 0;          // ring slot of the next request / of the next step to compute
   auto request = [&]() {
@@ -424,7 +431,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
 
   constexpr uint32_t MASKB = 2u * NT * NCG * NTH;      // mask bytes per layer (the LDS image, [((l*NT + t)*NCG + cg)*NTH + tid] u16)
   uint32_t wave_gmax = 0;      // (lane 0) the largest |dL/draw| this wave has merged into wg_gmax so far
-  for (int tile = a.tile0 + blockIdx.x; tile < a.tile1; tile += gridDim.x) {
+  for (int tile = a.tile0 + blockIdx.x; tile < tile1; tile += gridDim.x) {
     STAMP(7);
     if constexpr (P2) {
       // masks of this tile: HBM -> LDS by LDS-DMA (1 KiB per wave instruction), behind a barrier that retires every reader of the previous tile's;
@@ -445,7 +452,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
       m[cg] = (uint32_t)(tile - a.tile0) * TS + wave * (32 * NCG) + cg * 32 + col;
       so[cg] = S8 ? stash_off8<F>(m[cg], hh) : stash_off<F>(m[cg], hh);
       if constexpr (H6) so6 = stash_off6<F>(m[cg], hh);
-      sp[cg] = make_sample(a, n[cg]);
+      sp[cg] = make_sample(a, n[cg], n_total);
       // first-layer B fragments: element j of k-step q is encoded input k = 16q + 8*(lane>>5) + j
 #pragma unroll
       for (int q = 0; q < (P2 ? 0 : NK0); ++q) {
@@ -834,7 +841,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
           float od = tau;
 #pragma unroll
           for (int sh = 16; sh >= 1; sh >>= 1) od += __shfl_xor(od, sh);
-          if (lane == 0 && n[cg] < a.n_total) {
+          if (lane == 0 && n[cg] < n_total) {
             const int gpr = a.s_pad / GROUP;
             if (a.depth_mode == 4) a.od_part[n[cg] >> 5] = od;      // packed samples: one partial per group of the padded list
             else a.od_part[(int64_t)sp[cg].ray * gpr + (n[cg] - sp[cg].ray * a.s_pad) / GROUP] = od;
@@ -865,7 +872,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
         float od = 0.f;
         for (int k = 0; k < gpr; ++k) od += odb[g0 + k];
         const float T = expf(-od);
-        const bool rayok = n[cg] < a.n_total;
+        const bool rayok = n[cg] < n_total;
         const float tg = rayok ? a.target[sp[cg].ray] : 0.f;
         if (lane == 0 && grp == g0 && rayok) a.pixel[sp[cg].ray] = T;
         // L = mean_r (T_r - target_r)^2 over the GLOBAL batch: dL/dT = 2 (T - target) * inv_n; dT/d(od) = -T
@@ -1368,9 +1375,15 @@ __global__ void __launch_bounds__(512) k_wgrad_s8(const WgradArgs a) {
   const char* B = first < 0 ? (const char*)a.stash_h + (size_t)(layer - 1) * a.stride_rows * F
                             : (const char*)a.stash_e + (size_t)first * a.stride_rows * 64;
   const uint32_t* hexp = a.hexp + (size_t)(first < 0 ? layer - 1 : 0) * (size_t)(a.stride_rows >> 5);      // (first layer: read, not used)
-  int64_t r0 = (int64_t)split * a.rows_per_split;
-  int64_t r1 = r0 + a.rows_per_split;
-  if (r1 > a.rows) r1 = a.rows;
+  int64_t rows = a.rows, rps = a.rows_per_split;
+  int n_splits = a.n_splits;
+  if (a.dsz) {      // capacity launch: the device-resident sizes; splits beyond the device's split count write nothing (the reductions stop there)
+    rows = min(rows, a.dsz[SZ_ROWS]); rps = a.dsz[SZ_RPS]; n_splits = (int)a.dsz[SZ_SPLITS];
+    if (split >= n_splits) return;
+  }
+  int64_t r0 = (int64_t)split * rps;
+  int64_t r1 = r0 + rps;
+  if (r1 > rows) r1 = rows;
   const int nst = r1 > r0 ? (int)((r1 - r0) / KB) : 0;
   const bool active = wave < WR * WC;
   const int wr = wave / WC, wc = wave % WC;
@@ -1495,7 +1508,7 @@ __global__ void __launch_bounds__(512) k_wgrad_s8(const WgradArgs a) {
       }
     }
   }
-  float* P = a.partial + ((size_t)slot * a.n_splits + split) * F * F;
+  float* P = a.partial + ((size_t)slot * n_splits + split) * F * F;
   if (active && first < 0) {
 #pragma unroll
     for (int i = 0; i < TR; ++i)
@@ -1518,7 +1531,7 @@ __global__ void __launch_bounds__(512) k_wgrad_s8(const WgradArgs a) {
   if (has_bias && col == 0 && first <= 0) {        // every column of accb holds the row sums
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      a.partial2[((size_t)layer * a.n_splits + split) * (F + 4) + fperm8(32 * (wr * TR + wc) + rowperm(r) + 4 * hh)] = accb[r];
+      a.partial2[((size_t)layer * n_splits + split) * (F + 4) + fperm8(32 * (wr * TR + wc) + rowperm(r) + 4 * hh)] = accb[r];
   }
 }
 
@@ -1606,8 +1619,12 @@ __global__ void __launch_bounds__(4 * F) k_small_from_groups(const WgradArgs a) 
   // loads (group -> ray -> dod), and at the reference's batch sizes four times the waves in flight is what shortens it
   __shared__ float red[3][6][F];
   const int p = threadIdx.x, f = fperm(p), q = threadIdx.y;
-  const int64_t ngroups = a.rows >> 5;
-  const int64_t per = (ngroups + gridDim.x - 1) / gridDim.x;
+  int64_t ngroups = a.rows >> 5, nblk = gridDim.x, n_valid = a.n_groups_valid;
+  if (a.dsz) {      // capacity launch: the device's record count (blocks beyond it write no record; the reduction stops there)
+    ngroups = min(ngroups, a.dsz[SZ_ROWS] >> 5); nblk = a.dsz[SZ_SMALL]; n_valid = a.dsz[SZ_GROUPS];
+    if ((int64_t)blockIdx.x >= nblk) return;
+  }
+  const int64_t per = (ngroups + nblk - 1) / nblk;
   int64_t g0 = (int64_t)blockIdx.x * per, g1 = g0 + per;
   if (g1 > ngroups) g1 = ngroups;
   constexpr int RS = 3 * F + 8;
@@ -1621,7 +1638,7 @@ __global__ void __launch_bounds__(4 * F) k_small_from_groups(const WgradArgs a) 
     float ds = 1.f;
     if (a.dod) {
       const int64_t gg = a.group0 + g;
-      ds = gg < a.n_groups_valid ? a.dod[a.group_ray ? (int64_t)a.group_ray[gg] : gg / a.gpr] : 0.f;
+      ds = gg < n_valid ? a.dod[a.group_ray ? (int64_t)a.group_ray[gg] : gg / a.gpr] : 0.f;
     }
     const float sw = a.no_sw ? 0.f : rec[p] * ds;
     if (a.enc16) {          // encoded inputs: only the output layer's sums are in the records (first layer: k_wgrad_s8)
@@ -1667,8 +1684,12 @@ template <int F>
 __global__ void __launch_bounds__(2 * F) k_wout_stash8(const WgradArgs a) {
   const int rr = threadIdx.x & 31, ch = threadIdx.x >> 5;      // row within the group, 16-byte chunk column
   constexpr int NCH = F / 16;
-  const int64_t ngroups = a.rows >> 5;
-  const int64_t per = (ngroups + gridDim.x - 1) / gridDim.x;
+  int64_t ngroups = a.rows >> 5, nblk = gridDim.x;
+  if (a.dsz) {      // capacity launch: as k_small_from_groups
+    ngroups = min(ngroups, a.dsz[SZ_ROWS] >> 5); nblk = a.dsz[SZ_SMALL];
+    if ((int64_t)blockIdx.x >= nblk) return;
+  }
+  const int64_t per = (ngroups + nblk - 1) / nblk;
   int64_t g0 = (int64_t)blockIdx.x * per, g1 = g0 + per;
   if (g1 > ngroups) g1 = ngroups;
   const char* hN = (const char*)a.stash_h + (size_t)a.n_hidden * a.stride_rows * F;
@@ -1711,8 +1732,9 @@ __device__ __forceinline__ void reduce_small_body(const ReduceArgs& a, int bx, i
   const bool valid = e <= (size_t)F * a.k0pad + 2 * F;
   float s = 0.f;
   if (valid) {
-    const int per = (a.n_small + 3) / 4;
-    const int b1 = min((grp + 1) * per, a.n_small);
+    const int n_small = a.dsz ? (int)a.dsz[SZ_SMALL] : a.n_small;
+    const int per = (n_small + 3) / 4;
+    const int b1 = min((grp + 1) * per, n_small);
 #pragma unroll 8
     for (int b = grp * per; b < b1; ++b) s += a.partial_s[(size_t)b * SS + e];
   }
@@ -1739,6 +1761,7 @@ __global__ void __launch_bounds__(256) k_reduce_small(const ReduceArgs a) { redu
 template <int F>
 __global__ void __launch_bounds__(256) k_reduce_all(const ReduceArgs a, int nwx, int nw, int nb) {
   const int b = blockIdx.x, t = threadIdx.x;
+  if (a.dsz && a.dsz[SZ_ROWS] == 0) return;      // capacity launch, nothing survived the march: the gradient stays untouched
   if (b < nw) reduce_w_body<F>(a, b % nwx, b / nwx, t);
   else if (b < nw + nb) { if (t < F) reduce_b_body<F>(a, b - nw, t); }
   else reduce_small_body<F>(a, b - nw - nb, t & 63, t >> 6);
@@ -1751,9 +1774,11 @@ template <int F>
 __global__ void __launch_bounds__(F) k_reduce_coef(const ReduceArgs a) {
   __shared__ float red[F];
   const int m = blockIdx.x, f = threadIdx.x, nb = a.coef_cols;
+  if (a.dsz && a.dsz[SZ_ROWS] == 0) return;      // (capacity launch: as k_reduce_all)
+  const int n_splits = a.dsz ? (int)a.dsz[SZ_SPLITS] : a.n_splits;
   float g1 = 0.f, g2 = 0.f;
-  for (int sp = 0; sp < a.n_splits; ++sp) {
-    const float* P = a.partial + ((size_t)(a.n_hidden + 1) * a.n_splits + sp) * F * F + (size_t)f * a.k0pad;
+  for (int sp = 0; sp < n_splits; ++sp) {
+    const float* P = a.partial + ((size_t)(a.n_hidden + 1) * n_splits + sp) * F * F + (size_t)f * a.k0pad;
     g1 += P[m];
     g2 += P[nb + m];
   }

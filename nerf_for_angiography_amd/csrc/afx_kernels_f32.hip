@@ -174,10 +174,11 @@ __device__ __forceinline__ float strat_z(const ChainArgs& a, int i) {
   return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), u));
 }
 
-__device__ __forceinline__ Sample make_sample(const ChainArgs& a, int64_t n) {
+// (n_total: the samples of the work range - a.n_total, or the device-resident count of a capacity launch, ChainArgs::n_dev)
+__device__ __forceinline__ Sample make_sample(const ChainArgs& a, int64_t n, int64_t n_total) {
   Sample sp;
   sp.px = sp.py = sp.pz = 0.f; sp.dt = 0.f; sp.ray = 0; sp.s = 0; sp.live = false;
-  if (n >= a.n_total) return sp;
+  if (n >= n_total) return sp;
   if (a.mode == 0) {
     sp.px = a.pts[3 * n + 0]; sp.py = a.pts[3 * n + 1]; sp.pz = a.pts[3 * n + 2];
     sp.live = true;
@@ -238,6 +239,7 @@ __device__ __forceinline__ Sample make_sample(const ChainArgs& a, int64_t n) {
   }
   return sp;
 }
+__device__ __forceinline__ Sample make_sample(const ChainArgs& a, int64_t n) { return make_sample(a, n, a.n_total); }
 
 // Ray parameter t of a (rays-mode) sample, p = o + t d as make_sample formed it, and the ray's direction d.
 __device__ __forceinline__ void ray_param(const ChainArgs& a, const Sample& sp, float& t, float& dx, float& dy, float& dz) {
@@ -685,8 +687,9 @@ __device__ __forceinline__ void reduce_w_body(const ReduceArgs& a, int bx, int l
   const int row = e / ncols, c = e % ncols;
   if (c >= ncr) return;
   float s = 0.f;
+  const int n_splits = a.dsz ? (int)a.dsz[SZ_SPLITS] : a.n_splits;      // (capacity launch: the device-resident split count)
 #pragma unroll 8      // (independent loads in flight: the loop is latency-bound at the reference's batch sizes)
-  for (int sp = 0; sp < a.n_splits; ++sp) s += a.partial[((size_t)layer * a.n_splits + sp) * F * F + e];
+  for (int sp = 0; sp < n_splits; ++sp) s += a.partial[((size_t)layer * n_splits + sp) * F * F + e];
   // flat layout: W0[F,k0] b0[F] then (W_l[F,F] b_l[F])*, Wout[F] bout
   size_t off = layer == 0 ? 0 : (size_t)F * a.k0 + F + (size_t)(layer - 1) * (F * F + F);
   if (a.gmax) s *= ldexpf(1.f, wgrad_scale_exp(a.gmax) - a.scale_shift);       // f16 mode (hidden layers only reach here): undo Ls, exact
@@ -700,9 +703,10 @@ template <int F>
 __device__ __forceinline__ void reduce_b_body(const ReduceArgs& a, int y, int f) {
   if (a.hidden_only && ((y == 0 && !a.layer0_mfma) || y == a.n_hidden + 1)) return;
   float s = 0.f, sg = 0.f;
+  const int n_splits = a.dsz ? (int)a.dsz[SZ_SPLITS] : a.n_splits;
 #pragma unroll 8
-  for (int sp = 0; sp < a.n_splits; ++sp) {
-    const float* P = a.partial2 + ((size_t)y * a.n_splits + sp) * (F + 4);
+  for (int sp = 0; sp < n_splits; ++sp) {
+    const float* P = a.partial2 + ((size_t)y * n_splits + sp) * (F + 4);
     s += P[f];
     if (y == a.n_hidden + 1 && f == 0) sg += P[F];
   }
@@ -822,9 +826,11 @@ __global__ void k_finish_mse(const float* od_part, int groups, int64_t n_rays, c
 
 // the same for packed samples: ray r owns the groups [goff[r], goff[r+1]) (none: pixel = 1, the empty product of scatter_mul into ones,
 // nerf/nerf_helpers_acc.py:58)
-__global__ void k_finish_mse_packed(const float* od_part, const int64_t* goff, int64_t n_rays, const float* target, float inv_n, float* pixel, float* dod) {
+// n_dev (capturable step): the device-resident sample count of the packed list; 0 = nothing survived the march, pixel and dod stay untouched
+__global__ void k_finish_mse_packed(const float* od_part, const int64_t* goff, int64_t n_rays, const float* target, float inv_n, float* pixel, float* dod,
+                                    const int64_t* n_dev = nullptr) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rays) return;
+  if (r >= n_rays || (n_dev && *n_dev == 0)) return;
   float od = 0.f;
   for (int64_t g = goff[r]; g < goff[r + 1]; ++g) od += od_part[g];
   const float T = expf(-od);

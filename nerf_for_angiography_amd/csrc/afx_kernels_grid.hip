@@ -354,6 +354,29 @@ __global__ void __launch_bounds__(1024) k_ray_offsets(const int32_t* counts, int
   }
 }
 
+// The sizes of a grid training iteration, on the device (afx_march_train_step_mse_capturable): from the totals of the two offsets kernels
+// (totals[0] candidates, totals[2] kept samples, totals[3] their 32-sample groups) the counters the caller reads (counts[3] = candidates, kept,
+// groups), the optimizer's skip flag (1.0 when nothing survived the march) and the size block the capacity launches of the packed step read
+// (SZ_* slots) - the formulas run_backward applies on the host for one chunk of `tile`-sample tiles, so the weight-gradient sums run in the
+// same order as in afx_march_train_step_mse.  One thread.
+__global__ void k_grid_step_sizes(const int64_t* totals, int tile, int splits0, int max_splits, int max_small, int64_t* counts, float* skip, int64_t* dsz) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int64_t n = totals[0], kept = totals[2], ng = totals[3];
+  counts[0] = n; counts[1] = kept; counts[2] = ng;
+  *skip = kept == 0 ? 1.f : 0.f;
+  const int64_t n_total = ng * GROUP, rows = (n_total + tile - 1) / tile * tile;
+  int64_t splits = splits0;
+  if (splits > rows / 256) splits = rows / 256;
+  if (splits < 1) splits = 1;
+  if (splits > max_splits) splits = max_splits;
+  int64_t rps = (rows + splits - 1) / splits;
+  rps = (rps + 63) / 64 * 64;
+  int64_t n_small = (rows / GROUP + 3) / 4;
+  if (n_small < 64) n_small = 64;
+  if (n_small > max_small) n_small = max_small;
+  dsz[SZ_NTOTAL] = n_total; dsz[SZ_ROWS] = rows; dsz[SZ_SPLITS] = splits; dsz[SZ_RPS] = rps; dsz[SZ_SMALL] = n_small; dsz[SZ_GROUPS] = ng;
+}
+
 __global__ void __launch_bounds__(256) k_march_compact(const uint8_t* keep, const int64_t* offsets_in, const int64_t* offsets_out, int64_t n_rays,
                                                        const float* ts_in, const float* te_in, int32_t* ri_out, float* ts_out, float* te_out) {
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);

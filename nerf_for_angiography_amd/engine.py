@@ -79,6 +79,10 @@ class Engine:
     def _check(self, rc, what):
         _lib.check(rc, what, self.lib)
 
+    def _last_error(self) -> str:
+        msg = self.lib.afx_last_error()
+        return msg.decode() if msg else "?"
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
@@ -314,8 +318,54 @@ class Engine:
                 need = int(a.workspace_needed)
                 continue
             self._check(rc, "afx_march_train_step_mse")
+            self.last_march_counts = (int(a.n_candidates), int(a.n_kept), int(a.n_groups))      # (the group count as well, for comparisons)
             return pixel, int(a.n_candidates), int(a.n_kept)
         raise AfxError("march_train_step_mse: the workspace did not converge")
+
+    def march_train_workspace_bytes(self, prec: str, n_rays: int, max_steps_per_ray: int) -> int:
+        """Workspace of afx_march_train_step_mse_capturable: fixed by the ray count and the per-ray step bound (march_max_steps), not by data."""
+        nbytes = int(self.lib.afx_march_train_workspace_bytes(self.h, _lib.PREC[prec], int(n_rays), int(max_steps_per_ray)))
+        if nbytes < 0:
+            raise AfxError(f"afx_march_train_workspace_bytes: {self._last_error()}")
+        return nbytes
+
+    def march_train_step_mse_capturable(self, prepared, origins, dirs, target, inv_n: float, grad_flat, prec: str, scene_aabb, near_plane,
+                                        far_plane, step: float, early_stop_eps: float, alpha_thre: float, grid_bits=None, grid_aabb=None,
+                                        grid_res=None, pixel=None, counts=None, skip=None):
+        """afx_march_train_step_mse_capturable: the grid iteration of march_train_step_mse with its sizes on the device - no host read-back,
+        so it can be captured into a HIP graph.  The workspace is sized once, from the worst case of the march arguments (every step of every
+        ray occupied); a capture never grows it (size it with one eager call first).  Writes pixel [n_rays] (float32), counts [3] (int64:
+        candidates, kept samples, groups) and skip [1] (float32: 1.0 when nothing was kept - pixel / grad_flat untouched); pass them to
+        reuse static buffers.  Returns (pixel, counts, skip), device tensors only."""
+        dev = prepared.device
+        o, d, target = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(target, "target", dev)
+        n_rays = o.shape[0]
+        if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3) or target.numel() != n_rays:
+            raise ValueError("march_train_step_mse_capturable: origins/dirs [n_rays,3] and target [n_rays] expected")
+        if far_plane is None:
+            raise ValueError("march_train_step_mse_capturable: the workspace bound needs a far plane")
+        pixel = torch.empty(n_rays, dtype=torch.float32, device=dev) if pixel is None else pixel
+        counts = torch.empty(3, dtype=torch.int64, device=dev) if counts is None else counts
+        skip = torch.empty(1, dtype=torch.float32, device=dev) if skip is None else skip
+        for t, dt, n, name in ((pixel, torch.float32, n_rays, "pixel"), (counts, torch.int64, 3, "counts"), (skip, torch.float32, 1, "skip")):
+            if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"march_train_step_mse_capturable: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+        a = _lib.MarchTrainArgs()
+        _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+        a.early_stop_eps, a.alpha_thre, a.inv_n = float(early_stop_eps), float(alpha_thre), float(inv_n)
+        a.target, a.pixel, a.grad_flat = target.data_ptr(), pixel.data_ptr(), grad_flat.data_ptr()
+        max_steps = int(self.lib.afx_march_max_steps(C.byref(a.march)))
+        if max_steps < 0:
+            raise AfxError(f"afx_march_max_steps: {self._last_error()}")
+        need = self.march_train_workspace_bytes(prec, n_rays, max_steps)
+        if need > self.max_workspace_bytes:
+            raise AfxError(f"march_train_step_mse_capturable: {n_rays} rays x {max_steps} steps need a {need >> 20} MiB workspace "
+                           f"(max_workspace_bytes = {self.max_workspace_bytes >> 20} MiB)")
+        ws = self._workspace(need, dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        self._check(self.lib.afx_march_train_step_mse_capturable(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), _ptr(counts), _ptr(skip),
+                                                                 self._stream(dev)), "afx_march_train_step_mse_capturable")
+        return pixel, counts, skip
 
     def hier_train_step_mse(self, prepared, spec: RenderSpec, n_fine: int, u, target, inv_n: float, grad_flat, prec: str, want_z_all=True):
         """afx_hier_train_step_mse: hierarchical step with coarse re-use; `spec` carries the rays and the COARSE depths (mode 'dense').

@@ -11,7 +11,8 @@ MLP -> Beer-Lambert -> MSE -> backward; render + autograd with --precision f32);
 run_nerf_acc.py:284-306 - acc_update_n_step for both grids, acc_ray_marching with the occupancy grid (HIP march / visibility
 kernels, nerf/occupancy.py), then positions / get_predictions / acc_render_volume_density / mse_loss / backward as ONE fused pass
 over the march's packed samples, march included, in one library call (`march_train_step_mse`; f16s8); `grid_ops` is the same body call for call through
-the mirrored functions (also what `grid` does at the other precisions).
+the mirrored functions (also what `grid` does at the other precisions).  `--graph` (with `grid`, f16s8) replays that iteration, Adam
+included, from a HIP graph captured once (`render.GridTrainGraph`): the sizes stay on the device and the host never waits for the GPU.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -33,7 +34,7 @@ from ..engine import RenderSpec
 from ..model.CPPN import CPPN
 from ..phantomdata import dataset as ds
 from .. import engine as _engine
-from ..render import render_rays, train_step_mse, march_train_step_mse
+from ..render import render_rays, train_step_mse, march_train_step_mse, GridTrainGraph
 from .nerf_helpers import sample_pixel_rays, get_predictions
 from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
@@ -66,6 +67,10 @@ def build_parser():
                    help='dense: fused fixed-step march (one launch per ray chunk); grid: the reference loop with the occupancy grid, its body behind '
                         'the march (positions, get_predictions, acc_render_volume_density, mse, backward) as ONE fused packed step at the f16s8 '
                         'precision; grid_ops: the same loop call for call through the mirrored functions')
+    p.add_argument('--graph', action='store_true',
+                   help='--march grid --precision f16s8: capture the whole iteration (re-tiling, march, alpha pass, visibility, packed step, loss, '
+                        'Adam) once into a HIP graph and replay it; sizes stay on the device and the host never waits for the GPU (the '
+                        'occupancy-grid update every 16 iterations stays eager; counts and loss are read at the display cadence only)')
     p.add_argument('--adam', default='fused', choices=['fused', 'foreach'], help="PyTorch Adam implementation (same update rule)")
     p.add_argument('--host_sampler', action='store_true', help="draw each batch with pandas on the host (the reference's sample_pixel_rays)")
     p.add_argument('--log_dir', default='runs/afx')
@@ -145,7 +150,12 @@ def main(argv=None):
         coarse_model.output_linear[0].bias.fill_(args.out_bias_init)
     # run_nerf_acc.py:206.  fused=True: PyTorch's single multi-tensor Adam kernel instead of its foreach sequence of ~7 launches - same
     # update, and on the reference's 1.3 ms iteration the difference is 10 % (host-side dispatch: 0.95 -> 0.55 ms with the grid march)
-    coarse_optimizer = torch.optim.Adam(list(coarse_model.parameters()), lr=coarse_lr, fused=(args.adam == 'fused'))
+    if args.graph and (args.march != 'grid' or args.precision != 'f16s8' or args.adam != 'fused' or args.pos_enc != 'none'):
+        raise ValueError("--graph: needs --march grid --precision f16s8 --adam fused --pos_enc none (the capturable grid step is f16s8; "
+                         "the captured optimizer is the fused, capturable Adam; the encodings' schedules and coefficients are not captured)")
+    # --graph: a device-resident lr (changed with fill_ between replays) and an Adam whose step can be captured
+    coarse_optimizer = torch.optim.Adam(list(coarse_model.parameters()), lr=torch.tensor(coarse_lr, device=device) if args.graph else coarse_lr,
+                                        fused=(args.adam == 'fused'), capturable=args.graph)
 
     # device-resident ray table (R13): built once; every batch is drawn and gathered on the GPU
     tab_o, tab_d = cols(train_ray_df, 'ray_origins'), cols(train_ray_df, 'ray_directions')
@@ -171,6 +181,11 @@ def main(argv=None):
     new_lr_coarse = coarse_lr
     loss_coarse = torch.tensor(float('nan'), device=device)
     n_marched = 0
+    train_graph = None
+    if args.graph:      # captured once; every iteration then copies its batch into the graph's static tensors and replays
+        train_graph = GridTrainGraph(coarse_model, coarse_optimizer, acc_grid, scene_aabb, img_sample_size, depth_samples_per_ray_coarse, near_thresh,
+                                     far_thresh, early_stop_eps, alpha_thre)
+        n_marched = torch.zeros((), dtype=torch.int64, device=device)
     t_last = time.time()
     for n_iter in range(n_iters + 1):
         coarse_model.train()
@@ -181,7 +196,8 @@ def main(argv=None):
                                                                                weights='distance_pixel_value')
         else:
             batch_origins, batch_directions, batch_pix_vals, _ = ray_batches.draw(n_iter)      # == sample_rays(..., seed, stream_id=n_iter)
-        coarse_optimizer.zero_grad()
+        if train_graph is None:
+            coarse_optimizer.zero_grad()      # (--graph: the captured step zeroes the gradient buffer it accumulates into)
         if args.march != 'dense':
             # the reference's iteration body, run_nerf_acc.py:284-306
             with torch.no_grad():
@@ -189,7 +205,13 @@ def main(argv=None):
                 vessel_acc_grid.train()
                 acc_grid = acc_update_n_step(acc_grid, coarse_model, n_iter, occ_thre=alpha_thre)
                 vessel_acc_grid = acc_update_n_step(vessel_acc_grid, coarse_model, n_iter, occ_thre=vessel_alpha_thre)
-            if packed_step:
+            if train_graph is not None:
+                # the same iteration replayed from the graph: no host read-back; an empty march skips the Adam step on the device
+                loss_k, pred, counts = train_graph.step(batch_origins, batch_directions, batch_pix_vals)
+                loss_coarse = torch.where(train_graph.skip[0] > 0, loss_coarse, loss_k)      # (the last step that kept samples, as below)
+                n_marched += counts[1]
+                ray_indices = ()      # (the optimizer step is part of the graph)
+            elif packed_step:
                 # :287-306 - march, alpha pass, visibility and the fused packed step - as ONE library call (the entry points of the
                 # operator branch below, in the same order: ~30 launches that a Python loop issues slower than the GPU runs them)
                 loss_k, pred_k, n_kept = march_train_step_mse(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
@@ -225,7 +247,10 @@ def main(argv=None):
             coarse_optimizer.step()
         new_lr_coarse = coarse_lr * (decay_rate ** (n_iter / decay_steps))
         for param_group in coarse_optimizer.param_groups:
-            param_group['lr'] = new_lr_coarse
+            if train_graph is not None:
+                param_group['lr'].fill_(new_lr_coarse)
+            else:
+                param_group['lr'] = new_lr_coarse
 
         if n_iter % display_every == 0:
             coarse_model.eval()
@@ -250,9 +275,9 @@ def main(argv=None):
                        test_psnr=psnr, test_vessel_psnr=vessel_psnr, lr=new_lr_coarse,
                        barf_alpha=float(getattr(coarse_model, 'barf_alpha', 0.0)), sec=round(time.time() - t_last, 3),
                        it_per_s=round(display_every / max(time.time() - t_last, 1e-9), 1) if n_iter else 0.0,
-                       marched_samples_per_iter=(n_marched // max(display_every, 1)) if args.march != 'dense' else
+                       marched_samples_per_iter=(int(n_marched) // max(display_every, 1)) if args.march != 'dense' else
                        img_sample_size * depth_samples_per_ray_coarse)
-            n_marched = 0
+            n_marched = 0 if train_graph is None else n_marched.zero_()
             t_last = time.time()
             history.append(rec)
             log.write(json.dumps(rec) + "\n")

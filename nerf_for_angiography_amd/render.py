@@ -341,3 +341,107 @@ def density_grid(model, outside: float, n: int, precision: Optional[str] = None)
     finally:
         model.precision = keep
     return sig.reshape(n + 1, n + 1, n + 1)
+
+
+class GridTrainGraph:
+    """The reference's grid training iteration (nerf/run_nerf_acc.py:284-306: march, alpha pass, render_visibility, graded pass, backward,
+    optimizer step) captured ONCE into a HIP graph and replayed: weight re-tiling into the module's prepared buffer,
+    afx_march_train_step_mse_capturable (sizes stay on the device), the loss, the gradients into `.grad`, `optimizer.step()`.
+
+    `step(origins, dirs, target)` copies the batch into static tensors (device to device), replays, and returns device tensors
+    (loss, pixel, counts) - counts = (candidates, kept samples, groups) - without reading anything back.  When nothing survives the march
+    the optimizer step is skipped exactly as the reference skips it (:293): `optimizer.found_inf` points at the step's skip flag, which
+    PyTorch's fused Adam honours (parameters, moments and `step` unchanged); pixel and loss then hold the previous replay's values.
+    Requires `Adam(fused=True, capturable=True)` (a tensor lr can be changed between replays with `fill_`).  The occupancy grid is read
+    by address: update it in place between replays (`OccupancyGrid.update_every_n_steps`, `set_binary`), never rebind it.  After a
+    replay the module's cached prepared weights are marked stale, so eager renders re-tile the updated parameters."""
+
+    def __init__(self, model, optimizer, grid, scene_aabb, n_rays: int, depth_samples_per_ray: int, near: float, far: float,
+                 early_stop_eps: float, alpha_thre: float, n_global: Optional[int] = None):
+        if _grad_hook is not None and getattr(_grad_hook, "world", 1) > 1:
+            raise AfxError("GridTrainGraph: a multi-rank gradient hook (dist.GradSync) is installed; the all-reduce cannot be captured - "
+                           "use march_train_step_mse")
+        if not isinstance(optimizer, torch.optim.Adam) or not all(g.get("fused") and g.get("capturable") for g in optimizer.param_groups):
+            raise ValueError("GridTrainGraph: needs torch.optim.Adam(..., fused=True, capturable=True) (the skip of an empty step is its found_inf)")
+        _check_model(model)
+        if model.precision != "f16s8":
+            raise NotImplementedError("GridTrainGraph: precision 'f16s8' only")
+        if model._coef_trainable():
+            raise NotImplementedError("GridTrainGraph: trainable fourier coefficients are not captured; freeze them or use march_train_step_mse")
+        from .nerf.occupancy import _aabb_on_host
+        self.model, self.optimizer, self.grid = model, optimizer, grid
+        dev = model.flat_params.device
+        eng = model.engine
+        self.n_rays = int(n_rays)
+        n = _global_rays(self.n_rays, n_global, dev)
+        inv_n = 1.0 / n
+        self.origins = torch.zeros(self.n_rays, 3, device=dev)
+        self.dirs = torch.zeros(self.n_rays, 3, device=dev)
+        self.dirs[:, 2] = 1.0
+        self.target = torch.zeros(self.n_rays, device=dev)
+        self.pixel = torch.ones(self.n_rays, device=dev)
+        self.counts = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.skip = torch.ones(1, device=dev)
+        self.flat_grad = torch.zeros(eng.param_count, device=dev)
+        for p, g in zip(model._hip_params(), model._split_grad(self.flat_grad)):
+            p.grad = g      # the gradients live in the static buffer the captured step accumulates into
+        self._aux_key = self._aux()
+        self._buf = model._prepared()      # the module's prepared buffer: the graph re-tiles into it
+        aabb = None if scene_aabb is None else _aabb_on_host(scene_aabb)
+        step = (float(far) - float(near)) / int(depth_samples_per_ray)
+        march = dict(scene_aabb=aabb, near_plane=float(near), far_plane=float(far), step=step, early_stop_eps=float(early_stop_eps),
+                     alpha_thre=float(alpha_thre), grid_bits=None if grid is None else grid.bits,
+                     grid_aabb=None if grid is None else grid._aabb_host, grid_res=None if grid is None else grid._res_host)
+
+        def body(with_optimizer):
+            eng.prepare(model.flat_params, model._enc_aux(), model.precision)      # into the cached buffer (key None: always re-tiles)
+            self.flat_grad.zero_()
+            eng.march_train_step_mse_capturable(self._buf, self.origins, self.dirs, self.target, inv_n, self.flat_grad, model.precision,
+                                                pixel=self.pixel, counts=self.counts, skip=self.skip, **march)
+            loss = (torch.nn.functional.mse_loss(self.pixel, self.target) if n == self.n_rays
+                    else ((self.pixel - self.target) ** 2).sum() / n)      # (as march_train_step_mse forms it)
+            if with_optimizer:
+                optimizer.step()
+            return loss
+
+        # eager warm-up of the library call (sizes the workspace, sets the kernels' attributes; grads are re-zeroed by every replay), and
+        # the optimizer's state created by a step it skips (found_inf = 1): state created during the capture would be re-initialised by
+        # every replay
+        body(False)
+        optimizer.found_inf = torch.ones((), device=dev)
+        optimizer.step()
+        self._found_inf = self.skip.view(())      # (fused Adam takes a 0-dim flag; a view of the step's skip flag)
+        optimizer.found_inf = self._found_inf
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(self.graph, stream=side):
+                self.loss = body(True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._mark_stale()
+
+    def _aux(self):
+        m = self.model
+        return float(m.barf_alpha) if m.use_pos_enc == "barf" else None
+
+    def _mark_stale(self):
+        # replays update the parameters without a host-visible optimizer step: the cache keys would still match; a None key makes the next
+        # eager model._prepared() re-tile into the same buffer (every precision's: evaluation renders and grid updates may use another)
+        cache = self.model.engine._prepared
+        for prec, (buf, _) in list(cache.items()):
+            cache[prec] = (buf, None)
+        cache[self.model.precision] = (self._buf, None)
+
+    def step(self, origins, dirs, target):
+        if self._aux() != self._aux_key:
+            raise AfxError("GridTrainGraph: the BARF schedule moved since the capture (the encoding weights are captured by address); "
+                           "build a new GridTrainGraph")
+        if self.optimizer.found_inf is not self._found_inf:
+            raise AfxError("GridTrainGraph: optimizer.found_inf was replaced; the captured step reads the skip flag by address")
+        self.origins.copy_(origins)
+        self.dirs.copy_(dirs)
+        self.target.copy_(target)
+        self.graph.replay()
+        self._mark_stale()
+        return self.loss, self.pixel, self.counts
