@@ -14,7 +14,7 @@
  *     holds only immutable descriptors => calls are hipGraph-capturable, with
  *     two exceptions: afx_march_train_step_mse reads two sizes back (it polls),
  *     and afx_profile_read synchronises.  The grid iteration's capturable form
- *     is afx_march_train_step_mse_capturable.
+ *     is afx_march_train_step_mse_capturable (or afx_march_train_step_mse_single_eval).
  *   - all other calls are asynchronous on the stream passed in.
  *   - results are deterministic: no floating-point atomics anywhere.
  */
@@ -366,6 +366,22 @@ int64_t afx_march_max_steps(const afx_march_args* args);      /* >= the steps k_
 int64_t afx_march_train_workspace_bytes(const afx_ctx* ctx, int prec, int64_t n_rays, int64_t max_steps_per_ray);      /* -1: error */
 int afx_march_train_step_mse_capturable(afx_ctx* ctx, int prec, const void* prepared, afx_march_train_args* args, int64_t* counts_dev,
                                         float* skip_dev, void* stream);
+
+/* The same iteration with ONE evaluation of the model: the packed step's forward half runs over the march's candidates (group-aligned) and
+ * doubles as the alpha pass - visibility is decided on its own raw output with afx_march_visibility's arithmetic, the optical depth of the kept
+ * samples is summed in the order of the compacted list, and the backward half and weight gradients run over the candidate rows with dL/draw = 0
+ * for dropped samples.  Nothing is compacted; the only data-dependent size is the candidate count, kept on the device, so the call is
+ * graph-capturable (no host read-back, synchronisation or allocation).  Same arguments and out-contract as afx_march_train_step_mse_capturable
+ * (counts_dev[3] = (n_candidates, n_kept, n_kept_groups) - the kept groups being those the compacted list would have; skip_dev[1] = 1.0f when
+ * nothing was kept: pixel and grad_flat untouched).  Relation to the two-evaluation step: where the forward half's raw output equals
+ * afx_mlp_infer's at the mid-points (tests/test_gpu_grid_single_eval.py pins it), the counters, pixels, loss and skip flag are equal bit for bit;
+ * the weight gradient sums over the candidate rows in another order and agrees to the f16s8 tolerance.  The backward work grows with the candidates,
+ * not the kept samples.  f16s8, ReLU, no input encoding, a far plane; the workspace must hold afx_march_single_eval_workspace_bytes(ctx, prec,
+ * n_rays, afx_march_max_steps(&args->march)) bytes (else AFX_E_WORKSPACE with workspace_needed set); a worst case beyond the one-chunk sample
+ * limit is refused with AFX_E_INVALID. */
+int64_t afx_march_single_eval_workspace_bytes(const afx_ctx* ctx, int prec, int64_t n_rays, int64_t max_steps_per_ray);      /* -1: error */
+int afx_march_train_step_mse_single_eval(afx_ctx* ctx, int prec, const void* prepared, afx_march_train_args* args, int64_t* counts_dev,
+                                         float* skip_dev, void* stream);
 
 /* Indices of the k largest of keys[n] (ties: lowest index first), written in ASCENDING INDEX order - the selection step of the
  * weighted ray sampler (the batch of nerf/nerf_helpers.py:137-150 is a set; its order carries no meaning).  Radix select:

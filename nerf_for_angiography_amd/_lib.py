@@ -104,6 +104,9 @@ _SIGS = {
     "afx_march_train_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_int64]),
     "afx_march_train_step_mse_capturable": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MarchTrainArgs), C.c_void_p, C.c_void_p,
                                                       C.c_void_p]),
+    "afx_march_single_eval_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_int64]),
+    "afx_march_train_step_mse_single_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MarchTrainArgs), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
     "afx_ray_offsets": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_march_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1582,3 +1582,155 @@ extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const v
   return packed_step(c, prec, prepared, m.origins, m.dirs, R, goff, gray, std::max<int64_t>(L.g_cap, 1), tsp, tep, t->target, t->inv_n, t->pixel,
                      t->grad_flat, ws + L.o_step, t->workspace_bytes - L.o_step, stream, dsz);
 }
+
+// ---- the grid iteration with ONE evaluation of the model (afx_march_train_step_mse_single_eval): the packed step's forward half runs over the
+// march's candidates (group-aligned, as afx_pack_groups lays them out) and doubles as the alpha pass.  k_single_eval_composite decides the kept
+// set from the forward half's own raw output, forms pixel / loss gradient and the finished dL/draw per row (0 for dropped samples); the backward
+// half and the weight gradients then run over the candidate rows in the arrangement of the hierarchical step (defer_out: PHASE 2 reads the
+// finished dL/draw, the output layer's gradient is contracted from the stash of H_N by k_wout_stash8).  The only size that shapes the work is the
+// candidate count, which stays on the device: every buffer is carved for the worst case, as in the capturable step, and nothing is compacted.
+struct SeLayout {
+  size_t o_counts, o_offsets, o_totals, o_goff, o_counts2, o_off2, o_goff2, o_dsz, o_pix;
+  size_t o_ri, o_ts, o_te, o_keep, o_tsp, o_tep, o_gray, o_raw, o_tau, o_od;
+  size_t o_partial, o_partial2, o_partial_s, o_gmax;
+  size_t o_sh, o_sdz, o_gexp, o_gpart, o_masks, o_rec, o_hexp;
+  size_t total;
+  int64_t n_cap, g_cap, rows;      // candidates and 32-sample groups of the worst case, stash rows (whole 256-sample tiles)
+};
+static int se_layout(const afx_ctx* c, int64_t R, int64_t S, SeLayout& L, const char* who) {
+  if (R <= 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays > 0 and max_steps_per_ray >= 0", who);
+  L.n_cap = R * S;
+  L.g_cap = R * ((S + GROUP - 1) / GROUP);
+  // one chunk: a layer plane of the 8-bit stash stays below 4 GiB (the chain kernels' 32-bit stash offsets), as in the capturable step
+  const int64_t max_samples = (int64_t)(((uint64_t)1 << 32) / ((uint64_t)256 * c->d.width)) * 256;
+  if (L.g_cap * GROUP > max_samples || L.n_cap > ((int64_t)1 << 31) - 256)
+    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed the single-evaluation step's sample limit (%lld group-padded samples at width %d, "
+                "one chunk of the packed step); use afx_march_train_step_mse or fewer rays per step", who, (long long)R, (long long)S,
+                (long long)max_samples, c->d.width);
+  const size_t F = c->d.width, N = c->d.n_hidden;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
+  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(4 * 8); L.o_goff = take((size_t)(R + 1) * 8);
+  L.o_counts2 = take((size_t)R * 4); L.o_off2 = take((size_t)(R + 1) * 8); L.o_goff2 = take((size_t)(R + 1) * 8); L.o_dsz = take(SZ_COUNT * 8);
+  L.o_pix = take((size_t)R * 4);
+  const size_t n = (size_t)std::max<int64_t>(L.n_cap, 1), g = (size_t)std::max<int64_t>(L.g_cap, 1);
+  L.o_ri = take(n * 4); L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_keep = take(n);
+  L.o_tsp = take(g * 32 * 4); L.o_tep = take(g * 32 * 4); L.o_gray = take(g * 4); L.o_raw = take(g * 32 * 4); L.o_tau = take(g * 32 * 4);
+  L.o_od = take(g * 4);
+  L.o_partial = take((N + 2) * (size_t)kSplits * F * F * 4); L.o_partial2 = take((N + 2) * (size_t)kSplits * (F + 4) * 4);
+  L.o_partial_s = take((size_t)kSmallBlocks * (F * 16 + 2 * F + 4) * 4); L.o_gmax = take(256);
+  const size_t rows = (g * 32 + 255) / 256 * 256;
+  L.rows = (int64_t)rows;
+  L.o_sh = take((N + 1) * rows * F); L.o_sdz = take((N + 1) * rows * F);
+  L.o_gexp = take(rows * 4); L.o_gpart = take(rows * 4);
+  L.o_masks = take((rows / 256) * (N + 1) * c->nt * 1024);
+  L.o_rec = take((rows / 32) * (3 * F + 8) * 4);
+  L.o_hexp = take(N * (rows / 32) * 4);
+  L.total = off;
+  return AFX_OK;
+}
+
+extern "C" int64_t afx_march_single_eval_workspace_bytes(const afx_ctx* c, int prec, int64_t n_rays, int64_t max_steps_per_ray) {
+  if (!c) { fail(AFX_E_INVALID, "afx_march_single_eval_workspace_bytes: null ctx"); return -1; }
+  if (prec != AFX_PREC_F16S8) { fail(AFX_E_INVALID, "afx_march_single_eval_workspace_bytes: AFX_PREC_F16S8 only"); return -1; }
+  SeLayout L;
+  if (se_layout(c, n_rays, max_steps_per_ray, L, "afx_march_single_eval_workspace_bytes")) return -1;
+  return (int64_t)L.total;
+}
+
+extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const void* prepared, afx_march_train_args* t, int64_t* counts_dev,
+                                                    float* skip_dev, void* stream) {
+  const char* who = "afx_march_train_step_mse_single_eval";
+  if (!c || !prepared || !t || !counts_dev || !skip_dev) return fail(AFX_E_INVALID, "%s: null argument", who);
+  t->workspace_needed = 0;
+  const afx_march_args& m = t->march;
+  const int64_t R = m.n_rays;
+  if (R <= 0) return fail(AFX_E_INVALID, "%s: n_rays must be > 0", who);
+  if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "%s: AFX_PREC_F16S8 only", who);
+  if (c->d.act != AFX_ACT_RELU) return fail(AFX_E_INVALID, "%s: ReLU models only (tanh / sine train in the exact-fp32 kernels)", who);
+  if (c->d.enc != AFX_ENC_NONE)
+    return fail(AFX_E_INVALID, "%s: no input encoding (the deferred output-layer path of the backward half does not carry one); use "
+                "afx_march_train_step_mse_capturable", who);
+  if (!m.has_far) return fail(AFX_E_INVALID, "%s: the march needs a far plane (the worst-case workspace bound)", who);
+  const int64_t S = afx_march_max_steps(&m);
+  if (S < 0) return AFX_E_INVALID;
+  SeLayout L;
+  if (int rc = se_layout(c, R, S, L, who)) return rc;
+  if (L.total > t->workspace_bytes) {
+    t->workspace_needed = L.total;
+    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_single_eval_workspace_bytes)", who, t->workspace_bytes, L.total);
+  }
+  if (int rc = check_dev(c, who)) return rc;
+  const int F = c->d.width, N = c->d.n_hidden;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)t->workspace;
+  int32_t *counts = (int32_t*)(ws + L.o_counts), *counts2 = (int32_t*)(ws + L.o_counts2);
+  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals), *goff = (int64_t*)(ws + L.o_goff),
+          *off2 = (int64_t*)(ws + L.o_off2), *goff2 = (int64_t*)(ws + L.o_goff2), *dsz = (int64_t*)(ws + L.o_dsz);
+  int32_t *ri = (int32_t*)(ws + L.o_ri), *gray = (int32_t*)(ws + L.o_gray);
+  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *tsp = (float*)(ws + L.o_tsp), *tep = (float*)(ws + L.o_tep);
+  float *row_raw = (float*)(ws + L.o_raw), *row_tau = (float*)(ws + L.o_tau), *pix = (float*)(ws + L.o_pix), *gpart = (float*)(ws + L.o_gpart);
+  uint8_t* keep = (uint8_t*)(ws + L.o_keep);
+  uint32_t* gmax = (uint32_t*)(ws + L.o_gmax);
+  const int tile = bwd_tile(prec), splits0 = c->n_cu / N;
+  int rc;
+  // 1. candidates, their group-aligned copy (totals[0] / totals[1]: candidates and their groups, on the device only) and the step's size block
+  if ((rc = afx_march_count(&m, counts, stream))) return rc;
+  if ((rc = afx_ray_offsets(counts, R, offsets, goff, totals, stream))) return rc;
+  if ((rc = afx_march_write(&m, offsets, ri, ts, te, nullptr, stream))) return rc;
+  if ((rc = afx_pack_groups(offsets, goff, R, ts, te, tsp, tep, gray, stream))) return rc;
+  hipLaunchKernelGGL(k_single_eval_sizes, dim3(1), dim3(64), 0, st, (const int64_t*)totals, tile, splits0, kSplits, kSmallBlocks, dsz);
+  HIPCHK(hipGetLastError());
+  // 2. forward half over the candidates: H_l (H_N too), masks, g', raw and tau per row
+  ChainArgs a = {};
+  fill_model(c, prec, true, prepared, a);
+  a.mode = 1; a.org = m.origins; a.dir = m.dirs; a.poses = nullptr;
+  a.depth_mode = 4; a.z = tsp; a.te = tep; a.group_ray = gray;
+  a.n_samples = GROUP; a.s_pad = GROUP; a.n_total = std::max<int64_t>(L.g_cap, 1) * GROUP;
+  a.fused = 0; a.stash8 = 1; a.coef_cols = 0; a.debug = 0; a.persistent = 1; a.defer_out = 1; a.dod = nullptr;
+  a.od_part = (float*)(ws + L.o_od); a.gmax = gmax;
+  a.tile0 = 0; a.tile1 = (int)((a.n_total + tile - 1) / tile);
+  a.stash_h = (float*)(ws + L.o_sh); a.stash_dz = (float*)(ws + L.o_sdz); a.stash_e = nullptr;
+  a.graw = (float*)(ws + L.o_gexp); a.gexp = (int32_t*)(ws + L.o_gexp); a.gpart = gpart; a.masks = ws + L.o_masks;
+  a.small_part = (float*)(ws + L.o_rec); a.stash_rows = L.rows; a.hexp = (uint32_t*)(ws + L.o_hexp);
+  a.n_dev = dsz + SZ_NTOTAL;
+  a.row_raw = row_raw; a.row_tau = row_tau;
+  if ((rc = launch_chain(c, prec, true, a, st, 1))) return rc;
+  // 3. visibility + composite + MSE per ray, the kept totals, the caller's counters / skip flag / pixels
+  hipLaunchKernelGGL(k_single_eval_composite, blocks_for(R, 4), dim3(256), 0, st, (const float*)row_raw, (const float*)row_tau, (const float*)ts,
+                     (const float*)te, (const int64_t*)offsets, (const int64_t*)goff, R, t->early_stop_eps, t->alpha_thre, t->target, t->inv_n, keep,
+                     gpart, counts2, pix);
+  HIPCHK(hipGetLastError());
+  if ((rc = afx_ray_offsets(counts2, R, off2, goff2, totals + 2, stream))) return rc;
+  hipLaunchKernelGGL(k_single_eval_finish, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, (const int64_t*)totals, (const float*)pix, R, t->pixel,
+                     counts_dev, skip_dev, dsz);
+  HIPCHK(hipGetLastError());
+  // 4. backward half over the candidate rows (dL/draw finished in gpart), then the weight gradients (output layer from the stash of H_N)
+  HIPCHK(hipMemsetAsync(gmax, 0, 4, st));
+  a.row_raw = nullptr; a.row_tau = nullptr;
+  if ((rc = launch_chain(c, prec, true, a, st, 2))) return rc;
+  WgradArgs w = {};
+  w.stash_h = a.stash_h; w.stash_dz = a.stash_dz; w.stash_e = nullptr; w.graw = a.graw;
+  w.rows = L.rows; w.stride_rows = L.rows;
+  w.n_hidden = N; w.k0 = c->k0; w.k0pad = 16;
+  int splits = splits0;      // (the capacity's; the kernels take the device's from dsz)
+  if (splits > (int)(w.rows / 256)) splits = (int)(w.rows / 256);
+  if (splits < 1) splits = 1;
+  if (splits > kSplits) splits = kSplits;
+  w.n_splits = splits;
+  w.rows_per_split = (int)(((w.rows + splits - 1) / splits + 63) / 64 * 64);
+  w.partial = (float*)(ws + L.o_partial); w.partial2 = (float*)(ws + L.o_partial2); w.partial_s = (float*)(ws + L.o_partial_s);
+  w.debug = 0; w.small_groups = 1;
+  w.gmax = gmax; w.stash_esz = 1; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = 0; w.coef_cols = 0;
+  w.dod = nullptr; w.gpr = 1; w.group0 = 0; w.n_groups_valid = 0; w.group_ray = nullptr;
+  w.records = a.small_part; w.no_sw = 1; w.gfull = gpart;
+  w.dsz = dsz;
+  ReduceArgs rd = {};
+  rd.partial = w.partial; rd.partial2 = w.partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = 16; rd.n_splits = splits;
+  rd.grad = t->grad_flat; rd.hidden_only = 1; rd.partial_s = w.partial_s;
+  rd.n_small = (int)std::min<int64_t>(kSmallBlocks, std::max<int64_t>(64, (w.rows / GROUP + 3) / 4));
+  rd.gmax = gmax; rd.scale_shift = AFX_S8_JSHIFT; rd.layer0_mfma = 0; rd.w0 = nullptr; rd.d_coef = nullptr; rd.coef_cols = 0;
+  rd.dsz = dsz;
+  return F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, st) : launch_wgrad8_t<256>(c, w, rd, N, st));
+}

@@ -109,6 +109,10 @@ struct ChainArgs {
   // device-resident sample count (afx_march_train_step_mse_capturable): null = n_total / tile1 are the work range (every other caller).
   // Otherwise the launch is sized for the capacity n_total / tile1 and the kernel bounds its work by min(*n_dev, n_total) samples.
   const int64_t* n_dev;
+  // single-evaluation grid step (afx_march_train_step_mse_single_eval): PHASE 1 also writes, per padded row n of a live sample, the output-layer
+  // value before the sigmoid (row_raw[n]) and tau = sigma dt (row_tau[n]) - the inputs of the visibility / composite kernel.  Null: not written.
+  float* row_raw;
+  float* row_tau;
 };
 
 struct WgradArgs {

@@ -825,6 +825,9 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
       d += __shfl_xor(d, 32);
       const float raw = d + sm[(N + 2) * F];
       g[cg] = 0.f;
+      if constexpr (P1 && !ENC) {      // (single-evaluation grid step, afx_march_train_step_mse_single_eval: the output before the sigmoid; uniform branch)
+        if (a.row_raw && hh == 0 && sp[cg].live) a.row_raw[n[cg]] = raw;
+      }
       if constexpr (P2) {      // backward half: dL/draw = dL/d(optical depth of the ray) * g' (PHASE 1 left g' = dt sigma (1 - sigma))
         g[cg] = sp[cg].live ? (a.dod ? a.dod[sp[cg].ray] : 1.f) * a.gpart[m[cg]] : 0.f;      // (dod null: gpart holds the finished dL/draw)
       } else if (a.mode == 0) {
@@ -836,6 +839,9 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
         if (hh == 0 && sp[cg].live) {
           if (a.sigma) a.sigma[(int64_t)sp[cg].ray * a.n_samples + sp[cg].s] = sig;
           if (a.tau) a.tau[(int64_t)sp[cg].ray * a.n_samples + sp[cg].s] = tau;
+          if constexpr (P1 && !ENC) {      // (single-evaluation grid step: the composite kernel decides visibility from this and raw; uniform branch)
+            if (a.row_tau) a.row_tau[n[cg]] = tau;
+          }
         }
         if (!BWD || P1) {
           float od = tau;

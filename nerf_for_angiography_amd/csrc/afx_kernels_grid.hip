@@ -255,6 +255,43 @@ __global__ void __launch_bounds__(256) k_march_write(const MarchArgs a, const in
 // attenuating T; the ray stops once T < early_stop_eps.  keep[i] in {0,1}; counts[r] = kept steps of ray r.
 // The 64 lanes form the alphas of 64 samples at once (the transcendental part); the transmittance product then runs over them IN ORDER
 // (wave-uniform loop of lane broadcasts: the same multiplications in the same order as a sequential march, so the kept set is the same bit for bit).
+// alpha_fn's expression for one candidate (nerf_helpers_acc.py:19-23) - shared by k_march_visibility and the single-evaluation composite kernel,
+// so both decide the kept set from the same bits
+__device__ __forceinline__ float march_alpha(float raw, float ts, float te) {
+  const float sg = 1.f / (1.f + expf(-raw));
+  return 1.f - expf(-__fmul_rn(sg, __fsub_rn(te, ts)));
+}
+// One 64-sample chunk of render_visibility, one wavefront (`valid`: the lane holds a sample; `sfw`: the wave's 64 floats of LDS).  Returns whether
+// the lane's sample is kept and advances the transmittance T (wave-uniform) past the chunk.
+// The transmittance in front of each of the 64 samples, IN ORDER and branch-free.  A thin (or absent) sample multiplies by exactly 1, so lane j's
+// p = ((T f_0) f_1) ... f_(j-1) is the sequential march's value bit for bit: every lane runs the same 64 multiplications on factors that come
+// back from LDS as broadcast reads (all issued up front), with f_k replaced by 1 in the lanes <= k.  Sample j is kept iff it is thick and p has
+// not fallen below early_stop_eps (T never grows, so the products behind the stop - which a sequential march does not form - cannot bring a
+// sample back).  Replaces a loop with two branches and a ds_bpermute per sample, on which the kernel was latency-bound.
+__device__ __forceinline__ bool vis_chunk(float alpha, bool valid, float early_stop_eps, float alpha_thre, float& T, float* sfw, int lane) {
+  const bool thick = valid && !(alpha < alpha_thre);
+  bool mine = false;
+  if (!(T < early_stop_eps)) {                   // (wave-uniform)
+    const float f = thick ? 1.f - alpha : 1.f;
+    sfw[lane] = f;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (one wave: its LDS operations complete in order; the fence is for the compiler)
+    float fk[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) fk[k] = sfw[k];
+    float p = T;
+#pragma unroll
+    for (int k = 0; k < 64; ++k) p = __fmul_rn(p, k < lane ? fk[k] : 1.f);
+    mine = thick && !(p < early_stop_eps);
+    T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, __fmul_rn(p, f)), 63));
+    asm volatile("" ::: "memory");               // (the next chunk overwrites the factors behind these reads)
+  }
+  return mine;
+}
+// alpha of the candidates from the raw MLP output: 1 - exp(-sigmoid(raw) * (t_e - t_s))  (alpha_fn, nerf_helpers_acc.py:19-23),
+// then nerfacc's render_visibility per ray over its packed segment: steps with alpha < alpha_thre are skipped WITHOUT
+// attenuating T; the ray stops once T < early_stop_eps.  keep[i] in {0,1}; counts[r] = kept steps of ray r.
+// The 64 lanes form the alphas of 64 samples at once (the transcendental part); the transmittance product then runs over them IN ORDER
+// (vis_chunk: the same multiplications in the same order as a sequential march, so the kept set is the same bit for bit).
 __global__ void __launch_bounds__(256) k_march_visibility(const float* raw, int is_alpha, const float* t_starts, const float* t_ends, const int64_t* offsets, int64_t n_rays,
                                                           float early_stop_eps, float alpha_thre, uint8_t* keep, int32_t* counts) {
   __shared__ float sf[4][64];
@@ -269,38 +306,71 @@ __global__ void __launch_bounds__(256) k_march_visibility(const float* raw, int 
     float alpha = 0.f;
     if (i < i1) {
       alpha = raw[i];           // is_alpha: the caller's alpha_fn output
-      if (!is_alpha) {
-        const float sg = 1.f / (1.f + expf(-alpha));
-        alpha = 1.f - expf(-__fmul_rn(sg, __fsub_rn(t_ends[i], t_starts[i])));
-      }
+      if (!is_alpha) alpha = march_alpha(alpha, t_starts[i], t_ends[i]);
     }
-    const bool thick = i < i1 && !(alpha < alpha_thre);
-    // The transmittance in front of each of the 64 samples, IN ORDER and branch-free.  A thin (or absent) sample multiplies by exactly 1, so lane j's
-    // p = ((T f_0) f_1) ... f_(j-1) is the sequential march's value bit for bit: every lane runs the same 64 multiplications on factors that come
-    // back from LDS as broadcast reads (all issued up front), with f_k replaced by 1 in the lanes <= k.  Sample j is kept iff it is thick and p has
-    // not fallen below early_stop_eps (T never grows, so the products behind the stop - which a sequential march does not form - cannot bring a
-    // sample back).  Replaces a loop with two branches and a ds_bpermute per sample, on which the kernel was latency-bound.
-    bool mine = false;
-    if (!(T < early_stop_eps)) {                   // (wave-uniform)
-      const float f = thick ? 1.f - alpha : 1.f;
-      const int w = threadIdx.x >> 6;
-      sf[w][lane] = f;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (one wave: its LDS operations complete in order; the fence is for the compiler)
-      float fk[64];
-#pragma unroll
-      for (int k = 0; k < 64; ++k) fk[k] = sf[w][k];
-      float p = T;
-#pragma unroll
-      for (int k = 0; k < 64; ++k) p = __fmul_rn(p, k < lane ? fk[k] : 1.f);
-      mine = thick && !(p < early_stop_eps);
-      T = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, __fmul_rn(p, f)), 63));
-      asm volatile("" ::: "memory");               // (the next chunk overwrites the factors behind these reads)
-    }
+    const bool mine = vis_chunk(alpha, i < i1, early_stop_eps, alpha_thre, T, sf[threadIdx.x >> 6], lane);
     if (i < i1) keep[i] = mine ? 1 : 0;
     c += __popcll(__ballot(mine));
   }
   if (lane == 0) counts[r] = c;
 }
+
+// Single-evaluation grid step (afx_march_train_step_mse_single_eval): visibility, optical depth, MSE and the finished dL/draw per ray, from the
+// outputs of the packed step's forward half run over the CANDIDATES (candidate i of ray r sits at padded row 32 goff[r] + i - offsets[r]).
+//  - the kept set: k_march_visibility's arithmetic (march_alpha, vis_chunk) on the forward half's own raw output;
+//  - the optical depth: tau of the kept samples summed as the compacted list of afx_march_train_step_mse sums it - 32-sample groups of consecutive
+//    kept samples, each reduced by the forward half's 16/8/4/2/1 butterfly (lane 0's value; padding slots add 0), the group partials added in
+//    order as k_finish_mse_packed does - so pixel and dL/d(optical depth) are those of the two-evaluation step bit for bit;
+//  - gpart[row] (PHASE 1 left g' = dt sigma (1 - sigma)): dod g' for kept rows (PHASE 2's product), 0 for dropped ones (padding rows are 0 already).
+// Writes keep[i], kept_counts[r] and the ray's pixel into pix[r]; k_single_eval_finish publishes the pixels once the kept total is known.
+// One wavefront per ray; `stg` stages the tau of kept samples until a group of 32 is complete.
+__global__ void __launch_bounds__(256) k_single_eval_composite(const float* row_raw, const float* row_tau, const float* t_starts, const float* t_ends,
+                                                               const int64_t* offsets, const int64_t* goff, int64_t n_rays, float early_stop_eps,
+                                                               float alpha_thre, const float* target, float inv_n, uint8_t* keep, float* gpart,
+                                                               int32_t* kept_counts, float* pix) {
+  __shared__ float sf[4][64];
+  __shared__ float stg[4][96];
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (r >= n_rays) return;
+  const int64_t i0 = offsets[r], i1 = offsets[r + 1], row0 = goff[r] * GROUP - i0;      // padded row of candidate i: row0 + i
+  float* st = stg[w];
+  auto group_sum = [&](int cnt) {      // the butterfly of the forward half over slots 0 .. cnt-1 (cnt <= 32) of the stage; lane 0's value
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    float v = lane < cnt ? st[lane] : 0.f;
+#pragma unroll
+    for (int sh = 16; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
+  };
+  float T = 1.f, od = 0.f;
+  int c = 0, ns = 0;      // kept samples of the ray, staged ones (< 32 between chunks)
+  for (int64_t b = i0; b < i1; b += 64) {
+    const int64_t i = b + lane;
+    const bool valid = i < i1;
+    const float alpha = valid ? march_alpha(row_raw[row0 + i], t_starts[i], t_ends[i]) : 0.f;
+    const bool mine = vis_chunk(alpha, valid, early_stop_eps, alpha_thre, T, sf[w], lane);
+    const uint64_t bal = __ballot(mine);
+    if (valid) keep[i] = mine ? 1 : 0;
+    if (mine) st[ns + lane_prefix(bal)] = row_tau[row0 + i];
+    else if (valid) gpart[row0 + i] = 0.f;
+    ns += __popcll(bal);
+    c += __popcll(bal);
+    while (ns >= 32) {
+      od += group_sum(32);
+      const float x = lane < ns - 32 ? st[32 + lane] : 0.f;      // shift the rest of the stage down (reads complete before the writes)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (lane < ns - 32) st[lane] = x;
+      ns -= 32;
+    }
+  }
+  if (ns > 0) od += group_sum(ns);
+  const float T_ = expf(-od);      // k_finish_mse_packed
+  const float dod = -T_ * (2.f * (T_ - target[r]) * inv_n);
+  for (int64_t i = i0 + lane; i < i1; i += 64)
+    if (keep[i]) gpart[row0 + i] = dod * gpart[row0 + i];
+  if (lane == 0) { kept_counts[r] = c; pix[r] = T_; }
+}
+
 // counts[R] -> offsets[R+1] (exclusive prefix sums, int64), optionally the offsets of the group-aligned copy (ceil(count / 32) groups per
 // ray) and the two totals in one place for the host's single read.  One block: R is a batch of rays (5 625 in the reference), and the
 // torch sequence this replaces (zeros, cumsum = 2 rocprim launches, for the groups another 4) was a quarter of the launches of the
@@ -359,11 +429,8 @@ __global__ void __launch_bounds__(1024) k_ray_offsets(const int32_t* counts, int
 // groups), the optimizer's skip flag (1.0 when nothing survived the march) and the size block the capacity launches of the packed step read
 // (SZ_* slots) - the formulas run_backward applies on the host for one chunk of `tile`-sample tiles, so the weight-gradient sums run in the
 // same order as in afx_march_train_step_mse.  One thread.
-__global__ void k_grid_step_sizes(const int64_t* totals, int tile, int splits0, int max_splits, int max_small, int64_t* counts, float* skip, int64_t* dsz) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const int64_t n = totals[0], kept = totals[2], ng = totals[3];
-  counts[0] = n; counts[1] = kept; counts[2] = ng;
-  *skip = kept == 0 ? 1.f : 0.f;
+// (the formulas of one chunk of `tile`-sample tiles holding ng groups, as run_backward applies them on the host)
+__device__ __forceinline__ void grid_step_sizes(int64_t ng, int tile, int splits0, int max_splits, int max_small, int64_t* dsz) {
   const int64_t n_total = ng * GROUP, rows = (n_total + tile - 1) / tile * tile;
   int64_t splits = splits0;
   if (splits > rows / 256) splits = rows / 256;
@@ -375,6 +442,32 @@ __global__ void k_grid_step_sizes(const int64_t* totals, int tile, int splits0, 
   if (n_small < 64) n_small = 64;
   if (n_small > max_small) n_small = max_small;
   dsz[SZ_NTOTAL] = n_total; dsz[SZ_ROWS] = rows; dsz[SZ_SPLITS] = splits; dsz[SZ_RPS] = rps; dsz[SZ_SMALL] = n_small; dsz[SZ_GROUPS] = ng;
+}
+__global__ void k_grid_step_sizes(const int64_t* totals, int tile, int splits0, int max_splits, int max_small, int64_t* counts, float* skip, int64_t* dsz) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int64_t n = totals[0], kept = totals[2], ng = totals[3];
+  counts[0] = n; counts[1] = kept; counts[2] = ng;
+  *skip = kept == 0 ? 1.f : 0.f;
+  grid_step_sizes(ng, tile, splits0, max_splits, max_small, dsz);
+}
+// The single-evaluation step's size block: the step runs over the candidates' groups (totals[1], afx_ray_offsets over the march's counts).  One thread.
+__global__ void k_single_eval_sizes(const int64_t* totals, int tile, int splits0, int max_splits, int max_small, int64_t* dsz) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  grid_step_sizes(totals[1], tile, splits0, max_splits, max_small, dsz);
+}
+// ... and its end: totals[2] / totals[3] = kept samples and the groups the compacted list would have (afx_ray_offsets over kept_counts).  The
+// caller's counters and skip flag; when nothing was kept the pixels stay untouched and the size block is cut to zero rows, so the backward half
+// and the weight-gradient kernels behind this one do nothing and leave the gradient untouched (k_reduce_all / k_reduce_coef); else pix -> pixel.
+__global__ void k_single_eval_finish(const int64_t* totals, const float* pix, int64_t n_rays, float* pixel, int64_t* counts, float* skip, int64_t* dsz) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t kept = totals[2];
+  if (r == 0) {
+    counts[0] = totals[0]; counts[1] = kept; counts[2] = totals[3];
+    *skip = kept == 0 ? 1.f : 0.f;
+    if (kept == 0) { dsz[SZ_NTOTAL] = 0; dsz[SZ_ROWS] = 0; }
+  }
+  if (kept == 0 || r >= n_rays) return;
+  pixel[r] = pix[r];
 }
 
 __global__ void __launch_bounds__(256) k_march_compact(const uint8_t* keep, const int64_t* offsets_in, const int64_t* offsets_out, int64_t n_rays,

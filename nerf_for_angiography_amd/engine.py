@@ -329,6 +329,13 @@ class Engine:
             raise AfxError(f"afx_march_train_workspace_bytes: {self._last_error()}")
         return nbytes
 
+    def march_single_eval_workspace_bytes(self, prec: str, n_rays: int, max_steps_per_ray: int) -> int:
+        """Workspace of afx_march_train_step_mse_single_eval: fixed by the ray count and the per-ray step bound, not by data."""
+        nbytes = int(self.lib.afx_march_single_eval_workspace_bytes(self.h, _lib.PREC[prec], int(n_rays), int(max_steps_per_ray)))
+        if nbytes < 0:
+            raise AfxError(f"afx_march_single_eval_workspace_bytes: {self._last_error()}")
+        return nbytes
+
     def march_train_step_mse_capturable(self, prepared, origins, dirs, target, inv_n: float, grad_flat, prec: str, scene_aabb, near_plane,
                                         far_plane, step: float, early_stop_eps: float, alpha_thre: float, grid_bits=None, grid_aabb=None,
                                         grid_res=None, pixel=None, counts=None, skip=None):
@@ -337,19 +344,36 @@ class Engine:
         ray occupied); a capture never grows it (size it with one eager call first).  Writes pixel [n_rays] (float32), counts [3] (int64:
         candidates, kept samples, groups) and skip [1] (float32: 1.0 when nothing was kept - pixel / grad_flat untouched); pass them to
         reuse static buffers.  Returns (pixel, counts, skip), device tensors only."""
+        return self._march_step_device_sizes("afx_march_train_step_mse_capturable", "afx_march_train_workspace_bytes", prepared, origins, dirs,
+                                             target, inv_n, grad_flat, prec, scene_aabb, near_plane, far_plane, step, early_stop_eps, alpha_thre,
+                                             grid_bits, grid_aabb, grid_res, pixel, counts, skip)
+
+    def march_train_step_mse_single_eval(self, prepared, origins, dirs, target, inv_n: float, grad_flat, prec: str, scene_aabb, near_plane,
+                                         far_plane, step: float, early_stop_eps: float, alpha_thre: float, grid_bits=None, grid_aabb=None,
+                                         grid_res=None, pixel=None, counts=None, skip=None):
+        """afx_march_train_step_mse_single_eval: the grid iteration with ONE evaluation of the model - the training step's forward half over the
+        march's candidates doubles as the alpha pass.  Same arguments, buffers and results as march_train_step_mse_capturable (counts[2]: the
+        kept samples' groups); graph-capturable likewise.  f16s8, ReLU, no input encoding."""
+        return self._march_step_device_sizes("afx_march_train_step_mse_single_eval", "afx_march_single_eval_workspace_bytes", prepared, origins,
+                                             dirs, target, inv_n, grad_flat, prec, scene_aabb, near_plane, far_plane, step, early_stop_eps,
+                                             alpha_thre, grid_bits, grid_aabb, grid_res, pixel, counts, skip)
+
+    def _march_step_device_sizes(self, fn: str, ws_fn: str, prepared, origins, dirs, target, inv_n, grad_flat, prec, scene_aabb, near_plane,
+                                 far_plane, step, early_stop_eps, alpha_thre, grid_bits, grid_aabb, grid_res, pixel, counts, skip):
+        who = fn[4:]
         dev = prepared.device
         o, d, target = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(target, "target", dev)
         n_rays = o.shape[0]
         if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3) or target.numel() != n_rays:
-            raise ValueError("march_train_step_mse_capturable: origins/dirs [n_rays,3] and target [n_rays] expected")
+            raise ValueError(f"{who}: origins/dirs [n_rays,3] and target [n_rays] expected")
         if far_plane is None:
-            raise ValueError("march_train_step_mse_capturable: the workspace bound needs a far plane")
+            raise ValueError(f"{who}: the workspace bound needs a far plane")
         pixel = torch.empty(n_rays, dtype=torch.float32, device=dev) if pixel is None else pixel
         counts = torch.empty(3, dtype=torch.int64, device=dev) if counts is None else counts
         skip = torch.empty(1, dtype=torch.float32, device=dev) if skip is None else skip
         for t, dt, n, name in ((pixel, torch.float32, n_rays, "pixel"), (counts, torch.int64, 3, "counts"), (skip, torch.float32, 1, "skip")):
             if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
-                raise ValueError(f"march_train_step_mse_capturable: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+                raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
         a = _lib.MarchTrainArgs()
         _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
         a.early_stop_eps, a.alpha_thre, a.inv_n = float(early_stop_eps), float(alpha_thre), float(inv_n)
@@ -357,14 +381,15 @@ class Engine:
         max_steps = int(self.lib.afx_march_max_steps(C.byref(a.march)))
         if max_steps < 0:
             raise AfxError(f"afx_march_max_steps: {self._last_error()}")
-        need = self.march_train_workspace_bytes(prec, n_rays, max_steps)
-        if need > self.max_workspace_bytes:
-            raise AfxError(f"march_train_step_mse_capturable: {n_rays} rays x {max_steps} steps need a {need >> 20} MiB workspace "
+        nbytes = int(getattr(self.lib, ws_fn)(self.h, _lib.PREC[prec], int(n_rays), int(max_steps)))
+        if nbytes < 0:
+            raise AfxError(f"{ws_fn}: {self._last_error()}")
+        if nbytes > self.max_workspace_bytes:
+            raise AfxError(f"{who}: {n_rays} rays x {max_steps} steps need a {nbytes >> 20} MiB workspace "
                            f"(max_workspace_bytes = {self.max_workspace_bytes >> 20} MiB)")
-        ws = self._workspace(need, dev)
+        ws = self._workspace(nbytes, dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        self._check(self.lib.afx_march_train_step_mse_capturable(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), _ptr(counts), _ptr(skip),
-                                                                 self._stream(dev)), "afx_march_train_step_mse_capturable")
+        self._check(getattr(self.lib, fn)(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), _ptr(counts), _ptr(skip), self._stream(dev)), fn)
         return pixel, counts, skip
 
     def hier_train_step_mse(self, prepared, spec: RenderSpec, n_fine: int, u, target, inv_n: float, grad_flat, prec: str, want_z_all=True):

@@ -13,6 +13,8 @@ kernels, nerf/occupancy.py), then positions / get_predictions / acc_render_volum
 over the march's packed samples, march included, in one library call (`march_train_step_mse`; f16s8); `grid_ops` is the same body call for call through
 the mirrored functions (also what `grid` does at the other precisions).  `--graph` (with `grid`, f16s8) replays that iteration, Adam
 included, from a HIP graph captured once (`render.GridTrainGraph`): the sizes stay on the device and the host never waits for the GPU.
+`--single-eval` (with `grid`, f16s8, with or without `--graph`) evaluates the model once per iteration: the training step's forward half over
+the march's candidates doubles as the alpha pass.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -71,6 +73,9 @@ def build_parser():
                    help='--march grid --precision f16s8: capture the whole iteration (re-tiling, march, alpha pass, visibility, packed step, loss, '
                         'Adam) once into a HIP graph and replay it; sizes stay on the device and the host never waits for the GPU (the '
                         'occupancy-grid update every 16 iterations stays eager; counts and loss are read at the display cadence only)')
+    p.add_argument('--single-eval', dest='single_eval', action='store_true',
+                   help='--march grid --precision f16s8 --pos_enc none (with or without --graph): evaluate the model ONCE per iteration - the '
+                        'training step\'s forward half over the march\'s candidates doubles as the alpha pass (afx_march_train_step_mse_single_eval)')
     p.add_argument('--adam', default='fused', choices=['fused', 'foreach'], help="PyTorch Adam implementation (same update rule)")
     p.add_argument('--host_sampler', action='store_true', help="draw each batch with pandas on the host (the reference's sample_pixel_rays)")
     p.add_argument('--log_dir', default='runs/afx')
@@ -84,6 +89,9 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.single_eval and (args.march != 'grid' or args.precision != 'f16s8' or args.pos_enc != 'none'):
+        raise ValueError("--single-eval: needs --march grid --precision f16s8 --pos_enc none (the single-evaluation grid step is f16s8, ReLU, "
+                         "without an input encoding)")
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if device.type != "cuda":
         raise SystemExit("run_nerf_acc: needs an MI355X; there is no CPU fallback")
@@ -184,7 +192,7 @@ def main(argv=None):
     train_graph = None
     if args.graph:      # captured once; every iteration then copies its batch into the graph's static tensors and replays
         train_graph = GridTrainGraph(coarse_model, coarse_optimizer, acc_grid, scene_aabb, img_sample_size, depth_samples_per_ray_coarse, near_thresh,
-                                     far_thresh, early_stop_eps, alpha_thre)
+                                     far_thresh, early_stop_eps, alpha_thre, single_eval=args.single_eval)
         n_marched = torch.zeros((), dtype=torch.int64, device=device)
     t_last = time.time()
     for n_iter in range(n_iters + 1):
@@ -216,7 +224,7 @@ def main(argv=None):
                 # operator branch below, in the same order: ~30 launches that a Python loop issues slower than the GPU runs them)
                 loss_k, pred_k, n_kept = march_train_step_mse(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
                                                               depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps,
-                                                              alpha_thre, batch_pix_vals)
+                                                              alpha_thre, batch_pix_vals, single_eval=args.single_eval)
                 ray_indices = range(n_kept)      # (only its length is used below: the reference steps when the march kept samples)
                 if n_kept:
                     loss_coarse, pred = loss_k, pred_k

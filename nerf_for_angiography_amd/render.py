@@ -207,13 +207,18 @@ def train_step_packed_mse(model, ray_origins, ray_directions, packed, target: to
 
 
 def march_train_step_mse(model, grid, scene_aabb, ray_origins, ray_directions, depth_samples_per_ray: int, near_thresh: float, far_thresh: float,
-                         early_stop_eps: float, alpha_thre: float, target: torch.Tensor, n_global: Optional[int] = None):
+                         early_stop_eps: float, alpha_thre: float, target: torch.Tensor, n_global: Optional[int] = None, single_eval: bool = False):
     """The reference's whole grid iteration - acc_ray_marching (march through the occupancy grid, alpha_fn pass, render_visibility) followed by the
     body (positions, get_predictions, acc_render_volume_density, mse_loss, backward; nerf/run_nerf_acc.py:284-306) - as ONE library call
     (afx_march_train_step_mse): what `nerf_helpers_acc.acc_ray_marching(..., return_packed=True)` + `train_step_packed_mse` do, entry point for
     entry point and bit for bit, without a Python round trip per launch.  `grid`: nerf.occupancy.OccupancyGrid or None.  f16s8.
     Gradients are ACCUMULATED into `.grad`.  Returns (loss, pixels[n_rays], n_kept) - (None, None, 0) when no sample survived the march (the
-    reference then skips the optimizer step, :293)."""
+    reference then skips the optimizer step, :293).
+    `single_eval=True`: afx_march_train_step_mse_single_eval - ONE evaluation of the model (the training step's forward half over the
+    candidates doubles as the alpha pass); same pixels and loss where the two forward kernels agree (afx.h), ReLU, no input encoding.  The
+    counters are read back once, for the return value."""
+    if single_eval and model.use_pos_enc != "none":
+        raise NotImplementedError("march_train_step_mse(single_eval=True): no input encoding (pos_enc 'none')")
     _check_model(model)
     if model.precision != "f16s8":
         raise NotImplementedError("march_train_step_mse: precision 'f16s8' (other precisions: acc_ray_marching + the operator sequence)")
@@ -223,12 +228,20 @@ def march_train_step_mse(model, grid, scene_aabb, ray_origins, ray_directions, d
     flat_grad = torch.zeros(model.engine.param_count, dtype=torch.float32, device=model.flat_params.device)
     coef_grad = model._coef_grad_buffer()
     step = (float(far_thresh) - float(near_thresh)) / int(depth_samples_per_ray)
+    grid_kw = dict(grid_bits=None if grid is None else grid.bits, grid_aabb=None if grid is None else grid._aabb_host,
+                   grid_res=None if grid is None else grid._res_host)
+    aabb = None if scene_aabb is None else _aabb_on_host(scene_aabb)
     with model.engine.encoding_grad(model.flat_params, coef_grad):
-        pixel, _, n_kept = model.engine.march_train_step_mse(
-            model._prepared(), ray_origins, ray_directions, target, 1.0 / n, flat_grad, model.precision,
-            None if scene_aabb is None else _aabb_on_host(scene_aabb), near_thresh, far_thresh, step, early_stop_eps, alpha_thre,
-            grid_bits=None if grid is None else grid.bits, grid_aabb=None if grid is None else grid._aabb_host,
-            grid_res=None if grid is None else grid._res_host)
+        if single_eval:
+            pixel, counts, _ = model.engine.march_train_step_mse_single_eval(
+                model._prepared(), ray_origins, ray_directions, target, 1.0 / n, flat_grad, model.precision, aabb, near_thresh, far_thresh,
+                step, early_stop_eps, alpha_thre, **grid_kw)
+            model.engine.last_single_eval_counts = tuple(int(x) for x in counts.tolist())      # (candidates, kept, kept groups)
+            n_kept = model.engine.last_single_eval_counts[1]
+        else:
+            pixel, _, n_kept = model.engine.march_train_step_mse(
+                model._prepared(), ray_origins, ray_directions, target, 1.0 / n, flat_grad, model.precision, aabb, near_thresh, far_thresh,
+                step, early_stop_eps, alpha_thre, **grid_kw)
     if n_kept == 0:
         return None, None, 0
     if _grad_hook is not None:
@@ -354,10 +367,12 @@ class GridTrainGraph:
     PyTorch's fused Adam honours (parameters, moments and `step` unchanged); pixel and loss then hold the previous replay's values.
     Requires `Adam(fused=True, capturable=True)` (a tensor lr can be changed between replays with `fill_`).  The occupancy grid is read
     by address: update it in place between replays (`OccupancyGrid.update_every_n_steps`, `set_binary`), never rebind it.  After a
-    replay the module's cached prepared weights are marked stale, so eager renders re-tile the updated parameters."""
+    replay the module's cached prepared weights are marked stale, so eager renders re-tile the updated parameters.
+    `single_eval=True` captures afx_march_train_step_mse_single_eval instead (one evaluation of the model per iteration; ReLU, no input
+    encoding); everything else is the same."""
 
     def __init__(self, model, optimizer, grid, scene_aabb, n_rays: int, depth_samples_per_ray: int, near: float, far: float,
-                 early_stop_eps: float, alpha_thre: float, n_global: Optional[int] = None):
+                 early_stop_eps: float, alpha_thre: float, n_global: Optional[int] = None, single_eval: bool = False):
         if _grad_hook is not None and getattr(_grad_hook, "world", 1) > 1:
             raise AfxError("GridTrainGraph: a multi-rank gradient hook (dist.GradSync) is installed; the all-reduce cannot be captured - "
                            "use march_train_step_mse")
@@ -368,6 +383,9 @@ class GridTrainGraph:
             raise NotImplementedError("GridTrainGraph: precision 'f16s8' only")
         if model._coef_trainable():
             raise NotImplementedError("GridTrainGraph: trainable fourier coefficients are not captured; freeze them or use march_train_step_mse")
+        if single_eval and model.use_pos_enc != "none":
+            raise NotImplementedError("GridTrainGraph(single_eval=True): no input encoding (pos_enc 'none')")
+        self.single_eval = bool(single_eval)
         from .nerf.occupancy import _aabb_on_host
         self.model, self.optimizer, self.grid = model, optimizer, grid
         dev = model.flat_params.device
@@ -396,8 +414,9 @@ class GridTrainGraph:
         def body(with_optimizer):
             eng.prepare(model.flat_params, model._enc_aux(), model.precision)      # into the cached buffer (key None: always re-tiles)
             self.flat_grad.zero_()
-            eng.march_train_step_mse_capturable(self._buf, self.origins, self.dirs, self.target, inv_n, self.flat_grad, model.precision,
-                                                pixel=self.pixel, counts=self.counts, skip=self.skip, **march)
+            fn = eng.march_train_step_mse_single_eval if self.single_eval else eng.march_train_step_mse_capturable
+            fn(self._buf, self.origins, self.dirs, self.target, inv_n, self.flat_grad, model.precision, pixel=self.pixel, counts=self.counts,
+               skip=self.skip, **march)
             loss = (torch.nn.functional.mse_loss(self.pixel, self.target) if n == self.n_rays
                     else ((self.pixel - self.target) ** 2).sum() / n)      # (as march_train_step_mse forms it)
             if with_optimizer:

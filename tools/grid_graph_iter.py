@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""ms per grid training iteration (nerf/run_nerf_acc.py:284-306, with the Adam step) at the reference's 5 625 rays x 300 steps, three ways:
+"""ms per grid training iteration (nerf/run_nerf_acc.py:284-306, with the Adam step) at the reference's 5 625 rays x 300 steps, five ways:
   one      - render.march_train_step_mse (afx_march_train_step_mse: two polled size read-backs per iteration) + Adam(fused)
   capt     - afx_march_train_step_mse_capturable issued eagerly (re-tiling, step, loss, Adam(fused, capturable) with found_inf = skip)
   graph    - render.GridTrainGraph: the same iteration captured once and replayed
+  se       - afx_march_train_step_mse_single_eval issued eagerly like `capt` (one evaluation of the model per iteration)
+  se_graph - render.GridTrainGraph(single_eval=True)
 on a trained-like occupancy grid (cells within 4 units of a capsule vessel tree) and on a full grid, for 4x128 and 8x256.  Prints a
 markdown table (and writes it to the path given as the first argument).  usage: grid_graph_iter.py [out.md [iters]]"""
 import os, sys, time
@@ -48,6 +50,7 @@ def model(layers, width):
 def run(path, layers, width, grid):
     m = model(layers, width)
     kept = torch.zeros((), dtype=torch.int64, device=dev)
+    cand = torch.zeros((), dtype=torch.int64, device=dev)
     if path == "one":
         opt = torch.optim.Adam(m.parameters(), lr=1e-4, fused=True)
 
@@ -57,7 +60,7 @@ def run(path, layers, width, grid):
             kept.add_(k)
             if k:
                 opt.step()
-    elif path == "capt":
+    elif path in ("capt", "se"):
         opt = torch.optim.Adam(m.parameters(), lr=torch.tensor(1e-4, device=dev), fused=True, capturable=True)
         eng = m.engine
         flat_grad = torch.zeros(eng.param_count, device=dev)
@@ -70,28 +73,32 @@ def run(path, layers, width, grid):
         def it(o, d, t):
             prepared = eng.prepare(m.flat_params, None, "f16s8")
             flat_grad.zero_()
-            eng.march_train_step_mse_capturable(prepared, o, d, t, 1.0 / R, flat_grad, "f16s8", aabb, near, far, step, eps, thre, grid_bits=grid.bits,
-                                                grid_aabb=grid._aabb_host, grid_res=grid._res_host, pixel=pixel, counts=counts, skip=skip)
+            fn = eng.march_train_step_mse_capturable if path == "capt" else eng.march_train_step_mse_single_eval
+            fn(prepared, o, d, t, 1.0 / R, flat_grad, "f16s8", aabb, near, far, step, eps, thre, grid_bits=grid.bits, grid_aabb=grid._aabb_host,
+               grid_res=grid._res_host, pixel=pixel, counts=counts, skip=skip)
             torch.nn.functional.mse_loss(pixel, t)
             opt.step()
             kept.add_(counts[1])
+            cand.add_(counts[0])
     else:
         opt = torch.optim.Adam(m.parameters(), lr=torch.tensor(1e-4, device=dev), fused=True, capturable=True)
-        gtg = GridTrainGraph(m, opt, grid, aabb, R, S, near, far, eps, thre)
+        gtg = GridTrainGraph(m, opt, grid, aabb, R, S, near, far, eps, thre, single_eval=path == "se_graph")
 
         def it(o, d, t):
             _, _, counts = gtg.step(o, d, t)
             kept.add_(counts[1])
+            cand.add_(counts[0])
     for i in range(20):
         it(*batches[i % 16])
     kept.zero_()
+    cand.zero_()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(iters):
         it(*batches[i % 16])
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / iters * 1e3
-    return ms, int(kept) / iters
+    return ms, int(kept) / iters, int(cand) / iters
 
 
 rows = []
@@ -100,16 +107,19 @@ for layers, width in [(4, 128), (8, 256)]:
         grid = OccupancyGrid(roi_aabb=torch.tensor(aabb, device=dev), resolution=res).to(dev)
         grid._binary = mask
         occ = float(mask.float().mean()) * 100
-        res_ = {p: run(p, layers, width, grid) for p in ("one", "capt", "graph")}
+        res_ = {p: run(p, layers, width, grid) for p in ("one", "capt", "graph", "se", "se_graph")}
         rows.append((f"{layers}x{width}", f"{gname} ({occ:.2f} % of cells)", res_))
         print(rows[-1], flush=True)
-lines = ["| model | grid | kept samples / it | one call (ms) | capturable, eager (ms) | graph replay (ms) |", "|---|---|---|---|---|---|"]
+lines = ["| model | grid | candidates / it | kept samples / it | candidates : kept | one call (ms) | capturable, eager (ms) | graph replay (ms) "
+         "| single eval, eager (ms) | single eval, graph (ms) | single eval vs capturable |", "|---|---|---|---|---|---|---|---|---|---|---|"]
 for mdl, g, r in rows:
-    lines.append(f"| {mdl} | {g} | {r['one'][1]:.0f} | {r['one'][0]:.3f} | {r['capt'][0]:.3f} | {r['graph'][0]:.3f} |")
+    nc, nk = r['se'][2], r['se'][1]
+    lines.append(f"| {mdl} | {g} | {nc:.0f} | {nk:.0f} | {nc / max(nk, 1):.1f} | {r['one'][0]:.3f} | {r['capt'][0]:.3f} | {r['graph'][0]:.3f} | "
+                 f"{r['se'][0]:.3f} | {r['se_graph'][0]:.3f} | {(1 - r['se'][0] / r['capt'][0]) * 100:+.1f} % |")
 table = "\n".join(lines)
 print(table)
 if out_path:
     with open(out_path, "w") as f:
-        f.write(f"# Grid training iteration: one call vs capturable vs graph replay\n\n`python tools/grid_graph_iter.py <out.md> {iters}` on one MI355X: "
+        f.write(f"# Grid training iteration: one call vs capturable vs graph replay vs single evaluation\n\n`python tools/grid_graph_iter.py <out.md> {iters}` on one MI355X: "
                 f"{R} rays x {S} steps, Adam step included, {iters} timed iterations after 20 warm-up ones (wall time / iteration, the host "
                 "synchronised only at both ends).\n\n" + table + "\n")
