@@ -12,8 +12,8 @@
  *   - the CALLER owns every buffer (parameters, gradients, outputs, prepared
  *     weights, workspace).  The library allocates nothing on the device and
  *     holds only immutable descriptors => calls are hipGraph-capturable, with
- *     two exceptions: afx_march_train_step_mse reads two sizes back (it polls),
- *     and afx_profile_read synchronises.  The grid iteration's capturable form
+ *     three exceptions: afx_march_train_step_mse reads two sizes back (it polls),
+ *     afx_march_render reads one, and afx_profile_read synchronises.  The grid iteration's capturable form
  *     is afx_march_train_step_mse_capturable (or afx_march_train_step_mse_single_eval).
  *   - all other calls are asynchronous on the stream passed in.
  *   - results are deterministic: no floating-point atomics anywhere.
@@ -382,6 +382,42 @@ int afx_march_train_step_mse_capturable(afx_ctx* ctx, int prec, const void* prep
 int64_t afx_march_single_eval_workspace_bytes(const afx_ctx* ctx, int prec, int64_t n_rays, int64_t max_steps_per_ray);      /* -1: error */
 int afx_march_train_step_mse_single_eval(afx_ctx* ctx, int prec, const void* prepared, afx_march_train_args* args, int64_t* counts_dev,
                                          float* skip_dev, void* stream);
+
+/* Forward-only render through the occupancy grid with ONE evaluation of the model: the evaluation renders of the reference
+ * (nerf/run_nerf_acc.py:338-349 under the grid; visualization/visualization.py:335-352, with the binary image) - acc_ray_marching (march,
+ * alpha pass, render_visibility), get_predictions over the kept samples, acc_render_volume_density - without evaluating the kept samples
+ * a second time.  Inside: the march (afx_march_count, afx_ray_offsets, afx_march_write: candidates and their mid-points), afx_mlp_infer
+ * at the mid-points (any precision and activation it takes), then one per-ray kernel that decides the kept set with afx_march_visibility's
+ * arithmetic and multiplies exp(-sigmoid(raw) (t_e - t_s)) over the kept samples in order, as afx_composite_packed does.  Each sample's raw
+ * output is a function of its own point, so the pixels equal the operator sequence's bit for bit.
+ * Rays: ray_mode AFX_RAYS_ARRAYS - march.origins / march.dirs, march.n_rays rays; AFX_RAYS_POSE - generated in-kernel as afx_render_forward
+ * does without ray_ids (ray r = ray_id0 + r of [n_proj, height, width]; n_rays rays; march.origins / dirs / n_rays are ignored).
+ * grid_bits == NULL: every step inside the box / planes is a candidate.  Outputs: pixel [R] (required); binary_pixel [R] (optional: the
+ * same product with sigma forced to 0 where sigmoid(raw) < binary_thresh, visualization.py:349-352); kept_counts [R] (optional); on the
+ * host, n_candidates.  A ray without candidates gets 1.
+ * ONE host read-back per call (the candidate count: the host polls a mapped mailbox, or with AFX_MAILBOX=0 copies and synchronises, as
+ * afx_march_train_step_mse does), so the call is NOT graph-capturable.  Every buffer is carved for the worst case before the first launch:
+ * every step of every ray a candidate, afx_march_max_steps(&march) steps (the march needs a far plane); the workspace must hold
+ * afx_march_render_workspace_bytes(ray_mode, R, that bound) bytes, else AFX_E_WORKSPACE with workspace_needed set and nothing the caller owns
+ * written.  A worst case beyond afx_mlp_infer's 2^31 - 256 points per call is refused with AFX_E_INVALID: split the rays. */
+typedef struct afx_march_render_args {
+  afx_march_args march;             /* scene box, planes, step, occupancy bits; the rays in AFX_RAYS_ARRAYS mode */
+  int32_t ray_mode;                 /* AFX_RAYS_ARRAYS or AFX_RAYS_POSE */
+  const double* poses;              /* [n_proj,3,4] row-major cam->world, device (AFX_RAYS_POSE) */
+  int32_t width, height;
+  double focal;
+  int64_t ray_id0, n_rays;          /* AFX_RAYS_POSE */
+  float early_stop_eps, alpha_thre; /* render_visibility thresholds */
+  float* pixel;                     /* out [R] */
+  float* binary_pixel;              /* optional out [R] */
+  float binary_thresh;
+  int32_t* kept_counts;             /* optional out [R] */
+  void* workspace; size_t workspace_bytes;
+  int64_t n_candidates;             /* out */
+  size_t workspace_needed;          /* out, with AFX_E_WORKSPACE */
+} afx_march_render_args;
+int64_t afx_march_render_workspace_bytes(int32_t ray_mode, int64_t n_rays, int64_t max_steps_per_ray);      /* -1: error */
+int afx_march_render(afx_ctx* ctx, int prec, const void* prepared, afx_march_render_args* args, void* stream);
 
 /* Indices of the k largest of keys[n] (ties: lowest index first), written in ASCENDING INDEX order - the selection step of the
  * weighted ray sampler (the batch of nerf/nerf_helpers.py:137-150 is a set; its order carries no meaning).  Radix select:

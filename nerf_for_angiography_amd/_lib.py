@@ -48,6 +48,13 @@ class MarchTrainArgs(C.Structure):
                 ("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("n_groups", C.c_int64), ("workspace_needed", C.c_size_t)]
 
 
+class MarchRenderArgs(C.Structure):
+    _fields_ = [("march", MarchArgs), ("ray_mode", C.c_int32), ("poses", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("focal", C.c_double), ("ray_id0", C.c_int64), ("n_rays", C.c_int64), ("early_stop_eps", C.c_float), ("alpha_thre", C.c_float),
+                ("pixel", C.c_void_p), ("binary_pixel", C.c_void_p), ("binary_thresh", C.c_float), ("kept_counts", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("n_candidates", C.c_int64), ("workspace_needed", C.c_size_t)]
+
+
 _SIGS = {
     "afx_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
     "afx_destroy": (None, [C.c_void_p]),
@@ -107,6 +114,8 @@ _SIGS = {
     "afx_march_single_eval_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64, C.c_int64]),
     "afx_march_train_step_mse_single_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MarchTrainArgs), C.c_void_p, C.c_void_p,
                                                        C.c_void_p]),
+    "afx_march_render_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int64, C.c_int64]),
+    "afx_march_render": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(MarchRenderArgs), C.c_void_p]),
     "afx_ray_offsets": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_march_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

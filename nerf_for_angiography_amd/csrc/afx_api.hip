@@ -1363,6 +1363,41 @@ extern "C" int afx_philox_uniform(uint64_t seed, uint64_t stream_id, int64_t n, 
   return AFX_OK;
 }
 
+// ---- the host read-back of an offsets kernel's two totals (afx_march_train_step_mse, afx_march_render): k_ray_offsets posts them and a sequence
+// tag to host-mapped memory and the host polls the tag (AFX_MAILBOX=0: a 16-byte copy + stream synchronisation behind the kernel instead - 27 us
+// per read-back slower, tools/grid_iter.py).  `slot` 0 or 1: the mailbox's two 4-word slots.  totals_dev: 2 device words; h: the totals, on the host.
+static int offsets_read_back(afx_ctx* c, const int32_t* cnt, int64_t R, int64_t* offs, int64_t* goffs, int64_t* totals_dev, int slot, int64_t* h,
+                             void* stream, const char* who) {
+  hipStream_t st = (hipStream_t)stream;
+  static const bool use_mailbox = !(getenv("AFX_MAILBOX") && atoi(getenv("AFX_MAILBOX")) == 0);
+  if (use_mailbox && !c->mailbox) {
+    if (hipHostMalloc((void**)&c->mailbox, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->mailbox_dev, c->mailbox, 0) != hipSuccess) {
+      if (c->mailbox) (void)hipHostFree(c->mailbox);
+      c->mailbox = c->mailbox_dev = nullptr;
+    } else for (int i = 0; i < 8; ++i) c->mailbox[i] = 0;
+  }
+  if (!(use_mailbox && c->mailbox)) {
+    if (int r = afx_ray_offsets(cnt, R, offs, goffs, totals_dev, stream)) return r;
+    HIPCHK(hipMemcpyAsync(h, totals_dev, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return AFX_OK;
+  }
+  const int64_t tag = ++c->mail_seq;
+  hipLaunchKernelGGL(k_ray_offsets, dim3(1), dim3(1024), 0, st, cnt, R, offs, goffs, totals_dev, (volatile int64_t*)(c->mailbox_dev + 4 * slot), tag);
+  HIPCHK(hipGetLastError());
+  volatile int64_t* mb = c->mailbox + 4 * slot;
+  for (uint64_t spins = 0; mb[2] != tag; ++spins) {
+    if ((spins & 0xfffff) == 0xfffff && hipStreamQuery(st) != hipErrorNotReady) {      // the stream has drained (or failed): one last look
+      HIPCHK(hipStreamSynchronize(st));
+      if (mb[2] != tag) return fail(AFX_E_HIP, "%s: the offsets kernel never posted its totals", who);
+      break;
+    }
+    __builtin_ia32_pause();
+  }
+  h[0] = mb[0]; h[1] = mb[1];
+  return AFX_OK;
+}
+
 // ---- the reference's grid iteration in ONE call (nerf/run_nerf_acc.py:284-306): march -> alpha pass -> visibility -> packed training step.
 // The same entry points, in the same order, that the Python mirror calls one by one (occupancy.ray_marching, render.train_step_packed_mse) -
 // composed here because at the reference's batch the GPU work of an iteration is 0.27 ms and ~30 launches issued from Python are not.
@@ -1376,7 +1411,6 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
     return fail(AFX_E_INVALID, "afx_march_train_step_mse: null argument");
   if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "afx_march_train_step_mse: AFX_PREC_F16S8 only");
   if (int rc = check_dev(c, "afx_march_train_step_mse")) return rc;
-  hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)t->workspace;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
@@ -1392,38 +1426,10 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
   int64_t* offsets = (int64_t*)(ws + o_offsets);
   int64_t* totals = (int64_t*)(ws + o_totals);
   int rc;
-  // The two size read-backs: the offsets kernel posts its totals and a sequence tag to host-mapped memory and the host polls the tag
-  // (AFX_MAILBOX=0: a 16-byte copy + stream synchronisation behind the kernel instead - 27 us per read-back slower, tools/grid_iter.py).
-  static const bool use_mailbox = !(getenv("AFX_MAILBOX") && atoi(getenv("AFX_MAILBOX")) == 0);
-  if (use_mailbox && !c->mailbox) {
-    if (hipHostMalloc((void**)&c->mailbox, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->mailbox_dev, c->mailbox, 0) != hipSuccess) {
-      if (c->mailbox) (void)hipHostFree(c->mailbox);
-      c->mailbox = c->mailbox_dev = nullptr;
-    } else for (int i = 0; i < 8; ++i) c->mailbox[i] = 0;
-  }
-  const bool mail = use_mailbox && c->mailbox;
+  // The two size read-backs (offsets_read_back: a mapped mailbox the host polls)
   int64_t h[4] = {0, 0, 0, 0};
   auto read_totals = [&](const int32_t* cnt, int64_t* offs, int64_t* goffs, int slot) -> int {
-    if (!mail) {
-      if (int r = afx_ray_offsets(cnt, R, offs, goffs, totals + 2 * slot, stream)) return r;
-      HIPCHK(hipMemcpyAsync(h + 2 * slot, totals + 2 * slot, 16, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      return AFX_OK;
-    }
-    const int64_t tag = ++c->mail_seq;
-    hipLaunchKernelGGL(k_ray_offsets, dim3(1), dim3(1024), 0, st, cnt, R, offs, goffs, totals + 2 * slot, (volatile int64_t*)(c->mailbox_dev + 4 * slot), tag);
-    HIPCHK(hipGetLastError());
-    volatile int64_t* mb = c->mailbox + 4 * slot;
-    for (uint64_t spins = 0; mb[2] != tag; ++spins) {
-      if ((spins & 0xfffff) == 0xfffff && hipStreamQuery(st) != hipErrorNotReady) {      // the stream has drained (or failed): one last look
-        HIPCHK(hipStreamSynchronize(st));
-        if (mb[2] != tag) return fail(AFX_E_HIP, "afx_march_train_step_mse: the offsets kernel never posted its totals");
-        break;
-      }
-      __builtin_ia32_pause();
-    }
-    h[2 * slot] = mb[0]; h[2 * slot + 1] = mb[1];
-    return AFX_OK;
+    return offsets_read_back(c, cnt, R, offs, goffs, totals + 2 * slot, slot, h + 2 * slot, stream, "afx_march_train_step_mse");
   };
   if ((rc = afx_march_count(&m, counts, stream))) return rc;
   if ((rc = read_totals(counts, offsets, nullptr, 0))) return rc;      // (sizes are data: the candidate count)
@@ -1733,4 +1739,101 @@ extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const 
   rd.gmax = gmax; rd.scale_shift = AFX_S8_JSHIFT; rd.layer0_mfma = 0; rd.w0 = nullptr; rd.d_coef = nullptr; rd.coef_cols = 0;
   rd.dsz = dsz;
   return F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, st) : launch_wgrad8_t<256>(c, w, rd, N, st));
+}
+
+// ---- forward-only render through the occupancy grid with ONE evaluation of the model (afx_march_render): march (candidates, mid-points), one
+// afx_mlp_infer over the candidates, k_march_render_composite (kept set, pixel, binary pixel per ray).  One host read-back: the candidate count.
+// Every buffer is carved for the worst case (every step of every ray a candidate, afx_march_max_steps) before the first launch.
+struct RenderLayout {
+  size_t o_org, o_dir, o_counts, o_offsets, o_totals, o_ts, o_te, o_pts, o_raw;
+  size_t total;
+  int64_t n_cap;
+};
+static int render_layout(int32_t ray_mode, int64_t R, int64_t S, RenderLayout& L, const char* who) {
+  if (ray_mode != AFX_RAYS_ARRAYS && ray_mode != AFX_RAYS_POSE) return fail(AFX_E_INVALID, "%s: bad ray_mode %d", who, ray_mode);
+  if (R < 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays >= 0 and max_steps_per_ray >= 0", who);
+  if (R > ((int64_t)1 << 31) - 256 || (S > 0 && R > (((int64_t)1 << 31) - 256) / S))
+    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed afx_mlp_infer's 2^31 - 256 points per call; split the rays", who, (long long)R,
+                (long long)S);
+  L.n_cap = R * S;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
+  const size_t pose = ray_mode == AFX_RAYS_POSE ? (size_t)R * 12 : 0, n = (size_t)std::max<int64_t>(L.n_cap, 1);
+  L.o_org = take(pose); L.o_dir = take(pose);
+  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(2 * 8);
+  L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_pts = take(n * 12);
+  L.o_raw = take(n * 4);      // (also k_march_write's ray_indices, which the render does not need: afx_mlp_infer overwrites them)
+  L.total = off;
+  return AFX_OK;
+}
+
+extern "C" int64_t afx_march_render_workspace_bytes(int32_t ray_mode, int64_t n_rays, int64_t max_steps_per_ray) {
+  RenderLayout L;
+  if (render_layout(ray_mode, n_rays, max_steps_per_ray, L, "afx_march_render_workspace_bytes")) return -1;
+  return (int64_t)L.total;
+}
+
+extern "C" int afx_march_render(afx_ctx* c, int prec, const void* prepared, afx_march_render_args* t, void* stream) {
+  const char* who = "afx_march_render";
+  if (!c || !prepared || !t) return fail(AFX_E_INVALID, "%s: null argument", who);
+  t->n_candidates = 0; t->workspace_needed = 0;
+  if (check_prec(prec, who)) return AFX_E_INVALID;
+  const bool pose = t->ray_mode == AFX_RAYS_POSE;
+  if (t->ray_mode != AFX_RAYS_ARRAYS && !pose) return fail(AFX_E_INVALID, "%s: bad ray_mode %d", who, t->ray_mode);
+  afx_march_args m = t->march;
+  const int64_t R = pose ? t->n_rays : m.n_rays;
+  if (R < 0) return fail(AFX_E_INVALID, "%s: n_rays < 0", who);
+  if (R == 0) return AFX_OK;
+  if (!t->pixel || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument (pixel and workspace are required)", who);
+  if (pose) {
+    if (!t->poses || t->width <= 0 || t->height <= 0 || !(t->focal > 0) || t->ray_id0 < 0)
+      return fail(AFX_E_INVALID, "%s: pose mode needs poses, width, height, focal > 0 and ray_id0 >= 0", who);
+    m.origins = m.dirs = nullptr; m.n_rays = R;
+  } else if (!m.origins || !m.dirs) return fail(AFX_E_INVALID, "%s: null argument (origins/dirs required)", who);
+  if (!m.has_far) return fail(AFX_E_INVALID, "%s: the march needs a far plane (the worst-case workspace bound)", who);
+  MarchArgs a = {};
+  if (pose) m.origins = m.dirs = (const float*)t->workspace;      // (placeholders for fill_march's checks; set below)
+  if (int rc = fill_march(&m, a, who)) return rc;
+  const int64_t S = afx_march_max_steps(&m);
+  if (S < 0) return AFX_E_INVALID;
+  RenderLayout L;
+  if (int rc = render_layout(t->ray_mode, R, S, L, who)) return rc;
+  if (L.total > t->workspace_bytes) {
+    t->workspace_needed = L.total;
+    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_render_workspace_bytes)", who, t->workspace_bytes, L.total);
+  }
+  if (int rc = check_dev(c, who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)t->workspace;
+  int32_t* counts = (int32_t*)(ws + L.o_counts);
+  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals);
+  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *pts = (float*)(ws + L.o_pts), *raw = (float*)(ws + L.o_raw);
+  // 1. pose mode: the rays, as the dense fused kernels generate them
+  if (pose) {
+    ChainArgs ra = {};
+    ra.poses = t->poses; ra.ray_ids = nullptr; ra.ray_id0 = t->ray_id0; ra.width = t->width; ra.height = t->height; ra.focal = t->focal;
+    float *org = (float*)(ws + L.o_org), *dir = (float*)(ws + L.o_dir);
+    hipLaunchKernelGGL(k_pose_rays, blocks_for(R), dim3(256), 0, st, ra, R, org, dir);
+    HIPCHK(hipGetLastError());
+    a.org = org; a.dir = dir;
+  }
+  // 2. candidates: count, offsets (the one read-back), t_starts / t_ends / mid-points
+  hipLaunchKernelGGL(k_march_count, blocks_for(R, 4), dim3(256), 0, st, a, counts);
+  HIPCHK(hipGetLastError());
+  int64_t h[2] = {0, 0};
+  if (int rc = offsets_read_back(c, counts, R, offsets, nullptr, totals, 0, h, stream, who)) return rc;
+  const int64_t n = h[0];
+  if (n < 0 || n > L.n_cap) return fail(AFX_E_HIP, "%s: %lld candidates exceed the worst-case bound %lld", who, (long long)n, (long long)L.n_cap);
+  t->n_candidates = n;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_march_write, blocks_for(R, 4), dim3(256), 0, st, a, (const int64_t*)offsets, (int32_t*)raw, ts, te, pts);
+    HIPCHK(hipGetLastError());
+    // 3. the one evaluation of the model: raw output at every candidate's mid-point
+    if (int rc = afx_mlp_infer(c, prec, prepared, pts, n, raw, 0, stream)) return rc;
+  }
+  // 4. kept set, pixel, binary pixel, kept counts per ray (rays without candidates: 1)
+  hipLaunchKernelGGL(k_march_render_composite, blocks_for(R, 4), dim3(256), 0, st, (const float*)raw, (const float*)ts, (const float*)te,
+                     (const int64_t*)offsets, R, t->early_stop_eps, t->alpha_thre, t->binary_thresh, t->pixel, t->binary_pixel, t->kept_counts);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
 }

@@ -315,6 +315,75 @@ __global__ void __launch_bounds__(256) k_march_visibility(const float* raw, int 
   if (lane == 0) counts[r] = c;
 }
 
+// Forward-only grid render (afx_march_render): visibility and compositing per ray from the ONE raw output of the candidates, i.e. what
+// afx_march_visibility -> afx_march_compact -> get_predictions over the kept samples -> afx_composite_packed gives, without the second evaluation.
+//  - the kept set: k_march_visibility's arithmetic (march_alpha, vis_chunk), bit for bit;
+//  - pixel = prod exp(-sigmoid(raw) (t_e - t_s)) over the kept samples IN ORDER, k_composite_packed's expressions.  A dropped sample (and an
+//    absent lane) contributes a factor of exactly 1, which leaves the product unchanged, so the 64 factors of a chunk are multiplied in lane order
+//    from an LDS broadcast, every lane forming the same product: the sequence of multiplications of k_composite_packed's loop, bit for bit;
+//  - binary_pixel (optional): the same product with factor 1 also for kept samples whose sigmoid(raw) < binary_thresh (the zero_idx of the
+//    reference's binary render, visualization/visualization.py:349-352: sigma forced to 0 gives exp(-0) = 1);
+//  - kept_counts (optional): kept samples per ray.  A ray without candidates gets 1 in both pixels.
+// One wavefront per ray; reads stay inside the ray's segment [offsets[r], offsets[r + 1]).
+__global__ void __launch_bounds__(256) k_march_render_composite(const float* raw, const float* t_starts, const float* t_ends, const int64_t* offsets,
+                                                                int64_t n_rays, float early_stop_eps, float alpha_thre, float binary_thresh,
+                                                                float* pixel, float* binary_pixel, int32_t* kept_counts) {
+  __shared__ float sf[4][64];      // vis_chunk's transmittance factors
+  __shared__ float sp[4][64];      // the chunk's pixel factors
+  __shared__ float sb[4][64];      // ... and binary-pixel factors
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (r >= n_rays) return;
+  const int64_t i0 = offsets[r], i1 = offsets[r + 1];
+  const bool want_binary = binary_pixel != nullptr;
+  float T = 1.f, P = 1.f, B = 1.f;
+  int c = 0;
+  for (int64_t b = i0; b < i1; b += 64) {
+    const int64_t i = b + lane;
+    const bool valid = i < i1;
+    float alpha = 0.f, sg = 0.f, e = 1.f;
+    if (valid) {
+      const float x = raw[i], ts = t_starts[i], te = t_ends[i];
+      alpha = march_alpha(x, ts, te);
+      sg = sigmoidf_(x);                                   // k_composite_packed's expressions
+      e = expf(-__fmul_rn(sg, __fsub_rn(te, ts)));
+    }
+    const bool mine = vis_chunk(alpha, valid, early_stop_eps, alpha_thre, T, sf[w], lane);
+    c += __popcll(__ballot(mine));
+    sp[w][lane] = mine ? e : 1.f;
+    if (want_binary) sb[w][lane] = (mine && !(sg < binary_thresh)) ? e : 1.f;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (one wave: its LDS operations complete in order; the fence is for the compiler)
+    float fk[64];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) fk[k] = sp[w][k];
+#pragma unroll
+    for (int k = 0; k < 64; ++k) P = __fmul_rn(P, fk[k]);
+    if (want_binary) {
+#pragma unroll
+      for (int k = 0; k < 64; ++k) fk[k] = sb[w][k];
+#pragma unroll
+      for (int k = 0; k < 64; ++k) B = __fmul_rn(B, fk[k]);
+    }
+    asm volatile("" ::: "memory");               // (the next chunk overwrites the factors behind these reads)
+  }
+  if (lane == 0) {
+    pixel[r] = P;
+    if (want_binary) binary_pixel[r] = B;
+    if (kept_counts) kept_counts[r] = c;
+  }
+}
+
+// Rays of afx_march_render's pose mode, written to its workspace: load_ray (the dense fused kernels' get_ray_values, ray r = ray_id0 + r of
+// [n_proj, H, W]), so the march sees the rays those kernels generate, bit for bit.  One thread per ray.
+__global__ void k_pose_rays(const ChainArgs a, int64_t n_rays, float* org, float* dir) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays) return;
+  float ox, oy, oz, dx, dy, dz;
+  load_ray(a, (int)r, ox, oy, oz, dx, dy, dz);
+  org[3 * r + 0] = ox; org[3 * r + 1] = oy; org[3 * r + 2] = oz;
+  dir[3 * r + 0] = dx; dir[3 * r + 1] = dy; dir[3 * r + 2] = dz;
+}
+
 // Single-evaluation grid step (afx_march_train_step_mse_single_eval): visibility, optical depth, MSE and the finished dL/draw per ray, from the
 // outputs of the packed step's forward half run over the CANDIDATES (candidate i of ray r sits at padded row 32 goff[r] + i - offsets[r]).
 //  - the kept set: k_march_visibility's arithmetic (march_alpha, vis_chunk) on the forward half's own raw output;

@@ -392,6 +392,77 @@ class Engine:
         self._check(getattr(self.lib, fn)(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), _ptr(counts), _ptr(skip), self._stream(dev)), fn)
         return pixel, counts, skip
 
+    def march_render(self, prepared, prec: str, scene_aabb, near_plane, far_plane, step: float, early_stop_eps: float, alpha_thre: float,
+                     origins=None, dirs=None, poses=None, width: int = 0, height: int = 0, focal: float = 0.0, ray_id0: int = 0, n_rays=None,
+                     grid_bits=None, grid_aabb=None, grid_res=None, binary_thresh=None):
+        """afx_march_render: forward-only render through the occupancy grid with one evaluation of the model (march, afx_mlp_infer over the
+        candidates, visibility and compositing per ray).  Rays: origins / dirs [R,3], or poses [n_proj,3,4] float64 + width / height / focal
+        (ray r = ray_id0 + r of [n_proj, H, W]; n_rays defaults to the rest of the table).  The rays are split into calls whose worst case
+        (every step of every ray a candidate) fits max_workspace_bytes and afx_mlp_infer's 2^31 - 256 points; each ray's result depends on
+        that ray alone, so the split changes nothing.  One host read-back per call.
+        Returns (pixel [R], binary_pixel [R] or None, kept_counts int32 [R], n_candidates)."""
+        dev = prepared.device
+        pose = poses is not None
+        if pose:
+            if poses.device != dev or poses.dtype != torch.float64:
+                raise ValueError(f"march_render: poses must be float64 on {dev}")
+            poses = poses[:, :3, :].contiguous()
+            if n_rays is None:
+                n_rays = poses.shape[0] * int(width) * int(height) - int(ray_id0)
+            if int(ray_id0) < 0 or int(ray_id0) + int(n_rays) > poses.shape[0] * int(width) * int(height):
+                raise ValueError(f"march_render: rays {ray_id0} .. {int(ray_id0) + int(n_rays)} outside the {poses.shape[0]} x {height} x {width} table")
+            o = d = None
+        else:
+            o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
+            n_rays = o.shape[0]
+            if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3):
+                raise ValueError("march_render: origins/dirs [n_rays,3] expected")
+        n_rays = int(n_rays)
+        if far_plane is None:
+            raise ValueError("march_render: the workspace bound needs a far plane")
+        a = _lib.MarchRenderArgs()
+        _fill_march_args(a.march, None, None, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+        mode = _lib.RAYS_POSE if pose else _lib.RAYS_ARRAYS
+        a.ray_mode = mode
+        if pose:
+            a.poses, a.width, a.height, a.focal = poses.data_ptr(), int(width), int(height), float(focal)
+        a.early_stop_eps, a.alpha_thre = float(early_stop_eps), float(alpha_thre)
+        a.binary_thresh = float(binary_thresh) if binary_thresh is not None else 0.0
+        pixel = torch.empty(n_rays, dtype=torch.float32, device=dev)
+        binary = torch.empty(n_rays, dtype=torch.float32, device=dev) if binary_thresh is not None else None
+        kept = torch.empty(n_rays, dtype=torch.int32, device=dev)
+        if n_rays == 0:
+            return pixel, binary, kept, 0
+        max_steps = int(self.lib.afx_march_max_steps(C.byref(a.march)))
+        if max_steps < 0:
+            raise AfxError(f"afx_march_max_steps: {self._last_error()}")
+
+        def ws_bytes(r):
+            nb = int(self.lib.afx_march_render_workspace_bytes(mode, int(r), max_steps))
+            if nb < 0:
+                raise AfxError(f"afx_march_render_workspace_bytes: {self._last_error()}")
+            return nb
+        chunk = min(n_rays, ((1 << 31) - 256) // max(max_steps, 1))
+        while ws_bytes(chunk) > self.max_workspace_bytes:
+            if chunk == 1:
+                raise AfxError(f"march_render: one ray of {max_steps} steps needs a {ws_bytes(1) >> 20} MiB workspace (max_workspace_bytes = "
+                               f"{self.max_workspace_bytes >> 20} MiB)")
+            chunk = max(1, min(chunk - 1, chunk * self.max_workspace_bytes // ws_bytes(chunk)))
+        ws = self._workspace(ws_bytes(chunk), dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        n_candidates = 0
+        for r0 in range(0, n_rays, chunk):
+            r1 = min(n_rays, r0 + chunk)
+            if pose:
+                a.ray_id0, a.n_rays = int(ray_id0) + r0, r1 - r0
+            else:
+                a.march.origins, a.march.dirs, a.march.n_rays = o[r0:r1].data_ptr(), d[r0:r1].data_ptr(), r1 - r0
+            a.pixel, a.kept_counts = pixel[r0:r1].data_ptr(), kept[r0:r1].data_ptr()
+            a.binary_pixel = binary[r0:r1].data_ptr() if binary is not None else None
+            self._check(self.lib.afx_march_render(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), self._stream(dev)), "afx_march_render")
+            n_candidates += int(a.n_candidates)
+        return pixel, binary, kept, n_candidates
+
     def hier_train_step_mse(self, prepared, spec: RenderSpec, n_fine: int, u, target, inv_n: float, grad_flat, prec: str, want_z_all=True):
         """afx_hier_train_step_mse: hierarchical step with coarse re-use; `spec` carries the rays and the COARSE depths (mode 'dense').
         Returns (pixels [R], merged depths [R, S + n_fine] | None)."""
@@ -634,7 +705,8 @@ def grid_pack(roi_aabb, resolution, binary_u8, bits):
 
 
 def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res):
-    m.origins, m.dirs, m.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
+    if o is not None:      # (None: the rays come from elsewhere - afx_march_render's pose mode)
+        m.origins, m.dirs, m.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
     if scene_aabb is not None:
         m.has_aabb = 1
         for i, v in enumerate([float(x) for x in scene_aabb]):

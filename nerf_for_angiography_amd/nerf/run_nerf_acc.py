@@ -36,7 +36,7 @@ from ..engine import RenderSpec
 from ..model.CPPN import CPPN
 from ..phantomdata import dataset as ds
 from .. import engine as _engine
-from ..render import render_rays, train_step_mse, march_train_step_mse, GridTrainGraph
+from ..render import render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph
 from .nerf_helpers import sample_pixel_rays, get_predictions
 from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
@@ -263,8 +263,13 @@ def main(argv=None):
         if n_iter % display_every == 0:
             coarse_model.eval()
             keep, coarse_model.precision = coarse_model.precision, args.eval_precision
+            eval_counts = None
             with torch.no_grad():
-                if args.march != 'dense':          # run_nerf_acc.py:338-349
+                if args.march == 'grid':           # run_nerf_acc.py:338-349 with ONE evaluation of the model: the alpha pass's raw output is
+                    # the one compositing uses - the operator sequence below (the `grid_ops` body) bit for bit
+                    test_pred, eval_counts = march_render(coarse_model, acc_grid, scene_aabb, test_origins, test_directions,
+                                                          depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps, alpha_thre)
+                elif args.march != 'dense':        # run_nerf_acc.py:338-349
                     ri_t, ts_t, te_t = acc_ray_marching(coarse_model, acc_grid, scene_aabb, test_origins, test_directions,
                                                         depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps, alpha_thre)
                     pos_t = test_origins[ri_t.long()] + test_directions[ri_t.long()] * (ts_t + te_t) / 2.0
@@ -285,6 +290,8 @@ def main(argv=None):
                        it_per_s=round(display_every / max(time.time() - t_last, 1e-9), 1) if n_iter else 0.0,
                        marched_samples_per_iter=(int(n_marched) // max(display_every, 1)) if args.march != 'dense' else
                        img_sample_size * depth_samples_per_ray_coarse)
+            if eval_counts is not None:      # candidates : kept samples of the test-view march
+                rec['eval_candidates_per_kept'] = eval_counts[0] / eval_counts[1] if eval_counts[1] else None
             n_marched = 0 if train_graph is None else n_marched.zero_()
             t_last = time.time()
             history.append(rec)

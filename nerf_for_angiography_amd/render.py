@@ -257,6 +257,57 @@ def march_train_step_mse(model, grid, scene_aabb, ray_origins, ray_directions, d
     return loss, pixel, n_kept
 
 
+def _check_forward_only(model, who: str):
+    """march_render / march_render_projection evaluate the model without recording a graph: refuse where autograd would record one."""
+    if torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters()):
+        raise RuntimeError(f"{who} is forward only (one evaluation of the model, no autograd graph): call it under torch.no_grad(); "
+                           "to train through the grid use render.march_train_step_mse")
+    if not getattr(model, "fused_forward", False):
+        raise NotImplementedError(f"{who}: this CPPN configuration is outside the fused kernels (ReLU, tanh or sine without an encoding, no "
+                                  "skip block, no view directions, one output channel)")
+    if model.flat_params is None or not model.flat_params.is_cuda:
+        raise AfxError(f"{who}: the model must live on a GPU; there is no CPU fallback")
+
+
+def _march_render(model, grid, scene_aabb, depth_samples_per_ray, near_thresh, far_thresh, early_stop_eps, alpha_thre, binary_thresh, **rays):
+    from .nerf.occupancy import _aabb_on_host
+    step = (float(far_thresh) - float(near_thresh)) / int(depth_samples_per_ray)
+    pixel, binary, kept, n_candidates = model.engine.march_render(
+        model._prepared(), model.precision, None if scene_aabb is None else _aabb_on_host(scene_aabb), near_thresh, far_thresh, step,
+        early_stop_eps, alpha_thre, grid_bits=None if grid is None else grid.bits, grid_aabb=None if grid is None else grid._aabb_host,
+        grid_res=None if grid is None else grid._res_host, binary_thresh=binary_thresh, **rays)
+    model.engine.last_kept_counts = kept      # (per ray, for comparisons)
+    counts = (int(n_candidates), int(kept.sum()))
+    return (pixel, counts) if binary_thresh is None else (pixel, binary, counts)
+
+
+def march_render(model, grid, scene_aabb, ray_origins, ray_directions, depth_samples_per_ray: int, near_thresh: float, far_thresh: float,
+                 early_stop_eps: float = 1e-2, alpha_thre: float = 1e-3, binary_thresh: Optional[float] = None):
+    """The reference's evaluation render through the occupancy grid - acc_ray_marching (march, alpha pass, render_visibility), get_predictions
+    over the kept samples, acc_render_volume_density (nerf/run_nerf_acc.py:338-349; visualization/visualization.py:335-352) - with ONE
+    evaluation of the model (afx_march_render): the raw output of the alpha pass is the one compositing uses, so the pixels equal the operator
+    sequence's bit for bit.  Step (far - near) / depth_samples_per_ray; `grid`: nerf.occupancy.OccupancyGrid or None (every step a candidate).
+    Forward only, at the model's precision.  Returns (pixels [R], (n_candidates, n_kept)), or with `binary_thresh` (pixels, binary pixels [R],
+    (n_candidates, n_kept)): the binary image forces sigma to 0 where sigmoid(raw) < binary_thresh (visualization.py:349-352)."""
+    _check_forward_only(model, "march_render")
+    if not (ray_origins.is_cuda and ray_directions.is_cuda):
+        raise AfxError("march_render: rays must live on a GPU; there is no CPU fallback")
+    return _march_render(model, grid, scene_aabb, depth_samples_per_ray, near_thresh, far_thresh, early_stop_eps, alpha_thre, binary_thresh,
+                         origins=ray_origins, dirs=ray_directions)
+
+
+def march_render_projection(model, grid, scene_aabb, poses, width: int, height: int, focal: float, depth_samples_per_ray: int,
+                            near_thresh: float, far_thresh: float, early_stop_eps: float = 1e-2, alpha_thre: float = 1e-3,
+                            binary_thresh: Optional[float] = None, ray_id0: int = 0, n_rays: Optional[int] = None):
+    """march_render for rays generated in-kernel from C-arm poses (float64 [n_proj,4,4] or [n_proj,3,4] cam->world), enumerated as
+    render_projection enumerates them without ray_ids: ray r = ray_id0 + r of [n_proj, H, W] - the rays of the dense fused kernels, bit for bit."""
+    _check_forward_only(model, "march_render_projection")
+    if not poses.is_cuda:
+        raise AfxError("march_render_projection: poses must live on a GPU; there is no CPU fallback")
+    return _march_render(model, grid, scene_aabb, depth_samples_per_ray, near_thresh, far_thresh, early_stop_eps, alpha_thre, binary_thresh,
+                         poses=poses, width=width, height=height, focal=focal, ray_id0=ray_id0, n_rays=n_rays)
+
+
 def hierarchical_train_step_mse(model, ray_origins, ray_directions, depth_values, depth_samples_per_ray_fine: int,
                                 target: torch.Tensor, u: Optional[torch.Tensor] = None, n_global: Optional[int] = None,
                                 fine_model=None, reuse_coarse: bool = True):

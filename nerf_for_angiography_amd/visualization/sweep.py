@@ -17,7 +17,7 @@ import pandas as pd
 import torch
 
 from ..phantomdata.proj_helpers import source_matrix
-from ..render import render_projection
+from ..render import march_render_projection, render_projection
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -38,8 +38,13 @@ def _poses(angles, src_pt, translation, device):
 @torch.no_grad()
 def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length, src_pt, near_thresh, far_thresh,
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
-                     views_per_launch=512):
+                     views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
+
+    grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
+    are then rendered as the reference renders CT models (:335-352): acc_ray_marching through the grid and `scene_aabb` with
+    (early_stop_eps, alpha_thre), the kept samples composited, the binary image from the same samples with sigma < binary_thresh zeroed -
+    each chunk of views ONE `march_render_projection` call (one evaluation of the model).  grid=None: the dense fixed-step render.
 
     targets: [n, H, W] ground-truth projections on the model's device (e.g. `ground_truth_sweep`), binary_targets likewise
     (optional; DICE 2D needs them).  Returns a DataFrame with the reference's columns (image_id, theta, phi, larm,
@@ -52,6 +57,14 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     bin_preds = torch.empty(n, hw, device=dev) if binary_targets is not None else None
     for v0 in range(0, n, views_per_launch):
         v1 = min(n, v0 + views_per_launch)
+        if grid is not None:
+            res = march_render_projection(model, grid, scene_aabb, poses[v0:v1], img_width, img_height, focal_length, depth_samples_per_ray,
+                                          near_thresh, far_thresh, early_stop_eps, alpha_thre,
+                                          binary_thresh=binary_thresh if bin_preds is not None else None)
+            preds[v0:v1] = res[0].view(v1 - v0, hw)
+            if bin_preds is not None:
+                bin_preds[v0:v1] = res[1].view(v1 - v0, hw)
+            continue
         out = render_projection(model, poses[v0:v1], img_width, img_height, focal_length, depth_samples_per_ray, near_thresh,
                                 far_thresh, want_aux=bin_preds is not None)
         preds[v0:v1] = out.rgb_map.view(v1 - v0, hw)
