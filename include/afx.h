@@ -301,6 +301,51 @@ int afx_grid_binarize(const afx_grid_desc* grid, const float* occs, float occ_th
  * bitfield the march reads. */
 int afx_grid_pack(const afx_grid_desc* grid, const uint8_t* binary, uint32_t* bits, void* stream);
 
+/* ---- The grid refresh on the device (OccupancyGrid.every_n_step's update with the cell draw made on the GPU): no allocation, no
+ * synchronisation, no copy to the host (device-to-device copies only), so the calls can be captured into a HIP graph.
+ *
+ * Draw rule of the post-warm-up cells (exact; tests restate it from afx_philox_uniform).  N = num_cells, n = n_draw (nerfacc: N / 4),
+ * n_occ = set bits of `bits` (the cells past N in the last word are ignored), u24_i = top 24 bits of number i of the Philox4x32-10 stream
+ * (seed, AFX_GRID_SELECT_TAG | step), i.e. afx_philox_uniform's u_i * 2^24:
+ *   cells[i]     = (u24_i * N) >> 24                                   i < n          (uniform cells)
+ *   cells[n + j] = occupied cell of rank (u24_(n+j) * n_occ) >> 24    j < n, when n < n_occ
+ *                = occupied cell of rank j                            j < n_occ, otherwise (all occupied cells, index order)
+ * (ranks count the occupied cells in index order from 0).  The selected count n + min(n, n_occ) stays on the device.
+ * The in-cell jitter of the refresh is afx_grid_points' Philox stream (seed, AFX_GRID_JITTER_TAG | step). */
+#define AFX_GRID_JITTER_TAG 0x4752494400000000ull   /* "GRID" << 32 */
+#define AFX_GRID_SELECT_TAG 0x53454C4300000000ull   /* "SELC" << 32 */
+
+/* The draw alone: cells_out[2 n_draw] (int32; slots behind the count unwritten), count_dev[1] (int64) = n_draw + min(n_draw, n_occ).  The step is
+ * *step_dev (device int64, read when the kernels run) or, with step_dev NULL, `step`; 0 <= step < 2^32.  workspace:
+ * afx_grid_select_workspace_bytes(grid) bytes of device memory.  1 <= n_draw <= num_cells < 2^31. */
+size_t afx_grid_select_workspace_bytes(const afx_grid_desc* grid);
+int afx_grid_select_cells(const afx_grid_desc* grid, const uint32_t* bits, int64_t n_draw, uint64_t seed, int64_t step, const int64_t* step_dev,
+                          int32_t* cells_out, int64_t* count_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One refresh of one grid, in place: the cells (all of them with all_cells != 0 - warm-up -, else the draw above from `bits`), one jittered
+ * point per cell (afx_grid_points, stream AFX_GRID_JITTER_TAG | step), occupancy = sigmoid(MLP) (afx_mlp_infer with apply_sigmoid, at `prec`
+ * on `prepared`; after the draw a launch over the capacity 2 n_draw bounded by the device count), then afx_grid_update's snapshot, decay and
+ * EMA (ema_decay) and afx_grid_binarize (occ_thre) into occs, binary and bits.  Equal bit for bit to that sequence of entry points on the same
+ * cells.  workspace: afx_grid_refresh_workspace_bytes(grid, n_draw, all_cells) bytes (-1: invalid arguments, see afx_last_error); a smaller
+ * one returns AFX_E_WORKSPACE before anything is written.  AFX_E_INVALID: null pointers, n_draw <= 0 or > num_cells (when all_cells == 0),
+ * num_cells >= 2^31, a capacity (num_cells or 2 n_draw) beyond afx_mlp_infer's 2^31 - 256 points, a host step outside [0, 2^32). */
+typedef struct afx_grid_refresh_args {
+  afx_grid_desc grid;
+  float* occs;                  /* [num_cells] */
+  uint8_t* binary;              /* [num_cells] */
+  uint32_t* bits;               /* [(num_cells + 31) / 32]: read by the draw, rewritten at the end */
+  int32_t all_cells;            /* 1: every cell (warm-up); 0: the draw */
+  int64_t n_draw;
+  uint64_t seed;
+  int64_t step;                 /* used when step_dev is NULL */
+  const int64_t* step_dev;      /* device int64: the training step, read when the kernels run */
+  float occ_thre, ema_decay;
+  void* workspace;
+  size_t workspace_bytes;
+} afx_grid_refresh_args;
+int64_t afx_grid_refresh_workspace_bytes(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells);
+int afx_grid_refresh(afx_ctx* ctx, int prec, const void* prepared, const afx_grid_refresh_args* args, void* stream);
+
 /* nerfacc.ray_marching: t range = ray / scene_aabb intersection clipped to [near, far]; fixed-step lattice
  * t_min + k*step; a step belongs to the ray while its mid-point lies before t_max (nerfacc marches `while (t_mid < far)`) and
  * is kept when the cell holding its mid-point is occupied (grid_bits NULL: every step). */

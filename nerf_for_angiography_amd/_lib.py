@@ -12,6 +12,7 @@ PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "f16": 3, "f16s8": 4}
 RAYS_ARRAYS, RAYS_POSE = 0, 1
 DEPTH_UNIFORM_MID, DEPTH_SHARED_Z, DEPTH_PER_RAY_Z, DEPTH_STRATIFIED = 0, 1, 2, 3
 Q_PARAM_COUNT, Q_K0, Q_PREPARED_BYTES, Q_FWD_WORKSPACE, Q_BWD_WORKSPACE_MIN, Q_BWD_WORKSPACE_FULL = range(6)
+GRID_JITTER_TAG, GRID_SELECT_TAG = 0x47524944 << 32, 0x53454C43 << 32      # Philox stream tags of the grid refresh (include/afx.h)
 
 
 class AfxError(RuntimeError):
@@ -34,6 +35,12 @@ class RenderArgs(C.Structure):
 
 class GridDesc(C.Structure):
     _fields_ = [("roi_aabb", C.c_float * 6), ("resolution", C.c_int32 * 3)]
+
+
+class GridRefreshArgs(C.Structure):
+    _fields_ = [("grid", GridDesc), ("occs", C.c_void_p), ("binary", C.c_void_p), ("bits", C.c_void_p), ("all_cells", C.c_int32),
+                ("n_draw", C.c_int64), ("seed", C.c_uint64), ("step", C.c_int64), ("step_dev", C.c_void_p), ("occ_thre", C.c_float),
+                ("ema_decay", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 class MarchArgs(C.Structure):
@@ -96,6 +103,11 @@ _SIGS = {
     "afx_grid_update": (C.c_int, [C.POINTER(GridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p]),
     "afx_grid_binarize": (C.c_int, [C.POINTER(GridDesc), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_grid_pack": (C.c_int, [C.POINTER(GridDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afx_grid_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridDesc)]),
+    "afx_grid_select_cells": (C.c_int, [C.POINTER(GridDesc), C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "afx_grid_refresh_workspace_bytes": (C.c_int64, [C.POINTER(GridDesc), C.c_int64, C.c_int32]),
+    "afx_grid_refresh": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GridRefreshArgs), C.c_void_p]),
     "afx_hier_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "afx_hier_train_step_mse": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RenderArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),

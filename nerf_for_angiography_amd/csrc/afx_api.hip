@@ -1195,6 +1195,141 @@ extern "C" int afx_grid_pack(const afx_grid_desc* grid, const uint8_t* binary, u
   return AFX_OK;
 }
 
+// ---- the grid refresh on the device (afx_grid_select_cells, afx_grid_refresh)
+struct SelLayout { size_t o_word_pre, o_block_tot, o_block_pre, o_n_occ, total; int64_t n_words, nb; };
+static SelLayout sel_layout(int64_t nc) {
+  SelLayout L;
+  L.n_words = (nc + 31) / 32;
+  L.nb = (L.n_words + SEL_WORDS - 1) / SEL_WORDS;
+  size_t o = 0;
+  L.o_word_pre = o; o = rup64(o + (size_t)L.n_words * 4, 256);
+  L.o_block_tot = o; o = rup64(o + (size_t)L.nb * 4, 256);
+  L.o_block_pre = o; o = rup64(o + (size_t)L.nb * 4, 256);
+  L.o_n_occ = o; o = rup64(o + 8, 256);
+  L.total = o;
+  return L;
+}
+// cells whose index fits the int32 cell lists and n_draw in 1..num_cells
+static int check_select(const afx_grid_desc* grid, int64_t n_draw, const char* who, int64_t* nc) {
+  if (int rc = check_grid(grid, who, nc)) return rc;
+  if (*nc > (int64_t)INT32_MAX) return fail(AFX_E_INVALID, "%s: %lld cells do not fit the int32 cell lists", who, (long long)*nc);
+  if (n_draw <= 0 || n_draw > *nc) return fail(AFX_E_INVALID, "%s: n_draw must be in 1..num_cells (got %lld)", who, (long long)n_draw);
+  return AFX_OK;
+}
+static int check_step(int64_t step, const int64_t* step_dev, const char* who) {
+  if (!step_dev && (step < 0 || step >= ((int64_t)1 << 32))) return fail(AFX_E_INVALID, "%s: step must be in [0, 2^32)", who);
+  return AFX_OK;
+}
+// the three selection kernels (sizes checked by the caller)
+static int launch_select(int64_t nc, const uint32_t* bits, int64_t n_draw, uint64_t seed, uint64_t stream_id,
+                         const int64_t* step_dev, int32_t* cells, int64_t* count_dev, char* ws, hipStream_t st) {
+  const SelLayout L = sel_layout(nc);
+  int32_t *word_pre = (int32_t*)(ws + L.o_word_pre), *block_tot = (int32_t*)(ws + L.o_block_tot), *block_pre = (int32_t*)(ws + L.o_block_pre);
+  int64_t* n_occ = (int64_t*)(ws + L.o_n_occ);
+  hipLaunchKernelGGL(k_grid_occ_count, dim3((unsigned)L.nb), dim3(256), 0, st, bits, nc, L.n_words, word_pre, block_tot);
+  hipLaunchKernelGGL(k_grid_occ_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)block_tot, L.nb, block_pre, n_draw, n_occ, count_dev);
+  hipLaunchKernelGGL(k_grid_select, blocks_for(2 * n_draw), dim3(256), 0, st, bits, nc, L.n_words, (const int32_t*)word_pre,
+                     (const int32_t*)block_pre, L.nb, n_draw, seed, stream_id, step_dev, (const int64_t*)n_occ, cells);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" size_t afx_grid_select_workspace_bytes(const afx_grid_desc* grid) {
+  int64_t nc;
+  if (check_grid(grid, "afx_grid_select_workspace_bytes", &nc)) return 0;
+  return sel_layout(nc).total;
+}
+
+extern "C" int afx_grid_select_cells(const afx_grid_desc* grid, const uint32_t* bits, int64_t n_draw, uint64_t seed, int64_t step,
+                                     const int64_t* step_dev, int32_t* cells_out, int64_t* count_dev, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  const char* who = "afx_grid_select_cells";
+  int64_t nc;
+  if (int rc = check_select(grid, n_draw, who, &nc)) return rc;
+  if (!bits || !cells_out || !count_dev || !workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (int rc = check_step(step, step_dev, who)) return rc;
+  const size_t need = sel_layout(nc).total;
+  if (workspace_bytes < need) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+  const uint64_t sid = AFX_GRID_SELECT_TAG | (step_dev ? 0 : (uint64_t)step);
+  return launch_select(nc, bits, n_draw, seed, sid, step_dev, cells_out, count_dev, (char*)workspace, (hipStream_t)stream);
+}
+
+// workspace of afx_grid_refresh: [cells (draw) | points | occupancies | occs snapshot | 256 partial sums | count (draw) | selection (draw)]
+struct RefreshLayout { size_t o_cells, o_pts, o_occ, o_scratch, o_partial, o_count, o_sel, total; int64_t cap; };
+static int refresh_layout(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells, RefreshLayout& L, int64_t* nc, const char* who) {
+  if (all_cells) {
+    if (int rc = check_grid(grid, who, nc)) return rc;
+    if (*nc > (int64_t)INT32_MAX) return fail(AFX_E_INVALID, "%s: %lld cells do not fit the int32 cell lists", who, (long long)*nc);
+  } else if (int rc = check_select(grid, n_draw, who, nc)) {
+    return rc;
+  }
+  L.cap = all_cells ? *nc : 2 * n_draw;
+  if (L.cap > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "%s: %lld points exceed afx_mlp_infer's 2^31 - 256 per call", who, (long long)L.cap);
+  size_t o = 0;
+  L.o_cells = o; o = rup64(o + (all_cells ? 0 : (size_t)L.cap * 4), 256);
+  L.o_pts = o; o = rup64(o + (size_t)L.cap * 12, 256);
+  L.o_occ = o; o = rup64(o + (size_t)L.cap * 4, 256);
+  L.o_scratch = o; o = rup64(o + (size_t)*nc * 4, 256);
+  L.o_partial = o; o = rup64(o + 256 * 8, 256);
+  L.o_count = o; o = rup64(o + (all_cells ? 0 : 8), 256);
+  L.o_sel = o; o += all_cells ? 0 : sel_layout(*nc).total;
+  L.total = o;
+  return AFX_OK;
+}
+
+extern "C" int64_t afx_grid_refresh_workspace_bytes(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells) {
+  RefreshLayout L;
+  int64_t nc;
+  if (refresh_layout(grid, n_draw, all_cells, L, &nc, "afx_grid_refresh_workspace_bytes")) return -1;
+  return (int64_t)L.total;
+}
+
+extern "C" int afx_grid_refresh(afx_ctx* c, int prec, const void* prepared, const afx_grid_refresh_args* a, void* stream) {
+  const char* who = "afx_grid_refresh";
+  if (!c || !prepared || !a) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (check_prec(prec, who)) return AFX_E_INVALID;
+  RefreshLayout L;
+  int64_t nc;
+  if (int rc = refresh_layout(&a->grid, a->n_draw, a->all_cells, L, &nc, who)) return rc;
+  if (!a->occs || !a->binary || !a->bits || !a->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (int rc = check_step(a->step, a->step_dev, who)) return rc;
+  if (a->workspace_bytes < L.total) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_grid_refresh_workspace_bytes)", who,
+                                                a->workspace_bytes, L.total);
+  if (int rc = check_dev(c, who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)a->workspace;
+  int32_t* cells = a->all_cells ? nullptr : (int32_t*)(ws + L.o_cells);
+  float *pts = (float*)(ws + L.o_pts), *occ = (float*)(ws + L.o_occ), *scratch = (float*)(ws + L.o_scratch);
+  int64_t* count = a->all_cells ? nullptr : (int64_t*)(ws + L.o_count);
+  const uint64_t step_host = a->step_dev ? 0 : (uint64_t)a->step;
+  const GridDesc g = grid_of(&a->grid);
+  int rc;
+  // 1. the cells (the draw: count on the device)
+  if (!a->all_cells &&
+      (rc = launch_select(nc, a->bits, a->n_draw, a->seed, AFX_GRID_SELECT_TAG | step_host, a->step_dev, cells, count, ws + L.o_sel, st)))
+    return rc;
+  // 2. one jittered point per cell
+  hipLaunchKernelGGL(k_grid_points, blocks_for(L.cap), dim3(256), 0, st, (const int32_t*)cells, L.cap, (const float*)nullptr, a->seed,
+                     AFX_GRID_JITTER_TAG | step_host, g, pts, (const int64_t*)count, a->step_dev);
+  HIPCHK(hipGetLastError());
+  // 3. occupancy = sigmoid(MLP): afx_mlp_infer's launch over the capacity, bounded by the device count
+  {
+    ChainArgs ca = {};
+    fill_model(c, prec, false, prepared, ca);
+    ca.tile0 = 0; ca.tile1 = (int)((L.cap + fwd_tile(prec) - 1) / fwd_tile(prec)); ca.n_total = L.cap; ca.mode = 0;
+    ca.pts = pts; ca.out = occ; ca.apply_sigmoid = 1; ca.n_dev = count;
+    if ((rc = launch_chain(c, prec, false, ca, st))) return rc;
+  }
+  // 4. snapshot, decay, EMA (afx_grid_update)
+  HIPCHK(hipMemcpyAsync(scratch, a->occs, (size_t)nc * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_grid_decay, blocks_for(L.cap), dim3(256), 0, st, a->occs, (const float*)scratch, (const int32_t*)cells, L.cap, a->ema_decay,
+                     (const int64_t*)count);
+  hipLaunchKernelGGL(k_grid_ema, blocks_for(L.cap), dim3(256), 0, st, a->occs, (const int32_t*)cells, (const float*)occ, L.cap, (const int64_t*)count);
+  HIPCHK(hipGetLastError());
+  // 5. threshold and bitfield (afx_grid_binarize)
+  return afx_grid_binarize(&a->grid, a->occs, a->occ_thre, a->binary, a->bits, (double*)(ws + L.o_partial), stream);
+}
+
 static int fill_march(const afx_march_args* m, MarchArgs& a, const char* who) {
   if (!m) return fail(AFX_E_INVALID, "%s: null args", who);
   if (m->n_rays < 0) return fail(AFX_E_INVALID, "%s: n_rays < 0", who);

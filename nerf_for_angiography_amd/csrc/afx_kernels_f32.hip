@@ -273,7 +273,14 @@ __global__ void __launch_bounds__(256, 1) k_chain_f32(const ChainArgs a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
   const int N = a.n_hidden;
-  if (a.tile0 + (int)blockIdx.x >= a.tile1) return;
+  // work range: the host's (a.n_total, a.tile1), or - capacity launch (a.n_dev, afx_grid_refresh) - the device-resident count, bounded by them
+  int64_t n_total = a.n_total;
+  int tile1 = a.tile1;
+  if (a.n_dev) {
+    n_total = min(n_total, *a.n_dev);
+    tile1 = min(tile1, (int)((n_total + TILE - 1) / TILE));
+  }
+  if (a.tile0 + (int)blockIdx.x >= tile1) return;
 
   float* sm = (float*)lds;
   for (uint32_t i = tid * 4; i < a.small_floats; i += 1024) *(f32x4*)(sm + i) = *(const f32x4*)(a.small + i);
@@ -312,11 +319,11 @@ __global__ void __launch_bounds__(256, 1) k_chain_f32(const ChainArgs a) {
 
   glds_copy(a.stream_fwd, slot0, a.slab0_bytes, wave, lane);
 
-  for (int tile = a.tile0 + blockIdx.x; tile < a.tile1; tile += gridDim.x) {
-    has_next = tile + (int)gridDim.x < a.tile1;
+  for (int tile = a.tile0 + blockIdx.x; tile < tile1; tile += gridDim.x) {
+    has_next = tile + (int)gridDim.x < tile1;
     const int64_t n = (int64_t)tile * TILE + wave * GROUP + col;
     const int64_t m = (int64_t)(tile - a.tile0) * TILE + wave * GROUP + col;   // stash row
-    const Sample sp = make_sample(a, n);
+    const Sample sp = make_sample(a, n, n_total);
 
     f32x16 h[NT];
     // ---------------- layer 0: K0 encoded inputs, natural k order, k = 2q + (lane>>5)
@@ -472,7 +479,7 @@ __global__ void __launch_bounds__(256, 1) k_chain_f32(const ChainArgs a) {
         float od = tau;
 #pragma unroll
         for (int sh = 16; sh >= 1; sh >>= 1) od += __shfl_xor(od, sh);
-        if (lane == 0 && n < a.n_total) {
+        if (lane == 0 && n < n_total) {
           const int gpr = a.s_pad / GROUP;
           a.od_part[(int64_t)sp.ray * gpr + (int)((n - (int64_t)sp.ray * a.s_pad) / GROUP)] = od;
         }

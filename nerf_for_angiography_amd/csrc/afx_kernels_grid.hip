@@ -61,9 +61,13 @@ __device__ __forceinline__ bool grid_cell(const GridDesc& g, float px, float py,
 
 // --- OccupancyGrid._update, step 1: one jittered world point per selected cell -----------------------------------
 // cell_idx == nullptr: all cells (cell i).  jitter [n,3] in [0,1) (parity mode) or nullptr: Philox(seed, stream 3*?).
-__global__ void k_grid_points(const int32_t* cell_idx, int64_t n, const float* jitter, uint64_t seed, uint64_t stream, GridDesc g, float* pts) {
+// afx_grid_refresh: count_dev bounds the work of a launch sized for the capacity n, and the stream id is stream | *step_dev, the training
+// step read on the device (a replayed graph does not freeze it).  Both null: the host's n and stream.
+__global__ void k_grid_points(const int32_t* cell_idx, int64_t n, const float* jitter, uint64_t seed, uint64_t stream, GridDesc g, float* pts,
+                              const int64_t* count_dev = nullptr, const int64_t* step_dev = nullptr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n || (count_dev && i >= *count_dev)) return;
+  if (step_dev) stream |= (uint64_t)*step_dev;
   const int64_t c = cell_idx ? cell_idx[i] : i;
   const int k = (int)(c % g.res[2]);
   const int j = (int)((c / g.res[2]) % g.res[1]);
@@ -81,16 +85,16 @@ __global__ void k_grid_points(const int32_t* cell_idx, int64_t n, const float* j
 // --- step 2: occs[c] = max(occs[c] * decay, occ).  Two passes so that a cell drawn twice gets max(old * decay, occ_a, occ_b)
 // whatever the order: (i) every selected cell drops to its decayed value, formed from a snapshot of the values BEFORE the
 // update (idempotent under duplicates); (ii) an integer atomicMax on the bit patterns of the non-negative floats folds
-// the new occupancies in - order-independent, so the result is deterministic.
-__global__ void k_grid_decay(float* occs, const float* occs_before, const int32_t* cell_idx, int64_t n, float decay) {
+// the new occupancies in - order-independent, so the result is deterministic.  (count_dev: as in k_grid_points.)
+__global__ void k_grid_decay(float* occs, const float* occs_before, const int32_t* cell_idx, int64_t n, float decay, const int64_t* count_dev = nullptr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n || (count_dev && i >= *count_dev)) return;
   const int64_t c = cell_idx ? cell_idx[i] : i;
   occs[c] = fmaxf(__fmul_rn(occs_before[c], decay), 0.f);
 }
-__global__ void k_grid_ema(float* occs, const int32_t* cell_idx, const float* occ_new, int64_t n) {
+__global__ void k_grid_ema(float* occs, const int32_t* cell_idx, const float* occ_new, int64_t n, const int64_t* count_dev = nullptr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n || (count_dev && i >= *count_dev)) return;
   const int64_t c = cell_idx ? cell_idx[i] : i;
   const float v = occ_new[i];
   if (v > 0.f) atomicMax((unsigned int*)(occs + c), __float_as_uint(v));
@@ -141,6 +145,112 @@ __global__ void k_grid_pack(const uint8_t* binary, int64_t n, uint32_t* bits) {
     word |= (binary[c] ? 1u : 0u) << b;
   }
   bits[w] = word;
+}
+
+// --- the cells of a post-warm-up refresh, drawn on the device (afx_grid_select_cells; the draw rule is written in include/afx.h) ---------------
+// nerfacc draws n = num_cells / 4 uniform cells and n among the occupied ones (all of them, in index order, when there are at most n).  The
+// occupied cells are read from the packed bitfield the march reads: k_grid_occ_count counts the set bits per word and forms per-workgroup word
+// prefixes, k_grid_occ_scan scans the workgroup totals (a few hundred at 128^3) and posts n_occ and the selected count n + min(n, n_occ), and
+// k_grid_select maps draw i to its cell (block by binary search over the block prefixes, word by binary search over the word prefixes, then the
+// set bit inside the word).  Nothing leaves the device.
+constexpr int SEL_WORDS = 256;      // bitfield words per workgroup of k_grid_occ_count (one per thread)
+
+// top 24 bits of number i of stream (seed, stream id): philox_uniform's u = philox_u24 / 2^24
+__host__ __device__ __forceinline__ uint32_t philox_u24(uint64_t seed, uint64_t stream, uint64_t i) {
+  uint32_t o[4];
+  philox4x32_10((uint32_t)(i >> 2), (uint32_t)(i >> 34), (uint32_t)stream, (uint32_t)(stream >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  return o[i & 3] >> 8;
+}
+// word w of the bitfield with the bits past the last cell cleared
+__device__ __forceinline__ uint32_t grid_word(const uint32_t* bits, int64_t w, int64_t n_cells) {
+  uint32_t v = bits[w];
+  const int64_t rem = n_cells - w * 32;
+  if (rem < 32) v &= (1u << rem) - 1u;
+  return v;
+}
+// word_pre[w]: set bits in the words of w's workgroup before w; block_tot[b]: set bits in workgroup b's SEL_WORDS words
+__global__ void __launch_bounds__(256) k_grid_occ_count(const uint32_t* bits, int64_t n_cells, int64_t n_words, int32_t* word_pre, int32_t* block_tot) {
+  __shared__ int32_t wsum[4];
+  const int64_t w = (int64_t)blockIdx.x * SEL_WORDS + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = w < n_words ? __popc(grid_word(bits, w, n_cells)) : 0;
+  int inc = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(inc, d);
+    if (lane >= d) inc += v;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int k = 0; k < wave; ++k) base += wsum[k];
+  if (w < n_words) word_pre[w] = base + inc - c;
+  if (threadIdx.x == 255) block_tot[blockIdx.x] = base + inc;
+}
+// one workgroup: block_pre = exclusive scan of block_tot[nb]; n_occ[0] = the total, count[0] = n_draw + min(n_draw, total)
+__global__ void __launch_bounds__(1024) k_grid_occ_scan(const int32_t* block_tot, int64_t nb, int32_t* block_pre, int64_t n_draw, int64_t* n_occ,
+                                                         int64_t* count) {
+  __shared__ int64_t ws_[16];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
+  int64_t s = 0;
+  for (int64_t b = b0; b < b1; ++b) s += block_tot[b];
+  int64_t is = s;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int64_t v = __shfl_up(is, d);
+    if (lane >= d) is += v;
+  }
+  if (lane == 63) ws_[wave] = is;
+  __syncthreads();
+  if (wave == 0) {
+    int64_t a = lane < 16 ? ws_[lane] : 0;
+    const int64_t a0 = a;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+      const int64_t v = __shfl_up(a, d);
+      if (lane >= d) a += v;
+    }
+    if (lane < 16) ws_[lane] = a - a0;      // exclusive
+  }
+  __syncthreads();
+  int64_t p = ws_[wave] + is - s;           // exclusive prefix of this thread's blocks
+  for (int64_t b = b0; b < b1; ++b) { block_pre[b] = (int32_t)p; p += block_tot[b]; }
+  if (t == 1023) {
+    *n_occ = p;
+    *count = n_draw + (n_draw < p ? n_draw : p);
+  }
+}
+// cells[i], i < n_draw: the uniform draw ((u24 * num_cells) >> 24); i = n_draw + j: the occupied cell of rank (u24 * n_occ) >> 24 when n_draw < n_occ,
+// else of rank j (j < n_occ; the slots behind the count are not written).  u24 = philox_u24(seed, stream | *step_dev, i).
+__global__ void k_grid_select(const uint32_t* bits, int64_t n_cells, int64_t n_words, const int32_t* word_pre, const int32_t* block_pre, int64_t nb,
+                              int64_t n_draw, uint64_t seed, uint64_t stream, const int64_t* step_dev, const int64_t* n_occ_dev, int32_t* cells) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 2 * n_draw) return;
+  if (step_dev) stream |= (uint64_t)*step_dev;
+  if (i < n_draw) {
+    cells[i] = (int32_t)(((uint64_t)philox_u24(seed, stream, (uint64_t)i) * (uint64_t)n_cells) >> 24);
+    return;
+  }
+  const int64_t j = i - n_draw, n_occ = *n_occ_dev;
+  int64_t k;
+  if (n_draw < n_occ) k = (int64_t)(((uint64_t)philox_u24(seed, stream, (uint64_t)i) * (uint64_t)n_occ) >> 24);
+  else if (j < n_occ) k = j;
+  else return;
+  int64_t lo = 0, hi = nb - 1;              // the last workgroup whose prefix is <= k holds the k-th set bit
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (block_pre[mid] <= k) lo = mid; else hi = mid - 1;
+  }
+  const int64_t r = k - block_pre[lo];
+  int64_t wlo = lo * SEL_WORDS, whi = (wlo + SEL_WORDS < n_words ? wlo + SEL_WORDS : n_words) - 1;
+  while (wlo < whi) {
+    const int64_t mid = (wlo + whi + 1) >> 1;
+    if (word_pre[mid] <= r) wlo = mid; else whi = mid - 1;
+  }
+  uint32_t v = grid_word(bits, wlo, n_cells);
+  for (int64_t q = r - word_pre[wlo]; q > 0; --q) v &= v - 1u;      // drop the lower set bits
+  cells[i] = (int32_t)(wlo * 32 + (v ? __ffs(v) - 1 : 0));
 }
 
 // --- ray marching (nerfacc.ray_marching, fixed-step lattice, AABB contraction) ----------------------------------------

@@ -704,6 +704,67 @@ def grid_pack(roi_aabb, resolution, binary_u8, bits):
     _lib.check(lib.afx_grid_pack(C.byref(g), _ptr(binary_u8), _ptr(bits), Engine._stream(binary_u8.device)), "afx_grid_pack")
 
 
+def _step_args(step, dev, who):
+    """(host step, device step pointer) of a training step given as an int or a 0-dim int64 tensor on `dev`."""
+    if torch.is_tensor(step):
+        if step.device != torch.device(dev) or step.dtype != torch.int64 or step.numel() != 1:
+            raise ValueError(f"{who}: a tensor step must be one int64 on {dev}")
+        return 0, step.data_ptr()
+    return int(step), None
+
+
+def grid_select_workspace_bytes(roi_aabb, resolution) -> int:
+    return int(_lib.load().afx_grid_select_workspace_bytes(C.byref(_grid_desc(roi_aabb, resolution))))
+
+
+def grid_select_cells(roi_aabb, resolution, bits, n_draw, seed, step, cells=None, count=None, workspace=None):
+    """afx_grid_select_cells: the post-warm-up cells of a refresh drawn on the device from the march's bitfield (draw rule: include/afx.h).
+    `step`: int or 0-dim int64 device tensor.  Returns (cells [2 n_draw] int32 - valid up to count -, count [1] int64), device tensors."""
+    lib = _lib.load()
+    if bits.device.type != "cuda":
+        raise AfxError("grid_select_cells: the occupancy grid lives on a GPU; there is no CPU fallback")
+    dev = bits.device
+    g = _grid_desc(roi_aabb, resolution)
+    cells = torch.empty(2 * int(n_draw), dtype=torch.int32, device=dev) if cells is None else cells
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.afx_grid_select_workspace_bytes(C.byref(g))), 1), dtype=torch.uint8, device=dev)
+    step_h, step_d = _step_args(step, dev, "grid_select_cells")
+    _lib.check(lib.afx_grid_select_cells(C.byref(g), _ptr(bits), int(n_draw), int(seed), step_h, step_d, _ptr(cells), _ptr(count), _ptr(workspace),
+                                         workspace.numel(), Engine._stream(dev)), "afx_grid_select_cells")
+    return cells, count
+
+
+def grid_refresh_workspace_bytes(roi_aabb, resolution, n_draw, all_cells) -> int:
+    lib = _lib.load()
+    n = int(lib.afx_grid_refresh_workspace_bytes(C.byref(_grid_desc(roi_aabb, resolution)), int(n_draw), int(bool(all_cells))))
+    if n < 0:
+        raise AfxError(f"afx_grid_refresh_workspace_bytes: {lib.afx_last_error().decode()}")
+    return n
+
+
+def grid_refresh(eng: Engine, prepared, prec: str, roi_aabb, resolution, occs, binary_u8, bits, n_draw, all_cells, seed, step, occ_thre,
+                 ema_decay, workspace):
+    """afx_grid_refresh: one refresh of one grid in place (occs, binary_u8, bits) - cells (all, or the device draw), jittered points,
+    sigmoid(MLP) at `prec` on `prepared`, decay / EMA, threshold - with no host synchronisation.  `step`: int or 0-dim int64 device tensor
+    (read when the kernels run: a captured call follows it)."""
+    dev = occs.device
+    if dev.type != "cuda":
+        raise AfxError("grid_refresh: the occupancy grid lives on a GPU; there is no CPU fallback")
+    a = _lib.GridRefreshArgs()
+    a.grid = _grid_desc(roi_aabb, resolution)
+    for t, name in ((binary_u8, "binary"), (bits, "bits"), (workspace, "workspace"), (prepared, "prepared")):
+        if t.device != dev:
+            raise ValueError(f"grid_refresh: {name} on {t.device}, expected {dev}")
+    a.occs, a.binary, a.bits = occs.data_ptr(), binary_u8.data_ptr(), bits.data_ptr()
+    a.all_cells, a.n_draw, a.seed = int(bool(all_cells)), int(n_draw), int(seed)
+    step_h, step_d = _step_args(step, dev, "grid_refresh")
+    a.step, a.step_dev = step_h, step_d
+    a.occ_thre, a.ema_decay = float(occ_thre), float(ema_decay)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    eng._check(eng.lib.afx_grid_refresh(eng.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), Engine._stream(dev)), "afx_grid_refresh")
+
+
 def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res):
     if o is not None:      # (None: the rays come from elsewhere - afx_march_render's pose mode)
         m.origins, m.dirs, m.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]

@@ -20,7 +20,8 @@ the CPU for the tests.  Semantics kept:
 
 The grid lives on the GPU (there is no CPU fallback).  Randomness: which cells are refreshed is a torch draw (an index
 list is data); the jitter inside a cell is drawn in the kernel from the counter-based Philox stream (seed, step) unless
-the caller passes `jitter` (parity tests).
+the caller passes `jitter` (parity tests).  `refresh` (afx_grid_refresh) makes the same update with the cells drawn on the GPU from the
+march's bitfield instead (rule in include/afx.h): no host synchronisation, so render.GridUpdateGraph can capture it.
 
 `ray_marching(..., return_packed=True)` additionally returns the kept samples group-aligned (engine.PackedGroups) for the fused
 packed training step (`render.train_step_packed_mse`: the reference's positions -> get_predictions -> acc_render_volume_density -> mse ->
@@ -141,6 +142,42 @@ class OccupancyGrid(torch.nn.Module):
             raise RuntimeError("every_n_step() is a training-time call; in eval mode use the grid as is")
         if step % n == 0:
             self._update(step, occ_eval_fn, occ_thre, ema_decay, warmup_steps)
+
+    # ---- the refresh on the device (afx_grid_refresh): the cells are drawn on the GPU from the march's bitfield, nothing is read back ----
+    def _refresh_workspace(self, nbytes: int):
+        """The refresh's workspace, grown on demand; a graph captured over refresh() keeps its address, so it never grows during a capture."""
+        ws = getattr(self, "_refresh_ws", None)
+        if ws is None or ws.numel() < nbytes or ws.device != self.occs.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise AfxError("OccupancyGrid.refresh: the workspace must be sized before graph capture (reserve_refresh_workspace)")
+            ws = self._refresh_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.occs.device)
+        return ws
+
+    def reserve_refresh_workspace(self):
+        """Size the refresh's workspace for both phases (warm-up: every cell; afterwards: the draw) - before a graph capture."""
+        self._require_gpu()
+        n = max(_engine.grid_refresh_workspace_bytes(self._aabb_host, self._res_host, self.num_cells // 4, all_cells)
+                for all_cells in (True, False))
+        self._refresh_workspace(n)
+
+    @torch.no_grad()
+    def refresh(self, model, step, occ_thre=1e-2, ema_decay=0.95, warmup_steps=256, all_cells=None):
+        """One update of the grid as every_n_step makes it at a refresh step, with the post-warm-up cells drawn on the GPU (afx_grid_refresh,
+        draw rule in include/afx.h: num_cells/4 uniform cells plus num_cells/4 of the occupied ones, or all of them when there are fewer):
+        occupancy = sigmoid(model) at `model.precision` on the module's prepared weights, no host synchronisation and no host copy.
+        `step`: int, or a 0-dim int64 tensor on the grid's device (read when the kernels run: a graph captured over this call follows it).
+        `all_cells` (the warm-up phase) defaults to step < warmup_steps; for a tensor step that reads the step back (a host
+        synchronisation) - pass it when the caller knows the phase (render.GridUpdateGraph does)."""
+        self._require_gpu()
+        if all_cells is None:
+            all_cells = int(step) < warmup_steps
+        self._refresh(model.engine, model._prepared(), model.precision, step, occ_thre, ema_decay, all_cells)
+
+    def _refresh(self, eng, prepared, prec, step, occ_thre, ema_decay, all_cells):
+        n_draw = self.num_cells // 4
+        ws = self._refresh_workspace(_engine.grid_refresh_workspace_bytes(self._aabb_host, self._res_host, n_draw, all_cells))
+        _engine.grid_refresh(eng, prepared, prec, self._aabb_host, self._res_host, self.occs, self._binary_u8, self.bits, n_draw, all_cells,
+                             self.seed, step, occ_thre, ema_decay, ws)
 
     @torch.no_grad()
     def query_occ(self, samples):

@@ -13,6 +13,8 @@ kernels, nerf/occupancy.py), then positions / get_predictions / acc_render_volum
 over the march's packed samples, march included, in one library call (`march_train_step_mse`; f16s8); `grid_ops` is the same body call for call through
 the mirrored functions (also what `grid` does at the other precisions).  `--graph` (with `grid`, f16s8) replays that iteration, Adam
 included, from a HIP graph captured once (`render.GridTrainGraph`): the sizes stay on the device and the host never waits for the GPU.
+`--graph-grid-update` (with `--graph`) also replays the refresh of both occupancy grids every 16th iteration from HIP graphs
+(`render.GridUpdateGraph`: the cells drawn on the device, no host synchronisation); without it the refresh stays eager.
 `--single-eval` (with `grid`, f16s8, with or without `--graph`) evaluates the model once per iteration: the training step's forward half over
 the march's candidates doubles as the alpha pass.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
@@ -36,7 +38,7 @@ from ..engine import RenderSpec
 from ..model.CPPN import CPPN
 from ..phantomdata import dataset as ds
 from .. import engine as _engine
-from ..render import render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph
+from ..render import render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph, GridUpdateGraph
 from .nerf_helpers import sample_pixel_rays, get_predictions
 from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
@@ -72,7 +74,12 @@ def build_parser():
     p.add_argument('--graph', action='store_true',
                    help='--march grid --precision f16s8: capture the whole iteration (re-tiling, march, alpha pass, visibility, packed step, loss, '
                         'Adam) once into a HIP graph and replay it; sizes stay on the device and the host never waits for the GPU (the '
-                        'occupancy-grid update every 16 iterations stays eager; counts and loss are read at the display cadence only)')
+                        'occupancy-grid update every 16 iterations stays eager unless --graph-grid-update; counts and loss are read at the display '
+                        'cadence only)')
+    p.add_argument('--graph-grid-update', dest='graph_grid_update', action='store_true',
+                   help='with --graph: refresh both occupancy grids every 16th iteration from HIP graphs too (render.GridUpdateGraph: the cells '
+                        'are drawn on the device, afx_grid_refresh), so the host never waits for the GPU; the draw differs from the eager '
+                        'refresh\'s torch draw')
     p.add_argument('--single-eval', dest='single_eval', action='store_true',
                    help='--march grid --precision f16s8 --pos_enc none (with or without --graph): evaluate the model ONCE per iteration - the '
                         'training step\'s forward half over the march\'s candidates doubles as the alpha pass (afx_march_train_step_mse_single_eval)')
@@ -92,6 +99,8 @@ def main(argv=None):
     if args.single_eval and (args.march != 'grid' or args.precision != 'f16s8' or args.pos_enc != 'none'):
         raise ValueError("--single-eval: needs --march grid --precision f16s8 --pos_enc none (the single-evaluation grid step is f16s8, ReLU, "
                          "without an input encoding)")
+    if args.graph_grid_update and not args.graph:
+        raise ValueError("--graph-grid-update: needs --graph")
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if device.type != "cuda":
         raise SystemExit("run_nerf_acc: needs an MI355X; there is no CPU fallback")
@@ -194,6 +203,9 @@ def main(argv=None):
         train_graph = GridTrainGraph(coarse_model, coarse_optimizer, acc_grid, scene_aabb, img_sample_size, depth_samples_per_ray_coarse, near_thresh,
                                      far_thresh, early_stop_eps, alpha_thre, single_eval=args.single_eval)
         n_marched = torch.zeros((), dtype=torch.int64, device=device)
+    update_graph = None
+    if args.graph_grid_update:      # both grids' refresh (:285-286) in graphs captured on first use; replayed before the training step
+        update_graph = GridUpdateGraph(coarse_model, [(acc_grid, alpha_thre), (vessel_acc_grid, vessel_alpha_thre)])
     t_last = time.time()
     for n_iter in range(n_iters + 1):
         coarse_model.train()
@@ -211,8 +223,11 @@ def main(argv=None):
             with torch.no_grad():
                 acc_grid.train()
                 vessel_acc_grid.train()
-                acc_grid = acc_update_n_step(acc_grid, coarse_model, n_iter, occ_thre=alpha_thre)
-                vessel_acc_grid = acc_update_n_step(vessel_acc_grid, coarse_model, n_iter, occ_thre=vessel_alpha_thre)
+                if update_graph is not None:
+                    update_graph.step(n_iter)
+                else:
+                    acc_grid = acc_update_n_step(acc_grid, coarse_model, n_iter, occ_thre=alpha_thre)
+                    vessel_acc_grid = acc_update_n_step(vessel_acc_grid, coarse_model, n_iter, occ_thre=vessel_alpha_thre)
             if train_graph is not None:
                 # the same iteration replayed from the graph: no host read-back; an empty march skips the Adam step on the device
                 loss_k, pred, counts = train_graph.step(batch_origins, batch_directions, batch_pix_vals)

@@ -417,7 +417,7 @@ class GridTrainGraph:
     the optimizer step is skipped exactly as the reference skips it (:293): `optimizer.found_inf` points at the step's skip flag, which
     PyTorch's fused Adam honours (parameters, moments and `step` unchanged); pixel and loss then hold the previous replay's values.
     Requires `Adam(fused=True, capturable=True)` (a tensor lr can be changed between replays with `fill_`).  The occupancy grid is read
-    by address: update it in place between replays (`OccupancyGrid.update_every_n_steps`, `set_binary`), never rebind it.  After a
+    by address: update it in place between replays (`OccupancyGrid.every_n_step`, `OccupancyGrid.refresh`, `GridUpdateGraph.step`, `set_binary`), never rebind it.  After a
     replay the module's cached prepared weights are marked stale, so eager renders re-tile the updated parameters.
     `single_eval=True` captures afx_march_train_step_mse_single_eval instead (one evaluation of the model per iteration; ReLU, no input
     encoding); everything else is the same."""
@@ -515,3 +515,68 @@ class GridTrainGraph:
         self.graph.replay()
         self._mark_stale()
         return self.loss, self.pixel, self.counts
+
+
+class GridUpdateGraph:
+    """The occupancy-grid refresh of the reference's grid iteration (nerf/run_nerf_acc.py:285-286: acc_update_n_step for each grid, every n-th
+    step) replayed from HIP graphs: re-tiling of the current parameters into the module's prepared buffer, then one afx_grid_refresh per grid
+    (`OccupancyGrid.refresh`: cells drawn on the device, sigmoid(MLP), decay / EMA, threshold), captured on one stream.  Two graphs, captured
+    lazily on first use: the warm-up one (every cell) and the post-warm-up one (the device draw).  The training step is a device counter that
+    `step(n_iter)` fills before the replay, so replays follow it; nothing is read back.
+
+    `grids`: [(grid, occ_thre), ...].  `step(n_iter)` does nothing unless n_iter % n == 0.  After a replay the module's cached prepared weights
+    are marked stale (as GridTrainGraph does).  The grids' buffers are used by address: update them in place, never rebind them."""
+
+    def __init__(self, model, grids, warmup_steps: int = 256, n: int = 16, ema_decay: float = 0.95):
+        _check_model(model)
+        if model._coef_trainable():
+            raise NotImplementedError("GridUpdateGraph: trainable fourier coefficients are not captured; freeze them")
+        self.model, self.grids = model, [(g, float(t)) for g, t in grids]
+        self.warmup_steps, self.n, self.ema_decay = int(warmup_steps), int(n), float(ema_decay)
+        self._aux_key = self._aux()
+        dev = model.flat_params.device
+        self.step_dev = torch.zeros((), dtype=torch.int64, device=dev)
+        self._graphs = {}      # all_cells -> CUDAGraph
+
+    def _aux(self):
+        m = self.model
+        return float(m.barf_alpha) if m.use_pos_enc == "barf" else None
+
+    def _capture(self, all_cells):
+        model, eng = self.model, self.model.engine
+        dev = model.flat_params.device
+        self._buf = model._prepared()      # the module's prepared buffer (allocated now): the graph re-tiles into it
+        for g, _ in self.grids:
+            g.reserve_refresh_workspace()
+        # kernel attributes of the chain launch are set on first use: set them outside the capture (the same kernel as afx_mlp_infer's)
+        eng.infer(self._buf, torch.zeros(1, 3, device=dev), model.precision, apply_sigmoid=True)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(graph, stream=side):
+                eng.prepare(model.flat_params, model._enc_aux(), model.precision)      # into the cached buffer (key None: always re-tiles)
+                for g, thre in self.grids:
+                    g._refresh(eng, self._buf, model.precision, self.step_dev, thre, self.ema_decay, all_cells)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._graphs[all_cells] = graph
+        return graph
+
+    def _mark_stale(self):
+        cache = self.model.engine._prepared
+        for prec, (buf, _) in list(cache.items()):
+            cache[prec] = (buf, None)
+
+    def step(self, n_iter: int):
+        if n_iter % self.n:
+            return
+        if self._aux() != self._aux_key:
+            raise AfxError("GridUpdateGraph: the BARF schedule moved since the capture (the encoding weights are captured by address); "
+                           "build a new GridUpdateGraph")
+        all_cells = n_iter < self.warmup_steps
+        graph = self._graphs.get(all_cells)
+        if graph is None:
+            graph = self._capture(all_cells)
+        self.step_dev.fill_(int(n_iter))
+        graph.replay()
+        self._mark_stale()
