@@ -94,6 +94,33 @@ struct ProfScope {
 static inline uint32_t rup(uint64_t v, uint64_t a) { return (uint32_t)((v + a - 1) / a * a); }
 static inline size_t rup64(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Hands out the regions of a workspace in order, each rounded up to `align` bytes; `end` is how far the carve has got.  The base is an
+// integer, so that the one function that describes a workspace both sizes it (base 0: nothing is dereferenced) and carves the caller's.
+struct Carve {
+  uintptr_t base = 0;
+  size_t end = 0;
+  template <class T = char>
+  T* take(size_t bytes, size_t align = 256) {
+    T* p = (T*)(base + end);
+    end += rup64(bytes, align);
+    return p;
+  }
+};
+
+// Runs f(std::integral_constant<int, F>()) for the context's layer width F (afx_create admits 64, 128 and 256 only).
+template <class Fn>
+static int with_width(const afx_ctx* c, Fn&& f) {
+  if (c->d.width == 64) return f(std::integral_constant<int, 64>());
+  if (c->d.width == 128) return f(std::integral_constant<int, 128>());
+  return f(std::integral_constant<int, 256>());
+}
+
+// The 16-/8-bit chain kernels address a layer's stash plane (rows x width x esz bytes) with 32-bit byte offsets: the most rows of one chunk,
+// in whole `tile`-row tiles, whose plane stays below 4 GiB.
+static int64_t stash_max_rows(const afx_ctx* c, size_t esz, int tile) {
+  return (int64_t)(((uint64_t)1 << 32) / ((uint64_t)tile * c->d.width * esz)) * tile;
+}
+
 // Layout of the prepared-weights buffer for one precision.
 struct PrepLayout {
   uint32_t small_floats, small_bytes_pad, slab0_bytes, slabh_stride, slabt_bytes;
@@ -305,10 +332,10 @@ extern "C" int64_t afx_query(const afx_ctx* c, int what, int64_t a0, int64_t a1,
       const int64_t samples = a0 > 0 ? a0 * s_pad_of((int)a1) : a1;
       int64_t tiles = (samples + bwd_tile((int)a2) - 1) / bwd_tile((int)a2);
       if (is_bf16((int)a2)) {      // a chunk never exceeds the 4 GiB layer plane the 32-bit stash offsets reach (run_backward): more is never used
-        const uint64_t plane_rows = ((uint64_t)1 << 32) / ((uint64_t)c->d.width * 2);
-        size_t need = (size_t)std::min<int64_t>(tiles, (int64_t)(plane_rows / bwd_tile((int)a2))) * B.per_tile_bytes;
+        const int tile = bwd_tile((int)a2);
+        size_t need = (size_t)std::min<int64_t>(tiles, stash_max_rows(c, 2, tile) / tile) * B.per_tile_bytes;
         if ((int)a2 == AFX_PREC_F16S8 && c->small_in_kernel) {      // rays mode stashes 1-byte elements: twice the rows per plane, ~half the bytes per row
-          need = std::max(need, (size_t)std::min<int64_t>(tiles, (int64_t)(2 * plane_rows / 256)) * per_tile_s8(c));
+          need = std::max(need, (size_t)std::min<int64_t>(tiles, stash_max_rows(c, 1, 256) / 256) * per_tile_s8(c));
         }
         return (int64_t)(B.fixed_bytes + need + 1024);
       }
@@ -412,7 +439,7 @@ static int launch_chain_f(afx_ctx* c, int prec, bool bwd, const ChainArgs& a, si
 }
 
 static int launch_chain(afx_ctx* c, int prec, bool bwd, const ChainArgs& a, hipStream_t st, int phase = 0) {
-  const int F = c->d.width, N = c->d.n_hidden;
+  const int N = c->d.n_hidden;
   const bool occ2 = chain_occ2(c->nt, phase);      // backward half at widths <= 128: two workgroups per CU, two-tile steps
   const size_t slot = occ2 ? chain_slot_bytes(c->nt, nk0_of(c), true, false, 2) : a.slot_bytes;
   size_t lds = (size_t)a.small_bytes_pad + (size_t)(is_bf16(prec) ? chain_ring(bwd) : 2) * slot;
@@ -424,9 +451,7 @@ static int launch_chain(afx_ctx* c, int prec, bool bwd, const ChainArgs& a, hipS
   if (int rc = check_dev(c, "afx chain launch")) return rc;
   const int wgs = occ2 ? 2 * c->n_cu : c->n_cu;
   const int grid = (tiles < wgs || !a.persistent) ? tiles : wgs;    // persistent: one workgroup per CU (occ2: two) loops over tiles
-  if (F == 64) return launch_chain_f<64>(c, prec, bwd, a, lds, grid, st, phase);
-  if (F == 128) return launch_chain_f<128>(c, prec, bwd, a, lds, grid, st, phase);
-  return launch_chain_f<256>(c, prec, bwd, a, lds, grid, st, phase);
+  return with_width(c, [&](auto f) { return launch_chain_f<decltype(f)::value>(c, prec, bwd, a, lds, grid, st, phase); });
 }
 
 static void fill_model(const afx_ctx* c, int prec, bool bwd, const void* prepared, ChainArgs& a) {
@@ -630,7 +655,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     // The 16-/8-bit chain kernels address a layer's stash with 32-bit byte offsets (one VGPR per lane instead of two): a chunk's
     // layer plane must stay below 4 GiB.  (Until round 2 nothing enforced this: with a 128 GiB workspace the 512^2 x 128 projection
     // ran as 2 chunks of 8.3 GB planes and the rows beyond 4 GiB wrapped onto the first ones - wrong weight gradients, same timing.)
-    const int64_t max_tiles = (int64_t)(((uint64_t)1 << 32) / ((uint64_t)TILE * F * esz));      // the largest offset used is plane - 16
+    const int64_t max_tiles = stash_max_rows(c, esz, TILE) / TILE;      // the largest offset used is plane - 16
     if (chunk > max_tiles) chunk = max_tiles;
   }
   if (chunk < tiles) {      // equal chunks instead of full ones and a remainder
@@ -686,6 +711,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
       hexp[bI] = (uint32_t*)(ws + off); off += (size_t)N * (rows / 32) * 4;
     }
   }
+  if (off > ws_bytes) return fail(AFX_E_WORKSPACE, "backward workspace layout exceeds the buffer (%zu > %zu)", off, ws_bytes);
   a.stash_rows = (int64_t)rows;
   a.debug = 0;
   if (dsz && (chunk < tiles || nbuf != 1)) return fail(AFX_E_WORKSPACE, "capturable training step: the capacity must fit one chunk");
@@ -741,32 +767,27 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     w.stride_rows = (int64_t)rows;   // a short last chunk keeps the full-chunk layer stride
     w.n_hidden = N; w.k0 = c->k0; w.k0pad = k0ld;
     // (splits x (N+1)) workgroups of 8 waves, one per CU at a time: fill the chip in whole rounds
-    int splits = b16 ? c->n_cu / N : (2 * c->n_cu) / (N + 1);
-    if (splits > (int)(w.rows / 256)) splits = (int)(w.rows / 256);
-    if (splits < 1) splits = 1;
-    if (splits > kSplits) splits = kSplits;
-    w.n_splits = splits;
-    int64_t rps = (w.rows + splits - 1) / splits;
-    rps = (rps + 63) / 64 * 64;        // whole 32-/64-sample stages
-    w.rows_per_split = (int)rps;
+    const WgradSplit sp = wgrad_split(w.rows, b16 ? c->n_cu / N : (2 * c->n_cu) / (N + 1), kSplits, kSmallBlocks);
+    w.n_splits = (int)sp.splits;
+    w.rows_per_split = (int)sp.rows_per_split;
     w.partial = partial; w.partial2 = partial2; w.partial_s = partial_s; w.debug = a.debug; w.small_groups = sg ? 1 : 0;
     w.gmax = a.gmax; w.stash_esz = (int)esz; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = enc16 ? 1 : 0; w.coef_cols = a.coef_cols;
     w.dod = split ? a.dod : nullptr; w.gpr = a.s_pad / GROUP; w.group0 = t0 * (TILE / GROUP); w.group_ray = goff ? a.group_ray : nullptr;
     w.n_groups_valid = goff ? a.n_total / GROUP : n_rays * (int64_t)(a.s_pad / GROUP);
     w.dsz = dsz;
     ReduceArgs rd = {};
-    rd.partial = partial; rd.partial2 = partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = k0ld; rd.n_splits = splits;
+    rd.partial = partial; rd.partial2 = partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = k0ld; rd.n_splits = w.n_splits;
     rd.grad = grad_flat; rd.hidden_only = b16 ? 1 : 0; rd.partial_s = partial_s;
-    // records (every one is written, possibly with zero rows): a block per ~4 groups of a small list, so that a sparse grid iteration (a few hundred
-    // groups) does not write and sum 1 024 records of which most are zeros
-    rd.n_small = (int)std::min<int64_t>(kSmallBlocks, std::max<int64_t>(64, (w.rows / GROUP + 3) / 4));
+    rd.n_small = (int)sp.n_small;      // records (every one is written, possibly with zero rows)
     rd.gmax = a.gmax; rd.scale_shift = s8 ? AFX_S8_JSHIFT : 0; rd.layer0_mfma = enc16 ? 1 : 0;
     rd.w0 = c->coef_params; rd.d_coef = c->d_coef; rd.coef_cols = a.coef_cols;
     rd.dsz = dsz;
-    if (!b16) rc = F == 64 ? launch_wgrad_t<64>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad_t<128>(c, w, rd, N, ws_st) : launch_wgrad_t<256>(c, w, rd, N, ws_st));
-    else if (s8) rc = F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, ws_st) : launch_wgrad8_t<256>(c, w, rd, N, ws_st));
-    else if (h16) rc = F == 64 ? launch_wgrad16_t<64, true>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad16_t<128, true>(c, w, rd, N, ws_st) : launch_wgrad16_t<256, true>(c, w, rd, N, ws_st));
-    else rc = F == 64 ? launch_wgrad16_t<64, false>(c, w, rd, N, ws_st) : (F == 128 ? launch_wgrad16_t<128, false>(c, w, rd, N, ws_st) : launch_wgrad16_t<256, false>(c, w, rd, N, ws_st));
+    rc = with_width(c, [&](auto f) {
+      constexpr int FW = decltype(f)::value;
+      if (!b16) return launch_wgrad_t<FW>(c, w, rd, N, ws_st);
+      if (s8) return launch_wgrad8_t<FW>(c, w, rd, N, ws_st);
+      return h16 ? launch_wgrad16_t<FW, true>(c, w, rd, N, ws_st) : launch_wgrad16_t<FW, false>(c, w, rd, N, ws_st);
+    });
     if (rc) return rc;
     if (nbuf == 2) HIPCHK(hipEventRecord(c->ev_wgrad[bI], c->side));
   }
@@ -885,31 +906,84 @@ static int packed_step(afx_ctx* c, int prec, const void* prepared, const float* 
   return run_backward(c, prec, a, dod_bytes + od_bytes, (char*)workspace, workspace_bytes, grad_flat, st, true, n_rays, group_offsets, dsz);
 }
 
-// ---- hierarchical training step with coarse re-use
-// Bytes of one sample set of a ray chunk (rows padded to whole tiles): 8-bit H_l and dZ'_l planes (N + 1 each: H_N is stashed here), group exponents,
-// dL/draw per row, the tiles' mask images, the group records.
-static size_t hier_set_bytes(const afx_ctx* c, size_t rows) {
-  const size_t F = c->d.width, N = c->d.n_hidden, tiles = rows / 256;
-  return 2 * (N + 1) * rows * F + rup64(rows * 4, 256) + rows * 4 + tiles * (N + 1) * c->nt * 1024 + rup64((rows / 32) * (3 * F + 8) * 4, 256) +
-         rup64(N * (rows / 32) * 4, 256);      // + H block scales
-}
-static size_t hier_fixed_bytes(const afx_ctx* c, int64_t n_rays, int S, int NF) {
+// ---- the deferred-output 8-bit-stash steps (hierarchical, single-evaluation): PHASE 1 stashes H_l (H_N too) and the masks, a composite kernel
+// leaves the finished dL/draw per row, PHASE 2 and the weight gradients follow (output layer from the stash of H_N, k_wout_stash8).
+// One sample set of `rows` rows (whole 256-sample tiles): 8-bit H_l and dZ'_l planes (N + 1 each), group exponents, dL/draw per row, the tiles'
+// mask images, the group records, the H block scales.
+struct StashSet { char *stash_h, *stash_dz, *gexp, *masks, *hexp; float *gpart, *records; int64_t rows; };
+static StashSet carve_stash_set(const afx_ctx* c, size_t rows, Carve& w) {
   const size_t F = c->d.width, N = c->d.n_hidden;
-  size_t b = 2 * rup64((size_t)n_rays * S * 4, 256) + 2 * rup64((size_t)n_rays * NF * 4, 256);                    // sigma / tau of the coarse set, new depths, sigma of the new set
-  b += rup64((size_t)n_rays * (size_t)(std::max(s_pad_of(S), s_pad_of(NF)) / GROUP) * 4, 256);                    // optical-depth partials (written by PHASE 1, unused here)
-  b += rup64((N + 2) * (size_t)kSplits * F * F * 4, 256) + rup64((N + 2) * (size_t)kSplits * (F + 4) * 4, 256);
-  b += rup64((size_t)kSmallBlocks * (F * 16 + 2 * F + 4) * 4, 256) + 256;
+  StashSet b;
+  b.rows = (int64_t)rows;
+  b.stash_h = w.take((N + 1) * rows * F); b.stash_dz = w.take((N + 1) * rows * F);
+  b.gexp = w.take(rows * 4); b.gpart = w.take<float>(rows * 4);
+  b.masks = w.take((rows / 256) * (N + 1) * c->nt * 1024);
+  b.records = w.take<float>((rows / 32) * (3 * F + 8) * 4);
+  b.hexp = w.take(N * (rows / 32) * 4);
   return b;
+}
+// ... and their weight-gradient scratch: per-split partials, the records' partial sums, the max |dL/draw| word
+struct Wgrad8Scratch { float *partial, *partial2, *partial_s; uint32_t* gmax; };
+static Wgrad8Scratch carve_wgrad8_scratch(const afx_ctx* c, Carve& w) {
+  const size_t F = c->d.width, N = c->d.n_hidden;
+  Wgrad8Scratch p;
+  p.partial = w.take<float>((N + 2) * (size_t)kSplits * F * F * 4);
+  p.partial2 = w.take<float>((N + 2) * (size_t)kSplits * (F + 4) * 4);
+  p.partial_s = w.take<float>((size_t)kSmallBlocks * (F * 16 + 2 * F + 4) * 4);
+  p.gmax = w.take<uint32_t>(256);
+  return p;
+}
+// The weight gradients of a set: k_wgrad_s8 over its first `rows` rows, k_wout_stash8 and the reductions into grad_flat.  n_small: the record
+// count, which fixes the order of the fp32 sums (each step keeps its own); dsz: the device-resident sizes of a capacity launch, or null.
+static int launch_wgrad8_set(afx_ctx* c, const StashSet& b, const Wgrad8Scratch& p, int64_t rows, int n_small, const int64_t* dsz,
+                             float* grad_flat, hipStream_t st) {
+  const int N = c->d.n_hidden;
+  const WgradSplit sp = wgrad_split(rows, c->n_cu / N, kSplits, kSmallBlocks);
+  WgradArgs w = {};      // (zero: fields these steps do not use read as "off")
+  w.stash_h = (float*)b.stash_h; w.stash_dz = (float*)b.stash_dz; w.graw = (float*)b.gexp; w.gexp = (int32_t*)b.gexp; w.hexp = (uint32_t*)b.hexp;
+  w.rows = rows; w.stride_rows = b.rows;
+  w.n_hidden = N; w.k0 = c->k0; w.k0pad = 16;
+  w.n_splits = (int)sp.splits; w.rows_per_split = (int)sp.rows_per_split;
+  w.partial = p.partial; w.partial2 = p.partial2; w.partial_s = p.partial_s; w.small_groups = 1;
+  w.gmax = p.gmax; w.stash_esz = 1; w.gpr = 1;
+  w.records = b.records; w.no_sw = 1; w.gfull = b.gpart;
+  w.dsz = dsz;
+  ReduceArgs rd = {};
+  rd.partial = p.partial; rd.partial2 = p.partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = 16; rd.n_splits = w.n_splits;
+  rd.grad = grad_flat; rd.hidden_only = 1; rd.partial_s = p.partial_s; rd.n_small = n_small;
+  rd.gmax = p.gmax; rd.scale_shift = AFX_S8_JSHIFT;
+  rd.dsz = dsz;
+  return with_width(c, [&](auto f) { return launch_wgrad8_t<decltype(f)::value>(c, w, rd, N, st); });
+}
+
+// ---- hierarchical training step with coarse re-use
+// Its workspace outside the two sample sets: sigma / tau of the coarse set, new depths, sigma of the new set, the optical-depth partials (written
+// by PHASE 1, unused here), the weight-gradient scratch.
+struct HierFixed { float *sigA, *tauA, *zf, *sigB, *od_part; Wgrad8Scratch p; };
+static HierFixed carve_hier_fixed(const afx_ctx* c, int64_t R, int S, int NF, Carve& w) {
+  HierFixed h;
+  h.sigA = w.take<float>((size_t)R * S * 4); h.tauA = w.take<float>((size_t)R * S * 4);
+  h.zf = w.take<float>((size_t)R * NF * 4); h.sigB = w.take<float>((size_t)R * NF * 4);
+  h.od_part = w.take<float>((size_t)R * (size_t)(std::max(s_pad_of(S), s_pad_of(NF)) / GROUP) * 4);
+  h.p = carve_wgrad8_scratch(c, w);
+  return h;
+}
+// rays per chunk: a multiple of 8 (so that a chunk's first sample of either set starts a 256-sample tile), both sets' planes below 4 GiB
+static int64_t hier_max_rays(const afx_ctx* c, int64_t R, int S) {
+  return std::min<int64_t>((R + 7) / 8 * 8, stash_max_rows(c, 1, 1) / s_pad_of(S) / 8 * 8);
+}
+// the workspace of chunks of nr rays (+ 4 KiB slack)
+static size_t hier_bytes(const afx_ctx* c, int64_t R, int S, int NF, int64_t nr) {
+  Carve w;
+  carve_hier_fixed(c, R, S, NF, w);
+  carve_stash_set(c, rup64((size_t)nr * s_pad_of(S), 256), w);
+  carve_stash_set(c, rup64((size_t)nr * s_pad_of(NF), 256), w);
+  return w.end + 4096;
 }
 
 extern "C" int64_t afx_hier_workspace_bytes(const afx_ctx* c, int64_t n_rays, int32_t n_coarse, int32_t n_fine) {
   if (!c || n_rays <= 0) return 0;
-  const uint64_t plane_rows = ((uint64_t)1 << 32) / (uint64_t)c->d.width;
-  int64_t nr = (n_rays + 7) / 8 * 8;
-  const int64_t cap = (int64_t)(plane_rows / (uint64_t)s_pad_of(n_coarse)) / 8 * 8;
-  if (nr > cap) nr = cap;
-  return (int64_t)(hier_fixed_bytes(c, n_rays, n_coarse, n_fine) + hier_set_bytes(c, rup64((size_t)nr * s_pad_of(n_coarse), 256)) +
-                   hier_set_bytes(c, rup64((size_t)nr * s_pad_of(n_fine), 256)) + 4096);
+  return (int64_t)hier_bytes(c, n_rays, n_coarse, n_fine, hier_max_rays(c, n_rays, n_coarse));
 }
 
 extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepared, const afx_render_args* r, int32_t n_fine, const float* u,
@@ -926,16 +1000,10 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
   if (S < 3 || S > AFX_MAX_COARSE || NF < 1 || NF > AFX_MAX_FINE) return fail(AFX_E_INVALID, "afx_hier_train_step_mse: n_coarse in 3..%d, n_fine in 1..%d", AFX_MAX_COARSE, AFX_MAX_FINE);
   if (NF < 2) return fail(AFX_E_INVALID, "afx_hier_train_step_mse: n_fine must be >= 2");
   hipStream_t st = (hipStream_t)stream;
-  const int F = c->d.width, N = c->d.n_hidden;
   const int64_t R = r->n_rays, spA = s_pad_of(S), spB = s_pad_of(NF);
-  char* ws = (char*)r->workspace;
-  const size_t fixed = hier_fixed_bytes(c, R, S, NF);
-  if (r->workspace_bytes < fixed + 4096) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace %zu too small", r->workspace_bytes);
-  // rays per chunk: a multiple of 8 (so that a chunk's first sample of either set starts a 256-sample tile), both sets' planes below 4 GiB
-  const uint64_t plane_rows = ((uint64_t)1 << 32) / (uint64_t)F;
-  int64_t nr = (R + 7) / 8 * 8;
-  nr = std::min<int64_t>(nr, (int64_t)(plane_rows / (uint64_t)spA) / 8 * 8);
-  while (nr >= 8 && fixed + hier_set_bytes(c, rup64((size_t)nr * spA, 256)) + hier_set_bytes(c, rup64((size_t)nr * spB, 256)) + 4096 > r->workspace_bytes) {
+  if (r->workspace_bytes < hier_bytes(c, R, S, NF, 0)) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace %zu too small", r->workspace_bytes);
+  int64_t nr = hier_max_rays(c, R, S);
+  while (nr >= 8 && hier_bytes(c, R, S, NF, nr) > r->workspace_bytes) {
     if (nr == 8) { nr = 0; break; }
     const int64_t n_chunks = (R + nr - 1) / nr + 1;          // next larger chunk count, equal chunks
     const int64_t next = ((R + n_chunks - 1) / n_chunks + 7) / 8 * 8;
@@ -943,38 +1011,22 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
   }
   if (nr < 8) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace %zu too small for 8 rays per chunk", r->workspace_bytes);
   if (int rc2 = check_dev(c, "afx_hier_train_step_mse")) return rc2;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = ws + off; off += rup64(bytes, 256); return p; };
-  float* sigA = (float*)take((size_t)R * S * 4);  float* tauA = (float*)take((size_t)R * S * 4);
-  float* zf = (float*)take((size_t)R * NF * 4);   float* sigB = (float*)take((size_t)R * NF * 4);
-  float* od_part = (float*)take((size_t)R * (size_t)(std::max(spA, spB) / GROUP) * 4);
-  float* partial = (float*)take((size_t)(N + 2) * kSplits * F * F * 4);
-  float* partial2 = (float*)take((size_t)(N + 2) * kSplits * (F + 4) * 4);
-  float* partial_s = (float*)take((size_t)kSmallBlocks * (F * 16 + 2 * F + 4) * 4);
-  uint32_t* gmax = (uint32_t*)take(256);
-  struct SetBuf { char *stash_h, *stash_dz, *gexp, *masks, *hexp; float *gpart, *records; size_t rows; };
-  auto carve = [&](size_t rows) {
-    SetBuf b; b.rows = rows;
-    b.stash_h = take((size_t)(N + 1) * rows * F); b.stash_dz = take((size_t)(N + 1) * rows * F);
-    b.gexp = take(rows * 4); b.gpart = (float*)take(rows * 4);
-    b.masks = take((rows / 256) * (size_t)(N + 1) * c->nt * 1024);
-    b.records = (float*)take((rows / 32) * (size_t)(3 * F + 8) * 4);
-    b.hexp = take((size_t)N * (rows / 32) * 4);
-    return b;
-  };
-  const SetBuf A = carve(rup64((size_t)nr * spA, 256)), B = carve(rup64((size_t)nr * spB, 256));
-  if (off > r->workspace_bytes) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace layout exceeds the buffer (%zu > %zu)", off, r->workspace_bytes);
+  Carve w{(uintptr_t)r->workspace};
+  const HierFixed h = carve_hier_fixed(c, R, S, NF, w);
+  const StashSet A = carve_stash_set(c, rup64((size_t)nr * spA, 256), w), B = carve_stash_set(c, rup64((size_t)nr * spB, 256), w);
+  if (w.end > r->workspace_bytes) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace layout exceeds the buffer (%zu > %zu)", w.end, r->workspace_bytes);
+  float *sigA = h.sigA, *tauA = h.tauA, *zf = h.zf, *sigB = h.sigB;
 
   ChainArgs base = {};
   fill_model(c, prec, true, prepared, base);
   fill_render(r, base);
   base.fused = 0; base.stash8 = 1; base.coef_cols = 0; base.debug = 0; base.persistent = 1;
-  base.od_part = od_part; base.gmax = gmax; base.defer_out = 1; base.dod = nullptr; base.pixel = r->pixel;
-  auto set_args = [&](const ChainArgs& src, const SetBuf& b, int64_t r0, int64_t r1, int64_t sp) {
+  base.od_part = h.od_part; base.gmax = h.p.gmax; base.defer_out = 1; base.dod = nullptr; base.pixel = r->pixel;
+  auto set_args = [&](const ChainArgs& src, const StashSet& b, int64_t r0, int64_t r1, int64_t sp) {
     ChainArgs a = src;
     a.tile0 = (int)(r0 * sp / 256); a.tile1 = (int)((r1 * sp + 255) / 256);
     a.stash_h = (float*)b.stash_h; a.stash_dz = (float*)b.stash_dz; a.stash_e = nullptr; a.graw = (float*)b.gexp; a.gexp = (int32_t*)b.gexp;
-    a.gpart = b.gpart; a.masks = b.masks; a.small_part = b.records; a.stash_rows = (int64_t)b.rows; a.hexp = (uint32_t*)b.hexp;
+    a.gpart = b.gpart; a.masks = b.masks; a.small_part = b.records; a.stash_rows = b.rows; a.hexp = (uint32_t*)b.hexp;
     return a;
   };
   ChainArgs argsA = base;                     // the coarse set: the caller's depths
@@ -982,27 +1034,6 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
   ChainArgs argsB = base;                     // the new set: per-ray depths zf[R, NF]
   argsB.depth_mode = AFX_DEPTH_PER_RAY_Z; argsB.z = zf; argsB.n_samples = NF; argsB.s_pad = (int)spB; argsB.n_total = R * spB;
   argsB.sigma = sigB; argsB.tau = nullptr;
-  auto wgrad_set = [&](const ChainArgs& a, const SetBuf& b) -> int {
-    WgradArgs w = {};
-    w.stash_h = a.stash_h; w.stash_dz = a.stash_dz; w.stash_e = nullptr; w.graw = a.graw;
-    w.rows = (int64_t)(a.tile1 - a.tile0) * 256; w.stride_rows = (int64_t)b.rows;
-    w.n_hidden = N; w.k0 = c->k0; w.k0pad = 16;
-    int splits = c->n_cu / N;
-    if (splits > (int)(w.rows / 256)) splits = (int)(w.rows / 256);
-    if (splits < 1) splits = 1;
-    if (splits > kSplits) splits = kSplits;
-    w.n_splits = splits;
-    w.rows_per_split = (int)(((w.rows + splits - 1) / splits + 63) / 64 * 64);
-    w.partial = partial; w.partial2 = partial2; w.partial_s = partial_s; w.debug = 0; w.small_groups = 1;
-    w.gmax = gmax; w.stash_esz = 1; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = 0; w.coef_cols = 0;
-    w.dod = nullptr; w.gpr = 1; w.group0 = 0; w.n_groups_valid = 0; w.group_ray = nullptr;
-    w.records = b.records; w.no_sw = 1; w.gfull = b.gpart;
-    ReduceArgs rd = {};
-    rd.partial = partial; rd.partial2 = partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = 16; rd.n_splits = splits;
-    rd.grad = grad_flat; rd.hidden_only = 1; rd.partial_s = partial_s; rd.n_small = kSmallBlocks;
-    rd.gmax = gmax; rd.scale_shift = AFX_S8_JSHIFT; rd.layer0_mfma = 0; rd.w0 = nullptr; rd.d_coef = nullptr; rd.coef_cols = 0;
-    return F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, st) : launch_wgrad8_t<256>(c, w, rd, N, st));
-  };
   for (int64_t r0 = 0; r0 < R; r0 += nr) {
     const int64_t r1 = std::min<int64_t>(r0 + nr, R), n = r1 - r0;
     const ChainArgs a = set_args(argsA, A, r0, r1, spA), b = set_args(argsB, B, r0, r1, spB);
@@ -1014,12 +1045,12 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
     if ((rc = launch_chain(c, prec, true, b, st, 1))) return rc;
     hipLaunchKernelGGL(k_hier_composite, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a, r0, n, (const float*)zf, NF, (const float*)sigA, (const float*)sigB,
                        target, inv_n, r->pixel, A.gpart, (int)spA, B.gpart, (int)spB, z_all);
-    HIPCHK(hipMemsetAsync(gmax, 0, 4, st));
+    HIPCHK(hipMemsetAsync(h.p.gmax, 0, 4, st));
     // backward halves (dL/draw per sample comes finished from the composite), then the weight gradients of both sets
     if ((rc = launch_chain(c, prec, true, a, st, 2))) return rc;
     if ((rc = launch_chain(c, prec, true, b, st, 2))) return rc;
-    if ((rc = wgrad_set(a, A))) return rc;
-    if ((rc = wgrad_set(b, B))) return rc;
+    if ((rc = launch_wgrad8_set(c, A, h.p, (int64_t)(a.tile1 - a.tile0) * 256, kSmallBlocks, nullptr, grad_flat, st))) return rc;
+    if ((rc = launch_wgrad8_set(c, B, h.p, (int64_t)(b.tile1 - b.tile0) * 256, kSmallBlocks, nullptr, grad_flat, st))) return rc;
   }
   HIPCHK(hipGetLastError());
   return AFX_OK;
@@ -1196,18 +1227,16 @@ extern "C" int afx_grid_pack(const afx_grid_desc* grid, const uint8_t* binary, u
 }
 
 // ---- the grid refresh on the device (afx_grid_select_cells, afx_grid_refresh)
-struct SelLayout { size_t o_word_pre, o_block_tot, o_block_pre, o_n_occ, total; int64_t n_words, nb; };
-static SelLayout sel_layout(int64_t nc) {
-  SelLayout L;
-  L.n_words = (nc + 31) / 32;
-  L.nb = (L.n_words + SEL_WORDS - 1) / SEL_WORDS;
-  size_t o = 0;
-  L.o_word_pre = o; o = rup64(o + (size_t)L.n_words * 4, 256);
-  L.o_block_tot = o; o = rup64(o + (size_t)L.nb * 4, 256);
-  L.o_block_pre = o; o = rup64(o + (size_t)L.nb * 4, 256);
-  L.o_n_occ = o; o = rup64(o + 8, 256);
-  L.total = o;
-  return L;
+struct SelBufs { int32_t *word_pre, *block_tot, *block_pre; int64_t* n_occ; int64_t n_words, nb; };
+static SelBufs carve_select(int64_t nc, Carve& w) {
+  SelBufs b;
+  b.n_words = (nc + 31) / 32;
+  b.nb = (b.n_words + SEL_WORDS - 1) / SEL_WORDS;
+  b.word_pre = w.take<int32_t>((size_t)b.n_words * 4);
+  b.block_tot = w.take<int32_t>((size_t)b.nb * 4);
+  b.block_pre = w.take<int32_t>((size_t)b.nb * 4);
+  b.n_occ = w.take<int64_t>(8);
+  return b;
 }
 // cells whose index fits the int32 cell lists and n_draw in 1..num_cells
 static int check_select(const afx_grid_desc* grid, int64_t n_draw, const char* who, int64_t* nc) {
@@ -1222,14 +1251,11 @@ static int check_step(int64_t step, const int64_t* step_dev, const char* who) {
 }
 // the three selection kernels (sizes checked by the caller)
 static int launch_select(int64_t nc, const uint32_t* bits, int64_t n_draw, uint64_t seed, uint64_t stream_id,
-                         const int64_t* step_dev, int32_t* cells, int64_t* count_dev, char* ws, hipStream_t st) {
-  const SelLayout L = sel_layout(nc);
-  int32_t *word_pre = (int32_t*)(ws + L.o_word_pre), *block_tot = (int32_t*)(ws + L.o_block_tot), *block_pre = (int32_t*)(ws + L.o_block_pre);
-  int64_t* n_occ = (int64_t*)(ws + L.o_n_occ);
-  hipLaunchKernelGGL(k_grid_occ_count, dim3((unsigned)L.nb), dim3(256), 0, st, bits, nc, L.n_words, word_pre, block_tot);
-  hipLaunchKernelGGL(k_grid_occ_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)block_tot, L.nb, block_pre, n_draw, n_occ, count_dev);
-  hipLaunchKernelGGL(k_grid_select, blocks_for(2 * n_draw), dim3(256), 0, st, bits, nc, L.n_words, (const int32_t*)word_pre,
-                     (const int32_t*)block_pre, L.nb, n_draw, seed, stream_id, step_dev, (const int64_t*)n_occ, cells);
+                         const int64_t* step_dev, int32_t* cells, int64_t* count_dev, const SelBufs& L, hipStream_t st) {
+  hipLaunchKernelGGL(k_grid_occ_count, dim3((unsigned)L.nb), dim3(256), 0, st, bits, nc, L.n_words, L.word_pre, L.block_tot);
+  hipLaunchKernelGGL(k_grid_occ_scan, dim3(1), dim3(1024), 0, st, (const int32_t*)L.block_tot, L.nb, L.block_pre, n_draw, L.n_occ, count_dev);
+  hipLaunchKernelGGL(k_grid_select, blocks_for(2 * n_draw), dim3(256), 0, st, bits, nc, L.n_words, (const int32_t*)L.word_pre,
+                     (const int32_t*)L.block_pre, L.nb, n_draw, seed, stream_id, step_dev, (const int64_t*)L.n_occ, cells);
   HIPCHK(hipGetLastError());
   return AFX_OK;
 }
@@ -1237,7 +1263,9 @@ static int launch_select(int64_t nc, const uint32_t* bits, int64_t n_draw, uint6
 extern "C" size_t afx_grid_select_workspace_bytes(const afx_grid_desc* grid) {
   int64_t nc;
   if (check_grid(grid, "afx_grid_select_workspace_bytes", &nc)) return 0;
-  return sel_layout(nc).total;
+  Carve w;
+  carve_select(nc, w);
+  return w.end;
 }
 
 extern "C" int afx_grid_select_cells(const afx_grid_desc* grid, const uint32_t* bits, int64_t n_draw, uint64_t seed, int64_t step,
@@ -1248,65 +1276,67 @@ extern "C" int afx_grid_select_cells(const afx_grid_desc* grid, const uint32_t* 
   if (int rc = check_select(grid, n_draw, who, &nc)) return rc;
   if (!bits || !cells_out || !count_dev || !workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
   if (int rc = check_step(step, step_dev, who)) return rc;
-  const size_t need = sel_layout(nc).total;
-  if (workspace_bytes < need) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+  Carve w{(uintptr_t)workspace};
+  const SelBufs b = carve_select(nc, w);
+  if (workspace_bytes < w.end) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.end);
   const uint64_t sid = AFX_GRID_SELECT_TAG | (step_dev ? 0 : (uint64_t)step);
-  return launch_select(nc, bits, n_draw, seed, sid, step_dev, cells_out, count_dev, (char*)workspace, (hipStream_t)stream);
+  return launch_select(nc, bits, n_draw, seed, sid, step_dev, cells_out, count_dev, b, (hipStream_t)stream);
 }
 
 // workspace of afx_grid_refresh: [cells (draw) | points | occupancies | occs snapshot | 256 partial sums | count (draw) | selection (draw)]
-struct RefreshLayout { size_t o_cells, o_pts, o_occ, o_scratch, o_partial, o_count, o_sel, total; int64_t cap; };
-static int refresh_layout(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells, RefreshLayout& L, int64_t* nc, const char* who) {
+struct RefreshBufs { int32_t* cells; float *pts, *occ, *scratch; double* partial; int64_t* count; SelBufs sel; int64_t cap; };
+static int carve_refresh(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells, Carve& w, RefreshBufs& b, int64_t* nc, const char* who) {
   if (all_cells) {
     if (int rc = check_grid(grid, who, nc)) return rc;
     if (*nc > (int64_t)INT32_MAX) return fail(AFX_E_INVALID, "%s: %lld cells do not fit the int32 cell lists", who, (long long)*nc);
   } else if (int rc = check_select(grid, n_draw, who, nc)) {
     return rc;
   }
-  L.cap = all_cells ? *nc : 2 * n_draw;
-  if (L.cap > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "%s: %lld points exceed afx_mlp_infer's 2^31 - 256 per call", who, (long long)L.cap);
-  size_t o = 0;
-  L.o_cells = o; o = rup64(o + (all_cells ? 0 : (size_t)L.cap * 4), 256);
-  L.o_pts = o; o = rup64(o + (size_t)L.cap * 12, 256);
-  L.o_occ = o; o = rup64(o + (size_t)L.cap * 4, 256);
-  L.o_scratch = o; o = rup64(o + (size_t)*nc * 4, 256);
-  L.o_partial = o; o = rup64(o + 256 * 8, 256);
-  L.o_count = o; o = rup64(o + (all_cells ? 0 : 8), 256);
-  L.o_sel = o; o += all_cells ? 0 : sel_layout(*nc).total;
-  L.total = o;
+  b.cap = all_cells ? *nc : 2 * n_draw;
+  if (b.cap > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "%s: %lld points exceed afx_mlp_infer's 2^31 - 256 per call", who, (long long)b.cap);
+  int32_t* cells = w.take<int32_t>(all_cells ? 0 : (size_t)b.cap * 4);
+  b.pts = w.take<float>((size_t)b.cap * 12);
+  b.occ = w.take<float>((size_t)b.cap * 4);
+  b.scratch = w.take<float>((size_t)*nc * 4);
+  b.partial = w.take<double>(256 * 8);
+  int64_t* count = w.take<int64_t>(all_cells ? 0 : 8);
+  b.cells = all_cells ? nullptr : cells;
+  b.count = all_cells ? nullptr : count;
+  b.sel = all_cells ? SelBufs{} : carve_select(*nc, w);
   return AFX_OK;
 }
 
 extern "C" int64_t afx_grid_refresh_workspace_bytes(const afx_grid_desc* grid, int64_t n_draw, int32_t all_cells) {
-  RefreshLayout L;
+  Carve w;
+  RefreshBufs b;
   int64_t nc;
-  if (refresh_layout(grid, n_draw, all_cells, L, &nc, "afx_grid_refresh_workspace_bytes")) return -1;
-  return (int64_t)L.total;
+  if (carve_refresh(grid, n_draw, all_cells, w, b, &nc, "afx_grid_refresh_workspace_bytes")) return -1;
+  return (int64_t)w.end;
 }
 
 extern "C" int afx_grid_refresh(afx_ctx* c, int prec, const void* prepared, const afx_grid_refresh_args* a, void* stream) {
   const char* who = "afx_grid_refresh";
   if (!c || !prepared || !a) return fail(AFX_E_INVALID, "%s: null argument", who);
   if (check_prec(prec, who)) return AFX_E_INVALID;
-  RefreshLayout L;
+  Carve w{(uintptr_t)a->workspace};
+  RefreshBufs L;
   int64_t nc;
-  if (int rc = refresh_layout(&a->grid, a->n_draw, a->all_cells, L, &nc, who)) return rc;
+  if (int rc = carve_refresh(&a->grid, a->n_draw, a->all_cells, w, L, &nc, who)) return rc;
   if (!a->occs || !a->binary || !a->bits || !a->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
   if (int rc = check_step(a->step, a->step_dev, who)) return rc;
-  if (a->workspace_bytes < L.total) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_grid_refresh_workspace_bytes)", who,
-                                                a->workspace_bytes, L.total);
+  if (a->workspace_bytes < w.end) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_grid_refresh_workspace_bytes)", who,
+                                              a->workspace_bytes, w.end);
   if (int rc = check_dev(c, who)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)a->workspace;
-  int32_t* cells = a->all_cells ? nullptr : (int32_t*)(ws + L.o_cells);
-  float *pts = (float*)(ws + L.o_pts), *occ = (float*)(ws + L.o_occ), *scratch = (float*)(ws + L.o_scratch);
-  int64_t* count = a->all_cells ? nullptr : (int64_t*)(ws + L.o_count);
+  int32_t* cells = L.cells;
+  float *pts = L.pts, *occ = L.occ, *scratch = L.scratch;
+  int64_t* count = L.count;
   const uint64_t step_host = a->step_dev ? 0 : (uint64_t)a->step;
   const GridDesc g = grid_of(&a->grid);
   int rc;
   // 1. the cells (the draw: count on the device)
   if (!a->all_cells &&
-      (rc = launch_select(nc, a->bits, a->n_draw, a->seed, AFX_GRID_SELECT_TAG | step_host, a->step_dev, cells, count, ws + L.o_sel, st)))
+      (rc = launch_select(nc, a->bits, a->n_draw, a->seed, AFX_GRID_SELECT_TAG | step_host, a->step_dev, cells, count, L.sel, st)))
     return rc;
   // 2. one jittered point per cell
   hipLaunchKernelGGL(k_grid_points, blocks_for(L.cap), dim3(256), 0, st, (const int32_t*)cells, L.cap, (const float*)nullptr, a->seed,
@@ -1327,7 +1357,7 @@ extern "C" int afx_grid_refresh(afx_ctx* c, int prec, const void* prepared, cons
   hipLaunchKernelGGL(k_grid_ema, blocks_for(L.cap), dim3(256), 0, st, a->occs, (const int32_t*)cells, (const float*)occ, L.cap, (const int64_t*)count);
   HIPCHK(hipGetLastError());
   // 5. threshold and bitfield (afx_grid_binarize)
-  return afx_grid_binarize(&a->grid, a->occs, a->occ_thre, a->binary, a->bits, (double*)(ws + L.o_partial), stream);
+  return afx_grid_binarize(&a->grid, a->occs, a->occ_thre, a->binary, a->bits, L.partial, stream);
 }
 
 static int fill_march(const afx_march_args* m, MarchArgs& a, const char* who) {
@@ -1546,20 +1576,18 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
     return fail(AFX_E_INVALID, "afx_march_train_step_mse: null argument");
   if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "afx_march_train_step_mse: AFX_PREC_F16S8 only");
   if (int rc = check_dev(c, "afx_march_train_step_mse")) return rc;
-  char* ws = (char*)t->workspace;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
+  // carved in stages as the sizes become known; a stage that does not fit reports what the call needs so far
+  Carve w{(uintptr_t)t->workspace};
   auto too_small = [&](size_t more) {
-    t->workspace_needed = off + more + 4096;
+    t->workspace_needed = w.end + more + 4096;
     return fail(AFX_E_WORKSPACE, "afx_march_train_step_mse: workspace %zu < %zu bytes", t->workspace_bytes, t->workspace_needed);
   };
   // 1. candidates: steps of the march whose cell is occupied
-  const size_t o_counts = take((size_t)R * 4), o_offsets = take((size_t)(R + 1) * 8), o_totals = take(4 * 8);
-  const size_t o_counts2 = take((size_t)R * 4), o_off2 = take((size_t)(R + 1) * 8), o_goff = take((size_t)(R + 1) * 8);
-  if (off > t->workspace_bytes) return too_small(0);
-  int32_t* counts = (int32_t*)(ws + o_counts);
-  int64_t* offsets = (int64_t*)(ws + o_offsets);
-  int64_t* totals = (int64_t*)(ws + o_totals);
+  int32_t* counts = w.take<int32_t>((size_t)R * 4);
+  int64_t *offsets = w.take<int64_t>((size_t)(R + 1) * 8), *totals = w.take<int64_t>(4 * 8);
+  int32_t* counts2 = w.take<int32_t>((size_t)R * 4);
+  int64_t *off2 = w.take<int64_t>((size_t)(R + 1) * 8), *goff = w.take<int64_t>((size_t)(R + 1) * 8);
+  if (w.end > t->workspace_bytes) return too_small(0);
   int rc;
   // The two size read-backs (offsets_read_back: a mapped mailbox the host polls)
   int64_t h[4] = {0, 0, 0, 0};
@@ -1572,34 +1600,29 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
   t->n_candidates = n;
   if (n == 0) return AFX_OK;
   if (n > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "afx_march_train_step_mse: %lld candidates", (long long)n);
-  const size_t o_ri = take((size_t)n * 4), o_ts = take((size_t)n * 4), o_te = take((size_t)n * 4), o_pts = take((size_t)n * 12),
-               o_raw = take((size_t)n * 4), o_keep = take((size_t)n);
-  if (off > t->workspace_bytes) return too_small(0);
-  int32_t* ri = (int32_t*)(ws + o_ri);
-  float *ts = (float*)(ws + o_ts), *te = (float*)(ws + o_te), *pts = (float*)(ws + o_pts), *raw = (float*)(ws + o_raw);
-  uint8_t* keep = (uint8_t*)(ws + o_keep);
+  int32_t* ri = w.take<int32_t>((size_t)n * 4);
+  float *ts = w.take<float>((size_t)n * 4), *te = w.take<float>((size_t)n * 4), *pts = w.take<float>((size_t)n * 12), *raw = w.take<float>((size_t)n * 4);
+  uint8_t* keep = w.take<uint8_t>((size_t)n);
+  if (w.end > t->workspace_bytes) return too_small(0);
   if ((rc = afx_march_write(&m, offsets, ri, ts, te, pts, stream))) return rc;
   // 2. alpha pass (alpha_fn, nerf_helpers_acc.py:11-25) + render_visibility
   if ((rc = afx_mlp_infer(c, prec, prepared, pts, n, raw, 0, stream))) return rc;
-  int32_t* counts2 = (int32_t*)(ws + o_counts2);
-  int64_t *off2 = (int64_t*)(ws + o_off2), *goff = (int64_t*)(ws + o_goff);
   if ((rc = afx_march_visibility(raw, 0, ts, te, offsets, R, t->early_stop_eps, t->alpha_thre, keep, counts2, stream))) return rc;
   if ((rc = read_totals(counts2, off2, goff, 1))) return rc;      // (the kept count and the group count)
   const int64_t n2 = h[2], ng = h[3];
   t->n_kept = n2; t->n_groups = ng;
   if (n2 == 0) return AFX_OK;            // nothing survived: the reference skips the step (:293)
   // 3. compaction, group-aligned copy, fused training step
-  const size_t o_ri2 = take((size_t)n2 * 4), o_ts2 = take((size_t)n2 * 4), o_te2 = take((size_t)n2 * 4);
-  const size_t o_tsp = take((size_t)ng * 32 * 4), o_tep = take((size_t)ng * 32 * 4), o_gray = take((size_t)ng * 4);
+  int32_t* ri2 = w.take<int32_t>((size_t)n2 * 4);
+  float *ts2 = w.take<float>((size_t)n2 * 4), *te2 = w.take<float>((size_t)n2 * 4);
+  float *tsp = w.take<float>((size_t)ng * 32 * 4), *tep = w.take<float>((size_t)ng * 32 * 4);
+  int32_t* gray = w.take<int32_t>((size_t)ng * 4);
   const size_t step_ws = (size_t)afx_query(c, AFX_Q_BWD_WORKSPACE_FULL, 0, ng * 32, prec) + 4 * (size_t)(R + ng) + 1024;
-  if (off + step_ws > t->workspace_bytes) return too_small(step_ws);
-  int32_t* ri2 = (int32_t*)(ws + o_ri2);
-  float *ts2 = (float*)(ws + o_ts2), *te2 = (float*)(ws + o_te2), *tsp = (float*)(ws + o_tsp), *tep = (float*)(ws + o_tep);
-  int32_t* gray = (int32_t*)(ws + o_gray);
+  if (w.end + step_ws > t->workspace_bytes) return too_small(step_ws);
   if ((rc = afx_march_compact(keep, offsets, off2, R, ts, te, ri2, ts2, te2, stream))) return rc;
   if ((rc = afx_pack_groups(off2, goff, R, ts2, te2, tsp, tep, gray, stream))) return rc;
   return afx_train_step_packed_mse(c, prec, prepared, m.origins, m.dirs, R, goff, gray, ng, tsp, tep, t->target, t->inv_n, t->pixel, t->grad_flat,
-                                   ws + off, t->workspace_bytes - off, stream);
+                                   (char*)t->workspace + w.end, t->workspace_bytes - w.end, stream);
 }
 
 // ---- the same iteration with device-resident sizes (afx_march_train_step_mse_capturable): every buffer is carved for the worst case the march
@@ -1629,74 +1652,100 @@ extern "C" int64_t afx_march_max_steps(const afx_march_args* m) {
   return n;
 }
 
-struct CapLayout {
-  size_t o_counts, o_offsets, o_totals, o_counts2, o_off2, o_goff, o_dsz;
-  size_t o_ri, o_ts, o_te, o_pts, o_raw, o_keep, o_ri2, o_ts2, o_te2, o_tsp, o_tep, o_gray, o_step;
-  size_t total;
-  int64_t n_cap, g_cap;      // candidates (= kept samples) and 32-sample groups of the worst case: every step of every ray occupied
-};
-static int cap_layout(const afx_ctx* c, int prec, int64_t R, int64_t S, CapLayout& L, const char* who) {
+// The device-sized grid steps run the packed step as ONE chunk over the worst case the march allows - n_cap candidates in g_cap 32-sample groups,
+// every step of every ray occupied - so its 8-bit layer plane must stay below 4 GiB.  `step` names the step in the refusal.
+static int grid_step_caps(const afx_ctx* c, int64_t R, int64_t S, const char* who, const char* step, int64_t* n_cap, int64_t* g_cap) {
   if (R <= 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays > 0 and max_steps_per_ray >= 0", who);
-  L.n_cap = R * S;
-  L.g_cap = R * ((S + GROUP - 1) / GROUP);
-  // the packed step runs as ONE chunk, and a chunk's 8-bit layer plane stays below 4 GiB (run_backward): at most 2^32 / width samples
-  const int64_t max_samples = (int64_t)(((uint64_t)1 << 32) / ((uint64_t)256 * c->d.width)) * 256;
-  if (L.g_cap * GROUP > max_samples || L.n_cap > ((int64_t)1 << 31) - 256)
-    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed the capturable step's sample limit (%lld group-padded samples at width %d, one "
-                "chunk of the packed step); use afx_march_train_step_mse or fewer rays per step", who, (long long)R, (long long)S,
+  *n_cap = R * S;
+  *g_cap = R * ((S + GROUP - 1) / GROUP);
+  const int64_t max_samples = stash_max_rows(c, 1, 256);
+  if (*g_cap * GROUP > max_samples || *n_cap > ((int64_t)1 << 31) - 256)
+    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed the %s step's sample limit (%lld group-padded samples at width %d, one "
+                "chunk of the packed step); use afx_march_train_step_mse or fewer rays per step", who, (long long)R, (long long)S, step,
                 (long long)max_samples, c->d.width);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
-  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(4 * 8);
-  L.o_counts2 = take((size_t)R * 4); L.o_off2 = take((size_t)(R + 1) * 8); L.o_goff = take((size_t)(R + 1) * 8); L.o_dsz = take(SZ_COUNT * 8);
-  const size_t n = (size_t)std::max<int64_t>(L.n_cap, 1), g = (size_t)std::max<int64_t>(L.g_cap, 1);
-  L.o_ri = take(n * 4); L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_pts = take(n * 12); L.o_raw = take(n * 4); L.o_keep = take(n);
-  L.o_ri2 = take(n * 4); L.o_ts2 = take(n * 4); L.o_te2 = take(n * 4);
-  L.o_tsp = take(g * 32 * 4); L.o_tep = take(g * 32 * 4); L.o_gray = take(g * 4);
-  L.o_step = off;
+  return AFX_OK;
+}
+
+// The arguments of the device-sized grid steps, checked in this order: pointers, n_rays, precision, (single_eval: ReLU, no input encoding,
+// a far plane), then *S = afx_march_max_steps.
+static int check_grid_step(const afx_ctx* c, int prec, const void* prepared, afx_march_train_args* t, const int64_t* counts_dev,
+                           const float* skip_dev, bool single_eval, const char* who, int64_t* S) {
+  if (!c || !prepared || !t || !counts_dev || !skip_dev) return fail(AFX_E_INVALID, "%s: null argument", who);
+  t->workspace_needed = 0;
+  const afx_march_args& m = t->march;
+  if (m.n_rays <= 0) return fail(AFX_E_INVALID, "%s: n_rays must be > 0", who);
+  if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "%s: AFX_PREC_F16S8 only", who);
+  if (single_eval) {
+    if (c->d.act != AFX_ACT_RELU) return fail(AFX_E_INVALID, "%s: ReLU models only (tanh / sine train in the exact-fp32 kernels)", who);
+    if (c->d.enc != AFX_ENC_NONE)
+      return fail(AFX_E_INVALID, "%s: no input encoding (the deferred output-layer path of the backward half does not carry one); use "
+                  "afx_march_train_step_mse_capturable", who);
+    if (!m.has_far) return fail(AFX_E_INVALID, "%s: the march needs a far plane (the worst-case workspace bound)", who);
+  }
+  *S = afx_march_max_steps(&m);
+  return *S < 0 ? AFX_E_INVALID : AFX_OK;
+}
+
+// A worst-case workspace (carved up to `end`) against the caller's (the shortfall reported in *needed), then the device.
+static int check_carve(const afx_ctx* c, size_t end, size_t bytes, size_t* needed, const char* who, const char* query) {
+  if (end > bytes) {
+    *needed = end;
+    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (%s)", who, bytes, end, query);
+  }
+  return check_dev(c, who);
+}
+
+struct CapBufs {
+  int32_t *counts, *counts2, *ri, *ri2, *gray;
+  int64_t *offsets, *totals, *off2, *goff, *dsz;
+  float *ts, *te, *pts, *raw, *ts2, *te2, *tsp, *tep;
+  uint8_t* keep;
+  char* step;                // the packed step's own workspace, to the end of the carve
+  int64_t n_cap, g_cap;
+};
+static int carve_capturable(const afx_ctx* c, int prec, int64_t R, int64_t S, Carve& w, CapBufs& b, const char* who) {
+  if (int rc = grid_step_caps(c, R, S, who, "capturable", &b.n_cap, &b.g_cap)) return rc;
+  b.counts = w.take<int32_t>((size_t)R * 4); b.offsets = w.take<int64_t>((size_t)(R + 1) * 8); b.totals = w.take<int64_t>(4 * 8);
+  b.counts2 = w.take<int32_t>((size_t)R * 4); b.off2 = w.take<int64_t>((size_t)(R + 1) * 8); b.goff = w.take<int64_t>((size_t)(R + 1) * 8);
+  b.dsz = w.take<int64_t>(SZ_COUNT * 8);
+  const size_t n = (size_t)std::max<int64_t>(b.n_cap, 1), g = (size_t)std::max<int64_t>(b.g_cap, 1);
+  b.ri = w.take<int32_t>(n * 4); b.ts = w.take<float>(n * 4); b.te = w.take<float>(n * 4); b.pts = w.take<float>(n * 12); b.raw = w.take<float>(n * 4);
+  b.keep = w.take<uint8_t>(n);
+  b.ri2 = w.take<int32_t>(n * 4); b.ts2 = w.take<float>(n * 4); b.te2 = w.take<float>(n * 4);
+  b.tsp = w.take<float>(g * 32 * 4); b.tep = w.take<float>(g * 32 * 4); b.gray = w.take<int32_t>(g * 4);
   // the packed step: dL/d(optical depth) per ray and optical-depth partials per group (packed_step's head), then run_backward's fixed part and
   // one chunk of the 8-bit stash over every tile of the capacity
   const size_t tiles = (g * 32 + 255) / 256;
-  L.total = off + rup64((size_t)R * 4, 256) + rup64(g * 4, 256) + bwd_layout(c, prec, 0).fixed_bytes + tiles * per_tile_s8(c) + 1024;
+  b.step = w.take(rup64((size_t)R * 4, 256) + rup64(g * 4, 256) + bwd_layout(c, prec, 0).fixed_bytes + tiles * per_tile_s8(c) + 1024, 1);
   return AFX_OK;
 }
 
 extern "C" int64_t afx_march_train_workspace_bytes(const afx_ctx* c, int prec, int64_t n_rays, int64_t max_steps_per_ray) {
   if (!c) { fail(AFX_E_INVALID, "afx_march_train_workspace_bytes: null ctx"); return -1; }
   if (prec != AFX_PREC_F16S8) { fail(AFX_E_INVALID, "afx_march_train_workspace_bytes: AFX_PREC_F16S8 only"); return -1; }
-  CapLayout L;
-  if (cap_layout(c, prec, n_rays, max_steps_per_ray, L, "afx_march_train_workspace_bytes")) return -1;
-  return (int64_t)L.total;
+  Carve w;
+  CapBufs b;
+  if (carve_capturable(c, prec, n_rays, max_steps_per_ray, w, b, "afx_march_train_workspace_bytes")) return -1;
+  return (int64_t)w.end;
 }
 
 extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const void* prepared, afx_march_train_args* t, int64_t* counts_dev,
                                                    float* skip_dev, void* stream) {
   const char* who = "afx_march_train_step_mse_capturable";
-  if (!c || !prepared || !t || !counts_dev || !skip_dev) return fail(AFX_E_INVALID, "%s: null argument", who);
-  t->workspace_needed = 0;
+  int64_t S;
+  if (int rc = check_grid_step(c, prec, prepared, t, counts_dev, skip_dev, false, who, &S)) return rc;
   const afx_march_args& m = t->march;
   const int64_t R = m.n_rays;
-  if (R <= 0) return fail(AFX_E_INVALID, "%s: n_rays must be > 0", who);
-  if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
-  if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "%s: AFX_PREC_F16S8 only", who);
-  const int64_t S = afx_march_max_steps(&m);
-  if (S < 0) return AFX_E_INVALID;
-  CapLayout L;
-  if (int rc = cap_layout(c, prec, R, S, L, who)) return rc;
-  if (L.total > t->workspace_bytes) {
-    t->workspace_needed = L.total;
-    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_train_workspace_bytes)", who, t->workspace_bytes, L.total);
-  }
-  if (int rc = check_dev(c, who)) return rc;
+  Carve w{(uintptr_t)t->workspace};
+  CapBufs L;
+  if (int rc = carve_capturable(c, prec, R, S, w, L, who)) return rc;
+  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_train_workspace_bytes")) return rc;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)t->workspace;
-  int32_t *counts = (int32_t*)(ws + L.o_counts), *counts2 = (int32_t*)(ws + L.o_counts2);
-  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals), *off2 = (int64_t*)(ws + L.o_off2),
-          *goff = (int64_t*)(ws + L.o_goff), *dsz = (int64_t*)(ws + L.o_dsz);
-  int32_t *ri = (int32_t*)(ws + L.o_ri), *ri2 = (int32_t*)(ws + L.o_ri2), *gray = (int32_t*)(ws + L.o_gray);
-  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *pts = (float*)(ws + L.o_pts), *raw = (float*)(ws + L.o_raw);
-  float *ts2 = (float*)(ws + L.o_ts2), *te2 = (float*)(ws + L.o_te2), *tsp = (float*)(ws + L.o_tsp), *tep = (float*)(ws + L.o_tep);
-  uint8_t* keep = (uint8_t*)(ws + L.o_keep);
+  int32_t *counts = L.counts, *counts2 = L.counts2, *ri = L.ri, *ri2 = L.ri2, *gray = L.gray;
+  int64_t *offsets = L.offsets, *totals = L.totals, *off2 = L.off2, *goff = L.goff, *dsz = L.dsz;
+  float *ts = L.ts, *te = L.te, *pts = L.pts, *raw = L.raw, *ts2 = L.ts2, *te2 = L.te2, *tsp = L.tsp, *tep = L.tep;
+  uint8_t* keep = L.keep;
   int rc;
   // 1. candidates (totals[0]: their count, on the device only)
   if ((rc = afx_march_count(&m, counts, stream))) return rc;
@@ -1721,7 +1770,7 @@ extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const v
   if ((rc = afx_march_compact(keep, offsets, off2, R, ts, te, ri2, ts2, te2, stream))) return rc;
   if ((rc = afx_pack_groups(off2, goff, R, ts2, te2, tsp, tep, gray, stream))) return rc;
   return packed_step(c, prec, prepared, m.origins, m.dirs, R, goff, gray, std::max<int64_t>(L.g_cap, 1), tsp, tep, t->target, t->inv_n, t->pixel,
-                     t->grad_flat, ws + L.o_step, t->workspace_bytes - L.o_step, stream, dsz);
+                     t->grad_flat, L.step, t->workspace_bytes - (size_t)(L.step - (char*)t->workspace), stream, dsz);
 }
 
 // ---- the grid iteration with ONE evaluation of the model (afx_march_train_step_mse_single_eval): the packed step's forward half runs over the
@@ -1730,90 +1779,58 @@ extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const v
 // half and the weight gradients then run over the candidate rows in the arrangement of the hierarchical step (defer_out: PHASE 2 reads the
 // finished dL/draw, the output layer's gradient is contracted from the stash of H_N by k_wout_stash8).  The only size that shapes the work is the
 // candidate count, which stays on the device: every buffer is carved for the worst case, as in the capturable step, and nothing is compacted.
-struct SeLayout {
-  size_t o_counts, o_offsets, o_totals, o_goff, o_counts2, o_off2, o_goff2, o_dsz, o_pix;
-  size_t o_ri, o_ts, o_te, o_keep, o_tsp, o_tep, o_gray, o_raw, o_tau, o_od;
-  size_t o_partial, o_partial2, o_partial_s, o_gmax;
-  size_t o_sh, o_sdz, o_gexp, o_gpart, o_masks, o_rec, o_hexp;
-  size_t total;
-  int64_t n_cap, g_cap, rows;      // candidates and 32-sample groups of the worst case, stash rows (whole 256-sample tiles)
+struct SeBufs {
+  int32_t *counts, *counts2, *ri, *gray;
+  int64_t *offsets, *totals, *goff, *off2, *goff2, *dsz;
+  float *pix, *ts, *te, *tsp, *tep, *raw, *tau, *od;
+  uint8_t* keep;
+  Wgrad8Scratch p;
+  StashSet set;              // over every candidate row (whole 256-sample tiles)
+  int64_t n_cap, g_cap;
 };
-static int se_layout(const afx_ctx* c, int64_t R, int64_t S, SeLayout& L, const char* who) {
-  if (R <= 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays > 0 and max_steps_per_ray >= 0", who);
-  L.n_cap = R * S;
-  L.g_cap = R * ((S + GROUP - 1) / GROUP);
-  // one chunk: a layer plane of the 8-bit stash stays below 4 GiB (the chain kernels' 32-bit stash offsets), as in the capturable step
-  const int64_t max_samples = (int64_t)(((uint64_t)1 << 32) / ((uint64_t)256 * c->d.width)) * 256;
-  if (L.g_cap * GROUP > max_samples || L.n_cap > ((int64_t)1 << 31) - 256)
-    return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed the single-evaluation step's sample limit (%lld group-padded samples at width %d, "
-                "one chunk of the packed step); use afx_march_train_step_mse or fewer rays per step", who, (long long)R, (long long)S,
-                (long long)max_samples, c->d.width);
-  const size_t F = c->d.width, N = c->d.n_hidden;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
-  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(4 * 8); L.o_goff = take((size_t)(R + 1) * 8);
-  L.o_counts2 = take((size_t)R * 4); L.o_off2 = take((size_t)(R + 1) * 8); L.o_goff2 = take((size_t)(R + 1) * 8); L.o_dsz = take(SZ_COUNT * 8);
-  L.o_pix = take((size_t)R * 4);
-  const size_t n = (size_t)std::max<int64_t>(L.n_cap, 1), g = (size_t)std::max<int64_t>(L.g_cap, 1);
-  L.o_ri = take(n * 4); L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_keep = take(n);
-  L.o_tsp = take(g * 32 * 4); L.o_tep = take(g * 32 * 4); L.o_gray = take(g * 4); L.o_raw = take(g * 32 * 4); L.o_tau = take(g * 32 * 4);
-  L.o_od = take(g * 4);
-  L.o_partial = take((N + 2) * (size_t)kSplits * F * F * 4); L.o_partial2 = take((N + 2) * (size_t)kSplits * (F + 4) * 4);
-  L.o_partial_s = take((size_t)kSmallBlocks * (F * 16 + 2 * F + 4) * 4); L.o_gmax = take(256);
-  const size_t rows = (g * 32 + 255) / 256 * 256;
-  L.rows = (int64_t)rows;
-  L.o_sh = take((N + 1) * rows * F); L.o_sdz = take((N + 1) * rows * F);
-  L.o_gexp = take(rows * 4); L.o_gpart = take(rows * 4);
-  L.o_masks = take((rows / 256) * (N + 1) * c->nt * 1024);
-  L.o_rec = take((rows / 32) * (3 * F + 8) * 4);
-  L.o_hexp = take(N * (rows / 32) * 4);
-  L.total = off;
+static int carve_single_eval(const afx_ctx* c, int64_t R, int64_t S, Carve& w, SeBufs& b, const char* who) {
+  if (int rc = grid_step_caps(c, R, S, who, "single-evaluation", &b.n_cap, &b.g_cap)) return rc;
+  b.counts = w.take<int32_t>((size_t)R * 4); b.offsets = w.take<int64_t>((size_t)(R + 1) * 8); b.totals = w.take<int64_t>(4 * 8);
+  b.goff = w.take<int64_t>((size_t)(R + 1) * 8);
+  b.counts2 = w.take<int32_t>((size_t)R * 4); b.off2 = w.take<int64_t>((size_t)(R + 1) * 8); b.goff2 = w.take<int64_t>((size_t)(R + 1) * 8);
+  b.dsz = w.take<int64_t>(SZ_COUNT * 8);
+  b.pix = w.take<float>((size_t)R * 4);
+  const size_t n = (size_t)std::max<int64_t>(b.n_cap, 1), g = (size_t)std::max<int64_t>(b.g_cap, 1);
+  b.ri = w.take<int32_t>(n * 4); b.ts = w.take<float>(n * 4); b.te = w.take<float>(n * 4); b.keep = w.take<uint8_t>(n);
+  b.tsp = w.take<float>(g * 32 * 4); b.tep = w.take<float>(g * 32 * 4); b.gray = w.take<int32_t>(g * 4);
+  b.raw = w.take<float>(g * 32 * 4); b.tau = w.take<float>(g * 32 * 4); b.od = w.take<float>(g * 4);
+  b.p = carve_wgrad8_scratch(c, w);
+  b.set = carve_stash_set(c, (g * 32 + 255) / 256 * 256, w);
   return AFX_OK;
 }
 
 extern "C" int64_t afx_march_single_eval_workspace_bytes(const afx_ctx* c, int prec, int64_t n_rays, int64_t max_steps_per_ray) {
   if (!c) { fail(AFX_E_INVALID, "afx_march_single_eval_workspace_bytes: null ctx"); return -1; }
   if (prec != AFX_PREC_F16S8) { fail(AFX_E_INVALID, "afx_march_single_eval_workspace_bytes: AFX_PREC_F16S8 only"); return -1; }
-  SeLayout L;
-  if (se_layout(c, n_rays, max_steps_per_ray, L, "afx_march_single_eval_workspace_bytes")) return -1;
-  return (int64_t)L.total;
+  Carve w;
+  SeBufs b;
+  if (carve_single_eval(c, n_rays, max_steps_per_ray, w, b, "afx_march_single_eval_workspace_bytes")) return -1;
+  return (int64_t)w.end;
 }
 
 extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const void* prepared, afx_march_train_args* t, int64_t* counts_dev,
                                                     float* skip_dev, void* stream) {
   const char* who = "afx_march_train_step_mse_single_eval";
-  if (!c || !prepared || !t || !counts_dev || !skip_dev) return fail(AFX_E_INVALID, "%s: null argument", who);
-  t->workspace_needed = 0;
+  int64_t S;
+  if (int rc = check_grid_step(c, prec, prepared, t, counts_dev, skip_dev, true, who, &S)) return rc;
   const afx_march_args& m = t->march;
   const int64_t R = m.n_rays;
-  if (R <= 0) return fail(AFX_E_INVALID, "%s: n_rays must be > 0", who);
-  if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
-  if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "%s: AFX_PREC_F16S8 only", who);
-  if (c->d.act != AFX_ACT_RELU) return fail(AFX_E_INVALID, "%s: ReLU models only (tanh / sine train in the exact-fp32 kernels)", who);
-  if (c->d.enc != AFX_ENC_NONE)
-    return fail(AFX_E_INVALID, "%s: no input encoding (the deferred output-layer path of the backward half does not carry one); use "
-                "afx_march_train_step_mse_capturable", who);
-  if (!m.has_far) return fail(AFX_E_INVALID, "%s: the march needs a far plane (the worst-case workspace bound)", who);
-  const int64_t S = afx_march_max_steps(&m);
-  if (S < 0) return AFX_E_INVALID;
-  SeLayout L;
-  if (int rc = se_layout(c, R, S, L, who)) return rc;
-  if (L.total > t->workspace_bytes) {
-    t->workspace_needed = L.total;
-    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_single_eval_workspace_bytes)", who, t->workspace_bytes, L.total);
-  }
-  if (int rc = check_dev(c, who)) return rc;
-  const int F = c->d.width, N = c->d.n_hidden;
+  Carve w{(uintptr_t)t->workspace};
+  SeBufs L;
+  if (int rc = carve_single_eval(c, R, S, w, L, who)) return rc;
+  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_single_eval_workspace_bytes")) return rc;
+  const int N = c->d.n_hidden;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)t->workspace;
-  int32_t *counts = (int32_t*)(ws + L.o_counts), *counts2 = (int32_t*)(ws + L.o_counts2);
-  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals), *goff = (int64_t*)(ws + L.o_goff),
-          *off2 = (int64_t*)(ws + L.o_off2), *goff2 = (int64_t*)(ws + L.o_goff2), *dsz = (int64_t*)(ws + L.o_dsz);
-  int32_t *ri = (int32_t*)(ws + L.o_ri), *gray = (int32_t*)(ws + L.o_gray);
-  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *tsp = (float*)(ws + L.o_tsp), *tep = (float*)(ws + L.o_tep);
-  float *row_raw = (float*)(ws + L.o_raw), *row_tau = (float*)(ws + L.o_tau), *pix = (float*)(ws + L.o_pix), *gpart = (float*)(ws + L.o_gpart);
-  uint8_t* keep = (uint8_t*)(ws + L.o_keep);
-  uint32_t* gmax = (uint32_t*)(ws + L.o_gmax);
+  int32_t *counts = L.counts, *counts2 = L.counts2, *ri = L.ri, *gray = L.gray;
+  int64_t *offsets = L.offsets, *totals = L.totals, *goff = L.goff, *off2 = L.off2, *goff2 = L.goff2, *dsz = L.dsz;
+  float *ts = L.ts, *te = L.te, *tsp = L.tsp, *tep = L.tep, *row_raw = L.raw, *row_tau = L.tau, *pix = L.pix, *gpart = L.set.gpart;
+  uint8_t* keep = L.keep;
+  const StashSet& set = L.set;
   const int tile = bwd_tile(prec), splits0 = c->n_cu / N;
   int rc;
   // 1. candidates, their group-aligned copy (totals[0] / totals[1]: candidates and their groups, on the device only) and the step's size block
@@ -1830,11 +1847,11 @@ extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const 
   a.depth_mode = 4; a.z = tsp; a.te = tep; a.group_ray = gray;
   a.n_samples = GROUP; a.s_pad = GROUP; a.n_total = std::max<int64_t>(L.g_cap, 1) * GROUP;
   a.fused = 0; a.stash8 = 1; a.coef_cols = 0; a.debug = 0; a.persistent = 1; a.defer_out = 1; a.dod = nullptr;
-  a.od_part = (float*)(ws + L.o_od); a.gmax = gmax;
+  a.od_part = L.od; a.gmax = L.p.gmax;
   a.tile0 = 0; a.tile1 = (int)((a.n_total + tile - 1) / tile);
-  a.stash_h = (float*)(ws + L.o_sh); a.stash_dz = (float*)(ws + L.o_sdz); a.stash_e = nullptr;
-  a.graw = (float*)(ws + L.o_gexp); a.gexp = (int32_t*)(ws + L.o_gexp); a.gpart = gpart; a.masks = ws + L.o_masks;
-  a.small_part = (float*)(ws + L.o_rec); a.stash_rows = L.rows; a.hexp = (uint32_t*)(ws + L.o_hexp);
+  a.stash_h = (float*)set.stash_h; a.stash_dz = (float*)set.stash_dz; a.stash_e = nullptr;
+  a.graw = (float*)set.gexp; a.gexp = (int32_t*)set.gexp; a.gpart = gpart; a.masks = set.masks;
+  a.small_part = set.records; a.stash_rows = set.rows; a.hexp = (uint32_t*)set.hexp;
   a.n_dev = dsz + SZ_NTOTAL;
   a.row_raw = row_raw; a.row_tau = row_tau;
   if ((rc = launch_chain(c, prec, true, a, st, 1))) return rc;
@@ -1848,64 +1865,43 @@ extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const 
                      counts_dev, skip_dev, dsz);
   HIPCHK(hipGetLastError());
   // 4. backward half over the candidate rows (dL/draw finished in gpart), then the weight gradients (output layer from the stash of H_N)
-  HIPCHK(hipMemsetAsync(gmax, 0, 4, st));
+  HIPCHK(hipMemsetAsync(L.p.gmax, 0, 4, st));
   a.row_raw = nullptr; a.row_tau = nullptr;
   if ((rc = launch_chain(c, prec, true, a, st, 2))) return rc;
-  WgradArgs w = {};
-  w.stash_h = a.stash_h; w.stash_dz = a.stash_dz; w.stash_e = nullptr; w.graw = a.graw;
-  w.rows = L.rows; w.stride_rows = L.rows;
-  w.n_hidden = N; w.k0 = c->k0; w.k0pad = 16;
-  int splits = splits0;      // (the capacity's; the kernels take the device's from dsz)
-  if (splits > (int)(w.rows / 256)) splits = (int)(w.rows / 256);
-  if (splits < 1) splits = 1;
-  if (splits > kSplits) splits = kSplits;
-  w.n_splits = splits;
-  w.rows_per_split = (int)(((w.rows + splits - 1) / splits + 63) / 64 * 64);
-  w.partial = (float*)(ws + L.o_partial); w.partial2 = (float*)(ws + L.o_partial2); w.partial_s = (float*)(ws + L.o_partial_s);
-  w.debug = 0; w.small_groups = 1;
-  w.gmax = gmax; w.stash_esz = 1; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = 0; w.coef_cols = 0;
-  w.dod = nullptr; w.gpr = 1; w.group0 = 0; w.n_groups_valid = 0; w.group_ray = nullptr;
-  w.records = a.small_part; w.no_sw = 1; w.gfull = gpart;
-  w.dsz = dsz;
-  ReduceArgs rd = {};
-  rd.partial = w.partial; rd.partial2 = w.partial2; rd.n_hidden = N; rd.k0 = c->k0; rd.k0pad = 16; rd.n_splits = splits;
-  rd.grad = t->grad_flat; rd.hidden_only = 1; rd.partial_s = w.partial_s;
-  rd.n_small = (int)std::min<int64_t>(kSmallBlocks, std::max<int64_t>(64, (w.rows / GROUP + 3) / 4));
-  rd.gmax = gmax; rd.scale_shift = AFX_S8_JSHIFT; rd.layer0_mfma = 0; rd.w0 = nullptr; rd.d_coef = nullptr; rd.coef_cols = 0;
-  rd.dsz = dsz;
-  return F == 64 ? launch_wgrad8_t<64>(c, w, rd, N, st) : (F == 128 ? launch_wgrad8_t<128>(c, w, rd, N, st) : launch_wgrad8_t<256>(c, w, rd, N, st));
+  // (the capacity's split and record count; the kernels take the device's from dsz)
+  return launch_wgrad8_set(c, set, L.p, set.rows, (int)wgrad_split(set.rows, splits0, kSplits, kSmallBlocks).n_small, dsz, t->grad_flat, st);
 }
 
 // ---- forward-only render through the occupancy grid with ONE evaluation of the model (afx_march_render): march (candidates, mid-points), one
 // afx_mlp_infer over the candidates, k_march_render_composite (kept set, pixel, binary pixel per ray).  One host read-back: the candidate count.
 // Every buffer is carved for the worst case (every step of every ray a candidate, afx_march_max_steps) before the first launch.
-struct RenderLayout {
-  size_t o_org, o_dir, o_counts, o_offsets, o_totals, o_ts, o_te, o_pts, o_raw;
-  size_t total;
+struct RenderBufs {
+  float *org, *dir;           // pose mode: the rays
+  int32_t* counts;
+  int64_t *offsets, *totals;
+  float *ts, *te, *pts, *raw;
   int64_t n_cap;
 };
-static int render_layout(int32_t ray_mode, int64_t R, int64_t S, RenderLayout& L, const char* who) {
+static int carve_render(int32_t ray_mode, int64_t R, int64_t S, Carve& w, RenderBufs& b, const char* who) {
   if (ray_mode != AFX_RAYS_ARRAYS && ray_mode != AFX_RAYS_POSE) return fail(AFX_E_INVALID, "%s: bad ray_mode %d", who, ray_mode);
   if (R < 0 || S < 0) return fail(AFX_E_INVALID, "%s: need n_rays >= 0 and max_steps_per_ray >= 0", who);
   if (R > ((int64_t)1 << 31) - 256 || (S > 0 && R > (((int64_t)1 << 31) - 256) / S))
     return fail(AFX_E_INVALID, "%s: %lld rays x %lld steps exceed afx_mlp_infer's 2^31 - 256 points per call; split the rays", who, (long long)R,
                 (long long)S);
-  L.n_cap = R * S;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += rup64(bytes, 256); return at; };
-  const size_t pose = ray_mode == AFX_RAYS_POSE ? (size_t)R * 12 : 0, n = (size_t)std::max<int64_t>(L.n_cap, 1);
-  L.o_org = take(pose); L.o_dir = take(pose);
-  L.o_counts = take((size_t)R * 4); L.o_offsets = take((size_t)(R + 1) * 8); L.o_totals = take(2 * 8);
-  L.o_ts = take(n * 4); L.o_te = take(n * 4); L.o_pts = take(n * 12);
-  L.o_raw = take(n * 4);      // (also k_march_write's ray_indices, which the render does not need: afx_mlp_infer overwrites them)
-  L.total = off;
+  b.n_cap = R * S;
+  const size_t pose = ray_mode == AFX_RAYS_POSE ? (size_t)R * 12 : 0, n = (size_t)std::max<int64_t>(b.n_cap, 1);
+  b.org = w.take<float>(pose); b.dir = w.take<float>(pose);
+  b.counts = w.take<int32_t>((size_t)R * 4); b.offsets = w.take<int64_t>((size_t)(R + 1) * 8); b.totals = w.take<int64_t>(2 * 8);
+  b.ts = w.take<float>(n * 4); b.te = w.take<float>(n * 4); b.pts = w.take<float>(n * 12);
+  b.raw = w.take<float>(n * 4);      // (also k_march_write's ray_indices, which the render does not need: afx_mlp_infer overwrites them)
   return AFX_OK;
 }
 
 extern "C" int64_t afx_march_render_workspace_bytes(int32_t ray_mode, int64_t n_rays, int64_t max_steps_per_ray) {
-  RenderLayout L;
-  if (render_layout(ray_mode, n_rays, max_steps_per_ray, L, "afx_march_render_workspace_bytes")) return -1;
-  return (int64_t)L.total;
+  Carve w;
+  RenderBufs b;
+  if (carve_render(ray_mode, n_rays, max_steps_per_ray, w, b, "afx_march_render_workspace_bytes")) return -1;
+  return (int64_t)w.end;
 }
 
 extern "C" int afx_march_render(afx_ctx* c, int prec, const void* prepared, afx_march_render_args* t, void* stream) {
@@ -1931,26 +1927,21 @@ extern "C" int afx_march_render(afx_ctx* c, int prec, const void* prepared, afx_
   if (int rc = fill_march(&m, a, who)) return rc;
   const int64_t S = afx_march_max_steps(&m);
   if (S < 0) return AFX_E_INVALID;
-  RenderLayout L;
-  if (int rc = render_layout(t->ray_mode, R, S, L, who)) return rc;
-  if (L.total > t->workspace_bytes) {
-    t->workspace_needed = L.total;
-    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_march_render_workspace_bytes)", who, t->workspace_bytes, L.total);
-  }
-  if (int rc = check_dev(c, who)) return rc;
+  Carve w{(uintptr_t)t->workspace};
+  RenderBufs L;
+  if (int rc = carve_render(t->ray_mode, R, S, w, L, who)) return rc;
+  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_render_workspace_bytes")) return rc;
   hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)t->workspace;
-  int32_t* counts = (int32_t*)(ws + L.o_counts);
-  int64_t *offsets = (int64_t*)(ws + L.o_offsets), *totals = (int64_t*)(ws + L.o_totals);
-  float *ts = (float*)(ws + L.o_ts), *te = (float*)(ws + L.o_te), *pts = (float*)(ws + L.o_pts), *raw = (float*)(ws + L.o_raw);
+  int32_t* counts = L.counts;
+  int64_t *offsets = L.offsets, *totals = L.totals;
+  float *ts = L.ts, *te = L.te, *pts = L.pts, *raw = L.raw;
   // 1. pose mode: the rays, as the dense fused kernels generate them
   if (pose) {
     ChainArgs ra = {};
     ra.poses = t->poses; ra.ray_ids = nullptr; ra.ray_id0 = t->ray_id0; ra.width = t->width; ra.height = t->height; ra.focal = t->focal;
-    float *org = (float*)(ws + L.o_org), *dir = (float*)(ws + L.o_dir);
-    hipLaunchKernelGGL(k_pose_rays, blocks_for(R), dim3(256), 0, st, ra, R, org, dir);
+    hipLaunchKernelGGL(k_pose_rays, blocks_for(R), dim3(256), 0, st, ra, R, L.org, L.dir);
     HIPCHK(hipGetLastError());
-    a.org = org; a.dir = dir;
+    a.org = L.org; a.dir = L.dir;
   }
   // 2. candidates: count, offsets (the one read-back), t_starts / t_ends / mid-points
   hipLaunchKernelGGL(k_march_count, blocks_for(R, 4), dim3(256), 0, st, a, counts);

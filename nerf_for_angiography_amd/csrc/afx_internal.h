@@ -1,5 +1,6 @@
 // afx_internal.h — shared between the C-ABI host code and the gfx950 kernels.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
 
@@ -169,7 +170,25 @@ struct ReduceArgs {
 };
 
 // Slots of the device-resident size block of afx_march_train_step_mse_capturable (k_grid_step_sizes writes them from the offsets kernels'
-// totals with the formulas run_backward applies on the host, so the capturable step sums in the same order as the one-call step)
+// totals with wgrad_split below, as the host does, so the capturable step sums in the same order as the one-call step)
 enum { SZ_NTOTAL = 0, SZ_ROWS = 1, SZ_SPLITS = 2, SZ_RPS = 3, SZ_SMALL = 4, SZ_GROUPS = 5, SZ_COUNT = 8 };
+
+// How the weight-gradient kernels share out `rows` stash rows: `splits` ranges of rows_per_split rows (whole 32-/64-sample stages) - splits0,
+// the launch's base count, cut to one range per 256 rows and to 1..max_splits - and n_small group records (a block per ~4 groups, so that a
+// sparse list does not write and sum max_small mostly-empty records).  The split and the record count fix the order of the fp32 sums: the
+// host launches and the device size block (grid_step_sizes) both take them from here.
+struct WgradSplit { int64_t splits, rows_per_split, n_small; };
+__host__ __device__ __forceinline__ WgradSplit wgrad_split(int64_t rows, int splits0, int max_splits, int max_small) {
+  int64_t splits = splits0;
+  if (splits > rows / 256) splits = rows / 256;
+  if (splits < 1) splits = 1;
+  if (splits > max_splits) splits = max_splits;
+  int64_t rps = (rows + splits - 1) / splits;
+  rps = (rps + 63) / 64 * 64;
+  int64_t n_small = (rows / GROUP + 3) / 4;
+  if (n_small < 64) n_small = 64;
+  if (n_small > max_small) n_small = max_small;
+  return {splits, rps, n_small};
+}
 
 }  // namespace afx

@@ -606,21 +606,13 @@ __global__ void __launch_bounds__(1024) k_ray_offsets(const int32_t* counts, int
 // The sizes of a grid training iteration, on the device (afx_march_train_step_mse_capturable): from the totals of the two offsets kernels
 // (totals[0] candidates, totals[2] kept samples, totals[3] their 32-sample groups) the counters the caller reads (counts[3] = candidates, kept,
 // groups), the optimizer's skip flag (1.0 when nothing survived the march) and the size block the capacity launches of the packed step read
-// (SZ_* slots) - the formulas run_backward applies on the host for one chunk of `tile`-sample tiles, so the weight-gradient sums run in the
-// same order as in afx_march_train_step_mse.  One thread.
-// (the formulas of one chunk of `tile`-sample tiles holding ng groups, as run_backward applies them on the host)
+// (SZ_* slots): one chunk of `tile`-sample tiles holding ng groups, split by wgrad_split as the host splits it, so the weight-gradient sums run
+// in the same order as in afx_march_train_step_mse.  One thread.
 __device__ __forceinline__ void grid_step_sizes(int64_t ng, int tile, int splits0, int max_splits, int max_small, int64_t* dsz) {
   const int64_t n_total = ng * GROUP, rows = (n_total + tile - 1) / tile * tile;
-  int64_t splits = splits0;
-  if (splits > rows / 256) splits = rows / 256;
-  if (splits < 1) splits = 1;
-  if (splits > max_splits) splits = max_splits;
-  int64_t rps = (rows + splits - 1) / splits;
-  rps = (rps + 63) / 64 * 64;
-  int64_t n_small = (rows / GROUP + 3) / 4;
-  if (n_small < 64) n_small = 64;
-  if (n_small > max_small) n_small = max_small;
-  dsz[SZ_NTOTAL] = n_total; dsz[SZ_ROWS] = rows; dsz[SZ_SPLITS] = splits; dsz[SZ_RPS] = rps; dsz[SZ_SMALL] = n_small; dsz[SZ_GROUPS] = ng;
+  const WgradSplit s = wgrad_split(rows, splits0, max_splits, max_small);
+  dsz[SZ_NTOTAL] = n_total; dsz[SZ_ROWS] = rows; dsz[SZ_SPLITS] = s.splits; dsz[SZ_RPS] = s.rows_per_split; dsz[SZ_SMALL] = s.n_small;
+  dsz[SZ_GROUPS] = ng;
 }
 __global__ void k_grid_step_sizes(const int64_t* totals, int tile, int splits0, int max_splits, int max_small, int64_t* counts, float* skip, int64_t* dsz) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;

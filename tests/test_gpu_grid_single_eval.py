@@ -24,7 +24,7 @@ def _rup(x):
 
 def _workspace_views(eng, n_rays, max_steps):
     """The candidates' offsets, group offsets, t_starts / t_ends and the per-row raw output the forward half wrote, read from the workspace of
-    the last call - the carving order of se_layout (csrc/afx_api.hip)."""
+    the last call - the carving order of carve_single_eval (csrc/afx_api.hip)."""
     ws = eng._ws
     R, n, g = n_rays, max(n_rays * max_steps, 1), max(n_rays * ((max_steps + 31) // 32), 1)
     sizes = [("counts", R * 4), ("offsets", (R + 1) * 8), ("totals", 32), ("goff", (R + 1) * 8), ("counts2", R * 4), ("off2", (R + 1) * 8),
