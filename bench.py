@@ -7,15 +7,23 @@ mid-point sampling -> MLP -> Beer-Lambert product), MSE loss, fused backward, gr
 (N > 1) and the PyTorch Adam step — the body of nerf/run_nerf_acc.py:263-307 upstream.
 Weak scaling: every rank renders its own projection each step.
 
-    python bench.py --gpus N --steps K --warmup W [--precision f16|f32|bf16x3|bf16]
+    python bench.py --gpus N --steps K --warmup W [--precision f16|f32|bf16x3|bf16] [--full]
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, ms_per_step,
-`roofline` for the dominant kernel (HIP-event timed inside the library on the launch stream) and
-`cpu_baseline` (the CPU oracle timed on this host's cores on a bounded ray sample, rank 0, N=1 only).
-The run FAILS (non-zero exit, no JSON) when the rendered pixels at the timed precision are outside the
-1e-4 relative-L2 parity bar against the CPU oracle, at the seeded initial weights or at the weights the
-timed steps produced.  N > 1 adds `dp_grad_parity` (all-reduced N-rank gradient vs rank 0's 1-rank
-gradient of the same global batch), `rccl_ranks` and the all-reduce time.
+Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, ms_per_step and
+`roofline` for the dominant kernel (HIP-event timed inside the library on the launch stream during the
+timed steps).  N > 1 adds `rccl_ranks` and the all-reduce time.  A plain run does only that: set-up,
+warm-up, the timed steps, --dump-outputs, the line.
+
+--full also runs, after the timed steps, everything the headline figure does not need:
+  * live HBM traffic of the dominant kernel: two `rocprofv3 --pmc` child runs of this script (N = 1;
+    before this process touches the GPU);
+  * the full-size weight-gradient check of the timed precision against the exact-fp32 kernels (N = 1);
+  * `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded ray sample, N = 1) and pixel
+    parity against that oracle at the seeded initial weights and at the weights the timed steps produced;
+  * `dp_grad_parity` (N > 1: all-reduced N-rank gradient vs rank 0's 1-rank gradient of the same global
+    batch).
+A --full run FAILS (non-zero exit, no JSON on stdout) when one of these checks misses its bar; --no-pmc,
+--no-grad-check and --no-cpu leave out single parts of it.
 """
 import argparse
 import json
@@ -166,15 +174,19 @@ def main():
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--layers", type=int, default=8)
     ap.add_argument("--width", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: live rocprofv3 --pmc "
+                         "traffic, the full-size gradient check, the CPU baseline and oracle parity (N = 1), data-parallel gradient "
+                         "parity (N > 1); a check that misses its bar fails the run")
     ap.add_argument("--cpu-rays", type=int, default=4096)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the oracle parity check")
     ap.add_argument("--workspace-gib", type=float, default=128.0,
                     help="backward stash workspace per GPU (an upper limit: the engine takes what two 4 GiB-per-layer-plane chunks need, 79 GB for the 512^2x128 projection)")
     ap.add_argument("--unfused", action="store_true",
                     help="render -> mse_loss -> autograd backward (forward rendered separately) instead of the fused train step")
-    ap.add_argument("--no-grad-check", action="store_true", help="skip the full-size gradient check against the fp32 kernels (about 2 s)")
+    ap.add_argument("--no-grad-check", action="store_true", help="with --full: skip the full-size gradient check against the fp32 kernels (about 2 s)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the live rocprofv3 --pmc passes for roofline.traffic (use the committed profile instead); "
+                    help="with --full: skip the live rocprofv3 --pmc passes for roofline.traffic (use the committed profile instead); "
                          "required when this command itself runs under rocprofv3")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (loss, pixels, parameter gradients, "
@@ -186,9 +198,10 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
-    live = (None, "not measured")
+    live = (None, "not measured" if args.full else "not measured (--full measures it)")
     # (device_count() does not initialise the GPU on this image)
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc and args.precision != "f32" and torch.cuda.device_count() > 0:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc and args.precision != "f32" \
+            and torch.cuda.device_count() > 0:
         live = live_traffic(args)        # child processes; this process has not touched the GPU yet
 
     from nerf_for_angiography_amd import dist as afx_dist
@@ -376,13 +389,16 @@ def main():
 
     if world > 1:
         if fused:
-            result.update(dp_parity(model, rank, world, poses[0], targets[0], W, H, focal, S, near, far, train_step_mse,
-                                    projection_spec, afx_dist))
-            # a data-parallel line is only reported when the collective really ran over all N ranks and reproduced the 1-rank gradient
+            result.update({"rccl_ranks": dist.get_world_size(), "dist_backend": dist.get_backend()})
+            if args.full:
+                result.update(dp_parity(model, rank, world, poses[0], targets[0], W, H, focal, S, near, far, train_step_mse,
+                                        projection_spec, afx_dist))
+            # a data-parallel line is only reported when the collective really ran over all N ranks (--full: and reproduced the
+            # 1-rank gradient)
             bad = None
             if result["rccl_ranks"] != args.gpus:
                 bad = f"process group has {result['rccl_ranks']} ranks, --gpus {args.gpus}"
-            elif rank == 0 and not result["dp_grad_parity"] <= DP_PARITY_BAR:
+            elif args.full and rank == 0 and not result["dp_grad_parity"] <= DP_PARITY_BAR:
                 bad = f"dp_grad_parity {result['dp_grad_parity']:.3e} > {DP_PARITY_BAR:g}"
             flag = torch.tensor([1.0 if bad else 0.0], device=device)
             dist.all_reduce(flag, op=dist.ReduceOp.MAX)
@@ -392,7 +408,7 @@ def main():
                 dist.destroy_process_group()
                 raise SystemExit(f"DATA-PARALLEL FAILURE: {bad or 'see rank 0'}")
     trained_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    if rank == 0 and world == 1 and fused and not args.no_grad_check:
+    if args.full and rank == 0 and world == 1 and fused and not args.no_grad_check:
         # Full-size gradient check of the timed configuration (same workspace, same chunking): the fused step's weight gradient of
         # projection 0 at the seeded weights against the exact-fp32 kernels (k_chain_f32 / k_wgrad_f32: fp32 MFMA, fp32 stash).
         # A forward-only parity check cannot see a wrong backward (round 2 found 32-bit stash offsets wrapping at this size).
@@ -417,7 +433,7 @@ def main():
             print(json.dumps(result), file=sys.stderr, flush=True)
             raise SystemExit(f"GRADIENT FAILURE: {args.precision} weight gradient is {gerr:.3e} relative L2 from the fp32 kernels "
                              f"(bar {GRAD_BAR[args.precision]:g})")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result.update(cpu_leg(model, args, poses[0], targets[0], W, H, focal, near, far, S, device, render_rays, init_state,
                               trained_state))
         par = result["parity_vs_cpu_oracle"]
@@ -495,7 +511,7 @@ def dp_parity(model, rank, world, pose, target, W, H, focal, S, near, far, train
         return torch.cat([p.grad.reshape(-1) for p in model._hip_params()]).clone()
 
     g_sharded = flat_grad(start, count, target[start:start + count].contiguous())      # the hook SUM-all-reduces it
-    out = {"rccl_ranks": dist.get_world_size(), "dist_backend": dist.get_backend()}
+    out = {}
     hook, afx_dist._render._grad_hook = afx_dist._render._grad_hook, None
     if rank == 0:
         g_single = flat_grad(0, n, target)

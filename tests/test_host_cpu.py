@@ -385,6 +385,31 @@ def test_bench_gpus_n_starts_torchrun_as_a_child(monkeypatch):
     assert os.path.basename(cmd[-7]) == "bench.py" and seen["kw"]["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_live_traffic_passes_only_with_full(monkeypatch, full):
+    """The rocprofv3 child passes for roofline.traffic run before set-up in `bench.py --full` only; a plain run goes straight
+    to set-up (stopped here at the process-group init, before any GPU work)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from nerf_for_angiography_amd import dist as afx_dist
+    passes = []
+
+    class Stop(Exception):
+        pass
+
+    def stop():
+        raise Stop
+    monkeypatch.setattr(bench, "live_traffic", lambda args: passes.append(args.precision) or (None, "stub"))
+    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(afx_dist, "init_from_env", stop)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"] + (["--full"] if full else []))
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.delenv("AFX_BENCH_PRECISION", raising=False)
+    with pytest.raises(Stop):
+        bench.main()
+    assert passes == (["f16s8"] if full else [])
+
+
 def test_bench_flop_model():
     sys.path.insert(0, ROOT)
     import bench

@@ -7,7 +7,7 @@ P=${1:-f16s8}
 T=${2:-r03}
 O=gpurun_out
 set -x
-python3 bench.py --precision $P > $O/${T}_bench_$P.log 2>&1 && grep "^{" $O/${T}_bench_$P.log | tail -1 > $O/${T}_bench_$P.json
+python3 bench.py --full --precision $P > $O/${T}_bench_$P.log 2>&1 && grep "^{" $O/${T}_bench_$P.log | tail -1 > $O/${T}_bench_$P.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --no-cpu --no-pmc --no-grad-check --precision $P > $O/prof_stats.log 2>&1
 python3 tools/pmc_reduce.py $O/prof_stats $O/${T}_${P}_stats.json > /dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -- python3 bench.py --no-cpu --no-pmc --no-grad-check --steps 1 --warmup 1 --precision $P > $O/prof_fetch.log 2>&1
