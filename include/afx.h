@@ -380,8 +380,8 @@ int afx_march_compact(const uint8_t* keep, const int64_t* offsets_in, const int6
  * afx_mlp_infer at the candidates' mid-points + afx_march_visibility (the reference's alpha_fn + nerfacc's render_visibility),
  * afx_march_compact / afx_pack_groups, afx_train_step_packed_mse - the same entry points in the same order, so the results are those of
  * the call-by-call sequence bit for bit.  (At the reference's batch the GPU is busy for 0.27 ms of an iteration; the ~30 launches cost more
- * when a Python loop issues them.)  Two host read-backs inside (sizes are data: the host polls a mapped mailbox, or with AFX_MAILBOX=0
- * copies and synchronises), so the call is NOT graph-capturable - see afx_march_train_step_mse_capturable below.  Every array
+ * when a Python loop issues them.)  Two host read-backs inside (sizes are data: the host polls a mapped mailbox, or copies and
+ * synchronises where no mapped memory can be had), so the call is NOT graph-capturable - see afx_march_train_step_mse_capturable below.  Every array
  * between the steps lives in `workspace`; when it is too small the call returns AFX_E_WORKSPACE with `workspace_needed` set (nothing the
  * caller owns has been written) - grow and call again.  n_kept == 0 on return: no sample survived, pixel / grad_flat untouched (the
  * reference skips the optimizer step, :293). */
@@ -440,8 +440,8 @@ int afx_march_train_step_mse_single_eval(afx_ctx* ctx, int prec, const void* pre
  * grid_bits == NULL: every step inside the box / planes is a candidate.  Outputs: pixel [R] (required); binary_pixel [R] (optional: the
  * same product with sigma forced to 0 where sigmoid(raw) < binary_thresh, visualization.py:349-352); kept_counts [R] (optional); on the
  * host, n_candidates.  A ray without candidates gets 1.
- * ONE host read-back per call (the candidate count: the host polls a mapped mailbox, or with AFX_MAILBOX=0 copies and synchronises, as
- * afx_march_train_step_mse does), so the call is NOT graph-capturable.  Every buffer is carved for the worst case before the first launch:
+ * ONE host read-back per call (the candidate count: the host polls a mapped mailbox, or copies and synchronises where no mapped
+ * memory can be had, as afx_march_train_step_mse does), so the call is NOT graph-capturable.  Every buffer is carved for the worst case before the first launch:
  * every step of every ray a candidate, afx_march_max_steps(&march) steps (the march needs a far plane); the workspace must hold
  * afx_march_render_workspace_bytes(ray_mode, R, that bound) bytes, else AFX_E_WORKSPACE with workspace_needed set and nothing the caller owns
  * written.  A worst case beyond afx_mlp_infer's 2^31 - 256 points per call is refused with AFX_E_INVALID: split the rays. */

@@ -14,12 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_inst.h", "afx_inst_chain16.hip",
         "afx_internal.h", os.path.join("..", "..", "include", "afx.h")]
 VARIANTS = {"": [], "safe": ["-DAFX_SAFE_WAITS"],
-            "window": ["-DAFX_STASH_WINDOW"],     # measurement: stash stores into an L2-resident window (no HBM write stream; wrong results)
-            "nogmax": ["-DAFX_NO_GMAX_ATOMIC"],      # measurement: the backward kernels without the max|g| atomics (wrong gradients; what do the remaining atomics cost?)
-            "p2one": ["-DAFX_P2_OCC2=0"],      # A/B: the backward half of the split step with ONE workgroup per CU at widths <= 128
             "h6": ["-DAFX_H6=1"],      # the 6-bit (bf6 + block scales) H stash: 12.5 % fewer stash bytes, no faster; tests/ compare it with the default
-            "h6c": ["-DAFX_H6=1", "-DAFX_H6_CONST"],  # measurement: ... without the scale computation (scale 1; gradients wrong when H leaves [1/16, 28])
-            "gaps": ["-DAFX_GAPS=1"],      # A/B: the 8-bit-stash backward kernel with the MFMA-gap schedule (slower)
             "stamp": ["-DAFX_STAMP", "-DAFX_SINGLE_TU"],
             "stamp128": ["-DAFX_STAMP", "-DAFX_STAMP_F=128", "-DAFX_SINGLE_TU"]}      # ... of the width-128 kernels      # diagnostic: per-phase cycle stamps of the backward chain kernel (one translation unit)
 

@@ -62,9 +62,6 @@ struct afx_ctx {
   int n_cu;
   std::set<const void*> attr_done;
   bool profiling;
-  hipStream_t side = nullptr;          // overlap mode: weight-gradient kernels run here (fork/join with events)
-  hipEvent_t ev_chain[2] = {nullptr, nullptr}, ev_wgrad[2] = {nullptr, nullptr};
-  int overlap, persistent_chain;
   int small_in_kernel;   // first-/output-layer gradient sums inside the backward chain kernel (AFX_SMALL_IN_KERNEL=0: off)
   int force_split;       // AFX_FORCE_SPLIT=1 (measurement): the split-phase training step also where the fused kernel applies
   int device;            // the HIP device this context was created on; every entry point checks it is current
@@ -195,11 +192,8 @@ extern "C" int afx_create(const afx_model_desc* d, afx_ctx** out) {
   else dev = -1;         // no GPU: queries and validation still work, launches fail with a HIP error
   c->device = dev;
   c->profiling = false;
-  c->overlap = 0; c->persistent_chain = 0;     // AFX_OVERLAP=1: chain(i+1) || wgrad(i) on two streams (+2.6 % on the 512^2x128 step; per-kernel times inflate)
   c->small_in_kernel = 1;
   // environment knobs are read ONCE, here (never on the launch path)
-  if (const char* e = getenv("AFX_OVERLAP")) c->overlap = atoi(e);
-  if (const char* e = getenv("AFX_PERSISTENT")) c->persistent_chain = atoi(e);
   if (const char* e = getenv("AFX_SMALL_IN_KERNEL")) c->small_in_kernel = atoi(e) != 0;
   c->force_split = 0;
   if (const char* e = getenv("AFX_FORCE_SPLIT")) c->force_split = atoi(e) != 0;
@@ -227,9 +221,6 @@ extern "C" void afx_destroy(afx_ctx* c) {
   }
 #endif
   for (auto& r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (auto e : c->ev_chain) if (e) (void)hipEventDestroy(e);
-  for (auto e : c->ev_wgrad) if (e) (void)hipEventDestroy(e);
-  if (c->side) (void)hipStreamDestroy(c->side);
   if (c->mailbox) (void)hipHostFree(c->mailbox);
   delete c;
 }
@@ -442,7 +433,7 @@ static int launch_chain(afx_ctx* c, int prec, bool bwd, const ChainArgs& a, hipS
   const int N = c->d.n_hidden;
   const bool occ2 = chain_occ2(c->nt, phase);      // backward half at widths <= 128: two workgroups per CU, two-tile steps
   const size_t slot = occ2 ? chain_slot_bytes(c->nt, nk0_of(c), true, false, 2) : a.slot_bytes;
-  size_t lds = (size_t)a.small_bytes_pad + (size_t)(is_bf16(prec) ? chain_ring(bwd) : 2) * slot;
+  size_t lds = (size_t)a.small_bytes_pad + 2 * slot;
   const int ncg = (is_bf16(prec) && (bwd || prec == AFX_PREC_BF16 || is_f16(prec))) ? 2 : 1;
   if (bwd) lds += (size_t)(N + 1) * ((c->nt + 1) / 2) * ncg * 256 * 4 + 256;   // ReLU masks + per-group optical depths
   if (lds > 160 * 1024) return fail(AFX_E_INVALID, "model needs %zu B of LDS (> 160 KiB)", lds);
@@ -450,7 +441,7 @@ static int launch_chain(afx_ctx* c, int prec, bool bwd, const ChainArgs& a, hipS
   if (tiles <= 0) return AFX_OK;
   if (int rc = check_dev(c, "afx chain launch")) return rc;
   const int wgs = occ2 ? 2 * c->n_cu : c->n_cu;
-  const int grid = (tiles < wgs || !a.persistent) ? tiles : wgs;    // persistent: one workgroup per CU (occ2: two) loops over tiles
+  const int grid = std::min(tiles, wgs);      // one workgroup per CU (occ2: two) loops over tiles
   return with_width(c, [&](auto f) { return launch_chain_f<decltype(f)::value>(c, prec, bwd, a, lds, grid, st, phase); });
 }
 
@@ -469,7 +460,6 @@ static void fill_model(const afx_ctx* c, int prec, bool bwd, const void* prepare
   if (is_bf16(prec)) a.slot_bytes = chain_slot_bytes(c->nt, nk0_of(c), bwd, prec == AFX_PREC_BF16X3 && !bwd);
   a.n_hidden = c->d.n_hidden; a.k0 = c->k0; a.nq = c->nq; a.enc = c->d.enc; a.n_freq = c->d.n_freq;
   a.act = c->d.act; a.act_w0 = c->d.act_w0;
-  a.persistent = 1;
 }
 
 extern "C" int afx_mlp_infer(afx_ctx* c, int prec, const void* prepared, const float* pts, int64_t n_pts, float* out,
@@ -591,7 +581,7 @@ template <int F>
 static int launch_wgrad8_t(afx_ctx* c, const WgradArgs& w, const ReduceArgs& rd, int N, hipStream_t st) {
   {
     const size_t lds = (size_t)4 * (2 * (F / 16) * (64 * 16 + 128) + 2 * 64 * 4);      // 4-stage ring of (J + H image, group exponents, H block scales)
-    constexpr bool H6 = AFX_H6_ON;      // hidden layers: B = the 6-bit H stash
+    constexpr bool H6 = AFX_H6;      // hidden layers: B = the 6-bit H stash
     for (const void* fn : {(const void*)k_wgrad_s8<F, H6>, (const void*)k_wgrad_s8<F, false>})
       if (!c->attr_done.count(fn)) {
         HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -668,26 +658,6 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     if (chunk < ray_tiles) return fail(AFX_E_WORKSPACE, "backward workspace too small for one group of whole rays (%lld tiles)", (long long)ray_tiles);
     chunk = chunk / ray_tiles * ray_tiles;
   }
-  // Overlap mode: two half-size stash buffers; the weight-gradient kernels of chunk i run on a side stream while
-  // the chain kernel of chunk i+1 runs on the caller's stream (one is MFMA/HBM-write heavy, the other HBM-read
-  // bound).  Fork/join with events only; the side stream always rejoins the caller's stream before returning.
-  int nbuf = 1;
-  // AFX_OVERLAP=2 (measurement): also a list that fits one chunk is cut in two, and the split-phase step takes part - the idea being that at the
-  // reference's batch the chain halves are VALU-bound and the weight-gradient kernel HBM-bound.  Measured (tools/ref_iter.py): SLOWER, 1.12 -> 1.21 ms
-  // per 5 625 x 300 iteration at 4x128, 5.32 -> 5.38 ms at 8x256 (two half-size launches of everything); the default stays off.
-  const bool force2 = c->overlap == 2 && tiles >= 16 && !goff;
-  if (c->overlap && (chunk < tiles || force2) && chunk >= 8 && (!split || force2)) {
-    if (!c->side) {
-      HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-      for (auto& e : c->ev_chain) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      for (auto& e : c->ev_wgrad) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    nbuf = 2;
-    const int64_t one = chunk;
-    chunk = force2 && chunk >= tiles ? (tiles + 1) / 2 : chunk / 2;
-    if (split) chunk = (chunk + ray_tiles - 1) / ray_tiles * ray_tiles;      // whole rays per chunk
-    if (chunk >= tiles || chunk < 1 || fixed + 1024 + (size_t)(2 * chunk) * B.per_tile_bytes > ws_bytes) { nbuf = 1; chunk = one; }      // (two buffers must fit)
-  }
   size_t off = head;
   float* partial = (float*)(ws + off); off += rup64((size_t)(N + 2) * kSplits * F * F * 4, 256);
   float* partial2 = (float*)(ws + off); off += rup64((size_t)(N + 2) * kSplits * (F + 4) * 4, 256);
@@ -696,25 +666,21 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
   uint32_t* gmax_words = (uint32_t*)(ws + off); off += 256;
   const bool h16 = is_f16(prec);
   const size_t rows = (size_t)chunk * TILE;
-  float *stash_h[2], *stash_dz[2], *stash_e[2], *graw[2], *gpart[2];
-  char* masks[2];
-  uint32_t* hexp[2];
-  for (int bI = 0; bI < nbuf; ++bI) {
-    stash_h[bI] = (float*)(ws + off); off += (size_t)(N + 1) * rows * F * esz;
-    stash_dz[bI] = (float*)(ws + off); off += (size_t)(N + 1) * rows * F * esz;
-    stash_e[bI] = (float*)(ws + off); off += rows * k0ld * 4;
-    graw[bI] = (float*)(ws + off); off += rup64(rows * 4, 256);
-    gpart[bI] = nullptr; masks[bI] = nullptr; hexp[bI] = nullptr;
-    if (s8) {
-      gpart[bI] = (float*)(ws + off); off += rows * 4;
-      masks[bI] = ws + off; off += (size_t)chunk * (N + 1) * c->nt * 1024;
-      hexp[bI] = (uint32_t*)(ws + off); off += (size_t)N * (rows / 32) * 4;
-    }
+  float* stash_h = (float*)(ws + off); off += (size_t)(N + 1) * rows * F * esz;
+  float* stash_dz = (float*)(ws + off); off += (size_t)(N + 1) * rows * F * esz;
+  float* stash_e = (float*)(ws + off); off += rows * k0ld * 4;
+  float* graw = (float*)(ws + off); off += rup64(rows * 4, 256);
+  float* gpart = nullptr;
+  char* masks = nullptr;
+  uint32_t* hexp = nullptr;
+  if (s8) {
+    gpart = (float*)(ws + off); off += rows * 4;
+    masks = ws + off; off += (size_t)chunk * (N + 1) * c->nt * 1024;
+    hexp = (uint32_t*)(ws + off); off += (size_t)N * (rows / 32) * 4;
   }
   if (off > ws_bytes) return fail(AFX_E_WORKSPACE, "backward workspace layout exceeds the buffer (%zu > %zu)", off, ws_bytes);
   a.stash_rows = (int64_t)rows;
-  a.debug = 0;
-  if (dsz && (chunk < tiles || nbuf != 1)) return fail(AFX_E_WORKSPACE, "capturable training step: the capacity must fit one chunk");
+  if (dsz && chunk < tiles) return fail(AFX_E_WORKSPACE, "capturable training step: the capacity must fit one chunk");
   a.n_dev = dsz ? dsz + SZ_NTOTAL : nullptr;
   // encoded inputs, 16-bit kernels: the inputs are stashed in 16-bit chunk-major form and the first layer's weight gradient (and the
   // fourier coefficients' gradient, afx_set_encoding_grad) is contracted on the matrix pipe by k_wgrad_bf16
@@ -722,19 +688,15 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
   a.coef_cols = (enc16 && c->d_coef && c->d.enc == AFX_ENC_FOURIER) ? 3 * c->d.n_freq : 0;
   // in-kernel small gradients: 8-wave bf16 backward kernel, rays, raw coordinates as inputs (AFX_SMALL_IN_KERNEL=0: off)
   a.stash8 = s8 ? 1 : 0;
-  a.persistent = (nbuf == 2 && !c->persistent_chain) ? 0 : 1;
-  int64_t ci = 0;
-  for (int64_t t0 = 0; t0 < tiles; t0 += chunk, ++ci) {
+  a.stash_h = stash_h; a.stash_dz = stash_dz; a.stash_e = stash_e; a.graw = graw;
+  a.gexp = (int32_t*)graw;       // 8-bit stash: dL/draw itself is not stashed; its slot holds the group exponents
+  a.small_part = sg ? (float*)((char*)stash_h + (size_t)N * rows * F * esz) : nullptr;     // H_N's stash is not written then
+  a.gmax = h16 ? gmax_words : nullptr;
+  a.gpart = gpart; a.masks = masks; a.hexp = hexp;
+  for (int64_t t0 = 0; t0 < tiles; t0 += chunk) {
     const int64_t t1 = t0 + chunk < tiles ? t0 + chunk : tiles;
-    const int bI = nbuf == 2 ? (int)(ci & 1) : 0;
     a.tile0 = (int)t0; a.tile1 = (int)t1;
-    a.stash_h = stash_h[bI]; a.stash_dz = stash_dz[bI]; a.stash_e = stash_e[bI]; a.graw = graw[bI];
-    a.gexp = (int32_t*)graw[bI];       // 8-bit stash: dL/draw itself is not stashed; its slot holds the group exponents
-    a.small_part = sg ? (float*)((char*)stash_h[bI] + (size_t)N * rows * F * esz) : nullptr;     // H_N's stash is not written then
-    if (nbuf == 2 && ci >= 2) HIPCHK(hipStreamWaitEvent(st, c->ev_wgrad[bI], 0));     // buffer bI has been consumed
-    a.gmax = h16 ? gmax_words + 16 * bI : nullptr;
     if (h16) HIPCHK(hipMemsetAsync(a.gmax, 0, 4, st));
-    a.gpart = gpart[bI]; a.masks = masks[bI]; a.hexp = hexp[bI];
     int rc;
     if (split) {
       // forward half of the chunk, then the per-ray reduction over the chunk's (whole) rays, then the backward half
@@ -755,12 +717,6 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
       rc = launch_chain(c, prec, true, p, st, 2);
     } else rc = launch_chain(c, prec, true, a, st);
     if (rc) return rc;
-    hipStream_t ws_st = st;
-    if (nbuf == 2) {
-      HIPCHK(hipEventRecord(c->ev_chain[bI], st));
-      HIPCHK(hipStreamWaitEvent(c->side, c->ev_chain[bI], 0));
-      ws_st = c->side;
-    }
     WgradArgs w = {};      // (zero: fields a path does not use must read as "off")
     w.stash_h = a.stash_h; w.stash_dz = a.stash_dz; w.stash_e = a.stash_e; w.graw = a.graw;
     w.rows = (t1 - t0) * TILE;
@@ -770,7 +726,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     const WgradSplit sp = wgrad_split(w.rows, b16 ? c->n_cu / N : (2 * c->n_cu) / (N + 1), kSplits, kSmallBlocks);
     w.n_splits = (int)sp.splits;
     w.rows_per_split = (int)sp.rows_per_split;
-    w.partial = partial; w.partial2 = partial2; w.partial_s = partial_s; w.debug = a.debug; w.small_groups = sg ? 1 : 0;
+    w.partial = partial; w.partial2 = partial2; w.partial_s = partial_s; w.small_groups = sg ? 1 : 0;
     w.gmax = a.gmax; w.stash_esz = (int)esz; w.gexp = a.gexp; w.hexp = a.hexp; w.enc16 = enc16 ? 1 : 0; w.coef_cols = a.coef_cols;
     w.dod = split ? a.dod : nullptr; w.gpr = a.s_pad / GROUP; w.group0 = t0 * (TILE / GROUP); w.group_ray = goff ? a.group_ray : nullptr;
     w.n_groups_valid = goff ? a.n_total / GROUP : n_rays * (int64_t)(a.s_pad / GROUP);
@@ -784,16 +740,11 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     rd.dsz = dsz;
     rc = with_width(c, [&](auto f) {
       constexpr int FW = decltype(f)::value;
-      if (!b16) return launch_wgrad_t<FW>(c, w, rd, N, ws_st);
-      if (s8) return launch_wgrad8_t<FW>(c, w, rd, N, ws_st);
-      return h16 ? launch_wgrad16_t<FW, true>(c, w, rd, N, ws_st) : launch_wgrad16_t<FW, false>(c, w, rd, N, ws_st);
+      if (!b16) return launch_wgrad_t<FW>(c, w, rd, N, st);
+      if (s8) return launch_wgrad8_t<FW>(c, w, rd, N, st);
+      return h16 ? launch_wgrad16_t<FW, true>(c, w, rd, N, st) : launch_wgrad16_t<FW, false>(c, w, rd, N, st);
     });
     if (rc) return rc;
-    if (nbuf == 2) HIPCHK(hipEventRecord(c->ev_wgrad[bI], c->side));
-  }
-  if (nbuf == 2) {       // join: everything on the side stream is ordered before whatever follows on the caller's stream
-    HIPCHK(hipStreamWaitEvent(st, c->ev_wgrad[0], 0));
-    if (ci >= 2) HIPCHK(hipStreamWaitEvent(st, c->ev_wgrad[1], 0));
   }
   return AFX_OK;
 }
@@ -1020,7 +971,7 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
   ChainArgs base = {};
   fill_model(c, prec, true, prepared, base);
   fill_render(r, base);
-  base.fused = 0; base.stash8 = 1; base.coef_cols = 0; base.debug = 0; base.persistent = 1;
+  base.fused = 0; base.stash8 = 1; base.coef_cols = 0;
   base.od_part = h.od_part; base.gmax = h.p.gmax; base.defer_out = 1; base.dod = nullptr; base.pixel = r->pixel;
   auto set_args = [&](const ChainArgs& src, const StashSet& b, int64_t r0, int64_t r1, int64_t sp) {
     ChainArgs a = src;
@@ -1529,19 +1480,18 @@ extern "C" int afx_philox_uniform(uint64_t seed, uint64_t stream_id, int64_t n, 
 }
 
 // ---- the host read-back of an offsets kernel's two totals (afx_march_train_step_mse, afx_march_render): k_ray_offsets posts them and a sequence
-// tag to host-mapped memory and the host polls the tag (AFX_MAILBOX=0: a 16-byte copy + stream synchronisation behind the kernel instead - 27 us
-// per read-back slower, tools/grid_iter.py).  `slot` 0 or 1: the mailbox's two 4-word slots.  totals_dev: 2 device words; h: the totals, on the host.
+// tag to host-mapped memory and the host polls the tag (where no mapped memory can be had: a 16-byte copy + stream synchronisation behind the
+// kernel instead - 27 us per read-back slower, tools/grid_iter.py).  `slot` 0 or 1: the mailbox's two 4-word slots.  totals_dev: 2 device words; h: the totals, on the host.
 static int offsets_read_back(afx_ctx* c, const int32_t* cnt, int64_t R, int64_t* offs, int64_t* goffs, int64_t* totals_dev, int slot, int64_t* h,
                              void* stream, const char* who) {
   hipStream_t st = (hipStream_t)stream;
-  static const bool use_mailbox = !(getenv("AFX_MAILBOX") && atoi(getenv("AFX_MAILBOX")) == 0);
-  if (use_mailbox && !c->mailbox) {
+  if (!c->mailbox) {
     if (hipHostMalloc((void**)&c->mailbox, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->mailbox_dev, c->mailbox, 0) != hipSuccess) {
       if (c->mailbox) (void)hipHostFree(c->mailbox);
       c->mailbox = c->mailbox_dev = nullptr;
     } else for (int i = 0; i < 8; ++i) c->mailbox[i] = 0;
   }
-  if (!(use_mailbox && c->mailbox)) {
+  if (!c->mailbox) {
     if (int r = afx_ray_offsets(cnt, R, offs, goffs, totals_dev, stream)) return r;
     HIPCHK(hipMemcpyAsync(h, totals_dev, 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -1846,7 +1796,7 @@ extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const 
   a.mode = 1; a.org = m.origins; a.dir = m.dirs; a.poses = nullptr;
   a.depth_mode = 4; a.z = tsp; a.te = tep; a.group_ray = gray;
   a.n_samples = GROUP; a.s_pad = GROUP; a.n_total = std::max<int64_t>(L.g_cap, 1) * GROUP;
-  a.fused = 0; a.stash8 = 1; a.coef_cols = 0; a.debug = 0; a.persistent = 1; a.defer_out = 1; a.dod = nullptr;
+  a.fused = 0; a.stash8 = 1; a.coef_cols = 0; a.defer_out = 1; a.dod = nullptr;
   a.od_part = L.od; a.gmax = L.p.gmax;
   a.tile0 = 0; a.tile1 = (int)((a.n_total + tile - 1) / tile);
   a.stash_h = (float*)set.stash_h; a.stash_dz = (float*)set.stash_dz; a.stash_e = nullptr;

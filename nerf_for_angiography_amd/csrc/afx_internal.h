@@ -16,18 +16,14 @@ constexpr int GROUP = 32;            // samples per wave column group; s_pad is 
 // ring of one-tile steps, requested 3 steps ahead, measured 5 ms slower per 512^2x128 step: twice the barriers).
 // tiles per step: 4 in the forward-only kernels and, at width 128 (a layer is 4 tiles, its slabs 32 KiB), also in the backward kernel -
 // one barrier per layer; at width 256 the backward kernel's ReLU masks leave LDS room for 2-tile steps only
-// PHASE 2 (the backward half of the split training step) at widths <= 128: TWO workgroups per CU (AFX_P2_OCC2, default on).  At those widths
+// PHASE 2 (the backward half of the split training step) at widths <= 128: TWO workgroups per CU.  At those widths
 // a tile is 8 MFMAs against an epilogue of the same length as at width 256, so a lone workgroup - whose two waves per SIMD run in lockstep
 // behind the step barrier - leaves the matrix pipe idle most of the time; a second, unsynchronised workgroup fills it.  That needs <= 128
 // VGPRs per wave (the backward half fits: no forward activations, no in-kernel group sums) and <= 80 KB of LDS: two-tile steps.
-#ifndef AFX_P2_OCC2
-#define AFX_P2_OCC2 1
-#endif
-constexpr bool chain_occ2(int nt, int phase) { return AFX_P2_OCC2 && phase == 2 && nt <= 4; }
+constexpr bool chain_occ2(int nt, int phase) { return phase == 2 && nt <= 4; }
 constexpr int chain_tps(int nt, bool bwd, bool x3, int phase = 0) {
   return chain_occ2(nt, phase) ? (nt >= 2 ? 2 : 1) : ((nt >= 4 && !x3 && (!bwd || nt == 4)) ? 4 : (nt >= 2 ? 2 : 1));
 }
-constexpr int chain_ring(bool bwd) { return 2; }
 constexpr uint32_t chain_slab0_bytes(int nk0) { return ((uint32_t)nk0 * 2048u + 4095u) / 4096u * 4096u; }
 constexpr uint32_t chain_slot_bytes(int nt, int nk0, bool bwd, bool x3, int phase = 0) {
   const uint32_t s0 = phase == 2 ? 0u : (uint32_t)chain_tps(nt, bwd, x3, phase) * chain_slab0_bytes(nk0);      // (the backward half streams no first-layer slab)
@@ -80,13 +76,12 @@ struct ChainArgs {
                             // the same layout of d(enc)/d(coef)/(2 pi) when coef_cols > 0
   float* graw;              // [rows]             dL/draw
   int64_t stash_rows;
-  int32_t persistent;       // 1: grid = #CUs, workgroups loop over tiles; 0: one workgroup per tile (lets the dispatcher
-                            //    interleave this grid with a concurrent kernel on another stream)
+  int32_t persistent;       // unused; kept for the layout
   int32_t fused;            // backward kernel computes pixel, MSE gradient and dL/draw itself (train step)
   const float* target;      // [R] (fused)
   float* pixel;             // [R] out (fused)
   float inv_n;              // 1 / global ray count (fused)
-  int32_t debug;            // unused
+  int32_t debug;            // unused; kept for the layout
   // in-kernel small gradients (bf16 backward, rays mode, no encoding): per 32-sample group [SW[F] S0[F] S1[F] c[3] d[3] sum_g -]
   float* small_part;        // null: H_N, dZ_0, encoded inputs and dL/draw are stashed for k_small_grads_bf16 instead
   uint32_t* gmax;           // f16 mode: bit pattern of max |dL/draw| over the chunk (integer atomicMax; zeroed per chunk)
@@ -127,7 +122,7 @@ struct WgradArgs {
   int32_t n_splits, rows_per_split;   // rows_per_split even
   float* partial;           // [(N+2), n_splits, F*F]: slot l = layer l; slot N+1 = the d(enc)/d(coef) contraction
   float* partial2;          // [(N+2), n_splits, F+4]
-  int32_t debug;            // timing experiments only (bit5: default-policy instead of non-temporal stash loads)
+  int32_t debug;            // unused; kept for the layout
   float* partial_s;         // bf16 path: [n_small, F*k0pad + 2F + 4] first-layer / output-layer partials
   int32_t small_groups;     // 1: the chain kernel left per-group sums where H_N's stash would be (k_small_from_groups)
   const uint32_t* gmax;     // f16 mode: the chunk's max |dL/draw| (scale of the contraction, wgrad_scale_exp)

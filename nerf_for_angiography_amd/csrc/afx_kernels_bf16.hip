@@ -85,10 +85,6 @@ template <int F> __device__ __forceinline__ uint32_t stash_off(uint32_t r, int c
 template <int F> __device__ __forceinline__ uint32_t stash_off8(uint32_t r, int ch16) {
   return ((((r >> 5) * (F / 16) + ch16) << 5) + (r & 31)) << 4;
 }
-#ifndef AFX_GAPS      // (the MFMA-gap schedule of the 8-bit-stash backward kernel, described below)
-#define AFX_GAPS 0
-#endif
-#define AFX_GAPS_ON AFX_GAPS
 // H6 (6-bit H stash; -DAFX_H6=1, build.py --variant=h6 - built, tested, NOT the default: on the 512^2 x 128 step it takes 1 ms off
 // k_wgrad_s8 and puts 1.6 ms on the chain kernel): the hidden
 // activations H_l (l < N), the B operand of the weight-gradient contraction, are stashed as bf6 (e3m2: the 2 mantissa bits of bf8, 3 exponent
@@ -102,7 +98,6 @@ template <int F> __device__ __forceinline__ uint32_t stash_off8(uint32_t r, int 
 #ifndef AFX_H6
 #define AFX_H6 0
 #endif
-#define AFX_H6_ON (AFX_H6 && !AFX_GAPS_ON)
 typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 typedef unsigned u32x6 __attribute__((ext_vector_type(6)));
 typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
@@ -155,26 +150,11 @@ __device__ __forceinline__ u32x2 to_bf8x8(unsigned p0, unsigned p1, unsigned p2,
   hi = __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(hi, __builtin_bit_cast(f16x2_t, p3), 1.0f, true);
   return (u32x2){__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
 }
-// one packed f16 pair -> two bf8 bytes in the low (HI = false) or high half of `acc` (the builtin wants HI as a constant)
-template <bool HI> __device__ __forceinline__ unsigned bf8_pair(unsigned acc, unsigned pair) {
-  if (HI) asm("v_cvt_scalef32_pk_bf8_f16 %0, %1, 1.0 op_sel:[0,0,1]" : "+v"(acc) : "v"(pair));
-  else asm("v_cvt_scalef32_pk_bf8_f16 %0, %1, 1.0" : "+v"(acc) : "v"(pair));
-  return acc;
-}
-// one v_pk_mul_f16 on dwords.  (asm: hipcc 7.2 miscompiles f16x2 arithmetic on bit-cast elements of a u32x4 - it folds the
-// element index away, see k_wgrad_bf16 - and the gap schedule wants exactly one instruction per slot anyway)
-__device__ __forceinline__ unsigned pk_mul_f16(unsigned a, unsigned b) {
-  unsigned r;
-  asm("v_pk_mul_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
 // compile-time unrolled loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
 template <int... I, class Fn> __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, Fn&& f) {
   (f(std::integral_constant<int, I>{}), ...);
 }
 template <int N_, class Fn> __device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(std::make_integer_sequence<int, N_>{}, f); }
-// AFX_GAPS=1 (build.py --variant=gaps): the MFMA-gap schedule of the 8-bit-stash backward kernel, kept for A/B.  It measured
-// 3 ms SLOWER per step than the plain order, with real and with all-zero operands, so the default is off.
 // stash position -> feature for the 8-bit layout (a permutation inside each block of 32)
 __device__ __forceinline__ int fperm8(int p) {
   const int hh = (p >> 4) & 1, s2 = (p >> 3) & 1, j = p & 7;
@@ -184,12 +164,7 @@ __device__ __forceinline__ int fperm8(int p) {
 // 16-byte stash store, non-temporal: the stash is written once and read once by another kernel, so it must not
 // displace the weight slabs every workgroup re-streams from L2.  A/B in one process on the 512^2x128 step,
 // k_chain<bwd>: plain 116 ms, nt 99 ms, sc1 (write-through) 121 ms.
-#ifdef AFX_STASH_WINDOW      // measurement build only (build.py --variant=window): every stash store lands in one 1 MiB window that stays in L2,
-__device__ char g_stash_window[1 << 20];      // i.e. the same instruction stream without the HBM write stream (results are garbage)
-__device__ __forceinline__ void stash_store(char* p, u32x4 v) { *(u32x4*)(g_stash_window + ((uintptr_t)p & 0xFFFF0u)) = v; }
-#else
 __device__ __forceinline__ void stash_store(char* p, u32x4 v) { __builtin_nontemporal_store(v, (u32x4*)p); }
-#endif
 
 // Packed-bf16 epilogue helpers.  The bf16 sign bit is the int16 sign bit, so ReLU of two packed values is
 // one v_pk_max_i16, [h != 0] per half one v_pk_min_u16, and a per-half 0xffff/0 mask from bit q of each
@@ -241,13 +216,6 @@ template <int K> __device__ __forceinline__ void lds_wait_frag(u32x4& r) {
   asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(r) : "n"(K) : "memory");
 #endif
 }
-#ifndef AFX_PF_FWD
-#define AFX_PF_FWD 4
-#define AFX_PF_BWD 4
-#endif
-#ifndef AFX_PP_FWD
-#define AFX_PP_FWD true
-#endif
 // SG ("small gradients in the kernel", backward, rays mode, no encoding): the first layer's and the output layer's
 // weight gradients contract over samples too, but have only 3 / 1 columns, and their operands dZ_0 and H_N were a ninth
 // of the stash traffic plus a pass of their own (k_small_grads_bf16).  A wave's 32 samples are one ray's 32-sample
@@ -301,7 +269,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
   uint64_t tlast = __builtin_amdgcn_s_memtime();
 #endif
   constexpr int TPS = chain_tps(NT, BWD, X3, PHASE);
-  constexpr int RING = chain_ring(BWD);               // LDS slots of the weight ring
+  constexpr int RING = 2;                             // LDS slots of the weight ring
   constexpr int PD = RING - 1;                        // a step's slabs are requested PD steps ahead
   static_assert(!SG || PD == 1, "SG marks its store-less steps for PD = 1 only");
   constexpr int SPL = NT / TPS;                       // steps per layer
@@ -379,34 +347,9 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
   // Raw s_barrier: __syncthreads() would re-insert vmcnt(0).
   constexpr int WAITN = (BWD ? PD * SPS : 0) + (PD - 1) * (PIECES0 < PIECESH ? PIECES0 : PIECESH);
   // `counted` = false: the previous step issued no stash stores (SG: the last forward layer's H_N is not stashed)
-  // GAPS (8-bit stash kernel): stash stores move between tiles, so the wave counts them; a step that issued fewer than SPS
-  // behind its request is followed by a full wait (wave-uniform scalar counter).
-  constexpr bool GAPS = S8 && AFX_GAPS && PHASE == 0;
-  constexpr bool H6 = S8 && AFX_H6_ON;      // bf6 H stash (the gap-schedule A/B build keeps the bf8 one)
+  constexpr bool H6 = S8 && AFX_H6;      // bf6 H stash
   static_assert(!H6 || (NCG == 1 && NT % 2 == 0 && TPS % 2 == 0), "6-bit H stash: a wave owns one 32-sample group and whole tile pairs per step");
-  constexpr int IPG = 16 / (2 * NT);     // work items per MFMA gap (GAPS)
-  int nstores = 0;
-  // GAPS: a hidden step's request is issued piece by piece in the first MFMA gaps of the step's first tile (defer = true):
-  // issued in one burst behind the barrier, the 8 waves' pieces queue in the vector-memory path and every wave sits in that
-  // queue before its first MFMA (12-20 % of the waves' cycles in the stamp build).  All pieces precede the step's stores.
-  bool req_pending = false;
-  auto request_piece = [&](int i) {
-    char* dst = slot0 + wslot * SLOT;
-    const uint32_t off = (uint32_t)i * (NW * 1024u);
-    if (cpos < SPL ? i < PIECES0 : i < PIECESH)
-      __builtin_amdgcn_global_load_lds(GPTR(wnext + off + voff), LPTR(dst + off + wave * 1024), 16, 0, 0);
-  };
-  auto request_end = [&]() {
-    wnext += cpos < SPL ? STEP0 : STEPH;
-    if (++cpos == steps_per_tile) { cpos = 0; wnext = a.stream_fwd; }
-    wslot = wslot + 1 == RING ? 0 : wslot + 1;
-    --to_issue;
-    nstores = 0;
-    req_pending = false;
-  };
-  static_assert(!GAPS || (PIECES0 <= PIECESH && PIECESH <= 2 * NT && (PIECESH - 1) * IPG < 7), "GAPS: the request's pieces precede the first stash store");
-  auto step_begin = [&](bool counted = true, bool defer = false) -> const char* {
-    if constexpr (GAPS) counted = nstores >= SPS;
+  auto step_begin = [&](bool counted = true) -> const char* {
 #ifdef AFX_SAFE_WAITS
     counted = false;
 #endif
@@ -419,10 +362,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       STAMP(1);
     }
-    if (to_issue > 0) {
-      if (GAPS && defer) req_pending = true;
-      else { request(); nstores = 0; }
-    }
+    if (to_issue > 0) request();
     STAMP(2);
     const char* cur = slot0 + rslot * SLOT;
     rslot = rslot + 1 == RING ? 0 : rslot + 1;
@@ -547,7 +487,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
           if (relu) p[q] = relu2(p[q]);
         }
         if (bt >= 0) acc = bias_init(bl, bt);
-        if (BWD && !(GAPS && (l >= 1 || t == NT - 1))) {
+        if (BWD) {
           unsigned bits = nz2(p[0], one2);
 #pragma unroll
           for (int q = 1; q < 8; ++q) bits |= nz2(p[q], one2) << q;
@@ -572,11 +512,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
                                        pk_max_u16(pk_max_u16(pr[1][0], pr[1][1]), pk_max_u16(pr[1][2], pr[1][3])));
               mx = pk_max_u16(mx, pk_max_u16(pk_max_u16(pk_max_u16(pr[2][0], pr[2][1]), pk_max_u16(pr[2][2], pr[2][3])),
                                              pk_max_u16(pk_max_u16(pr[3][0], pr[3][1]), pk_max_u16(pr[3][2], pr[3][3]))));
-#ifdef AFX_H6_CONST      // measurement build only (build.py --variant=h6c): no max, scale 1 - the cost of the scale computation by difference
-              const unsigned e8 = 127u + (mx & 0u);
-#else
               const unsigned e8 = 109u + (wave_max_u32(max(mx & 0xffffu, mx >> 16)) >> 10);      // E8M0 of 2^(exponent of the max - 3)
-#endif
               hx |= e8 << (8 * (t >> 1));
               const u32x16 v16 = {pr[0][0], pr[0][1], pr[0][2], pr[0][3], pr[1][0], pr[1][1], pr[1][2], pr[1][3],
                                   pr[2][0], pr[2][1], pr[2][2], pr[2][3], pr[3][0], pr[3][1], pr[3][2], pr[3][3]};
@@ -593,8 +529,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
             stash_store((char*)a.stash_h + (size_t)l * a.stash_rows * F + (so[cg] + (uint32_t)(2 * t) * 512u), to_bf8x16(nf[0], nf[1], 1.0f));
           }
         } else if constexpr (S8) {
-          if ((l != N || (P1 && a.defer_out)) && !(GAPS && (l >= 1 || t == NT - 1))) {     // one 16-byte store per tile: chunk 2t + h of the 8-bit layout
-            ++nstores;
+          if (l != N || (P1 && a.defer_out)) {     // one 16-byte store per tile: chunk 2t + h of the 8-bit layout
             stash_store((char*)a.stash_h + (size_t)l * a.stash_rows * F + (so[cg] + (uint32_t)(2 * t) * 512u), to_bf8x16(nf[0], nf[1], 1.0f));
           }
         }
@@ -605,13 +540,8 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
     };
 
     // Backward kernel: acc[cg] += W_tile . B with a rolling PF-deep fragment prefetch and hand-counted LDS waits.
-    // `gap(u)` (u a std::integral_constant): independent VALU / store work issued between MFMA u and MFMA u + 1.  The MFMAs of
-    // a tile form one dependent chain (same accumulator), so the wave's issue slots between them are free; the partner wave
-    // of the SIMD runs the same phase at the same time (the step barrier keeps the pair in lockstep), so work that sits in
-    // front of or behind the loop leaves the matrix pipe idle for both.
-    auto no_gap = [](auto) {};
-    auto rolling_mma_impl = [&](auto pf_c, const u32x4* sl, u32x4 (*bh)[NT][2], f32x16* acc, auto&& gap) {
-      constexpr int PF = decltype(pf_c)::value;
+    auto rolling_mma = [&](const u32x4* sl, u32x4 (*bh)[NT][2], f32x16* acc) {
+      constexpr int PF = 4;
       static_assert(PF >= 1 && PF <= 5 && PF <= 2 * NT, "the tail waits below cover PF <= 5");
       const uint32_t la = (uint32_t)(uintptr_t)LPTR(sl) + (uint32_t)lane * 16u;
       u32x4 ar[PF];
@@ -630,7 +560,6 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) acc[cg] = mfma_t<H16>(ah, bh[cg][u >> 1][u & 1], acc[cg]);
         if constexpr (u + PF < 2 * NT) lds_read_frag(ar[u % PF], la, (u + PF) * 1024);
-        gap(uc);
         __builtin_amdgcn_sched_barrier(0);
       });
     };
@@ -638,9 +567,9 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
     // One hidden-layer tile: acc[cg] += W_tile . B over all 2*NT k-steps.  A fragments are read from the
     // slab in groups of G k-steps, two groups in flight (explicit software pipeline; sched_barrier keeps
     // hipcc from sinking the reads back next to their MFMAs), so LDS latency hides behind >= G MFMAs.
-    auto mma_step = [&](const u32x4* sl, const u32x4* sll, u32x4 (*bh)[NT][2], u32x4 (*bl)[X3 ? NT : 1][2], f32x16* acc, auto&& gap) {
+    auto mma_step = [&](const u32x4* sl, const u32x4* sll, u32x4 (*bh)[NT][2], u32x4 (*bl)[X3 ? NT : 1][2], f32x16* acc) {
       if (BWD) {      // (forward-only kernels: the grouped reads below measure the same, 26.4 vs 26.5 ms)
-        rolling_mma_impl(std::integral_constant<int, AFX_PF_FWD>{}, sl, bh, acc, gap);
+        rolling_mma(sl, bh, acc);
         return;
       }
       constexpr int G = (X3 || NW == 8) ? 2 : 4;
@@ -716,47 +645,13 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
       f32x16 accp[NCG];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
-        if (t % TPS == 0) stepbase = step_begin(!(SG && l == N && t > 0), true);
+        if (t % TPS == 0) stepbase = step_begin(!(SG && l == N && t > 0));
         const u32x4* sl = (const u32x4*)(stepbase + (t % TPS) * SLABT);             // hi block [u*64 + lane]
         const u32x4* sll = (const u32x4*)(stepbase + STEPH + (t % TPS) * SLABT);    // lo block (X3)
         f32x16 acc[NCG];
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) acc[cg] = BWD ? accn[cg] : bias_init(l, t);
-        if constexpr (GAPS) {
-          // The part of a forward tile's epilogue that needs only its packed activations - ReLU mask bits, 8-bit stash - is
-          // issued in the gaps of the NEXT tile's MFMA loop: tile (l, t-1), or the previous layer's last tile at t == 0.
-          static_assert(NCG == 1, "");
-          const int pl = t > 0 ? l : l - 1, pt = t > 0 ? t - 1 : NT - 1;
-          const u32x4* pfr = t > 0 ? hd[0][t - 1] : hs[0][NT - 1];
-          unsigned bits = 0, r[4];
-          mma_step(sl, sll, hs, hsl, acc, [&](auto uc) {
-            if constexpr (decltype(uc)::value < PIECESH) {
-              if (t % TPS == 0 && req_pending) {
-                request_piece(decltype(uc)::value);
-                if constexpr (decltype(uc)::value == PIECESH - 1) request_end();
-              }
-            }
-            static_for<IPG>([&](auto kc) {       // 16 work items over the 2 NT gaps
-              constexpr int j = decltype(uc)::value * IPG + decltype(kc)::value;
-              if constexpr (j < 8) {
-                const unsigned z = nz2(pfr[j >> 2][j & 3], one2);
-                bits = j == 0 ? z : (bits | (z << j));
-              } else {
-                constexpr int i = j - 8;
-                r[i >> 1] = bf8_pair<(i & 1) != 0>((i & 1) ? r[i >> 1] : 0u, pfr[i >> 2][i & 3]);
-              }
-              if constexpr (j == 15) {
-                if (pl != N) {
-                  ++nstores;
-                  stash_store((char*)a.stash_h + (size_t)pl * a.stash_rows * F + (so[0] + (uint32_t)(2 * pt) * 512u), (u32x4){r[0], r[1], r[2], r[3]});
-                }
-              }
-            });
-          });
-          mk16[((pl * NT + pt) * NCG) * NTH + tid] = (unsigned short)(bits | (bits >> 8));
-        } else {
-          mma_step(sl, sll, hs, hsl, acc, no_gap);
-        }
+        mma_step(sl, sll, hs, hsl, acc);
         if (DEFER) {
           if (t > 0) {
 #pragma unroll
@@ -782,14 +677,6 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
         for (int cg = 0; cg < NCG; ++cg)
           epilogue(l, NT - 1, accp[cg], cg, hd[cg][NT - 1], hdl[X3 ? cg : 0][X3 ? NT - 1 : 0]);
       }
-      if constexpr (GAPS) {
-        if (l == N) {      // nothing follows the last layer's last tile: its mask bits here (H_N is not stashed)
-          unsigned bits = nz2(hd[0][NT - 1][0][0], one2);
-#pragma unroll
-          for (int q = 1; q < 8; ++q) bits |= nz2(hd[0][NT - 1][q >> 2][q & 3], one2) << q;
-          mk16[((N * NT + NT - 1) * NCG) * NTH + tid] = (unsigned short)(bits | (bits >> 8));
-        }
-      }
     };
     {
       u32x4 nf[NCG][NT][2];
@@ -797,7 +684,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
       int l = 1;
       // Forward-only kernels run two layers per loop trip, ping-ponging the two fragment sets (no register copies
       // between layers); the backward kernel and the encoding variants are register-bound and spill with the doubled body.
-      if (!BWD && !ENC && AFX_PP_FWD) {
+      if (!BWD && !ENC) {
         for (; l + 1 <= N; l += 2) {
           fwd_layer(l, hf, hl, nf, nl);
           fwd_layer(l + 1, nf, nl, hf, hl);
@@ -955,9 +842,7 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
           // wave waited its turn at the next step): the backward half ran 736 us with real gradients against 366 us with all-zero ones (where
           // `gm > 0` never fires); per-wave new maxima alone still cost 42 us of a 1.18 ms iteration at 4x128, 71 us of 0.66 ms at 4x64.
           const uint32_t gbits = __builtin_bit_cast(uint32_t, gm);
-#ifndef AFX_NO_GMAX_ATOMIC      // (measurement build --variant=nogmax: wrong weight-gradient scale, timing only)
           if (lane == 0 && gbits > wave_gmax) { atomicMax(wg_gmax_p, gbits); wave_gmax = gbits; }
-#endif
           if constexpr (S8) {
             // 8-bit stash: dZ' = g_hat J with g normalised by its 32-sample group's power of two, |g_hat| <= 1; the group's
             // exponent goes to the weight-gradient kernel as the block scale of the MX matrix instruction
@@ -982,7 +867,6 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
           }
         }
       }
-      auto mma_step_plain = [&](const u32x4* sl, u32x4 (*bh)[NT][2], f32x16* acc) { rolling_mma_impl(std::integral_constant<int, AFX_PF_BWD>{}, sl, bh, acc, no_gap); };
       auto stash_dz_tile = [&](int l, int t) {
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
@@ -1018,14 +902,13 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
           }
         }
       };
-      unsigned pk[8], mwprev = 0;      // GAPS: the previous tile's packed, not yet masked input gradients and its mask word
       for (int l = N; l >= 1; --l) {
         u32x4 dn[NCG][NT][2];
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          if (t % TPS == 0) stepbase = step_begin(!(SG && l == N && t == 0), true);
+          if (t % TPS == 0) stepbase = step_begin(!(SG && l == N && t == 0));
           const u32x4* sl = (const u32x4*)(stepbase + (t % TPS) * SLABT);
-          if constexpr (!GAPS) stash_dz_tile(l, t);                   // SPS stores per step, after the step's request
+          stash_dz_tile(l, t);                   // SPS stores per step, after the step's request
           f32x16 acc[NCG];
           unsigned mw[NCG];                      // ReLU mask words, read ahead of the MFMA loop
 #pragma unroll
@@ -1033,62 +916,17 @@ __global__ void __launch_bounds__(64 * NW, chain_occ2(F / 32, PHASE) ? 4 : NW / 
             acc[cg] = (f32x16){0.f};
             mw[cg] = mk16[(((l - 1) * NT + t) * NCG + cg) * NTH + tid];
           }
-          if constexpr (GAPS) {
-            // in the gaps of this tile's MFMA chain: the 8-bit stash of dZ'_l tile t (scale by g_hat, convert, store) and the
-            // ReLU masking of the previous tile's result; behind the loop only the fp32 -> f16 packing of this tile is left
-            unsigned r[4];
-            const unsigned b32p = mask_expand(mwprev);
-            rolling_mma_impl(std::integral_constant<int, AFX_PF_BWD>{}, sl, dz, acc, [&](auto uc) {
-              if constexpr (decltype(uc)::value < PIECESH) {
-                if (t % TPS == 0 && req_pending) {
-                  request_piece(decltype(uc)::value);
-                  if constexpr (decltype(uc)::value == PIECESH - 1) request_end();
-                }
-              }
-              static_for<IPG>([&](auto kc) {
-                constexpr int j = decltype(uc)::value * IPG + decltype(kc)::value;
-                if constexpr (j < 8) {
-                  const unsigned x = pk_mul_f16(dz[0][t][j >> 2][j & 3], ghat2[0]);
-                  r[j >> 1] = bf8_pair<(j & 1) != 0>((j & 1) ? r[j >> 1] : 0u, x);
-                  if constexpr (j == 7) {
-                    ++nstores;
-                    stash_store((char*)a.stash_dz + (size_t)l * a.stash_rows * F + (so[0] + (uint32_t)(2 * t) * 512u), (u32x4){r[0], r[1], r[2], r[3]});
-                  }
-                } else if (t > 0) {
-                  constexpr int q = j - 8;
-                  pk[q] &= halfmask(b32p, q);
-                  if constexpr (j == 15) {
-                    dn[0][t > 0 ? t - 1 : 0][0] = (u32x4){pk[0], pk[1], pk[2], pk[3]};
-                    dn[0][t > 0 ? t - 1 : 0][1] = (u32x4){pk[4], pk[5], pk[6], pk[7]};
-                  }
-                }
-              });
-            });
-            STAMP(5);
+          rolling_mma(sl, dz, acc);
+          STAMP(5);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) pk[q] = pack2t<H16>(acc[0][2 * q], acc[0][2 * q + 1]);
-            mwprev = mw[0];
-            if (t == NT - 1) {
-              const unsigned b32 = mask_expand(mw[0]);
+          for (int cg = 0; cg < NCG; ++cg) {
+            // dZ_{l-1} = dH_{l-1} masked by ReLU'(Z_{l-1}): round to bf16, AND the pairs with their half masks
+            const unsigned b32 = mask_expand(mw[cg]);
 #pragma unroll
-              for (int q = 0; q < 8; ++q) pk[q] &= halfmask(b32, q);
-              dn[0][t][0] = (u32x4){pk[0], pk[1], pk[2], pk[3]};
-              dn[0][t][1] = (u32x4){pk[4], pk[5], pk[6], pk[7]};
-            }
-            STAMP(6);
-          } else {
-            mma_step_plain(sl, dz, acc);
-            STAMP(5);
-#pragma unroll
-            for (int cg = 0; cg < NCG; ++cg) {
-              // dZ_{l-1} = dH_{l-1} masked by ReLU'(Z_{l-1}): round to bf16, AND the pairs with their half masks
-              const unsigned b32 = mask_expand(mw[cg]);
-#pragma unroll
-              for (int q = 0; q < 8; ++q)
-                dn[cg][t][q >> 2][q & 3] = pack2t<H16>(acc[cg][2 * q], acc[cg][2 * q + 1]) & halfmask(b32, q);
-            }
-            STAMP(6);
+            for (int q = 0; q < 8; ++q)
+              dn[cg][t][q >> 2][q & 3] = pack2t<H16>(acc[cg][2 * q], acc[cg][2 * q + 1]) & halfmask(b32, q);
           }
+          STAMP(6);
         }
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg)

@@ -10,7 +10,7 @@ from nerf_for_angiography_amd.render import train_step_mse, projection_spec
 from nerf_for_angiography_amd.phantomdata.helpers import get_ray_values
 
 dev = torch.device("cuda:0")
-VARIANT = os.environ.get("AFX_VARIANT", "")     # "gaps": libafx_gaps.so (build.py --variant=gaps)
+VARIANT = os.environ.get("AFX_VARIANT", "")     # a build.py variant: libafx_<variant>.so
 def model():
     torch.manual_seed(0)
     md = dict(num_early_layers=8, num_late_layers=0, num_filters=256, num_input_channels=3, num_output_channels=1,
