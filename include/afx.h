@@ -491,6 +491,53 @@ int afx_gather_rays(const float* origins, const float* dirs, const float* pixels
 /* out[i] = uniform [0,1) number i of Philox4x32-10 stream (seed, stream_id): the generator of every "perf mode" draw */
 int afx_philox_uniform(uint64_t seed, uint64_t stream_id, int64_t n, float* out, void* stream);
 
+/* ---- Ray-sampling weights of the projections (sampling_strategy='frangi' | 'segmentation'; phantomdata/cttoray.py:210-216 and
+ * get_weighted_img, phantomdata/helpers.py:226-247).  N images of one size h x w, row-major fp64 [N, h, w], in one fixed sequence of
+ * launches whatever N and the number of scales.  fp64 throughout, no floating-point atomics (deterministic), nothing allocated or
+ * synchronised (hipGraph-capturable); the image must be memory of the current device.  AFX_E_INVALID: null pointers, n outside
+ * 1..65535, h or w outside 1..16384 (2..16384 wherever a Hessian is taken), a bad sigma list or beta / gamma <= 0.  A workspace smaller
+ * than the query (the queries return 0 for arguments the call refuses) gives AFX_E_WORKSPACE, with *workspace_needed set when it is
+ * not NULL.
+ *
+ * afx_frangi: the Frangi vesselness filter as scikit-image 0.18.3 computes it (filters.ridges.frangi; 0.19 changed the default gamma,
+ * the Hessian and the background rule).  For each image I and each sigma in sigmas[n_sigmas] (1..16 values, each > 0 with
+ * int(4 sigma + 0.5) <= 1000):
+ *   1. black_ridges != 0: I <- 1 - I
+ *   2. G = scipy.ndimage.gaussian_filter(I, sigma): separable (axis 0, then axis 1), radius r = int(4 sigma + 0.5), weights
+ *      exp(-j^2 / 2 sigma^2) normalised to sum 1, mode 'reflect' (d c b a | a b c d | d c b a, period 2n, also for r >= n)
+ *   3. np.gradient of G along both axes, np.gradient of those (unit spacing, central inside, one-sided at the edges): Hrr, Hrc, Hcc
+ *   4. times sigma^2
+ *   5. l+- = (Hrr + Hcc) / 2 +- sqrt(4 Hrc^2 + (Hrr - Hcc)^2) / 2; lambda1 the one of smaller |l| (a tie: l+), lambda2 the other
+ *   6. v = exp(-rb / 2 beta^2) (1 - exp(-(lambda1^2 + lambda2^2) / 2 gamma^2)), rb = (lambda1 / d)^2, d = |lambda2| (1e-10 where 0);
+ *      v = 0 where lambda2 > 0 (alpha has no effect in 2-D: there is no alpha argument)
+ *   7. out = max over the scales of v
+ * Workspace: 2 regions of N x n_sigmas x h x w doubles, each rounded up to 256 bytes.
+ *
+ * afx_distance_transform_edt: scipy.ndimage.distance_transform_edt per image, bit for bit: the distance from every non-zero pixel to the
+ * nearest zero pixel (sqrt of the exact integer squared distance in fp64); +inf everywhere in an image without a zero pixel.
+ * Workspace: N x h x w uint32, rounded up to 256 bytes.
+ *
+ * afx_sampling_weights: strategy AFX_SAMPLING_FRANGI - binary == 0: pixels > np.percentile(img, 10) ('linear') are set to 1 first;
+ * f = afx_frangi(img, sigmas, beta, gamma, black ridges); f = (f - min f) / (max f - min f); e = EDT(f); out = (e - min e) / (max e -
+ * min e) + 1e-10 (cttoray.py passes beta = 0.5 and alpha = 12 (binary) / 0.5, which has no effect).  Where a max - min is 0 the reference
+ * divides by zero: out is NaN for that image and status[i] (when status is not NULL) gets bit 1 (flat vesselness) and / or bit 2 (flat
+ * distance transform); status[i] = 0 otherwise.  AFX_SAMPLING_SEGMENTATION - the host sampling_weights(img, 'segmentation') of
+ * phantomdata/dataset.py: mask = img < 1, min-subtracted and divided by its max when that is > 0, e = EDT(mask), the same normalisation
+ * skipped when max e - min e is 0, + 1e-10 (sigmas, beta, gamma, binary ignored; status[i] = 0).
+ * Workspace (afx_sampling_weights_workspace_bytes; n_sigmas ignored for segmentation): in order, each rounded up to 256 bytes, N doubles,
+ * 2 N doubles, 2 N doubles, N x h x w uint32, then (frangi) afx_frangi's two planes. */
+enum { AFX_SAMPLING_FRANGI = 0, AFX_SAMPLING_SEGMENTATION = 1 };
+size_t afx_frangi_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t n_sigmas);
+int afx_frangi(const double* img, int32_t n, int32_t h, int32_t w, const double* sigmas, int32_t n_sigmas, double beta, double gamma,
+               int32_t black_ridges, double* out, void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
+size_t afx_distance_transform_edt_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int afx_distance_transform_edt(const double* x, int32_t n, int32_t h, int32_t w, double* out, void* workspace, size_t workspace_bytes,
+                               size_t* workspace_needed, void* stream);
+size_t afx_sampling_weights_workspace_bytes(int32_t strategy, int32_t n, int32_t h, int32_t w, int32_t n_sigmas);
+int afx_sampling_weights(const double* img, int32_t n, int32_t h, int32_t w, int32_t strategy, int32_t binary, const double* sigmas,
+                         int32_t n_sigmas, double beta, double gamma, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
+                         size_t* workspace_needed, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

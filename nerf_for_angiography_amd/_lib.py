@@ -12,6 +12,7 @@ PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "f16": 3, "f16s8": 4}
 RAYS_ARRAYS, RAYS_POSE = 0, 1
 DEPTH_UNIFORM_MID, DEPTH_SHARED_Z, DEPTH_PER_RAY_Z, DEPTH_STRATIFIED = 0, 1, 2, 3
 Q_PARAM_COUNT, Q_K0, Q_PREPARED_BYTES, Q_FWD_WORKSPACE, Q_BWD_WORKSPACE_MIN, Q_BWD_WORKSPACE_FULL = range(6)
+SAMPLING = {"frangi": 0, "segmentation": 1}                                 # AFX_SAMPLING_* (include/afx.h)
 GRID_JITTER_TAG, GRID_SELECT_TAG = 0x47524944 << 32, 0x53454C43 << 32      # Philox stream tags of the grid refresh (include/afx.h)
 
 
@@ -135,6 +136,15 @@ _SIGS = {
     "afx_gather_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "afx_philox_uniform": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "afx_frangi_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "afx_frangi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double, C.c_int32,
+                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_distance_transform_edt_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "afx_distance_transform_edt": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_sampling_weights_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "afx_sampling_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                       C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
 }
 
 _libs = {}

@@ -91,19 +91,6 @@ struct ProfScope {
 static inline uint32_t rup(uint64_t v, uint64_t a) { return (uint32_t)((v + a - 1) / a * a); }
 static inline size_t rup64(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// Hands out the regions of a workspace in order, each rounded up to `align` bytes; `end` is how far the carve has got.  The base is an
-// integer, so that the one function that describes a workspace both sizes it (base 0: nothing is dereferenced) and carves the caller's.
-struct Carve {
-  uintptr_t base = 0;
-  size_t end = 0;
-  template <class T = char>
-  T* take(size_t bytes, size_t align = 256) {
-    T* p = (T*)(base + end);
-    end += rup64(bytes, align);
-    return p;
-  }
-};
-
 // Runs f(std::integral_constant<int, F>()) for the context's layer width F (afx_create admits 64, 128 and 256 only).
 template <class Fn>
 static int with_width(const afx_ctx* c, Fn&& f) {
@@ -161,6 +148,9 @@ static PrepLayout prep_layout(const afx_ctx* c, int prec) {
 }
 
 extern "C" const char* afx_last_error(void) { return g_err.c_str(); }
+
+// The error message of an entry point defined in another translation unit (afx_kernels_image.hip).
+int afx::set_error(int code, const char* who, const char* msg) { return fail(code, "%s: %s", who, msg); }
 
 extern "C" int afx_create(const afx_model_desc* d, afx_ctx** out) {
   if (!d || !out) return fail(AFX_E_INVALID, "afx_create: null argument");

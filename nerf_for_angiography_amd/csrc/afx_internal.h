@@ -186,4 +186,20 @@ __host__ __device__ __forceinline__ WgradSplit wgrad_split(int64_t rows, int spl
   return {splits, rps, n_small};
 }
 
+// Hands out the regions of a workspace in order, each rounded up to `align` bytes; `end` is how far the carve has got.  The base is an
+// integer, so that the one function that describes a workspace both sizes it (base 0: nothing is dereferenced) and carves the caller's.
+struct Carve {
+  uintptr_t base = 0;
+  size_t end = 0;
+  template <class T = char>
+  T* take(size_t bytes, size_t align = 256) {
+    T* p = (T*)(base + end);
+    end += (bytes + align - 1) / align * align;
+    return p;
+  }
+};
+
+// Sets afx_last_error()'s message to "<who>: <msg>" and returns `code` (defined in afx_api.hip, for the other translation units).
+int set_error(int code, const char* who, const char* msg);
+
 }  // namespace afx

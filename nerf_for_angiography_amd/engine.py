@@ -853,6 +853,68 @@ def topk_indices(keys: torch.Tensor, k: int) -> torch.Tensor:
     return out
 
 
+def _images_f64(x: torch.Tensor, who: str) -> torch.Tensor:
+    """[H, W] or [N, H, W] device tensor -> contiguous float64 [N, H, W]."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise AfxError(f"{who}: the images must be a tensor on a GPU; there is no CPU path")
+    if x.dim() not in (2, 3):
+        raise ValueError(f"{who}: expected [H, W] or [N, H, W], got shape {tuple(x.shape)}")
+    x = x if x.dim() == 3 else x[None]
+    return x.to(torch.float64).contiguous()
+
+
+def _sigma_array(sigmas):
+    s = [float(v) for v in sigmas]
+    return (C.c_double * max(len(s), 1))(*s), len(s)
+
+
+def frangi(images: torch.Tensor, sigmas=(1, 3, 5, 7, 9), beta: float = 0.5, gamma: float = 15.0, black_ridges: bool = True) -> torch.Tensor:
+    """afx_frangi: the Frangi vesselness (scikit-image 0.18.3) of every image of a [N, H, W] (or [H, W]) device tensor, float64 [N, H, W]."""
+    lib = _lib.load()
+    x = _images_f64(images, "frangi")
+    n, h, w = x.shape
+    sg, ns = _sigma_array(sigmas)
+    out = torch.empty_like(x)
+    nbytes = int(lib.afx_frangi_workspace_bytes(n, h, w, ns))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.afx_frangi(_ptr(x), n, h, w, sg, ns, float(beta), float(gamma), int(bool(black_ridges)), _ptr(out), _ptr(ws), nbytes, None,
+                              Engine._stream(x.device)), "afx_frangi")
+    return out
+
+
+def distance_transform_edt(x: torch.Tensor) -> torch.Tensor:
+    """afx_distance_transform_edt: scipy.ndimage.distance_transform_edt of every image (non-zero = foreground), bit for bit, float64."""
+    lib = _lib.load()
+    x = _images_f64(x, "distance_transform_edt")
+    n, h, w = x.shape
+    out = torch.empty_like(x)
+    nbytes = int(lib.afx_distance_transform_edt_workspace_bytes(n, h, w))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.afx_distance_transform_edt(_ptr(x), n, h, w, _ptr(out), _ptr(ws), nbytes, None, Engine._stream(x.device)),
+               "afx_distance_transform_edt")
+    return out
+
+
+def sampling_weights(images: torch.Tensor, strategy: str = "frangi", binary: bool = True, sigmas=(1, 3, 5, 7, 9), beta: float = 0.5,
+                     gamma: float = 15.0):
+    """afx_sampling_weights over a [N, H, W] device tensor -> (weights float64 [N, H, W], status int32 [N]).  Reads nothing back (the
+    call can be captured in a graph): status[i] != 0 marks an image whose weights are NaN (a flat vesselness or distance transform)."""
+    lib = _lib.load()
+    if strategy not in _lib.SAMPLING:
+        raise ValueError(f"sampling_weights: strategy must be one of {sorted(_lib.SAMPLING)}, got {strategy!r}")
+    x = _images_f64(images, "sampling_weights")
+    n, h, w = x.shape
+    sg, ns = _sigma_array(sigmas) if strategy == "frangi" else _sigma_array(())
+    st = _lib.SAMPLING[strategy]
+    out = torch.empty_like(x)
+    status = torch.empty(n, dtype=torch.int32, device=x.device)
+    nbytes = int(lib.afx_sampling_weights_workspace_bytes(st, n, h, w, ns))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.afx_sampling_weights(_ptr(x), n, h, w, st, int(bool(binary)), sg, ns, float(beta), float(gamma), _ptr(out), _ptr(status),
+                                        _ptr(ws), nbytes, None, Engine._stream(x.device)), "afx_sampling_weights")
+    return out, status
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

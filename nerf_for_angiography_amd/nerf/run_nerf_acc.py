@@ -121,7 +121,7 @@ def main(argv=None):
     if args.synthetic:
         proj_df, ray_df = ds.make_synthetic_dataset(ds.angle_grid(limited_size, int(number_angles), center_point),
                                                     img_size=args.img_size, sampling_strategy=sampling_strategy,
-                                                    device=device, seed=args.seed)
+                                                    device=device, seed=args.seed, binary=binary)
     else:
         step_size = limited_size / number_angles if number_angles > 0 else limited_size
         proj_df, ray_df, _, _ = ds.load_data(data_name, file_name, False, binary, args.img_size, step_size, args.data_root)

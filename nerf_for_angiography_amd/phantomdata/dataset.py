@@ -52,6 +52,32 @@ def sampling_weights(img: np.ndarray, sampling_strategy: str = "segmentation") -
     return edt + 1e-10
 
 
+def sampling_weights_device(images, sampling_strategy: str = "frangi", binary: bool = True):
+    """The ray-sampling weights of all projections at once, float64 [N, H, W] on the images' GPU.  images: [N, H, W] (or [H, W])
+    device tensor.
+
+    'frangi' (the reference's default, cttoray.py:50-52, 210-216): binary=False first sets the pixels above np.percentile(img, 10)
+    to 1; then get_weighted_img (helpers.py) with the scikit-image 0.18.3 Frangi filter (beta = 0.5; alpha has no effect in 2-D):
+    min-max normalised vesselness, its Euclidean distance transform, min-max normalised, + 1e-10.  A projection whose vesselness or
+    distance transform is flat (where the reference divides by zero) raises ValueError naming it.  'segmentation' and 'random'
+    follow the host `sampling_weights` (the former on the device distance transform, bit for bit the host result)."""
+    from ..engine import _images_f64, sampling_weights as afx_sampling_weights
+    if sampling_strategy == "random":
+        x = _images_f64(images, "sampling_weights_device")
+        return torch.ones(x.shape, dtype=torch.float64, device=x.device)
+    if sampling_strategy not in ("frangi", "segmentation"):
+        raise ValueError(f"sampling_weights_device: unknown sampling strategy {sampling_strategy!r}")
+    x = images if not isinstance(images, torch.Tensor) or images.dim() != 2 else images[None]
+    out, status = afx_sampling_weights(x, sampling_strategy, binary=binary)
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        i = bad[0]
+        what = "vesselness" if int(status[i]) & 1 else "distance transform"
+        raise ValueError(f"sampling_weights_device: projection {i} has a flat {what} (max == min): its '{sampling_strategy}' weights "
+                         f"are undefined ({len(bad)} such projection(s))")
+    return out
+
+
 def angle_grid(limited_size: float, number_angles: int, center_point=(90, 0)):
     """(theta, phi) grid of cttoray.py:88-105: number_angles+1 samples per axis over `limited_size` degrees around
     `center_point`, plus the centre itself as the last (held-out) projection."""
@@ -69,21 +95,31 @@ def angle_grid(limited_size: float, number_angles: int, center_point=(90, 0)):
 def make_synthetic_dataset(angles, img_size: int = 64, depth_samples_per_ray: int = 160, outside: float = 100.0,
                            src_z: float = 1500.0, sampling_strategy: str = "segmentation", device="cpu", seed: int = 0,
                            binary: bool = True):
-    """(proj_df, ray_df) for a capsule-tree phantom seen from `angles` = [(theta, phi), ...]; larm = 0, no shifts."""
+    """(proj_df, ray_df) for a capsule-tree phantom seen from `angles` = [(theta, phi), ...]; larm = 0, no shifts.
+    sampling_strategy 'frangi' computes the weights of all views with one sampling_weights_device call (`binary` False: with
+    cttoray's percentile pre-step) and needs a GPU `device`; 'segmentation' and 'random' run the host sampling_weights per view."""
     w = h = int(img_size)
     focal = 13.0 * w                       # same field of view as the reference's f=1300 @ 100 px (SURVEY §8d)
     src_pt = np.array([0.0, 0.0, src_z])
     near, far = src_z - outside, src_z + outside
     caps = capsule_tree(levels=5, seed=seed)
-    proj_rows, ray_frames = [], []
-    for image_id, (theta, phi) in enumerate(angles):
+    views = []
+    for theta, phi in angles:
         o, d, mat, ii, jj = get_ray_values(theta, phi, 0.0, src_pt, w, h, focal, device)
         z = get_depth_values(near, far, depth_samples_per_ray, device, stratified=False)
         with torch.no_grad():
             img = ray_tracing(lambda p: capsule_mu(p, caps), o.reshape(-1, 3).float(), d.reshape(-1, 3).float(),
                               z.float(), batch_rays=8192).reshape(h, w).cpu()
-        img_np = img.numpy().astype(np.float64)
-        wts = sampling_weights(img_np, sampling_strategy)
+        views.append((theta, phi, o, d, mat, ii, jj, z, img.numpy().astype(np.float64)))
+    if sampling_strategy == "frangi":
+        if torch.device(device).type != "cuda":
+            raise NotImplementedError("sampling_strategy='frangi' runs on the GPU only (sampling_weights_device): pass a cuda device")
+        stack = torch.from_numpy(np.stack([v[-1] for v in views])).to(device)
+        all_wts = list(sampling_weights_device(stack, "frangi", binary=binary).cpu().numpy())
+    else:
+        all_wts = [sampling_weights(v[-1], sampling_strategy) for v in views]
+    proj_rows, ray_frames = [], []
+    for image_id, ((theta, phi, o, d, mat, ii, jj, z, img_np), wts) in enumerate(zip(views, all_wts)):
         proj_rows.append(dict(image_id=image_id, theta=theta, phi=phi, larm=0.0, theta_shift=0.0, phi_shift=0.0,
                               larm_shift=0.0, translation_x=0.0, translation_y=0.0, translation_z=0.0,
                               tform_cam2world=mat.tolist(), unshifted_tform_cam2world=mat.tolist(),

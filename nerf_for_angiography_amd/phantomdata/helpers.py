@@ -42,6 +42,33 @@ def get_depth_values(near_thresh, far_thresh, depth_samples_per_ray, device, str
     return z_vals.to(device)
 
 
+def get_weighted_img(img, frangi_alpha, frangi_beta, theta, phi, larm, proj_folder_name, sampling_strategy='frangi', invert=False):
+    """helpers.py:226-247 -> the ray-sampling weights of one projection, a float64 device tensor [H, W] (afx_sampling_weights).
+
+    'frangi': f = frangi(img, alpha=frangi_alpha, beta=frangi_beta) (phantomdata/vesselness.py: scikit-image 0.18.3; alpha has no
+    effect in 2-D), f -= min f, f /= max f, e = distance_transform_edt(f), e -= min e, e /= max e, e += 1e-10.  A flat vesselness or
+    distance transform (max 0: the reference divides by zero) raises ValueError.  Otherwise the segmentation mask img < 1 takes f's
+    place, under the host sampling_weights' rule (dataset.py: the divisions are skipped where a max is 0).  The PNG of the weights
+    is written only when proj_folder_name is given; `invert` is accepted and unused, as upstream."""
+    from ..engine import sampling_weights
+    del invert
+    if not isinstance(img, torch.Tensor) or img.device.type != "cuda" or img.dim() != 2:
+        raise ValueError("get_weighted_img: img must be a [H, W] tensor on a GPU")
+    strategy = 'frangi' if sampling_strategy == 'frangi' else 'segmentation'
+    beta = 0.5 if frangi_beta is None else frangi_beta
+    out, status = sampling_weights(img, strategy, binary=True, beta=beta)
+    if strategy == 'frangi' and int(status[0]) != 0:
+        raise ValueError(f"get_weighted_img: projection ({theta}, {phi}, {larm}) has a flat "
+                         f"{'vesselness' if int(status[0]) & 1 else 'distance transform'}: its weights are undefined")
+    out = out[0]
+    if proj_folder_name:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        plt.imsave(f'{proj_folder_name}image-transform-{theta}-{phi}-{larm}.png', out.cpu().numpy())
+    return out
+
+
 def capsule_tree(levels=5, seed=0, extent=75.0, r0=3.0, r1=0.75):
     """Synthetic vessel tree: binary tree of 2^levels - 1 capsules inside +-extent -> [N,7] (a, b, radius)."""
     rng = np.random.RandomState(seed)
