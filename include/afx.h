@@ -538,6 +538,33 @@ int afx_sampling_weights(const double* img, int32_t n, int32_t h, int32_t w, int
                          int32_t n_sigmas, double beta, double gamma, double* out, int32_t* status, void* workspace, size_t workspace_bytes,
                          size_t* workspace_needed, void* stream);
 
+/* ---- Metrics of the evaluation sweep (visualization/visualization.py: SSIM per view :267, 411-417; DICE 3D / DOT 3D :203-231, 480-495).
+ * Device pointers; the calls allocate nothing, never synchronise and use no floating-point atomics: results are bitwise reproducible and
+ * the calls can be captured in a graph.
+ *
+ * afx_ssim: out[i] = SSIM(preds[i], targets[i]) (fp64) for n pairs of h x w fp32 images, row-major [n][h][w] - torchmetrics'
+ * StructuralSimilarityIndexMeasure(data_range=1.0) (_ssim_update, gaussian kernel), computed in fp64:
+ *   g[m] = exp(-((m - 5) / 1.5)^2 / 2), m = 0..10, normalised to sum 1; the 2-D window is g g^T (applied separably)
+ *   over every 11 x 11 window lying inside the image: mu_x, mu_y, E[x^2], E[y^2], E[xy] (window means)
+ *   s_x^2 = max(E[x^2] - mu_x^2, 0), s_y^2 = max(E[y^2] - mu_y^2, 0), s_xy = E[xy] - mu_x mu_y, c1 = 0.01^2, c2 = 0.03^2
+ *   map = ((2 mu_x mu_y + c1)(2 s_xy + c2)) / ((mu_x^2 + mu_y^2 + c1)(s_x^2 + s_y^2 + c2))
+ *   out[i] = mean of the map over the (h - 10) x (w - 10) windows (torchmetrics pads by 5 and crops 5 from every side: the same windows)
+ * A view's result does not depend on n or on the other views.  AFX_E_INVALID: a null pointer, n < 1, h < 11, w < 11, h w > 2^31 - 1, or
+ * n ceil((h - 10) / 16) ceil((w - 10) / 64) > 2^24 - 1 (workgroups of one launch).  Workspace (afx_ssim_workspace_bytes; 0 for those
+ * shapes): n ceil((h - 10) / 16) ceil((w - 10) / 64) doubles (per-tile partial sums), rounded up to 256 bytes; AFX_E_WORKSPACE when it
+ * is smaller, with workspace_needed (when not NULL) set.
+ *
+ * afx_volume_grid: the ground-truth density grid, out[i][j][k] (fp32, n^3) = mu(t[j], t[i], t[k]) (np.meshgrid(t, t, t) with its 'xy'
+ * order, as the reconstructed grid is laid out), t = np.linspace(lo, hi, n) in fp64 - t[m] = m ((hi - lo) / (n - 1)) + lo, t[n - 1] = hi -
+ * rounded to fp32.  mu is afx_project_volume's lookup: trilinear on the regular grid vol[nx][ny][nz] (axis a: origin[a] + spacing[a] x
+ * index), fill_value outside it, in fp64 (scipy RegularGridInterpolator(method='linear', bounds_error=False, fill_value)), rounded to fp32.
+ * AFX_E_INVALID: a null pointer, fewer than 2 voxels on an axis, a spacing <= 0, n < 2 or n > 2^20, lo >= hi or either not finite. */
+size_t afx_ssim_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int afx_ssim(const float* preds, const float* targets, int32_t n, int32_t h, int32_t w, double* out, void* workspace, size_t workspace_bytes,
+             size_t* workspace_needed, void* stream);
+int afx_volume_grid(const float* vol, int32_t nx, int32_t ny, int32_t nz, const double origin[3], const double spacing[3], float fill_value,
+                    double lo, double hi, int32_t n, float* out, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

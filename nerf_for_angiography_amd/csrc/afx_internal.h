@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
+#include "../../include/afx.h"
 
 namespace afx {
 
@@ -199,7 +201,69 @@ struct Carve {
   }
 };
 
+// A voxel volume vol[nx][ny][nz] (fp32) on a regular grid: axis a has its first sample at a0 and spacing da.  vol_sample is scipy's
+// RegularGridInterpolator(method='linear', bounds_error=False, fill_value=fill) at (px, py, pz) in fp64: the 8-voxel trilinear blend,
+// `fill` outside the box (the box's faces belong to it).  k_project_volume (ground-truth projections) and k_volume_grid (the
+// ground-truth density grid) share it; type_ct is the projector's only.
+struct VolArgs {
+  const float* vol;
+  int32_t nx, ny, nz;
+  double x0, y0, z0, dx, dy, dz;
+  float fill;
+  int32_t type_ct;
+};
+
+__device__ __forceinline__ bool vol_axis(double p, double a0, double da, int n, int& i, double& t) {
+  const double a1 = a0 + da * (n - 1);
+  if (!(p >= a0 && p <= a1)) return false;
+  double u = (p - a0) / da;
+  i = (int)u;
+  if (i > n - 2) i = n - 2;
+  if (i < 0) i = 0;
+  t = u - i;
+  return true;
+}
+
+__device__ __forceinline__ double vol_sample(const VolArgs& v, double px, double py, double pz) {
+  const size_t sy = (size_t)v.nz, sx = (size_t)v.ny * v.nz;
+  int ix, iy, iz;
+  double tx, ty, tz;
+  double mu = v.fill;
+  if (vol_axis(px, v.x0, v.dx, v.nx, ix, tx) && vol_axis(py, v.y0, v.dy, v.ny, iy, ty) && vol_axis(pz, v.z0, v.dz, v.nz, iz, tz)) {
+    const float* b = v.vol + ix * sx + iy * sy + iz;
+    const double c00 = b[0] * (1 - tz) + b[1] * tz, c01 = b[sy] * (1 - tz) + b[sy + 1] * tz;
+    const double c10 = b[sx] * (1 - tz) + b[sx + 1] * tz, c11 = b[sx + sy] * (1 - tz) + b[sx + sy + 1] * tz;
+    mu = (c00 * (1 - ty) + c01 * ty) * (1 - tx) + (c10 * (1 - ty) + c11 * ty) * tx;
+  }
+  return mu;
+}
+
 // Sets afx_last_error()'s message to "<who>: <msg>" and returns `code` (defined in afx_api.hip, for the other translation units).
 int set_error(int code, const char* who, const char* msg);
+
+// The C entry points of the image and metric units: `p` (named `what` in the message) is memory of the current device (launches go to a
+// stream of the current device); and the launches just made were accepted.
+inline int check_device(const void* p, const char* what, const char* who) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return set_error(AFX_E_HIP, who, "no HIP device");
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();                          // not HIP memory: leave no error behind for the next launch check
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s is not memory of a HIP device", what);
+    return set_error(AFX_E_INVALID, who, msg);
+  }
+  if (at.device != dev) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s lives on another device than the current one", what);
+    return set_error(AFX_E_INVALID, who, msg);
+  }
+  return AFX_OK;
+}
+
+inline int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AFX_OK : set_error(AFX_E_HIP, who, hipGetErrorString(e));
+}
 
 }  // namespace afx

@@ -982,24 +982,7 @@ __global__ void k_composite_packed_bwd(const float* pred, const int32_t* ri, con
 // 'ct': img = prod_s exp(-mu * dz_s * ||d||) with dz_last = 1e10; otherwise img = prod_s exp(-mu).
 // One thread per ray: neighbouring threads are neighbouring pixels, so the 8 voxel reads per sample of a wave
 // fall in the same few cache lines (the kernel is L2/HBM-bound: 32 B of volume per sample, no reuse in registers).
-struct VolArgs {
-  const float* vol;
-  int32_t nx, ny, nz;
-  double x0, y0, z0, dx, dy, dz;
-  float fill;
-  int32_t type_ct;
-};
-
-__device__ __forceinline__ bool vol_axis(double p, double a0, double da, int n, int& i, double& t) {
-  const double a1 = a0 + da * (n - 1);
-  if (!(p >= a0 && p <= a1)) return false;
-  double u = (p - a0) / da;
-  i = (int)u;
-  if (i > n - 2) i = n - 2;
-  if (i < 0) i = 0;
-  t = u - i;
-  return true;
-}
+// The lookup (VolArgs, vol_sample) lives in afx_internal.h: afx_volume_grid samples the same field.
 
 __global__ void k_project_volume(const ChainArgs a, const VolArgs v) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1023,20 +1006,11 @@ __global__ void k_project_volume(const ChainArgs a, const VolArgs v) {
   }
   const double nrm = sqrt(dx * dx + dy * dy + dz * dz);
   const int S = a.n_samples;
-  const size_t sy = (size_t)v.nz, sx = (size_t)v.ny * v.nz;
   double prod = 1.0;
   for (int s = 0; s < S; ++s) {
     const double zs = (double)a.z[s];
     const double px = ox + dx * zs, py = oy + dy * zs, pz = oz + dz * zs;
-    int ix, iy, iz;
-    double tx, ty, tz;
-    double mu = v.fill;
-    if (vol_axis(px, v.x0, v.dx, v.nx, ix, tx) && vol_axis(py, v.y0, v.dy, v.ny, iy, ty) && vol_axis(pz, v.z0, v.dz, v.nz, iz, tz)) {
-      const float* b = v.vol + ix * sx + iy * sy + iz;
-      const double c00 = b[0] * (1 - tz) + b[1] * tz, c01 = b[sy] * (1 - tz) + b[sy + 1] * tz;
-      const double c10 = b[sx] * (1 - tz) + b[sx + 1] * tz, c11 = b[sx + sy] * (1 - tz) + b[sx + sy + 1] * tz;
-      mu = (c00 * (1 - ty) + c01 * ty) * (1 - tx) + (c10 * (1 - ty) + c11 * ty) * tx;
-    }
+    const double mu = vol_sample(v, px, py, pz);
     if (v.type_ct) {
       const double dist = s + 1 < S ? (double)__fsub_rn(a.z[s + 1], a.z[s]) : (double)1e10f;
       prod *= exp(-mu * (dist * nrm));

@@ -364,24 +364,6 @@ int max_radius(const Scales& sc) {
   return r;
 }
 
-// The pointer the call reads belongs to the current device (launches go to a stream of the current device).
-int check_device(const void* p, const char* who) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return afx::set_error(AFX_E_HIP, who, "no HIP device");
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();                          // not HIP memory: leave no error behind for the next launch check
-    return afx::set_error(AFX_E_INVALID, who, "the image is not memory of a HIP device");
-  }
-  if (at.device != dev) return afx::set_error(AFX_E_INVALID, who, "the image lives on another device than the current one");
-  return AFX_OK;
-}
-
-int launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? AFX_OK : afx::set_error(AFX_E_HIP, who, hipGetErrorString(e));
-}
-
 struct FrangiBufs { double* t; double* g; };
 FrangiBufs carve_frangi(afx::Carve& c, int32_t n, int32_t h, int32_t w, int32_t n_sigmas) {
   const size_t plane = (size_t)n * n_sigmas * h * w * sizeof(double);
@@ -437,12 +419,12 @@ extern "C" int afx_frangi(const double* img, int32_t n, int32_t h, int32_t w, co
   const size_t need = afx_frangi_workspace_bytes(n, h, w, n_sigmas);
   if (workspace_needed) *workspace_needed = need;
   if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
-  if (int rc = check_device(img, who)) return rc;
+  if (int rc = afx::check_device(img, "the image", who)) return rc;
   afx::Carve c;
   c.base = (uintptr_t)workspace;
   const FrangiBufs b = carve_frangi(c, n, h, w, n_sigmas);
   launch_frangi(img, n, h, w, sc, beta, gamma, black_ridges, nullptr, out, b, (hipStream_t)stream);
-  return launched(who);
+  return afx::launched(who);
 }
 
 extern "C" size_t afx_distance_transform_edt_workspace_bytes(int32_t n, int32_t h, int32_t w) {
@@ -460,9 +442,9 @@ extern "C" int afx_distance_transform_edt(const double* x, int32_t n, int32_t h,
   const size_t need = afx_distance_transform_edt_workspace_bytes(n, h, w);
   if (workspace_needed) *workspace_needed = need;
   if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
-  if (int rc = check_device(x, who)) return rc;
+  if (int rc = afx::check_device(x, "the image", who)) return rc;
   launch_edt(x, n, h, w, FG_NONZERO, nullptr, (uint32_t*)workspace, out, (hipStream_t)stream);
-  return launched(who);
+  return afx::launched(who);
 }
 
 extern "C" size_t afx_sampling_weights_workspace_bytes(int32_t strategy, int32_t n, int32_t h, int32_t w, int32_t n_sigmas) {
@@ -496,7 +478,7 @@ extern "C" int afx_sampling_weights(const double* img, int32_t n, int32_t h, int
   const size_t need = afx_sampling_weights_workspace_bytes(strategy, n, h, w, frangi ? n_sigmas : 0);
   if (workspace_needed) *workspace_needed = need;
   if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
-  if (int rc = check_device(img, who)) return rc;
+  if (int rc = afx::check_device(img, "the image", who)) return rc;
   hipStream_t st = (hipStream_t)stream;
   afx::Carve c;
   c.base = (uintptr_t)workspace;
@@ -515,5 +497,5 @@ extern "C" int afx_sampling_weights(const double* img, int32_t n, int32_t h, int
   }
   hipLaunchKernelGGL(k_minmax, dim3((unsigned)n), dim3(IMG_RED_BLOCK), 0, st, out, hw, 0, b.emm);
   hipLaunchKernelGGL(k_weights_final, dim3(bx, (unsigned)n), dim3(IMG_BLOCK), 0, st, out, hw, frangi ? 1 : 0, b.fmm, b.emm, status);
-  return launched(who);
+  return afx::launched(who);
 }

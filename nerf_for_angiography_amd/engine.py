@@ -915,6 +915,47 @@ def sampling_weights(images: torch.Tensor, strategy: str = "frangi", binary: boo
     return out, status
 
 
+def ssim(preds: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """afx_ssim: the SSIM (torchmetrics StructuralSimilarityIndexMeasure(data_range=1.0), computed in fp64) of every pair of two [N, H, W]
+    (or [H, W]) device tensors, float64 [N].  All views in one launch sequence; nothing is read back."""
+    lib = _lib.load()
+    for name, t in (("preds", preds), ("targets", targets)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"ssim: {name} must be a tensor on a GPU; there is no CPU path")
+    if preds.shape != targets.shape or preds.dim() not in (2, 3):
+        raise ValueError(f"ssim: expected two [H, W] or [N, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(targets.shape)}")
+    if preds.device != targets.device:
+        raise ValueError(f"ssim: preds on {preds.device}, targets on {targets.device}")
+    x = (preds if preds.dim() == 3 else preds[None]).to(torch.float32).contiguous()
+    y = (targets if targets.dim() == 3 else targets[None]).to(torch.float32).contiguous()
+    n, h, w = x.shape
+    out = torch.empty(n, dtype=torch.float64, device=x.device)
+    nbytes = int(lib.afx_ssim_workspace_bytes(n, h, w))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.afx_ssim(_ptr(x), _ptr(y), n, h, w, _ptr(out), _ptr(ws), nbytes, None, Engine._stream(x.device)), "afx_ssim")
+    return out
+
+
+def volume_grid(volume_values: torch.Tensor, origin, spacing, fill, lo: float, hi: float, n: int) -> torch.Tensor:
+    """afx_volume_grid: a voxel volume [nx, ny, nz] (trilinear, `fill` outside; what VoxelVolume stands for) sampled at
+    np.meshgrid(t, t, t), t = np.linspace(lo, hi, n) rounded to fp32 - float32 [n, n, n], grid[i, j, k] = mu(t[j], t[i], t[k])."""
+    lib = _lib.load()
+    if not isinstance(volume_values, torch.Tensor) or volume_values.device.type != "cuda":
+        raise AfxError("volume_grid: the volume must be a tensor on a GPU; there is no CPU fallback")
+    dev = volume_values.device
+    vol = _f32(volume_values, "volume", dev)
+    if vol.dim() != 3:
+        raise ValueError("volume: expected [nx,ny,nz]")
+    n = int(n)
+    # an n the library refuses gets a one-element buffer: the call reports the range instead of the allocator failing first
+    out = torch.empty((n,) * 3 if 2 <= n <= 1 << 20 else (1,), dtype=torch.float32, device=dev)
+    org = (C.c_double * 3)(*[float(x) for x in origin])
+    spc = (C.c_double * 3)(*[float(x) for x in spacing])
+    _lib.check(lib.afx_volume_grid(_ptr(vol), vol.shape[0], vol.shape[1], vol.shape[2], org, spc, float(fill), float(lo), float(hi), n,
+                                   _ptr(out), Engine._stream(dev)), "afx_volume_grid")
+    return out
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

@@ -1,13 +1,15 @@
-"""Evaluation sweep — the metric loop of the reference's visualization/visualization.py:188-191,277-454: render the model
+"""Evaluation sweep — the metric loop of the reference's visualization/visualization.py:188-191,277-505: render the model
 from a grid of C-arm angles (th x ph, the "37 x 37" sweep at limited_size_vis = 180, angle_step_vis = 5), compare every
-projection with the ground truth and tabulate per-view metrics.
+projection with the ground truth and tabulate per-view metrics, and compare the reconstructed density grid with the ground-truth volume.
 
 What differs from upstream is where the work happens: ALL views of the sweep are ONE fused launch (rays of every pose are
 generated in the kernel from the [n_views, 3, 4] pose table, `render_projection`), the ground truth of a voxel phantom is one
-`afx_project_volume` launch over the same poses, and the metrics are reductions on the GPU.  Metrics kept: PSNR (:406-409,
-data range 1), normalised DOT 2D (:440-450), DICE 2D on the binarised projections (:433-438; prediction binarised by zeroing
-densities below `binary_thresh`, :172,349-352).  SSIM / LPIPS / DISTS upstream come from piq / torchmetrics networks (absent
-here) and are out of scope."""
+`afx_project_volume` launch over the same poses, and the metrics are reductions on the GPU.  Metrics: PSNR (:406-409,
+data range 1), SSIM (:411-417: torchmetrics' StructuralSimilarityIndexMeasure(data_range=1.0), a fixed 11-tap Gaussian window with
+no network - every view in one `afx_ssim` call, in fp64), normalised DOT 2D (:440-450), DICE 2D on the binarised projections
+(:433-438; prediction binarised by zeroing densities below `binary_thresh`, :172,349-352), and the two whole-volume scores DICE 3D and
+DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against the ground-truth volume sampled at the same points
+(`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope."""
 from __future__ import annotations
 
 import itertools
@@ -17,7 +19,11 @@ import pandas as pd
 import torch
 
 from ..phantomdata.proj_helpers import source_matrix
-from ..render import march_render_projection, render_projection
+from ..render import density_grid, march_render_projection, render_projection
+
+# the reference's metric columns in its order (visualization.py:455-495); LPIPS and DISTS need pretrained networks
+METRICS = ("PSNR", "SSIM", "LPIPS", "DISTS", "DICE 2D", "DOT 2D", "DICE 3D", "DOT 3D")
+_NETWORK_METRICS = ("LPIPS", "DISTS")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -38,7 +44,8 @@ def _poses(angles, src_pt, translation, device):
 @torch.no_grad()
 def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length, src_pt, near_thresh, far_thresh,
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
-                     views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3):
+                     views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3, metrics=None, volume=None,
+                     volume_outside=100.0, volume_points=None):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
 
     grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
@@ -48,13 +55,21 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
 
     targets: [n, H, W] ground-truth projections on the model's device (e.g. `ground_truth_sweep`), binary_targets likewise
     (optional; DICE 2D needs them).  Returns a DataFrame with the reference's columns (image_id, theta, phi, larm,
-    theta_360, phi_360, cam_pose_x/y/z, PSNR, DOT 2D[, DICE 2D]) and the predicted images [n, H, W]."""
+    theta_360, phi_360, cam_pose_x/y/z, then the metrics) and the predicted images [n, H, W].
+
+    metrics=None: the metric columns PSNR, DOT 2D[, DICE 2D when binary_targets are given].  Otherwise a list drawn from METRICS, tabulated
+    in the reference's order (PSNR, SSIM, DICE 2D, DOT 2D, DICE 3D, DOT 3D); LPIPS and DISTS raise NotImplementedError.  DICE 2D needs
+    binary_targets, DICE 3D / DOT 3D need `volume` (a VoxelVolume): `reconstruction_metrics(model, volume, volume_outside, volume_points)`,
+    volume_points defaulting to depth_samples_per_ray + 1 as upstream (:102), its two scores repeated on every row (:490, :495).  The
+    arguments are checked before any work on the GPU."""
+    from ..engine import ssim
+    want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
     n = len(angles)
     poses = _poses(angles, src_pt, translation, dev)
     hw = int(img_width) * int(img_height)
     preds = torch.empty(n, hw, device=dev)
-    bin_preds = torch.empty(n, hw, device=dev) if binary_targets is not None else None
+    bin_preds = torch.empty(n, hw, device=dev) if "DICE 2D" in want else None
     for v0 in range(0, n, views_per_launch):
         v1 = min(n, v0 + views_per_launch)
         if grid is not None:
@@ -85,13 +100,66 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
             "theta_360": [float(a[0] if a[0] >= 0 else 360 + a[0]) for a in angles],
             "phi_360": [float(a[1] if a[1] >= 0 else 360 + a[1]) for a in angles],
             "cam_pose_x": poses[:, 0, 3].cpu().tolist(), "cam_pose_y": poses[:, 1, 3].cpu().tolist(),
-            "cam_pose_z": poses[:, 2, 3].cpu().tolist(), "PSNR": psnr.cpu().tolist(), "DOT 2D": dot2d.cpu().tolist()}
+            "cam_pose_z": poses[:, 2, 3].cpu().tolist()}
+    scores = {"PSNR": psnr.cpu().tolist(), "DOT 2D": dot2d.cpu().tolist()}
     if bin_preds is not None:
         bp = (bin_preds >= 1).to(torch.int64)               # :434-435: everything below 1 is vessel -> 0
         bt = (binary_targets.reshape(n, hw).to(dev) >= 1).to(torch.int64)
         # Dice(average='micro') over the two classes of a binary image = pixel accuracy
-        cols["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
+        scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
+    if "SSIM" in want:
+        scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
+    if "DICE 3D" in want or "DOT 3D" in want:
+        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+        dice3d, dot3d, _, _ = reconstruction_metrics(model, volume, volume_outside, pts)
+        scores["DICE 3D"], scores["DOT 3D"] = [dice3d] * n, [dot3d] * n
+    for name in want:
+        cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
+
+
+def _check_metrics(metrics, binary_targets, volume):
+    """The metric columns evaluation_sweep fills, in order; raises on a request it cannot serve (before any GPU work)."""
+    if metrics is None:
+        return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
+    metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+    unknown = [m for m in metrics if m not in METRICS]
+    if unknown:
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS)}")
+    nets = [m for m in metrics if m in _NETWORK_METRICS]
+    if nets:
+        raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
+                                  "with learned weights) whose weights this project does not ship")
+    if "DICE 2D" in metrics and binary_targets is None:
+        raise ValueError("evaluation_sweep: DICE 2D needs binary_targets")
+    if ("DICE 3D" in metrics or "DOT 3D" in metrics) and volume is None:
+        raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS if m in metrics]
+
+
+@torch.no_grad()
+def ground_truth_grid(volume, outside, n):
+    """The ground-truth density of a `VoxelVolume` at np.meshgrid(t, t, t), t = linspace(-outside, outside, n) (visualization.py:100-102,
+    229: gt_interpolator(query_pts)): one afx_volume_grid launch, float32 [n, n, n] in density_grid's layout."""
+    from ..engine import volume_grid
+    return volume_grid(volume.values, volume.origin, volume.spacing, volume.fill_value, -float(outside), float(outside), int(n))
+
+
+@torch.no_grad()
+def reconstruction_metrics(model, volume, outside, n):
+    """DICE 3D and DOT 3D of visualization.py:480-495 for 'ct' data -> (dice_3d, dot_3d, predicted grid, ground-truth grid).
+
+    The predicted grid is the model's density at every one of the n^3 points (query_occ masks nothing there: `occ_pts >= 0` keeps them all,
+    :216-219), `density_grid(model, outside, n - 1)`; the ground truth `ground_truth_grid(volume, outside, n)`.  thr = mean(gt) in fp32 as
+    torch.mean gives it; DICE 3D is the fraction of points where (pred >= thr) == (gt >= thr) (Dice(average='micro') over both classes of a
+    0/1 volume, as DICE 2D); DOT 3D = mean(pred * gt), the products in fp32, their mean accumulated in fp64."""
+    pred = density_grid(model, outside, int(n) - 1)
+    gt = ground_truth_grid(volume, outside, n)
+    thr = torch.mean(gt)
+    agree = ((pred >= thr) == (gt >= thr)).sum()
+    dice = agree.double() / gt.numel()
+    dot = torch.mean(pred * gt, dtype=torch.float64)
+    return float(dice), float(dot), pred, gt
 
 
 @torch.no_grad()
