@@ -102,7 +102,10 @@ enum afx_query_what {
   AFX_Q_PREPARED_BYTES = 2,    /* bytes of the prepared-weights buffer (arg = prec) */
   AFX_Q_FWD_WORKSPACE = 3,     /* bytes needed by afx_render_forward  (arg0 = n_rays, arg1 = n_samples) */
   AFX_Q_BWD_WORKSPACE_MIN = 4, /* smallest sensible backward workspace (arg0 = n_rays, 0 for afx_mlp_backward; arg1 = n_samples when the split training step is meant) */
-  AFX_Q_BWD_WORKSPACE_FULL = 5 /* workspace that lets backward run in one chunk (arg0 = n_rays, arg1 = n_samples; afx_mlp_backward: arg0 = 0, arg1 = n_pts) */
+  AFX_Q_BWD_WORKSPACE_FULL = 5, /* workspace that lets backward run in one chunk (arg0 = n_rays, arg1 = n_samples; afx_mlp_backward: arg0 = 0, arg1 = n_pts) */
+  AFX_Q_BWD_INPUTS_WORKSPACE_MIN = 6,  /* smallest workspace afx_mlp_backward_inputs / afx_render_backward_inputs take (arg0 = n_rays, 0 for points;
+                                          arg1 = n_samples, or n_pts; arg2 = prec) */
+  AFX_Q_BWD_INPUTS_WORKSPACE_FULL = 7  /* the same, letting the call run in one chunk */
 };
 int64_t afx_query(const afx_ctx* ctx, int what, int64_t arg0, int64_t arg1, int64_t arg2);
 
@@ -133,6 +136,19 @@ int afx_mlp_infer(afx_ctx* ctx, int prec, const void* prepared, const float* pts
 int afx_mlp_backward(afx_ctx* ctx, int prec, const void* prepared, const float* pts, int64_t n_pts,
                      const float* d_out, float* grad_flat, void* workspace, size_t workspace_bytes,
                      void* stream);
+
+/* Backward of afx_mlp_infer with respect to the POINTS as well: d_pts[p] = d(sum_q d_out[q]*raw[q])/d(pts[p]) (written, [n_pts,3]),
+ * and, when grad_flat is not NULL, grad_flat += the parameter gradient exactly as afx_mlp_backward adds it (same kernels, same order:
+ * bit-identical when both run in one chunk).  grad_flat == NULL: the weight-gradient kernels are not launched (a frozen model).
+ * This is what autograd returns for x through CPPN.forward (model/CPPN.py:166-205) when x requires grad.  Input encodings: the BARF
+ * weights are constants (as upstream), the fourier coefficients too (their own gradient: afx_set_encoding_grad).
+ * How: the chain kernel runs in the configuration that stashes dZ_0 = dL/d(first-layer pre-activation) per sample (fp32 in the exact
+ * kernel; bf16, or f16 normalised by dL/draw, in the 16-bit ones - never the 8-bit stash: AFX_PREC_F16S8 runs as AFX_PREC_F16 here) and a
+ * second kernel contracts it per sample in fp32: dx = J_enc(x)^T W_0^T dZ_0.  Deterministic (no atomics, results
+ * independent of the chunking); nothing allocated, no synchronisation: graph-capturable.  The workspace must hold at least
+ * afx_query(AFX_Q_BWD_INPUTS_WORKSPACE_MIN, 0, n_pts, prec) bytes, else AFX_E_WORKSPACE (AFX_Q_BWD_INPUTS_WORKSPACE_FULL: one chunk). */
+int afx_mlp_backward_inputs(afx_ctx* ctx, int prec, const void* prepared, const float* pts, int64_t n_pts, const float* d_out,
+                            float* grad_flat /* nullable */, float* d_pts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Where rays come from. */
 enum { AFX_RAYS_ARRAYS = 0,   /* origins[R,3], dirs[R,3] fp32 (sample_pixel_rays output, nerf_helpers.py:137-150) */
@@ -182,6 +198,21 @@ int afx_render_forward(afx_ctx* ctx, int prec, const void* prepared, const afx_r
  * the weight-gradient contraction over samples). */
 int afx_render_backward(afx_ctx* ctx, int prec, const void* prepared, const afx_render_args* args,
                         const float* dL_dpixel, float* grad_flat, void* stream);
+
+/* Backward of afx_render_forward with respect to the RAYS as well (AFX_RAYS_ARRAYS): with p_s = o + t_s d the sample points,
+ *   d_origins[r] = sum_s dL/dp_s,   d_dirs[r] = sum_s t_s dL/dp_s  (+ for the render_volume_density conventions - AFX_DEPTH_SHARED_Z,
+ *   PER_RAY_Z, STRATIFIED - the step lengths dt_s = dist_s ||d||: + dL/dOD * OD * d / ||d||^2, OD = the ray's optical depth, the 1e10 tail
+ *   included; AFX_DEPTH_UNIFORM_MID has dt = t_e - t_s and no such term).
+ * Both are written ([R,3]); either may be NULL.  grad_flat (nullable) += the parameter gradient as afx_render_backward adds it (same
+ * kernels and order: bit-identical when the call runs in one chunk); grad_flat == NULL skips the weight-gradient kernels.  Where
+ * afx_render_backward keeps no dZ_0 stash (16-bit rays without an encoding, the 8-bit-stash precision) the input gradients take a chain pass
+ * of their own (AFX_PREC_F16S8 runs it as AFX_PREC_F16); the dense conventions add one forward pass (the optical depths) when d_dirs is set.
+ * The per-sample gradients are summed per 32-sample group, then per ray in group order: deterministic whatever the chunking, no atomics,
+ * nothing allocated, graph-capturable.  AFX_E_INVALID: AFX_RAYS_POSE with d_origins or d_dirs (rays made in the kernel have no input to
+ * differentiate), nothing requested, or what afx_render_backward refuses.  args->workspace: at least afx_query(AFX_Q_BWD_INPUTS_WORKSPACE_MIN,
+ * n_rays, n_samples, prec) bytes, else AFX_E_WORKSPACE. */
+int afx_render_backward_inputs(afx_ctx* ctx, int prec, const void* prepared, const afx_render_args* args, const float* dL_dpixel,
+                               float* grad_flat /* nullable */, float* d_origins, float* d_dirs, void* stream);
 
 /* ---- The reference's own iteration body on packed samples (nerf/run_nerf_acc.py:287-306): after the occupancy-grid march
  * (afx_march_* -> packed, ray-sorted t_starts / t_ends, offsets[R+1]) the reference gathers positions, evaluates the MLP (get_predictions),

@@ -11,7 +11,8 @@ ENC = {"none": 0, "barf": 1, "fourier": 2}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2, "f16": 3, "f16s8": 4}
 RAYS_ARRAYS, RAYS_POSE = 0, 1
 DEPTH_UNIFORM_MID, DEPTH_SHARED_Z, DEPTH_PER_RAY_Z, DEPTH_STRATIFIED = 0, 1, 2, 3
-Q_PARAM_COUNT, Q_K0, Q_PREPARED_BYTES, Q_FWD_WORKSPACE, Q_BWD_WORKSPACE_MIN, Q_BWD_WORKSPACE_FULL = range(6)
+(Q_PARAM_COUNT, Q_K0, Q_PREPARED_BYTES, Q_FWD_WORKSPACE, Q_BWD_WORKSPACE_MIN, Q_BWD_WORKSPACE_FULL, Q_BWD_INPUTS_WORKSPACE_MIN,
+ Q_BWD_INPUTS_WORKSPACE_FULL) = range(8)
 SAMPLING = {"frangi": 0, "segmentation": 1}                                 # AFX_SAMPLING_* (include/afx.h)
 GRID_JITTER_TAG, GRID_SELECT_TAG = 0x47524944 << 32, 0x53454C43 << 32      # Philox stream tags of the grid refresh (include/afx.h)
 
@@ -74,6 +75,10 @@ _SIGS = {
     "afx_mlp_infer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
     "afx_mlp_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "afx_mlp_backward_inputs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "afx_render_backward_inputs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RenderArgs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "afx_render_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RenderArgs), C.c_void_p]),
     "afx_render_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RenderArgs), C.c_void_p, C.c_void_p,
                                       C.c_void_p]),

@@ -12,6 +12,7 @@
 #include "afx_kernels_f32.hip"
 #include "afx_kernels_bf16.hip"
 #include "afx_kernels_grid.hip"
+#include "afx_kernels_ingrad.hip"
 #include "afx_inst.h"
 #include <algorithm>
 #include <set>
@@ -297,6 +298,27 @@ static BwdLayout bwd_layout(const afx_ctx* c, int prec, int64_t n_rays, int64_t 
 
 static int64_t s_pad_of(int s) { return (int64_t)(s + GROUP - 1) / GROUP * GROUP; }
 
+static int check_prec(int prec, const char* who);
+// Head of the input-gradient render workspace (afx_render_backward_inputs): dL/d(optical depth) per ray, the per-group input-gradient
+// partials (8 floats per 32-sample group) and the forward pass's per-group optical depths (dense conventions).
+static size_t ingrad_head_bytes(int64_t n_rays, int n_samples) {
+  const size_t groups = (size_t)n_rays * (size_t)(s_pad_of(n_samples) / GROUP);
+  return rup64((size_t)n_rays * 4, 256) + rup64(groups * 32, 256) + rup64(groups * 4, 256);
+}
+// Workspace of the input-gradient backward (arg0 = n_rays, 0 for points; arg1 = n_samples or n_pts): the chain runs in the configuration
+// that stashes dZ_0, whose per-tile bytes are bwd_layout's; min_tiles < 0: as many tiles as one chunk can use.
+static int64_t ingrad_workspace(const afx_ctx* c, int prec, int64_t a0, int64_t a1, int64_t min_tiles) {
+  if (check_prec(prec, "afx_query")) return -1;
+  const BwdLayout B = bwd_layout(c, prec, 0);
+  const int tile = bwd_tile(prec);
+  const size_t head = a0 > 0 ? ingrad_head_bytes(a0, (int)a1) : 0;
+  const int64_t samples = a0 > 0 ? a0 * s_pad_of((int)a1) : a1;
+  int64_t tiles = (samples + tile - 1) / tile;
+  if (is_bf16(prec)) tiles = std::min<int64_t>(tiles, stash_max_rows(c, 2, tile) / tile);
+  if (min_tiles > 0) tiles = min_tiles;
+  return (int64_t)(head + B.fixed_bytes + (size_t)std::max<int64_t>(tiles, 1) * B.per_tile_bytes + 1024);
+}
+
 extern "C" int64_t afx_query(const afx_ctx* c, int what, int64_t a0, int64_t a1, int64_t a2) {
   if (!c) { fail(AFX_E_INVALID, "afx_query: null ctx"); return -1; }
   switch (what) {
@@ -322,6 +344,8 @@ extern "C" int64_t afx_query(const afx_ctx* c, int what, int64_t a0, int64_t a1,
       }
       return (int64_t)(B.fixed_bytes + (size_t)tiles * B.per_tile_bytes + 1024);
     }
+    case AFX_Q_BWD_INPUTS_WORKSPACE_MIN: return ingrad_workspace(c, (int)a2, a0, a1, 1);
+    case AFX_Q_BWD_INPUTS_WORKSPACE_FULL: return ingrad_workspace(c, (int)a2, a0, a1, -1);
   }
   fail(AFX_E_INVALID, "afx_query: unknown query %d", what);
   return -1;
@@ -604,8 +628,12 @@ static int launch_wgrad8_t(afx_ctx* c, const WgradArgs& w, const ReduceArgs& rd,
 // a.dod / a.od_part / a.target / a.pixel / a.inv_n are set by the caller; chunks hold whole rays.
 // `dsz` (capacity launch, afx_march_train_step_mse_capturable): a.n_total is the capacity and the device-resident size block (SZ_* slots) bounds
 // the work of every kernel; the launches are those of the capacity, which must fit one chunk.
+// `ig` (afx_mlp_backward_inputs / afx_render_backward_inputs): the chain runs in the configuration that stashes dZ_0 (no in-kernel group
+// sums, no 8-bit stash) and k_input_grads contracts it after each chunk's chain launch; grad_flat == null then skips the weight gradients.
+static int launch_input_grads(afx_ctx* c, int prec, const ChainArgs& a, InGradArgs g, int64_t t0, int64_t t1, int TILE, hipStream_t st);
 static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws, size_t ws_bytes, float* grad_flat, hipStream_t st,
-                        bool split = false, int64_t n_rays = 0, const int64_t* goff = nullptr, const int64_t* dsz = nullptr) {
+                        bool split = false, int64_t n_rays = 0, const int64_t* goff = nullptr, const int64_t* dsz = nullptr,
+                        const InGradArgs* ig = nullptr) {
   const int F = c->d.width, N = c->d.n_hidden;
   if (c->d.act != AFX_ACT_RELU && prec != AFX_PREC_F32)
     return fail(AFX_E_INVALID, "backward: tanh / sine models train in the exact-fp32 kernels only (AFX_PREC_F32); the 16-bit kernels are forward-only for them");
@@ -617,12 +645,11 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
     return fail(AFX_E_INVALID, "backward: the fourier coefficients' gradient (afx_set_encoding_grad) needs a 16-bit precision");
   // in-kernel small gradients: 8-wave 16-bit backward kernel, rays, raw coordinates as inputs (AFX_SMALL_IN_KERNEL=0: off)
   // (with an input encoding only the 8-bit-stash kernel has the in-kernel output-layer sums; its first layer goes through k_wgrad_s8)
-  const bool sg = b16 && a.mode == 1 && c->small_in_kernel && (c->d.enc == AFX_ENC_NONE || prec == AFX_PREC_F16S8);
+  const bool sg = !ig && b16 && a.mode == 1 && c->small_in_kernel && (c->d.enc == AFX_ENC_NONE || prec == AFX_PREC_F16S8);
   const bool s8 = prec == AFX_PREC_F16S8 && sg;          // 8-bit stash: that configuration only; otherwise the 16-bit f16 path
   const size_t esz = s8 ? 1 : (b16 ? 2 : 4);            // stash element size
   const int k0ld = b16 ? 16 * nk0_of(c) : c->k0pad;     // row length of the encoded-input stash
-  if (is_bf16(prec) && prec == AFX_PREC_F16S8 && a.mode == 1 && c->small_in_kernel)
-    B.per_tile_bytes = per_tile_s8(c);     // 1 byte per stash element
+  if (s8) B.per_tile_bytes = per_tile_s8(c);     // 1 byte per stash element
   if (split && !s8) return fail(AFX_E_INVALID, "split training step: needs the 8-bit-stash kernel (AFX_PREC_F16S8)");
   // a chunk of the split step holds whole rays: a multiple of lcm(s_pad, tile) / tile tiles
   int64_t ray_tiles = 1;
@@ -675,7 +702,7 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
   // encoded inputs, 16-bit kernels: the inputs are stashed in 16-bit chunk-major form and the first layer's weight gradient (and the
   // fourier coefficients' gradient, afx_set_encoding_grad) is contracted on the matrix pipe by k_wgrad_bf16
   const bool enc16 = b16 && c->d.enc != AFX_ENC_NONE;
-  a.coef_cols = (enc16 && c->d_coef && c->d.enc == AFX_ENC_FOURIER) ? 3 * c->d.n_freq : 0;
+  a.coef_cols = (grad_flat && enc16 && c->d_coef && c->d.enc == AFX_ENC_FOURIER) ? 3 * c->d.n_freq : 0;
   // in-kernel small gradients: 8-wave bf16 backward kernel, rays, raw coordinates as inputs (AFX_SMALL_IN_KERNEL=0: off)
   a.stash8 = s8 ? 1 : 0;
   a.stash_h = stash_h; a.stash_dz = stash_dz; a.stash_e = stash_e; a.graw = graw;
@@ -707,6 +734,12 @@ static int run_backward(afx_ctx* c, int prec, ChainArgs a, size_t head, char* ws
       rc = launch_chain(c, prec, true, p, st, 2);
     } else rc = launch_chain(c, prec, true, a, st);
     if (rc) return rc;
+    if (ig) {
+      InGradArgs g = *ig;
+      g.stash_dz = (const char*)a.stash_dz; g.graw = a.graw;
+      if ((rc = launch_input_grads(c, prec, a, g, t0, t1, TILE, st))) return rc;
+    }
+    if (!grad_flat) continue;
     WgradArgs w = {};      // (zero: fields a path does not use must read as "off")
     w.stash_h = a.stash_h; w.stash_dz = a.stash_dz; w.stash_e = a.stash_e; w.graw = a.graw;
     w.rows = (t1 - t0) * TILE;
@@ -1007,6 +1040,130 @@ extern "C" int afx_mlp_backward(afx_ctx* c, int prec, const void* prepared, cons
   fill_model(c, prec, true, prepared, a);
   a.n_total = n_pts; a.mode = 0; a.pts = pts; a.dod = d_out;
   return run_backward(c, prec, a, 0, (char*)workspace, workspace_bytes, grad_flat, (hipStream_t)stream);
+}
+
+// ---- Gradients with respect to the inputs (afx_kernels_ingrad.hip) ----
+static InGradArgs ingrad_args(const afx_ctx* c, int prec, const void* prepared) {
+  const PrepLayout L = prep_layout(c, prec);
+  InGradArgs g = {};
+  g.slab0 = (const char*)prepared + L.slab0_off;
+  g.slab0_bytes = L.slab0_bytes;
+  g.aux = (const float*)((const char*)prepared + L.small_off) + (size_t)(c->d.n_hidden + 2) * c->d.width + 4;
+  g.k0 = c->k0; g.enc = c->d.enc; g.n_freq = c->d.n_freq; g.n_tiles = c->nt;
+  return g;
+}
+
+template <class K>
+static int launch_ingrad_k(afx_ctx* c, K kern, const ChainArgs& a, const InGradArgs& g, size_t lds, int grid, hipStream_t st) {
+  if (!c->attr_done.count((const void*)kern)) {
+    HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    c->attr_done.insert((const void*)kern);
+  }
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, g);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+// k_input_grads over the stash rows of chunk [t0, t1) (tiles of TILE samples), right behind the chunk's chain launch
+static int launch_input_grads(afx_ctx* c, int prec, const ChainArgs& a, InGradArgs g, int64_t t0, int64_t t1, int TILE, hipStream_t st) {
+  g.row0 = t0 * TILE;
+  g.rows = (t1 - t0) * TILE;
+  const int fmt = prec == AFX_PREC_F32 ? 0 : (is_f16(prec) ? 2 : 1);
+  const bool enc = c->d.enc != AFX_ENC_NONE;
+  const int grid = (int)std::min<int64_t>((g.rows + 255) / 256, (int64_t)4 * c->n_cu);
+  return with_width(c, [&](auto f) {
+    constexpr int FW = decltype(f)::value;
+    if (!enc) {
+      const size_t lds = (size_t)FW * 4 * 4;
+      if (fmt == 0) return launch_ingrad_k(c, k_input_grads<FW, 4, 0>, a, g, lds, grid, st);
+      if (fmt == 1) return launch_ingrad_k(c, k_input_grads<FW, 4, 1>, a, g, lds, grid, st);
+      return launch_ingrad_k(c, k_input_grads<FW, 4, 2>, a, g, lds, grid, st);
+    }
+    const size_t lds = (size_t)FW * 64 * 4;
+    if (fmt == 0) return launch_ingrad_k(c, k_input_grads<FW, 64, 0>, a, g, lds, grid, st);
+    if (fmt == 1) return launch_ingrad_k(c, k_input_grads<FW, 64, 1>, a, g, lds, grid, st);
+    return launch_ingrad_k(c, k_input_grads<FW, 64, 2>, a, g, lds, grid, st);
+  });
+}
+
+extern "C" int afx_mlp_backward_inputs(afx_ctx* c, int prec, const void* prepared, const float* pts, int64_t n_pts, const float* d_out,
+                                       float* grad_flat, float* d_pts, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!c || !prepared || !pts || !d_out || !d_pts || !workspace) return fail(AFX_E_INVALID, "afx_mlp_backward_inputs: null argument");
+  if (check_prec(prec, "afx_mlp_backward_inputs")) return AFX_E_INVALID;
+  if (n_pts < 0 || n_pts > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "afx_mlp_backward_inputs: n_pts must be < 2^31 per call");
+  if (n_pts == 0) return AFX_OK;
+  const size_t need = (size_t)ingrad_workspace(c, prec, 0, n_pts, 1);
+  if (workspace_bytes < need)
+    return fail(AFX_E_WORKSPACE, "afx_mlp_backward_inputs: workspace %zu < %zu bytes (AFX_Q_BWD_INPUTS_WORKSPACE_MIN)", workspace_bytes, need);
+  if (int rc = check_dev(c, "afx_mlp_backward_inputs")) return rc;
+  ChainArgs a = {};
+  fill_model(c, prec, true, prepared, a);
+  a.n_total = n_pts; a.mode = 0; a.pts = pts; a.dod = d_out;
+  InGradArgs g = ingrad_args(c, prec, prepared);
+  g.d_pts = d_pts;
+  return run_backward(c, prec, a, 0, (char*)workspace, workspace_bytes, grad_flat, (hipStream_t)stream, false, 0, nullptr, nullptr, &g);
+}
+
+extern "C" int afx_render_backward_inputs(afx_ctx* c, int prec, const void* prepared, const afx_render_args* r, const float* dL_dpixel,
+                                          float* grad_flat, float* d_origins, float* d_dirs, void* stream) {
+  const char* who = "afx_render_backward_inputs";
+  if (c && r && r->n_rays == 0) return AFX_OK;
+  int rc = check_render(c, r, who);
+  if (rc) return rc;
+  if (check_prec(prec, who)) return AFX_E_INVALID;
+  if (!prepared || !dL_dpixel) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (!grad_flat && !d_origins && !d_dirs) return fail(AFX_E_INVALID, "%s: nothing requested (grad_flat, d_origins and d_dirs are all null)", who);
+  if (r->ray_mode != AFX_RAYS_ARRAYS && (d_origins || d_dirs))
+    return fail(AFX_E_INVALID, "%s: ray gradients need rays given as origin / direction arrays (AFX_RAYS_ARRAYS); rays generated from poses in the "
+                "kernel (AFX_RAYS_POSE) have none", who);
+  if (!r->workspace) return fail(AFX_E_WORKSPACE, "%s: workspace required", who);
+  const size_t need = (size_t)ingrad_workspace(c, prec, r->n_rays, r->n_samples, 1);
+  if (r->workspace_bytes < need)
+    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (AFX_Q_BWD_INPUTS_WORKSPACE_MIN)", who, r->workspace_bytes, need);
+  if ((rc = check_dev(c, who))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)r->workspace;
+  const int gpr = (int)(s_pad_of(r->n_samples) / GROUP);
+  const size_t groups = (size_t)r->n_rays * gpr;
+  float* dod = (float*)ws;
+  float* gpart = (float*)(ws + rup64((size_t)r->n_rays * 4, 256));
+  float* od = (float*)((char*)gpart + rup64(groups * 32, 256));
+  const size_t head = ingrad_head_bytes(r->n_rays, r->n_samples);
+  ChainArgs a = {};
+  fill_model(c, prec, true, prepared, a);
+  fill_render(r, a);
+  a.sigma = nullptr; a.tau = nullptr;
+  hipLaunchKernelGGL(k_finish_bwd, dim3((unsigned)((r->n_rays + 255) / 256)), dim3(256), 0, st, r->pixel, dL_dpixel, r->n_rays, dod);
+  HIPCHK(hipGetLastError());
+  a.dod = dod;
+  const bool want_in = d_origins || d_dirs;
+  // the weight gradients run exactly as afx_render_backward runs them; where that configuration keeps no dZ_0 stash (in-kernel group sums,
+  // the 8-bit stash) the input gradients take a pass of their own
+  const bool sg = is_bf16(prec) && c->small_in_kernel && (c->d.enc == AFX_ENC_NONE || prec == AFX_PREC_F16S8);
+  float* grad_in_pass = grad_flat;
+  if (grad_flat && (sg || !want_in)) {
+    rc = run_backward(c, prec, a, rup64((size_t)r->n_rays * 4, 256), ws, r->workspace_bytes, grad_flat, st);
+    if (rc || !want_in) return rc;
+    grad_in_pass = nullptr;
+  }
+  InGradArgs g = ingrad_args(c, prec, prepared);
+  g.gpart = gpart;
+  rc = run_backward(c, prec, a, head, ws, r->workspace_bytes, grad_in_pass, st, false, 0, nullptr, nullptr, &g);
+  if (rc) return rc;
+  const bool dense = r->depth_mode != AFX_DEPTH_UNIFORM_MID;
+  if (dense && d_dirs) {      // the rays' optical depths: the forward pass's per-group partials
+    ChainArgs f = {};
+    fill_model(c, prec, false, prepared, f);
+    fill_render(r, f);
+    f.sigma = nullptr; f.tau = nullptr;
+    f.od_part = od;
+    f.tile0 = 0; f.tile1 = (int)((f.n_total + fwd_tile(prec) - 1) / fwd_tile(prec));
+    if ((rc = launch_chain(c, prec, false, f, st))) return rc;
+  }
+  hipLaunchKernelGGL(k_ray_input_grads, dim3((unsigned)((r->n_rays + 255) / 256)), dim3(256), 0, st, (const float*)gpart,
+                     (const float*)(dense && d_dirs ? od : nullptr), (const float*)dod, r->dirs, r->n_rays, gpr, d_origins, d_dirs);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
 }
 
 extern "C" int afx_project_volume(const float* vol, int32_t nx, int32_t ny, int32_t nz, const double origin[3], const double spacing[3],

@@ -58,7 +58,9 @@ class GradSync:
       * the autograd path (`render_*` -> your loss -> `.backward()`) must divide by the global count as well:
         `dist.global_mse(pred, target)` does; a loss that is a LOCAL mean (`F.mse_loss(pred, target)`) needs
         `GradSync(local_mean=True)`, which averages instead of summing (exact for equal shards only - the reason the
-        global-count form is the default)."""
+        global-count form is the default).
+    Gradients with respect to the INPUTS (points through `model(x)`, ray origins / directions through `render_rays`) are
+    not all-reduced: they belong to the rank's own samples and rays, so the hook only ever sees the flat parameter gradient."""
 
     def __init__(self, group=None, local_mean: bool = False):
         self.group = group

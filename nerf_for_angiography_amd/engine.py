@@ -196,6 +196,21 @@ class Engine:
                                              _ptr(grad_flat), _ptr(ws), ws.numel(), self._stream(dev)),
                    "afx_mlp_backward")
 
+    def mlp_backward_inputs(self, prepared, pts, d_out, grad_flat, d_pts, prec: str):
+        """afx_mlp_backward_inputs: d_pts [P,3] = dL/dpts (written); grad_flat += dL/dparams unless it is None."""
+        dev = prepared.device
+        pts = _f32(pts, "points", dev)
+        d_out = _f32(d_out, "d_out", dev)
+        n = pts.shape[0]
+        if d_out.numel() != n:
+            raise ValueError("d_out: one value per point expected")
+        if tuple(d_pts.shape) != (n, 3) or d_pts.dtype != torch.float32 or not d_pts.is_contiguous():
+            raise ValueError("d_pts: expected a contiguous float32 [P,3] tensor")
+        full = int(self.lib.afx_query(self.h, _lib.Q_BWD_INPUTS_WORKSPACE_FULL, 0, n, _lib.PREC[prec]))
+        ws = self._workspace(min(full, self.max_workspace_bytes), dev)
+        self._check(self.lib.afx_mlp_backward_inputs(self.h, _lib.PREC[prec], _ptr(prepared), _ptr(pts), n, _ptr(d_out), _ptr(grad_flat),
+                                                    _ptr(d_pts), _ptr(ws), ws.numel(), self._stream(dev)), "afx_mlp_backward_inputs")
+
     # ---- fused renderer ----------------------------------------------------------------------
     def _render_args(self, spec: RenderSpec, dev, pixel, sigma=None, tau=None):
         a = RenderArgs()
@@ -271,6 +286,23 @@ class Engine:
                                                 _ptr(grad_flat), self._stream(dev)), "afx_render_backward")
         del keep
 
+
+    def render_backward_inputs(self, prepared, spec: RenderSpec, pixel, d_pixel, grad_flat, d_origins, d_dirs, prec: str):
+        """afx_render_backward_inputs: d_origins / d_dirs [R,3] (either None) = dL/d(ray origins / directions), written;
+        grad_flat += dL/dparams unless it is None."""
+        dev = prepared.device
+        pixel = _f32(pixel, "pixel", dev)
+        d_pixel = _f32(d_pixel, "d_pixel", dev)
+        for t, name in ((d_origins, "d_origins"), (d_dirs, "d_dirs")):
+            if t is not None and (tuple(t.shape) != (spec.n_rays, 3) or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous float32 [n_rays,3] tensor")
+        a, keep = self._render_args(spec, dev, pixel)
+        full = int(self.lib.afx_query(self.h, _lib.Q_BWD_INPUTS_WORKSPACE_FULL, spec.n_rays, spec.n_samples, _lib.PREC[prec]))
+        ws = self._workspace(min(full, self.max_workspace_bytes), dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        self._check(self.lib.afx_render_backward_inputs(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), _ptr(d_pixel), _ptr(grad_flat),
+                                                       _ptr(d_origins), _ptr(d_dirs), self._stream(dev)), "afx_render_backward_inputs")
+        del keep
 
     def train_step_packed_mse(self, prepared, origins, dirs, packed: "PackedGroups", target, inv_n: float, grad_flat, prec: str):
         """afx_train_step_packed_mse: the reference's iteration body on the march's packed samples; returns the pixels [n_rays]."""

@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
 
@@ -44,7 +45,8 @@ class Sine(nn.Module):
 
 
 class _MlpFn(torch.autograd.Function):
-    """raw = MLP(points) through afx_mlp_infer / afx_mlp_backward."""
+    """raw = MLP(points) through afx_mlp_infer / afx_mlp_backward; with points that require grad, afx_mlp_backward_inputs also
+    returns dL/dpoints.  The backward is not itself differentiable (once_differentiable: create_graph=True raises on use)."""
 
     @staticmethod
     def forward(ctx, model, pts, *params):
@@ -56,14 +58,30 @@ class _MlpFn(torch.autograd.Function):
         return out.unsqueeze(-1)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_out):
         model = ctx.model
         (pts,) = ctx.saved_tensors
+        if ctx.needs_input_grad[1]:
+            return _MlpFn._backward_inputs(ctx, model, pts, d_out)
         flat_grad = torch.zeros(model.engine.param_count, dtype=torch.float32, device=pts.device)
         coef_grad = model._coef_grad_buffer()
         with model.engine.encoding_grad(model._flat, coef_grad):
             model.engine.mlp_backward(model._prepared(), pts, d_out.reshape(-1).contiguous(), flat_grad, model.precision)
         return (None, None) + model._fn_grads(flat_grad, coef_grad)
+
+    @staticmethod
+    def _backward_inputs(ctx, model, pts, d_out):
+        d_pts = torch.empty(pts.shape[0], 3, dtype=torch.float32, device=pts.device)
+        d_out = d_out.reshape(-1).contiguous()
+        if not any(ctx.needs_input_grad[2:]):      # frozen model: no weight-gradient kernels
+            model.engine.mlp_backward_inputs(model._prepared(), pts, d_out, None, d_pts, model.precision)
+            return (None, d_pts) + (None,) * ctx.n_params
+        flat_grad = torch.zeros(model.engine.param_count, dtype=torch.float32, device=pts.device)
+        coef_grad = model._coef_grad_buffer()
+        with model.engine.encoding_grad(model._flat, coef_grad):
+            model.engine.mlp_backward_inputs(model._prepared(), pts, d_out, flat_grad, d_pts, model.precision)
+        return (None, d_pts) + model._fn_grads(flat_grad, coef_grad)
 
 
 class CPPN(nn.Module):

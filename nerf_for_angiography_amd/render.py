@@ -7,6 +7,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .engine import RenderSpec
 from ._lib import AfxError
@@ -26,8 +27,12 @@ _grad_hook = None
 
 
 class _RenderFn(torch.autograd.Function):
+    """pixel = render(rays) through afx_render_forward / afx_render_backward.  `origins` / `dirs` are the spec's ray arrays (None for
+    rays made from poses): when they require grad, afx_render_backward_inputs also returns dL/d(origins, directions).  The backward is
+    not itself differentiable (once_differentiable: create_graph=True raises on use)."""
+
     @staticmethod
-    def forward(ctx, model, spec, want_st, *params):
+    def forward(ctx, model, spec, want_st, origins, dirs, *params):
         prepared = model._prepared()
         pixel, sigma, tau = model.engine.render_forward(prepared, spec, model.precision, want_sigma=want_st,
                                                         want_tau=want_st)
@@ -39,9 +44,12 @@ class _RenderFn(torch.autograd.Function):
         return pixel
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, d_pixel, *unused):
         model, spec = ctx.model, ctx.spec
         (pixel,) = ctx.saved_tensors
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            return _RenderFn._backward_inputs(ctx, model, spec, pixel, d_pixel)
         flat_grad = torch.zeros(model.engine.param_count, dtype=torch.float32, device=pixel.device)
         coef_grad = model._coef_grad_buffer()
         with model.engine.encoding_grad(model.flat_params, coef_grad):
@@ -50,7 +58,25 @@ class _RenderFn(torch.autograd.Function):
             _grad_hook(flat_grad)
             if coef_grad is not None:
                 _grad_hook(coef_grad)
-        return (None, None, None) + model._fn_grads(flat_grad, coef_grad)
+        return (None, None, None, None, None) + model._fn_grads(flat_grad, coef_grad)
+
+    @staticmethod
+    def _backward_inputs(ctx, model, spec, pixel, d_pixel):
+        dev = pixel.device
+        d_o = torch.empty(spec.n_rays, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        d_d = torch.empty(spec.n_rays, 3, dtype=torch.float32, device=dev) if ctx.needs_input_grad[4] else None
+        if not any(ctx.needs_input_grad[5:]):      # frozen model: no weight-gradient kernels
+            model.engine.render_backward_inputs(model._prepared(), spec, pixel, d_pixel.contiguous(), None, d_o, d_d, model.precision)
+            return (None, None, None, d_o, d_d) + (None,) * (len(ctx.needs_input_grad) - 5)
+        flat_grad = torch.zeros(model.engine.param_count, dtype=torch.float32, device=dev)
+        coef_grad = model._coef_grad_buffer()
+        with model.engine.encoding_grad(model.flat_params, coef_grad):
+            model.engine.render_backward_inputs(model._prepared(), spec, pixel, d_pixel.contiguous(), flat_grad, d_o, d_d, model.precision)
+        if _grad_hook is not None:      # the parameter gradient only: ray gradients belong to this rank's rays
+            _grad_hook(flat_grad)
+            if coef_grad is not None:
+                _grad_hook(coef_grad)
+        return (None, None, None, d_o, d_d) + model._fn_grads(flat_grad, coef_grad)
 
 
 def _check_model(model):
@@ -67,8 +93,8 @@ def _check_model(model):
 def render_spec(spec: RenderSpec, model, want_aux: bool = False) -> RenderOutput:
     _check_model(model)
     if not want_aux:
-        return RenderOutput(_RenderFn.apply(model, spec, False, *model._fn_params()))
-    pixel, sigma, tau = _RenderFn.apply(model, spec, True, *model._fn_params())
+        return RenderOutput(_RenderFn.apply(model, spec, False, spec.origins, spec.dirs, *model._fn_params()))
+    pixel, sigma, tau = _RenderFn.apply(model, spec, True, spec.origins, spec.dirs, *model._fn_params())
     out = RenderOutput(pixel, sigma=sigma)
     if spec.mode == "dense":
         # weights / depth_map / entropy of render_volume_density (nerf_helpers.py:107-119) from the
