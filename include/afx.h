@@ -511,6 +511,40 @@ int afx_topk_indices(const float* keys, int64_t n, int64_t k, int64_t* out_idx, 
 size_t afx_sample_batches_workspace_bytes(int64_t n, int32_t n_batches);
 int afx_sample_batches(const float* weights, int64_t n, uint64_t seed, uint64_t stream_id0, int32_t n_batches, int64_t k, int64_t* out_idx,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* afx_sample_batches with the first stream id in device memory: batch b uses Philox stream (seed, *stream_id0_dev + b), and the value is
+ * read by the kernels when they run, not by the host when the call is issued - out_idx equals afx_sample_batches(..., stream_id0 = that
+ * value, ...) index for index (the same kernels).  The call is launches only - no host read-back, synchronisation or allocation - so it can
+ * be captured into a HIP graph, whose replays follow the counter.  The counter is taken as non-negative and below 2^32 (the range of the
+ * refresh step).  Same workspace.  AFX_E_INVALID (before any HIP call): a null stream_id0_dev, out_idx or workspace, n_batches outside
+ * 1..65535, n outside 1..2^32 - 1, k outside 0..n. */
+int afx_sample_batches_dev(const float* weights, int64_t n, uint64_t seed, const int64_t* stream_id0_dev, int32_t n_batches, int64_t k,
+                           int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The host's bookkeeping between two grid training iterations as ONE single-lane kernel, so that a HIP graph can hold several iterations
+ * (render.GridTrainRoundGraph captures it behind every iteration's optimizer step).  With s = *step_dev, in this order:
+ *   lr_dev[0] = lr_table[min(s, n_table - 1)]           the learning rate of the NEXT iteration, from a table the host built (a pow on the
+ *                                                        device would not reproduce the host's double-precision schedule bit for bit);
+ *   loss_hist[s % round_len] = *loss;  counts_hist[s % round_len][0..2] = counts[0..2];  skip_hist[s % round_len] = *skip;
+ *   *last_loss = *skip > 0 ? *last_loss : *loss         the loss of the last step that kept samples;
+ *   *n_marched += counts[1];  *step_dev = s + 1.
+ * skip / counts: the outputs of afx_march_train_step_mse_capturable (or _single_eval); loss: one float on the device.  Every pointer is
+ * device memory; every write is a plain vector store.  AFX_E_INVALID (before any HIP call): a null pointer, n_table < 1, round_len < 1. */
+typedef struct afx_train_round_args {
+  int64_t* step_dev;            /* the iteration counter */
+  const float* lr_table;        /* [n_table] */
+  int64_t n_table;
+  float* lr_dev;                /* [1] the optimizer's device-resident learning rate */
+  const float* skip;            /* [1] */
+  const float* loss;            /* [1] */
+  const int64_t* counts;        /* [3] candidates, kept samples, groups */
+  int64_t round_len;
+  float* loss_hist;             /* [round_len] */
+  int64_t* counts_hist;         /* [round_len][3] */
+  float* skip_hist;             /* [round_len] */
+  float* last_loss;             /* [1] */
+  int64_t* n_marched;           /* [1] */
+} afx_train_round_args;
+int afx_train_round_advance(const afx_train_round_args* args, void* stream);
 
 /* ---- Device-resident ray batches (sample_pixel_rays, nerf/nerf_helpers.py:137-150: weighted sampling without
  * replacement over all pixels of all training projections).  keys[i] = log(u_i) / w_i (Efraimidis-Spirakis): the k

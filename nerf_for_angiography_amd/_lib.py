@@ -64,6 +64,12 @@ class MarchRenderArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("n_candidates", C.c_int64), ("workspace_needed", C.c_size_t)]
 
 
+class TrainRoundArgs(C.Structure):
+    _fields_ = [("step_dev", C.c_void_p), ("lr_table", C.c_void_p), ("n_table", C.c_int64), ("lr_dev", C.c_void_p), ("skip", C.c_void_p),
+                ("loss", C.c_void_p), ("counts", C.c_void_p), ("round_len", C.c_int64), ("loss_hist", C.c_void_p), ("counts_hist", C.c_void_p),
+                ("skip_hist", C.c_void_p), ("last_loss", C.c_void_p), ("n_marched", C.c_void_p)]
+
+
 _SIGS = {
     "afx_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_void_p)]),
     "afx_destroy": (None, [C.c_void_p]),
@@ -98,6 +104,9 @@ _SIGS = {
     "afx_topk_indices": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "afx_sample_batches_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "afx_sample_batches": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "afx_sample_batches_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+    "afx_train_round_advance": (C.c_int, [C.POINTER(TrainRoundArgs), C.c_void_p]),
     "afx_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "afx_set_encoding_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_profile_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

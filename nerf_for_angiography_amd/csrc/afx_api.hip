@@ -1574,14 +1574,9 @@ extern "C" size_t afx_sample_batches_workspace_bytes(int64_t n, int32_t n_batche
   return (size_t)B * ((size_t)(n > 0 ? n : 0) * 4 + (size_t)SEL_BINS * 4 + sizeof(SelState) + (size_t)2 * (nb > 0 ? nb : 1) * 4) + 1024;
 }
 
-extern "C" int afx_sample_batches(const float* weights, int64_t n, uint64_t seed, uint64_t stream_id0, int32_t n_batches, int64_t k,
-                                  int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-  if (k == 0 || n_batches == 0) return AFX_OK;
-  if (n <= 0 || k < 0 || k > n || n >= ((int64_t)1 << 32) || n_batches < 0 || n_batches > 65535)
-    return fail(AFX_E_INVALID, "afx_sample_batches: need 0 <= k <= n < 2^32 and 0 <= n_batches <= 65535");
-  if (!out_idx || !workspace) return fail(AFX_E_INVALID, "afx_sample_batches: null argument");
-  if (workspace_bytes < afx_sample_batches_workspace_bytes(n, n_batches)) return fail(AFX_E_WORKSPACE, "afx_sample_batches: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
+// the launch sequence of a block of draws (sizes checked by the caller); the first stream id is stream_id0 (+ *stream_dev when given)
+static int launch_sample_batches(const float* weights, int64_t n, uint64_t seed, uint64_t stream_id0, const int64_t* stream_dev, int32_t n_batches,
+                                 int64_t k, int64_t* out_idx, void* workspace, hipStream_t st) {
   const unsigned B = (unsigned)n_batches;
   const int64_t nb = (n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
   char* w = (char*)workspace;
@@ -1593,7 +1588,8 @@ extern "C" int afx_sample_batches(const float* weights, int64_t n, uint64_t seed
   int hb = (int)((n + 256 * 16 - 1) / (256 * 16));
   if (hb < 1) hb = 1;
   if (hb > 2048) hb = 2048;
-  hipLaunchKernelGGL(k_sample_keys, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, weights, n, (const float*)nullptr, seed, stream_id0, keys);
+  hipLaunchKernelGGL(k_sample_keys, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, weights, n, (const float*)nullptr, seed, stream_id0, keys,
+                     stream_dev);
   hipLaunchKernelGGL(k_sel_init, dim3(1, B), dim3(256), 0, st, state, (uint32_t)k, hist);
   const int shifts[3] = {21, 10, 0};
   const uint32_t binmask[3] = {0x7ffu, 0x7ffu, 0x3ffu}, himask[3] = {0u, 0xffe00000u, 0xfffffc00u};
@@ -1605,6 +1601,48 @@ extern "C" int afx_sample_batches(const float* weights, int64_t n, uint64_t seed
   hipLaunchKernelGGL(k_sel_offsets, dim3(1, B), dim3(1024), 0, st, cnt_gt, cnt_eq, nb);
   hipLaunchKernelGGL(k_sel_write, dim3((unsigned)nb, B), dim3(256), 0, st, (const float*)keys, n, (const SelState*)state, (const uint32_t*)cnt_gt,
                      (const uint32_t*)cnt_eq, k, out_idx);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" int afx_sample_batches(const float* weights, int64_t n, uint64_t seed, uint64_t stream_id0, int32_t n_batches, int64_t k,
+                                  int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (k == 0 || n_batches == 0) return AFX_OK;
+  if (n <= 0 || k < 0 || k > n || n >= ((int64_t)1 << 32) || n_batches < 0 || n_batches > 65535)
+    return fail(AFX_E_INVALID, "afx_sample_batches: need 0 <= k <= n < 2^32 and 0 <= n_batches <= 65535");
+  if (!out_idx || !workspace) return fail(AFX_E_INVALID, "afx_sample_batches: null argument");
+  if (workspace_bytes < afx_sample_batches_workspace_bytes(n, n_batches)) return fail(AFX_E_WORKSPACE, "afx_sample_batches: workspace too small");
+  return launch_sample_batches(weights, n, seed, stream_id0, nullptr, n_batches, k, out_idx, workspace, (hipStream_t)stream);
+}
+
+// the same draws with the first stream id in device memory: nothing but launches (the selection keeps its ranks and counts on the device
+// already), so a graph captured over the call follows the counter
+extern "C" int afx_sample_batches_dev(const float* weights, int64_t n, uint64_t seed, const int64_t* stream_id0_dev, int32_t n_batches, int64_t k,
+                                      int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "afx_sample_batches_dev";
+  if (!stream_id0_dev || !out_idx || !workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (n_batches < 1 || n_batches > 65535) return fail(AFX_E_INVALID, "%s: n_batches must be in 1..65535 (got %d)", who, (int)n_batches);
+  if (n <= 0 || n >= ((int64_t)1 << 32)) return fail(AFX_E_INVALID, "%s: need 0 < n < 2^32 (got %lld)", who, (long long)n);
+  if (k < 0 || k > n) return fail(AFX_E_INVALID, "%s: need 0 <= k <= n (k = %lld, n = %lld)", who, (long long)k, (long long)n);
+  if (workspace_bytes < afx_sample_batches_workspace_bytes(n, n_batches)) return fail(AFX_E_WORKSPACE, "%s: workspace too small", who);
+  if (k == 0) return AFX_OK;
+  return launch_sample_batches(weights, n, seed, 0, stream_id0_dev, n_batches, k, out_idx, workspace, (hipStream_t)stream);
+}
+
+extern "C" int afx_train_round_advance(const afx_train_round_args* a, void* stream) {
+  const char* who = "afx_train_round_advance";
+  if (!a) return fail(AFX_E_INVALID, "%s: null args", who);
+  if (!a->step_dev || !a->lr_table || !a->lr_dev || !a->skip || !a->loss || !a->counts || !a->loss_hist || !a->counts_hist || !a->skip_hist ||
+      !a->last_loss || !a->n_marched)
+    return fail(AFX_E_INVALID, "%s: null argument", who);
+  if (a->n_table < 1) return fail(AFX_E_INVALID, "%s: n_table must be >= 1 (got %lld)", who, (long long)a->n_table);
+  if (a->round_len < 1) return fail(AFX_E_INVALID, "%s: round_len must be >= 1 (got %lld)", who, (long long)a->round_len);
+  TrainRoundArgs t;
+  t.step_dev = a->step_dev; t.lr_table = a->lr_table; t.n_table = a->n_table; t.lr_dev = a->lr_dev;
+  t.skip = a->skip; t.loss = a->loss; t.counts = a->counts;
+  t.round_len = a->round_len; t.loss_hist = a->loss_hist; t.counts_hist = a->counts_hist; t.skip_hist = a->skip_hist;
+  t.last_loss = a->last_loss; t.n_marched = a->n_marched;
+  hipLaunchKernelGGL(k_train_round_advance, dim3(1), dim3(64), 0, (hipStream_t)stream, t);
   HIPCHK(hipGetLastError());
   return AFX_OK;
 }

@@ -679,9 +679,12 @@ __global__ void __launch_bounds__(256) k_pack_groups(const int64_t* offsets, con
 // rays.  Efraimidis-Spirakis keys: key_i = u_i^(1/w_i) (log form: log(u_i)/w_i), the k largest keys are a weighted sample
 // without replacement; u from Philox (perf mode) or supplied.  The top-k selection is the radix select below.
 // (blockIdx.y = batch b of afx_sample_batches: Philox stream `stream + b`, keys row b; a plain call has one row)
-__global__ void k_sample_keys(const float* weights, int64_t n, const float* u_in, uint64_t seed, uint64_t stream, float* keys) {
+// afx_sample_batches_dev: the first stream id is stream + *stream_dev, a device counter read when the kernel runs (a captured call follows it).
+__global__ void k_sample_keys(const float* weights, int64_t n, const float* u_in, uint64_t seed, uint64_t stream, float* keys,
+                              const int64_t* stream_dev = nullptr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (stream_dev) stream += (uint64_t)*stream_dev;
   const float w = weights ? weights[i] : 1.f;
   float u = u_in ? u_in[i] : philox_uniform(seed, stream + blockIdx.y, (uint64_t)i);
   u = fmaxf(u, 5.9604645e-08f);
@@ -838,6 +841,31 @@ __global__ void k_gather_rays(const float* org, const float* dir, const float* p
 __global__ void k_philox_fill(uint64_t seed, uint64_t stream, int64_t n, float* out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = philox_uniform(seed, stream, (uint64_t)i);
+}
+
+// --- the bookkeeping between two captured grid iterations (afx_train_round_advance): what the training loop does on the host after a
+// step - the next learning rate, the step's loss / counts / skip flag kept for the display point, the sample total, the step counter -
+// from device memory, so that a graph holding several iterations needs no host in between.  One lane; every write is a plain store.
+struct TrainRoundArgs {
+  int64_t* step_dev; const float* lr_table; int64_t n_table; float* lr_dev;
+  const float *skip, *loss; const int64_t* counts;
+  int64_t round_len; float* loss_hist; int64_t* counts_hist; float* skip_hist; float* last_loss; int64_t* n_marched;
+};
+__global__ void k_train_round_advance(TrainRoundArgs a) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t s = *a.step_dev;
+  const int64_t li = s < 0 ? 0 : (s < a.n_table ? s : a.n_table - 1);      // (a negative counter never indexes before the table)
+  int64_t slot = s % a.round_len;
+  if (slot < 0) slot += a.round_len;
+  const float loss = *a.loss, skip = *a.skip;
+  const int64_t c0 = a.counts[0], c1 = a.counts[1], c2 = a.counts[2];
+  a.lr_dev[0] = a.lr_table[li];
+  a.loss_hist[slot] = loss;
+  a.counts_hist[3 * slot + 0] = c0; a.counts_hist[3 * slot + 1] = c1; a.counts_hist[3 * slot + 2] = c2;
+  a.skip_hist[slot] = skip;
+  if (!(skip > 0.f)) *a.last_loss = loss;      // (the last step that kept samples)
+  *a.n_marched += c1;
+  *a.step_dev = s + 1;
 }
 
 }  // namespace afx

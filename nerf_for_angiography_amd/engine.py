@@ -1027,6 +1027,68 @@ class RayBatchSampler:
         return o, d, p, idx
 
 
+def sample_batches_workspace_bytes(n: int, n_batches: int) -> int:
+    return int(_lib.load().afx_sample_batches_workspace_bytes(int(n), int(n_batches)))
+
+
+def sample_batches_dev(weights, seed: int, stream_id0_dev, n_batches: int, k: int, out_idx=None, workspace=None):
+    """afx_sample_batches_dev: the index rows of `n_batches` consecutive draws, out_idx[b] = the draw of Philox stream (seed, stream_id0_dev + b)
+    - what RayBatchSampler / sample_rays draw for that stream id, index for index - with the first id read from a 0-dim int64 device tensor
+    when the kernels run.  Launches only: a graph captured over the call follows the counter.  Pass out_idx [n_batches, k] (int64) and a
+    workspace of sample_batches_workspace_bytes(n, n_batches) bytes to reuse static buffers.  Returns out_idx."""
+    lib = _lib.load()
+    dev = weights.device
+    if dev.type != "cuda":
+        raise AfxError("sample_batches_dev: the ray table must live on a GPU; there is no CPU fallback")
+    weights = _f32(weights, "weights", dev)
+    n, n_batches, k = weights.numel(), int(n_batches), int(k)
+    if not torch.is_tensor(stream_id0_dev):
+        raise ValueError("sample_batches_dev: the first stream id must be a 0-dim int64 device tensor (RayBatchSampler takes host ids)")
+    _, step_d = _step_args(stream_id0_dev, dev, "sample_batches_dev")
+    if out_idx is None:
+        out_idx = torch.empty(max(n_batches, 0), max(k, 0), dtype=torch.int64, device=dev)
+    elif out_idx.device != dev or out_idx.dtype != torch.int64 or out_idx.numel() != n_batches * k or not out_idx.is_contiguous():
+        raise ValueError(f"sample_batches_dev: out_idx must be a contiguous int64 tensor of {n_batches} x {k} elements on {dev}")
+    if workspace is None:
+        workspace = torch.empty(max(int(lib.afx_sample_batches_workspace_bytes(n, max(n_batches, 1))), 1), dtype=torch.uint8, device=dev)
+    elif workspace.device != dev:
+        raise ValueError(f"sample_batches_dev: workspace on {workspace.device}, expected {dev}")
+    _lib.check(lib.afx_sample_batches_dev(_ptr(weights), n, int(seed), step_d, n_batches, k, _ptr(out_idx), _ptr(workspace), workspace.numel(),
+                                          Engine._stream(dev)), "afx_sample_batches_dev")
+    return out_idx
+
+
+def gather_rays(origins, dirs, pixels, idx, origins_out, dirs_out, pixels_out):
+    """afx_gather_rays into the caller's buffers: rows idx [k] (int64) of a float32 ray table [n,3], [n,3], [n]."""
+    lib = _lib.load()
+    _lib.check(lib.afx_gather_rays(_ptr(origins), _ptr(dirs), _ptr(pixels), _ptr(idx), idx.numel(), _ptr(origins_out), _ptr(dirs_out),
+                                   _ptr(pixels_out), Engine._stream(origins.device)), "afx_gather_rays")
+
+
+def train_round_advance(step_dev, lr_table, lr_dev, skip, loss, counts, loss_hist, counts_hist, skip_hist, last_loss, n_marched):
+    """afx_train_round_advance: the bookkeeping behind one captured grid iteration, on the device (include/afx.h) - the next learning rate
+    from `lr_table`, the step's loss / counts / skip flag into slot step % round_len of the history (round_len = loss_hist.numel()),
+    last_loss, n_marched, step + 1.  Every argument is a device tensor: int64 step_dev [1], counts [3], counts_hist [round_len, 3],
+    n_marched [1]; float32 the rest."""
+    lib = _lib.load()
+    dev = step_dev.device
+    if dev.type != "cuda":
+        raise AfxError("train_round_advance: the counters live on a GPU; there is no CPU fallback")
+    L = loss_hist.numel()
+    spec = (("step_dev", step_dev, torch.int64, 1), ("lr_table", lr_table, torch.float32, None), ("lr_dev", lr_dev, torch.float32, 1),
+            ("skip", skip, torch.float32, 1), ("loss", loss, torch.float32, 1), ("counts", counts, torch.int64, 3),
+            ("loss_hist", loss_hist, torch.float32, L), ("counts_hist", counts_hist, torch.int64, 3 * L), ("skip_hist", skip_hist, torch.float32, L),
+            ("last_loss", last_loss, torch.float32, 1), ("n_marched", n_marched, torch.int64, 1))
+    for name, t, dt, n in spec:
+        if t.device != dev or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_contiguous():
+            raise ValueError(f"train_round_advance: {name} must be a contiguous {dt} tensor of {n if n is not None else 'n_table'} elements on {dev}")
+    a = _lib.TrainRoundArgs()
+    a.n_table, a.round_len = lr_table.numel(), L
+    for name, t, _, _ in spec:
+        setattr(a, name, t.data_ptr())
+    _lib.check(lib.afx_train_round_advance(C.byref(a), Engine._stream(dev)), "afx_train_round_advance")
+
+
 def sample_rays(origins, dirs, pixels, weights, k, u=None, seed=0, stream_id=0):
     """Weighted sample WITHOUT replacement of k rows of a device-resident ray table (sample_pixel_rays, nerf_helpers.py:137-150):
     Efraimidis-Spirakis keys log(u)/w, radix-select top-k on the device (afx_topk_indices), gather.  Returns (origins[k,3], dirs[k,3], pixels[k] | None, idx)."""

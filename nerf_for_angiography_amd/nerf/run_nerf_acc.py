@@ -15,6 +15,8 @@ the mirrored functions (also what `grid` does at the other precisions).  `--grap
 included, from a HIP graph captured once (`render.GridTrainGraph`): the sizes stay on the device and the host never waits for the GPU.
 `--graph-grid-update` (with `--graph`) also replays the refresh of both occupancy grids every 16th iteration from HIP graphs
 (`render.GridUpdateGraph`: the cells drawn on the device, no host synchronisation); without it the refresh stays eager.
+`--graph-rounds` (with both) replays a whole refresh period - both refreshes, the draw of the 16 batches from a device step counter, 16
+iterations with Adam and the learning-rate update - from one graph launch (`render.GridTrainRoundGraph`); same numbers, opt-in.
 `--single-eval` (with `grid`, f16s8, with or without `--graph`) evaluates the model once per iteration: the training step's forward half over
 the march's candidates doubles as the alpha pass.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
@@ -38,7 +40,8 @@ from ..engine import RenderSpec
 from ..model.CPPN import CPPN
 from ..phantomdata import dataset as ds
 from .. import engine as _engine
-from ..render import render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph, GridUpdateGraph
+from ..render import (render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph, GridUpdateGraph, GridTrainRoundGraph,
+                      lr_decay_table)
 from .nerf_helpers import sample_pixel_rays, get_predictions
 from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
@@ -80,6 +83,11 @@ def build_parser():
                    help='with --graph: refresh both occupancy grids every 16th iteration from HIP graphs too (render.GridUpdateGraph: the cells '
                         'are drawn on the device, afx_grid_refresh), so the host never waits for the GPU; the draw differs from the eager '
                         'refresh\'s torch draw')
+    p.add_argument('--graph-rounds', dest='graph_rounds', action='store_true',
+                   help='with --graph --graph-grid-update: one graph launch per 16 iterations (render.GridTrainRoundGraph) - both grid refreshes, '
+                        'the draw of the 16 batches from a device step counter (afx_sample_batches_dev), then 16 times gather, step, Adam and the '
+                        'learning-rate update (afx_train_round_advance); the host launches up to the next display point and reads nothing back '
+                        'in between; same numbers as without the flag')
     p.add_argument('--single-eval', dest='single_eval', action='store_true',
                    help='--march grid --precision f16s8 --pos_enc none (with or without --graph): evaluate the model ONCE per iteration - the '
                         'training step\'s forward half over the march\'s candidates doubles as the alpha pass (afx_march_train_step_mse_single_eval)')
@@ -94,13 +102,22 @@ def build_parser():
     return p
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def check_args(args):
+    """The flag combinations the driver refuses (before any device work)."""
     if args.single_eval and (args.march != 'grid' or args.precision != 'f16s8' or args.pos_enc != 'none'):
         raise ValueError("--single-eval: needs --march grid --precision f16s8 --pos_enc none (the single-evaluation grid step is f16s8, ReLU, "
                          "without an input encoding)")
     if args.graph_grid_update and not args.graph:
         raise ValueError("--graph-grid-update: needs --graph")
+    if args.graph_rounds and not (args.graph and args.graph_grid_update):
+        raise ValueError("--graph-rounds: needs --graph --graph-grid-update")
+    if args.graph_rounds and args.host_sampler:
+        raise ValueError("--graph-rounds: the batches are drawn inside the graph; --host_sampler draws them on the host")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    check_args(args)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     if device.type != "cuda":
         raise SystemExit("run_nerf_acc: needs an MI355X; there is no CPU fallback")
@@ -193,87 +210,102 @@ def main(argv=None):
     os.makedirs(args.log_dir, exist_ok=True)
     log = open(os.path.join(args.log_dir, 'train_log.jsonl'), 'a')
     highest_psnr, highest_iter, history = 0.0, 0, []
-    if not args.host_sampler:      # the batches of 16 iterations per launch sequence
+    if not args.host_sampler and not args.graph_rounds:      # the batches of 16 iterations per launch sequence
         ray_batches = _engine.RayBatchSampler(tab_o, tab_d, tab_pix, tab_w, img_sample_size, seed=args.seed, prefetch=16)
     new_lr_coarse = coarse_lr
     loss_coarse = torch.tensor(float('nan'), device=device)
     n_marched = 0
     train_graph = None
-    if args.graph:      # captured once; every iteration then copies its batch into the graph's static tensors and replays
+    round_graph = None
+    if args.graph_rounds:      # whole refresh periods per graph launch: draw, refreshes, 16 iterations and their bookkeeping on the device
+        if acc_grid is None:
+            raise ValueError("--graph-rounds: needs --march grid")      # (--graph has checked the rest)
+        round_graph = GridTrainRoundGraph(coarse_model, coarse_optimizer, [(acc_grid, alpha_thre), (vessel_acc_grid, vessel_alpha_thre)],
+                                          (tab_o, tab_d, tab_pix, tab_w), scene_aabb, img_sample_size, depth_samples_per_ray_coarse, near_thresh,
+                                          far_thresh, early_stop_eps, alpha_thre, seed=args.seed,
+                                          lr_table=lr_decay_table(coarse_lr, decay_rate, decay_steps, n_iters + 1), single_eval=args.single_eval)
+    elif args.graph:      # captured once; every iteration then copies its batch into the graph's static tensors and replays
         train_graph = GridTrainGraph(coarse_model, coarse_optimizer, acc_grid, scene_aabb, img_sample_size, depth_samples_per_ray_coarse, near_thresh,
                                      far_thresh, early_stop_eps, alpha_thre, single_eval=args.single_eval)
         n_marched = torch.zeros((), dtype=torch.int64, device=device)
     update_graph = None
-    if args.graph_grid_update:      # both grids' refresh (:285-286) in graphs captured on first use; replayed before the training step
+    if args.graph_grid_update and round_graph is None:      # both grids' refresh (:285-286) in graphs captured on first use; replayed before the training step
         update_graph = GridUpdateGraph(coarse_model, [(acc_grid, alpha_thre), (vessel_acc_grid, vessel_alpha_thre)])
     t_last = time.time()
-    for n_iter in range(n_iters + 1):
+    # --graph-rounds: the loop visits the display points (and the last iteration) only; run() replays every iteration up to each of them
+    stops = range(n_iters + 1) if round_graph is None else sorted(set(range(0, n_iters + 1, display_every)) | {n_iters})
+    for n_iter in stops:
         coarse_model.train()
-        if coarse_model.use_pos_enc == 'barf' and barf_start <= n_iter < barf_stop:
-            coarse_model.update_barf_alpha(coarse_model.barf_alpha + barf_step_size, 'pts')
-        if args.host_sampler:
-            batch_origins, batch_directions, batch_pix_vals = sample_pixel_rays(train_ray_df, img_sample_size, device,
-                                                                               weights='distance_pixel_value')
+        if round_graph is not None:
+            round_graph.run(n_iter + 1 - round_graph.iter)      # iterations round_graph.iter .. n_iter; nothing is read back
+            loss_coarse, n_marched = round_graph.last_loss, round_graph.n_marched      # (device tensors, read at the display point below)
+            new_lr_coarse = coarse_lr * (decay_rate ** (n_iter / decay_steps))
         else:
-            batch_origins, batch_directions, batch_pix_vals, _ = ray_batches.draw(n_iter)      # == sample_rays(..., seed, stream_id=n_iter)
-        if train_graph is None:
-            coarse_optimizer.zero_grad()      # (--graph: the captured step zeroes the gradient buffer it accumulates into)
-        if args.march != 'dense':
-            # the reference's iteration body, run_nerf_acc.py:284-306
-            with torch.no_grad():
-                acc_grid.train()
-                vessel_acc_grid.train()
-                if update_graph is not None:
-                    update_graph.step(n_iter)
-                else:
-                    acc_grid = acc_update_n_step(acc_grid, coarse_model, n_iter, occ_thre=alpha_thre)
-                    vessel_acc_grid = acc_update_n_step(vessel_acc_grid, coarse_model, n_iter, occ_thre=vessel_alpha_thre)
-            if train_graph is not None:
-                # the same iteration replayed from the graph: no host read-back; an empty march skips the Adam step on the device
-                loss_k, pred, counts = train_graph.step(batch_origins, batch_directions, batch_pix_vals)
-                loss_coarse = torch.where(train_graph.skip[0] > 0, loss_coarse, loss_k)      # (the last step that kept samples, as below)
-                n_marched += counts[1]
-                ray_indices = ()      # (the optimizer step is part of the graph)
-            elif packed_step:
-                # :287-306 - march, alpha pass, visibility and the fused packed step - as ONE library call (the entry points of the
-                # operator branch below, in the same order: ~30 launches that a Python loop issues slower than the GPU runs them)
-                loss_k, pred_k, n_kept = march_train_step_mse(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
-                                                              depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps,
-                                                              alpha_thre, batch_pix_vals, single_eval=args.single_eval)
-                ray_indices = range(n_kept)      # (only its length is used below: the reference steps when the march kept samples)
-                if n_kept:
-                    loss_coarse, pred = loss_k, pred_k
-                    n_marched += n_kept
+            if coarse_model.use_pos_enc == 'barf' and barf_start <= n_iter < barf_stop:
+                coarse_model.update_barf_alpha(coarse_model.barf_alpha + barf_step_size, 'pts')
+            if args.host_sampler:
+                batch_origins, batch_directions, batch_pix_vals = sample_pixel_rays(train_ray_df, img_sample_size, device,
+                                                                                   weights='distance_pixel_value')
             else:
+                batch_origins, batch_directions, batch_pix_vals, _ = ray_batches.draw(n_iter)      # == sample_rays(..., seed, stream_id=n_iter)
+            if train_graph is None:
+                coarse_optimizer.zero_grad()      # (--graph: the captured step zeroes the gradient buffer it accumulates into)
+            if args.march != 'dense':
+                # the reference's iteration body, run_nerf_acc.py:284-306
                 with torch.no_grad():
-                    ray_indices, t_starts, t_ends = acc_ray_marching(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
-                                                                     depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps,
-                                                                     alpha_thre)
-                if len(ray_indices) > 0:
-                    positions = batch_origins[ray_indices.long()] + batch_directions[ray_indices.long()] * (t_starts + t_ends) / 2.0
-                    predictions = get_predictions(coarse_model, positions, batch_size)
-                    pred, _ = acc_render_volume_density(predictions, ray_indices, t_starts, t_ends, img_sample_size,
-                                                        depth_samples_per_ray_coarse)
-                    loss_coarse = torch.nn.functional.mse_loss(pred, batch_pix_vals)
-                    loss_coarse.backward()
-                    n_marched += int(len(ray_indices))
-        elif args.precision == 'f32':
-            pred = render_rays(coarse_model, batch_origins, batch_directions, depth_samples_per_ray_coarse, near_thresh,
-                               far_thresh, mode='acc').rgb_map
-            loss_coarse = torch.nn.functional.mse_loss(pred, batch_pix_vals)
-            loss_coarse.backward()
-        else:
-            loss_coarse, pred = train_step_mse(coarse_model, RenderSpec(
-                n_rays=img_sample_size, n_samples=depth_samples_per_ray_coarse, origins=batch_origins,
-                dirs=batch_directions, mode='acc', t_near=near_thresh, t_far=far_thresh), batch_pix_vals)
-        if args.march == 'dense' or len(ray_indices) > 0:      # (the reference steps only when the march kept samples, :293)
-            coarse_optimizer.step()
-        new_lr_coarse = coarse_lr * (decay_rate ** (n_iter / decay_steps))
-        for param_group in coarse_optimizer.param_groups:
-            if train_graph is not None:
-                param_group['lr'].fill_(new_lr_coarse)
+                    acc_grid.train()
+                    vessel_acc_grid.train()
+                    if update_graph is not None:
+                        update_graph.step(n_iter)
+                    else:
+                        acc_grid = acc_update_n_step(acc_grid, coarse_model, n_iter, occ_thre=alpha_thre)
+                        vessel_acc_grid = acc_update_n_step(vessel_acc_grid, coarse_model, n_iter, occ_thre=vessel_alpha_thre)
+                if train_graph is not None:
+                    # the same iteration replayed from the graph: no host read-back; an empty march skips the Adam step on the device
+                    loss_k, pred, counts = train_graph.step(batch_origins, batch_directions, batch_pix_vals)
+                    loss_coarse = torch.where(train_graph.skip[0] > 0, loss_coarse, loss_k)      # (the last step that kept samples, as below)
+                    n_marched += counts[1]
+                    ray_indices = ()      # (the optimizer step is part of the graph)
+                elif packed_step:
+                    # :287-306 - march, alpha pass, visibility and the fused packed step - as ONE library call (the entry points of the
+                    # operator branch below, in the same order: ~30 launches that a Python loop issues slower than the GPU runs them)
+                    loss_k, pred_k, n_kept = march_train_step_mse(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
+                                                                  depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps,
+                                                                  alpha_thre, batch_pix_vals, single_eval=args.single_eval)
+                    ray_indices = range(n_kept)      # (only its length is used below: the reference steps when the march kept samples)
+                    if n_kept:
+                        loss_coarse, pred = loss_k, pred_k
+                        n_marched += n_kept
+                else:
+                    with torch.no_grad():
+                        ray_indices, t_starts, t_ends = acc_ray_marching(coarse_model, acc_grid, scene_aabb, batch_origins, batch_directions,
+                                                                         depth_samples_per_ray_coarse, near_thresh, far_thresh, early_stop_eps,
+                                                                         alpha_thre)
+                    if len(ray_indices) > 0:
+                        positions = batch_origins[ray_indices.long()] + batch_directions[ray_indices.long()] * (t_starts + t_ends) / 2.0
+                        predictions = get_predictions(coarse_model, positions, batch_size)
+                        pred, _ = acc_render_volume_density(predictions, ray_indices, t_starts, t_ends, img_sample_size,
+                                                            depth_samples_per_ray_coarse)
+                        loss_coarse = torch.nn.functional.mse_loss(pred, batch_pix_vals)
+                        loss_coarse.backward()
+                        n_marched += int(len(ray_indices))
+            elif args.precision == 'f32':
+                pred = render_rays(coarse_model, batch_origins, batch_directions, depth_samples_per_ray_coarse, near_thresh,
+                                   far_thresh, mode='acc').rgb_map
+                loss_coarse = torch.nn.functional.mse_loss(pred, batch_pix_vals)
+                loss_coarse.backward()
             else:
-                param_group['lr'] = new_lr_coarse
+                loss_coarse, pred = train_step_mse(coarse_model, RenderSpec(
+                    n_rays=img_sample_size, n_samples=depth_samples_per_ray_coarse, origins=batch_origins,
+                    dirs=batch_directions, mode='acc', t_near=near_thresh, t_far=far_thresh), batch_pix_vals)
+            if args.march == 'dense' or len(ray_indices) > 0:      # (the reference steps only when the march kept samples, :293)
+                coarse_optimizer.step()
+            new_lr_coarse = coarse_lr * (decay_rate ** (n_iter / decay_steps))
+            for param_group in coarse_optimizer.param_groups:
+                if train_graph is not None:
+                    param_group['lr'].fill_(new_lr_coarse)
+                else:
+                    param_group['lr'] = new_lr_coarse
 
         if n_iter % display_every == 0:
             coarse_model.eval()
@@ -307,7 +339,7 @@ def main(argv=None):
                        img_sample_size * depth_samples_per_ray_coarse)
             if eval_counts is not None:      # candidates : kept samples of the test-view march
                 rec['eval_candidates_per_kept'] = eval_counts[0] / eval_counts[1] if eval_counts[1] else None
-            n_marched = 0 if train_graph is None else n_marched.zero_()
+            n_marched = 0 if train_graph is None and round_graph is None else n_marched.zero_()
             t_last = time.time()
             history.append(rec)
             log.write(json.dumps(rec) + "\n")

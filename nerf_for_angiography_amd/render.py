@@ -606,3 +606,231 @@ class GridUpdateGraph:
         self.step_dev.fill_(int(n_iter))
         graph.replay()
         self._mark_stale()
+
+
+def lr_decay_table(lr0: float, decay_rate: float, decay_steps: float, n: int):
+    """The training driver's learning-rate schedule as a float32 table: entry i = lr0 * decay_rate ** (i / decay_steps), evaluated in Python
+    doubles and rounded to float32 - the value `lr.fill_(...)` leaves in a float32 device tensor after iteration i, bit for bit."""
+    import numpy as np
+    return np.array([lr0 * (decay_rate ** (i / decay_steps)) for i in range(int(n))], dtype=np.float32)
+
+
+def grid_round_schedule(start: int, n: int, round_len: int = 16, warmup: int = 256):
+    """What GridTrainRoundGraph.run(n) replays from iteration `start`, as a list - a pure function of its arguments:
+      ("round", step, all_cells)    one graph launch: the refresh at `step` (a multiple of round_len), then iterations step .. step + round_len - 1
+      ("refresh", step, all_cells)  the refresh alone, ahead of a tail iteration at a multiple of round_len
+      ("tail", step)                one iteration without a refresh
+    all_cells = step < warmup (the warm-up refresh evaluates every cell).  A whole round runs when the step is a multiple of round_len and
+    at least round_len iterations remain; every multiple of round_len in [start, start + n) gets exactly one refresh."""
+    start, n, round_len, warmup = int(start), int(n), int(round_len), int(warmup)
+    if start < 0 or n < 0 or round_len < 1:
+        raise ValueError("grid_round_schedule: need start >= 0, n >= 0, round_len >= 1")
+    ops, s, end = [], start, start + n
+    while s < end:
+        if s % round_len == 0 and end - s >= round_len:
+            ops.append(("round", s, s < warmup))
+            s += round_len
+            continue
+        if s % round_len == 0:
+            ops.append(("refresh", s, s < warmup))
+        ops.append(("tail", s))
+        s += 1
+    return ops
+
+
+class GridTrainRoundGraph:
+    """Whole refresh periods of the grid training loop from ONE graph launch each: what the driver's loop does per iteration with
+    RayBatchSampler.draw, GridUpdateGraph.step, GridTrainGraph.step and the learning-rate `fill_` - in that order, with the same kernels on the
+    same inputs - captured with the batch draw (afx_sample_batches_dev: the Philox stream id is the device step counter) and the loop's
+    bookkeeping (afx_train_round_advance) inside.  A round graph holds: re-tiling, the refresh of every grid at the counter's step, the draw of
+    `round_len` batches, then round_len times [gather batch j into the static batch, re-tile, zero the gradient, the capturable (or
+    single-evaluation) step, the loss, optimizer.step() with found_inf = the skip flag, afx_train_round_advance].  Two of them (the warm-up
+    refresh evaluates every cell, the later ones draw their cells on the device) and a tail graph (one iteration, a draw of one, no refresh)
+    are captured on first use over one set of static buffers, each on one stream.
+
+    grids: [(grid, occ_thre), ...] - every one is refreshed, the first is marched.  ray_table: (origins [n,3], dirs [n,3], pixels [n],
+    weights [n]) on the device.  lr_table: float32 schedule (lr_decay_table); after iteration i the optimizer's learning rate - one float32
+    device tensor shared by every param group - is lr_table[min(i, len - 1)]; iteration start_iter runs at lr_table[start_iter - 1] (the tensor's
+    own value when start_iter is 0).  Requires Adam(fused=True, capturable=True), f16s8, no trainable fourier coefficients, one rank.
+
+    run(n) advances n iterations (grid_round_schedule); nothing is read back: the class keeps a host mirror of the counter (`iter`).  A tail
+    iteration at a multiple of round_len gets its refresh from the same calls issued eagerly.  history() returns the device tensors the
+    replays write: the last round_len iterations' loss, counts and skip flag (slot = iteration % round_len), last_loss (the loss of the last
+    iteration that kept samples), n_marched (kept samples summed; the caller may zero_() it) and the counter.  The grids' buffers, the ray table
+    and the learning-rate tensor are used by address: update them in place, never rebind them."""
+
+    def __init__(self, model, optimizer, grids, ray_table, scene_aabb, n_rays: int, depth_samples_per_ray: int, near: float, far: float,
+                 early_stop_eps: float, alpha_thre: float, seed: int = 0, lr_table=None, round_len: int = 16, single_eval: bool = False,
+                 start_iter: int = 0, warmup_steps: int = 256, ema_decay: float = 0.95, last_loss: float = float("nan")):
+        who = "GridTrainRoundGraph"
+        if _grad_hook is not None and getattr(_grad_hook, "world", 1) > 1:
+            raise AfxError(f"{who}: a multi-rank gradient hook (dist.GradSync) is installed; the all-reduce cannot be captured - "
+                           "use march_train_step_mse")
+        if not isinstance(optimizer, torch.optim.Adam) or not all(g.get("fused") and g.get("capturable") for g in optimizer.param_groups):
+            raise ValueError(f"{who}: needs torch.optim.Adam(..., fused=True, capturable=True) (the skip of an empty step is its found_inf)")
+        _check_model(model)
+        if model.precision != "f16s8":
+            raise NotImplementedError(f"{who}: precision 'f16s8' only")
+        if model._coef_trainable():
+            raise NotImplementedError(f"{who}: trainable fourier coefficients are not captured; freeze them or use march_train_step_mse")
+        if single_eval and model.use_pos_enc != "none":
+            raise NotImplementedError(f"{who}(single_eval=True): no input encoding (pos_enc 'none')")
+        from . import engine as _engine
+        from .nerf.occupancy import _aabb_on_host
+        dev = model.flat_params.device
+        lr = optimizer.param_groups[0]["lr"]
+        if not torch.is_tensor(lr) or lr.device != dev or lr.dtype != torch.float32 or lr.numel() != 1 \
+                or any(g["lr"] is not lr for g in optimizer.param_groups):
+            raise ValueError(f"{who}: the optimizer's lr must be ONE float32 tensor on {dev} shared by every param group (the captured "
+                             "bookkeeping writes the schedule into it)")
+        if lr_table is None or len(lr_table) < 1:
+            raise ValueError(f"{who}: lr_table (lr_decay_table) is required")
+        if not grids:
+            raise ValueError(f"{who}: at least one (grid, occ_thre)")
+        if int(round_len) < 1 or int(start_iter) < 0 or int(start_iter) + 1 >= 1 << 32:
+            raise ValueError(f"{who}: need round_len >= 1 and 0 <= start_iter < 2^32 - 1")
+        self._engine = _engine
+        self.single_eval = bool(single_eval)
+        self.model, self.optimizer = model, optimizer
+        self.grids = [(g, float(t)) for g, t in grids]
+        self.grid = self.grids[0][0]
+        self.round_len, self.warmup_steps, self.ema_decay, self.seed = int(round_len), int(warmup_steps), float(ema_decay), int(seed)
+        eng = model.engine
+        self.n_rays = int(n_rays)
+        self._table = tuple(t.to(device=dev, dtype=torch.float32).contiguous() for t in ray_table)
+        tab_o, tab_d, tab_p, tab_w = self._table
+        n_tab = tab_o.shape[0]
+        if tuple(tab_o.shape) != (n_tab, 3) or tuple(tab_d.shape) != (n_tab, 3) or tab_p.numel() != n_tab or tab_w.numel() != n_tab:
+            raise ValueError(f"{who}: ray_table = (origins [n,3], dirs [n,3], pixels [n], weights [n])")
+        if not 0 < self.n_rays <= n_tab:
+            raise ValueError(f"{who}: need 0 < n_rays <= {n_tab} table rays")
+        inv_n = 1.0 / self.n_rays
+        L = self.round_len
+        # the static buffers every graph is captured over
+        self.origins = torch.zeros(self.n_rays, 3, device=dev)
+        self.dirs = torch.zeros(self.n_rays, 3, device=dev)
+        self.dirs[:, 2] = 1.0
+        self.target = torch.zeros(self.n_rays, device=dev)
+        self.pixel = torch.ones(self.n_rays, device=dev)
+        self.counts = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.skip = torch.ones(1, device=dev)
+        self.flat_grad = torch.zeros(eng.param_count, device=dev)
+        for p, g in zip(model._hip_params(), model._split_grad(self.flat_grad)):
+            p.grad = g      # the gradients live in the static buffer the captured step accumulates into
+        self.iter = int(start_iter)      # the host's mirror of step_dev
+        self.step_dev = torch.full((), self.iter, dtype=torch.int64, device=dev)
+        self.lr, self.lr_table = lr, torch.as_tensor(lr_table, dtype=torch.float32).to(dev).contiguous()
+        if self.iter > 0:
+            lr.copy_(self.lr_table[min(self.iter, self.lr_table.numel()) - 1])
+        self.idx = torch.zeros(L, self.n_rays, dtype=torch.int64, device=dev)
+        self._sample_ws = torch.empty(max(_engine.sample_batches_workspace_bytes(n_tab, L), 1), dtype=torch.uint8, device=dev)
+        self.loss_hist = torch.full((L,), float("nan"), device=dev)
+        self.counts_hist = torch.zeros(L, 3, dtype=torch.int64, device=dev)
+        self.skip_hist = torch.ones(L, device=dev)
+        self.last_loss = torch.full((), float(last_loss), device=dev)
+        self.n_marched = torch.zeros((), dtype=torch.int64, device=dev)
+        self._aux_key = self._aux()
+        self._buf = model._prepared()      # the module's prepared buffer: the graphs re-tile into it
+        aabb = None if scene_aabb is None else _aabb_on_host(scene_aabb)
+        step = (float(far) - float(near)) / int(depth_samples_per_ray)
+        self._march = dict(scene_aabb=aabb, near_plane=float(near), far_plane=float(far), step=step, early_stop_eps=float(early_stop_eps),
+                           alpha_thre=float(alpha_thre), grid_bits=self.grid.bits, grid_aabb=self.grid._aabb_host, grid_res=self.grid._res_host)
+        self._inv_n = inv_n
+        # eagerly, before any capture (as GridTrainGraph and GridUpdateGraph do): the refresh workspaces, the chain kernels' attributes, the
+        # step's workspace (one call on the placeholder batch; every replay re-zeroes the gradient), and the optimizer's state, created by
+        # a step it skips (found_inf = 1)
+        for g, _ in self.grids:
+            g.reserve_refresh_workspace()
+        eng.infer(self._buf, torch.zeros(1, 3, device=dev), model.precision, apply_sigmoid=True)
+        self._train_step()
+        optimizer.found_inf = torch.ones((), device=dev)
+        optimizer.step()
+        self._found_inf = self.skip.view(())      # (fused Adam takes a 0-dim flag; a view of the step's skip flag)
+        optimizer.found_inf = self._found_inf
+        self._graphs = {}      # "warmup" | "round" | "tail" -> CUDAGraph
+        self._mark_stale()
+
+    def _aux(self):
+        m = self.model
+        return float(m.barf_alpha) if m.use_pos_enc == "barf" else None
+
+    def _mark_stale(self):
+        cache = self.model.engine._prepared
+        for prec, (buf, _) in list(cache.items()):
+            cache[prec] = (buf, None)
+        cache[self.model.precision] = (self._buf, None)
+
+    def _train_step(self):
+        """Re-tiling, zeroed gradient, the step on the static batch, the loss (GridTrainGraph's body)."""
+        model, eng = self.model, self.model.engine
+        eng.prepare(model.flat_params, model._enc_aux(), model.precision)      # into the cached buffer (key None: always re-tiles)
+        self.flat_grad.zero_()
+        fn = eng.march_train_step_mse_single_eval if self.single_eval else eng.march_train_step_mse_capturable
+        fn(self._buf, self.origins, self.dirs, self.target, self._inv_n, self.flat_grad, model.precision, pixel=self.pixel, counts=self.counts,
+           skip=self.skip, **self._march)
+        return torch.nn.functional.mse_loss(self.pixel, self.target)
+
+    def _refresh(self, all_cells):
+        """GridUpdateGraph's body: re-tiling, then every grid's refresh at the counter's step."""
+        model, eng = self.model, self.model.engine
+        eng.prepare(model.flat_params, model._enc_aux(), model.precision)
+        for g, thre in self.grids:
+            g._refresh(eng, self._buf, model.precision, self.step_dev, thre, self.ema_decay, all_cells)
+
+    def _iterations(self, n):
+        """The draw of n batches at the counter's step, then n iterations, each followed by the device bookkeeping."""
+        E = self._engine
+        tab_o, tab_d, tab_p, tab_w = self._table
+        E.sample_batches_dev(tab_w, self.seed, self.step_dev, n, self.n_rays, out_idx=self.idx[:n], workspace=self._sample_ws)
+        for j in range(n):
+            E.gather_rays(tab_o, tab_d, tab_p, self.idx[j], self.origins, self.dirs, self.target)
+            loss = self._train_step()
+            self.optimizer.step()
+            E.train_round_advance(self.step_dev, self.lr_table, self.lr, self.skip, loss, self.counts, self.loss_hist, self.counts_hist,
+                                  self.skip_hist, self.last_loss, self.n_marched)
+
+    def _graph(self, kind):
+        graph = self._graphs.get(kind)
+        if graph is not None:
+            return graph
+        dev = self.model.flat_params.device
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):      # one stream, no forked branches: a linear graph
+            with torch.cuda.graph(graph, stream=side):
+                if kind == "tail":
+                    self._iterations(1)
+                else:
+                    self._refresh(kind == "warmup")
+                    self._iterations(self.round_len)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self._graphs[kind] = graph
+        return graph
+
+    def run(self, n: int):
+        """Advance n iterations from the current counter."""
+        if self._aux() != self._aux_key:
+            raise AfxError("GridTrainRoundGraph: the BARF schedule moved since the capture (the encoding weights are captured by address); "
+                           "build a new GridTrainRoundGraph")
+        if self.optimizer.found_inf is not self._found_inf:
+            raise AfxError("GridTrainRoundGraph: optimizer.found_inf was replaced; the captured step reads the skip flag by address")
+        if self.iter + int(n) >= 1 << 32:
+            raise ValueError("GridTrainRoundGraph: the step counter stays below 2^32")
+        for op in grid_round_schedule(self.iter, n, self.round_len, self.warmup_steps):
+            if op[0] == "round":
+                self._graph("warmup" if op[2] else "round").replay()
+                self.iter += self.round_len
+            elif op[0] == "refresh":
+                with torch.no_grad():
+                    self._refresh(op[2])
+            else:
+                self._graph("tail").replay()
+                self.iter += 1
+        if n > 0:
+            self._mark_stale()
+
+    def history(self):
+        """The device tensors the replays write, without synchronising."""
+        return dict(loss=self.loss_hist, counts=self.counts_hist, skip=self.skip_hist, last_loss=self.last_loss, n_marched=self.n_marched,
+                    step=self.step_dev)
