@@ -270,6 +270,14 @@ class CPPN(nn.Module):
         if self._engine is not None:
             self._engine._prepared.clear()
 
+    def mark_prepared_stale(self):
+        """Like invalidate(), but the cached buffers stay: the next _prepared() re-tiles into the same memory (captured graphs re-tile
+        into these buffers by address; nerf/checkpoint.py calls this after copying restored parameters in)."""
+        if self._engine is not None:
+            cache = self._engine._prepared
+            for prec, (buf, _) in list(cache.items()):
+                cache[prec] = (buf, None)
+
     def _check_views(self):
         """Every Linear's weight / bias must still alias the flat buffer the kernels read: rebinding `p.data = ...`
         (e.g. torch.nn.utils.vector_to_parameters) detaches it.  Cheap pointer comparison; re-flatten when broken."""

@@ -96,6 +96,23 @@ class OccupancyGrid(torch.nn.Module):
         if self._binary_u8.is_cuda:
             _engine.grid_pack(self._aabb_host, self._res_host, self._binary_u8, self._bits)
 
+    # ---- training state (nerf/checkpoint.py).  nn.Module's own state_dict() stays as it is (it also carries the scratch buffers and no seed) ----
+    def training_state(self):
+        """What a resumed run needs of the grid: the EMA `occs`, the mask, the seed of its draws and its shape.  The grid keeps no step or
+        warm-up counter of its own: every_n_step / refresh take the training step from the caller, who saves it."""
+        return dict(occs=self.occs.detach().cpu(), binary=self._binary_u8.detach().cpu(), seed=self.seed, resolution=list(self._res_host),
+                    aabb=list(self._aabb_host))
+
+    @torch.no_grad()
+    def load_training_state(self, state):
+        """Copy a training_state() into the live buffers (graphs captured over them keep their addresses) and repack the march's bitfield
+        from the restored mask (set_binary: afx_grid_pack)."""
+        if list(state["resolution"]) != self._res_host or list(state["aabb"]) != self._aabb_host or int(state["seed"]) != self.seed:
+            raise ValueError(f"OccupancyGrid: the saved grid (resolution {state['resolution']}, seed {state['seed']}, box {state['aabb']}) "
+                             f"is not this one (resolution {self._res_host}, seed {self.seed}, box {self._aabb_host})")
+        self.occs.copy_(state["occs"])
+        self.set_binary(state["binary"])
+
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
         if getattr(self, "_bits_stale", False) and self._binary_u8.is_cuda:

@@ -45,6 +45,7 @@ from ..render import (render_rays, train_step_mse, march_train_step_mse, march_r
 from .nerf_helpers import sample_pixel_rays, get_predictions
 from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
+from . import checkpoint as _ckpt
 
 
 def build_parser():
@@ -93,6 +94,18 @@ def build_parser():
                         'training step\'s forward half over the march\'s candidates doubles as the alpha pass (afx_march_train_step_mse_single_eval)')
     p.add_argument('--adam', default='fused', choices=['fused', 'foreach'], help="PyTorch Adam implementation (same update rule)")
     p.add_argument('--host_sampler', action='store_true', help="draw each batch with pandas on the host (the reference's sample_pixel_rays)")
+    p.add_argument('--barf_start', type=int, default=8000, help='--pos_enc barf: first iteration of the coarse-to-fine schedule')
+    p.add_argument('--barf_stop', type=int, default=250000, help='--pos_enc barf: iteration at which every frequency band is open')
+    p.add_argument('--checkpoint_every', type=int, default=0,
+                   help='write the full training state (LOG_DIR/trainstate.pt: parameters, Adam state, both occupancy grids, counters, history, '
+                        'RNG states; nerf/checkpoint.py) every N iterations, atomically; 0 (default) never writes one.  With --graph-rounds a '
+                        'state can only be taken between rounds: N is rounded up to a multiple of the 16-iteration round.  A save waits for the '
+                        'GPU, reads the state back and writes 27 MB with the two 128^3 grids (55-75 ms for the host half alone, '
+                        'profiles/r10_resume.md: a hundred iterations of the grid loop) - keep N in the thousands.  A state whose loss or parameters are not finite is not written; when the run stops on a '
+                        'non-finite loss the last state written is kept as LOG_DIR/trainstate-before-nonfinite.pt')
+    p.add_argument('--resume', default=None, metavar='PATH',
+                   help='continue from a training-state file (or the trainstate.pt in a directory) at its iteration, bit for bit; every '
+                        'argument that changes the arithmetic must equal the saved run\'s (a mismatch names the fields)')
     p.add_argument('--log_dir', default='runs/afx')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out_bias_init', type=float, default=-5.0,
@@ -113,6 +126,16 @@ def check_args(args):
         raise ValueError("--graph-rounds: needs --graph --graph-grid-update")
     if args.graph_rounds and args.host_sampler:
         raise ValueError("--graph-rounds: the batches are drawn inside the graph; --host_sampler draws them on the host")
+
+
+    if args.checkpoint_every < 0:
+        raise ValueError("--checkpoint_every: needs N >= 0")
+
+
+def checkpoint_interval(checkpoint_every: int, graph_rounds: bool, round_len: int = 16) -> int:
+    """Iterations between two state files: --checkpoint_every, rounded up to whole rounds with --graph-rounds (0: none)."""
+    n = int(checkpoint_every)
+    return -(-n // round_len) * round_len if graph_rounds else n
 
 
 def main(argv=None):
@@ -169,7 +192,7 @@ def main(argv=None):
     coarse_lr, decay_rate, decay_steps = 1e-4, 0.1, 500 * 1000
     img_sample_size = args.sample_size ** 2
     start_pos_enc_basis, pos_enc_basis, fourier_sigma = 0, 5, 5
-    barf_start, barf_stop = 8000, 250000
+    barf_start, barf_stop = args.barf_start, args.barf_stop
     barf_step_size = pos_enc_basis / (barf_stop - barf_start)
     params = {'num_early_layers': num_layers, 'num_late_layers': 0, 'num_filters': num_hidden_units,
               'num_input_channels': 3, 'num_output_channels': 1, 'num_input_channels_views': 0, 'use_bias': True,
@@ -231,9 +254,42 @@ def main(argv=None):
     update_graph = None
     if args.graph_grid_update and round_graph is None:      # both grids' refresh (:285-286) in graphs captured on first use; replayed before the training step
         update_graph = GridUpdateGraph(coarse_model, [(acc_grid, alpha_thre), (vessel_acc_grid, vessel_alpha_thre)])
+    # training state (--checkpoint_every / --resume, nerf/checkpoint.py).  Everything above is built as in a fresh run, graphs captured
+    # included; a restored state is then copied INTO the live tensors
+    start_iter, state_file, last_state = 0, os.path.join(args.log_dir, _ckpt.STATE_FILE), None
+    ckpt_every = checkpoint_interval(args.checkpoint_every, args.graph_rounds)
+    if ckpt_every or args.resume:
+        fingerprint = _ckpt.config_fingerprint(args, params, (tab_o, tab_d, tab_pix, tab_w))
+        live = dict(model=coarse_model, optimizer=coarse_optimizer, grids=[g for g in (acc_grid, vessel_acc_grid) if g is not None],
+                    graphs={k: g for k, g in (('train', train_graph), ('update', update_graph), ('round', round_graph)) if g is not None})
+        if ckpt_every != args.checkpoint_every:
+            print(f'--checkpoint_every {args.checkpoint_every}: rounded up to {ckpt_every} (whole rounds of --graph-rounds)')
+    if args.resume:
+        state = _ckpt.load_training_state(args.resume, fingerprint=fingerprint, **live)
+        start_iter, history, kept = state['n_iter'], list(state['history']), state['counters']
+        highest_psnr, highest_iter, new_lr_coarse = kept['highest_psnr'], kept['highest_iter'], kept['lr']
+        if round_graph is None:      # (--graph-rounds keeps both on the device: restored with the round graph)
+            loss_coarse = kept['loss'].to(device)
+            n_marched = kept['n_marched'] if train_graph is None else n_marched.fill_(kept['n_marched'])
+        last_state = _ckpt.state_path(args.resume)
+        print(f'resumed from {last_state} at iteration {start_iter}')
+
+    def write_state(next_iter):
+        """trainstate.pt after iteration next_iter - 1, unless the loss or a parameter is not finite (the file then stays the last good one)."""
+        loss_now = (round_graph.last_loss if round_graph is not None else loss_coarse).detach()
+        if not (bool(torch.isfinite(loss_now)) and bool(torch.isfinite(coarse_model.flat_params).all())):
+            print(f'iteration {next_iter - 1}: non-finite loss or parameters, no state written')
+            return last_state
+        return _ckpt.save_training_state(state_file, fingerprint=fingerprint, n_iter=next_iter, history=history,
+                                         counters=dict(highest_psnr=highest_psnr, highest_iter=highest_iter, lr=new_lr_coarse,
+                                                       loss=loss_now.float(), n_marched=int(n_marched)), **live)
+
     t_last = time.time()
     # --graph-rounds: the loop visits the display points (and the last iteration) only; run() replays every iteration up to each of them
-    stops = range(n_iters + 1) if round_graph is None else sorted(set(range(0, n_iters + 1, display_every)) | {n_iters})
+    # (and up to the last iteration of every round after which a state is written)
+    stops = range(start_iter, n_iters + 1) if round_graph is None else \
+        [s for s in sorted(set(range(0, n_iters + 1, display_every)) | {n_iters} |
+                           (set(range(ckpt_every - 1, n_iters + 1, ckpt_every)) if ckpt_every else set())) if s >= start_iter]
     for n_iter in stops:
         coarse_model.train()
         if round_graph is not None:
@@ -346,6 +402,10 @@ def main(argv=None):
             log.flush()
             print(rec, flush=True)
             if not np.isfinite(rec['train_loss']):
+                if last_state is not None:      # the last finite state, under its own name: resume it by hand, e.g. at another precision
+                    import shutil
+                    shutil.copyfile(last_state, os.path.join(args.log_dir, _ckpt.NONFINITE_FILE))
+                    print('kept', os.path.join(args.log_dir, _ckpt.NONFINITE_FILE))
                 raise FloatingPointError(
                     f"non-finite training loss at iteration {n_iter} (precision {args.precision}): the f16 precisions hold hidden "
                     "activations up to 65504 (include/afx.h); re-run with --precision bf16 (fp32 exponent range) or bf16x3")
@@ -361,6 +421,8 @@ def main(argv=None):
             if n_iter - highest_iter > early_stop_iters:
                 print('early stopping at', n_iter)
                 break
+        if ckpt_every and (n_iter + 1) % ckpt_every == 0:
+            last_state = write_state(n_iter + 1)
     log.close()
     return dict(history=history, best_psnr=highest_psnr, best_iter=highest_iter, model=coarse_model,
                 optimizer=coarse_optimizer, test_image=test_img, log_dir=args.log_dir, acc_grid=acc_grid,

@@ -433,6 +433,18 @@ def density_grid(model, outside: float, n: int, precision: Optional[str] = None)
     return sig.reshape(n + 1, n + 1, n + 1)
 
 
+def _copy_state(who, live: dict, saved: dict):
+    """load_state_dict of the graph classes: copy every saved tensor INTO the live one (the graphs replay against these addresses)."""
+    if set(saved) != set(live):
+        raise ValueError(f"{who}.load_state_dict: keys {sorted(saved)}, expected {sorted(live)}")
+    with torch.no_grad():
+        for k, t in live.items():
+            v = torch.as_tensor(saved[k])
+            if tuple(v.shape) != tuple(t.shape):
+                raise ValueError(f"{who}.load_state_dict: {k} has shape {tuple(v.shape)}, expected {tuple(t.shape)}")
+            t.copy_(v)
+
+
 class GridTrainGraph:
     """The reference's grid training iteration (nerf/run_nerf_acc.py:284-306: march, alpha pass, render_visibility, graded pass, backward,
     optimizer step) captured ONCE into a HIP graph and replayed: weight re-tiling into the module's prepared buffer,
@@ -529,6 +541,17 @@ class GridTrainGraph:
             cache[prec] = (buf, None)
         cache[self.model.precision] = (self._buf, None)
 
+    def _state(self):
+        return dict(counts=self.counts, pixel=self.pixel, skip=self.skip)
+
+    def state_dict(self):
+        """The step's device-resident outputs that outlive a replay: counts, and pixel / skip (an empty march keeps the previous replay's)."""
+        return {k: t.detach().clone() for k, t in self._state().items()}
+
+    def load_state_dict(self, state):
+        """Copied into the static buffers, after the capture: the graph keeps replaying against the same addresses."""
+        _copy_state("GridTrainGraph", self._state(), state)
+
     def step(self, origins, dirs, target):
         if self._aux() != self._aux_key:
             raise AfxError("GridTrainGraph: the BARF schedule moved since the capture (the encoding weights are captured by address); "
@@ -592,6 +615,13 @@ class GridUpdateGraph:
         cache = self.model.engine._prepared
         for prec, (buf, _) in list(cache.items()):
             cache[prec] = (buf, None)
+
+    def state_dict(self):
+        """The device step counter (step() fills it before every replay; kept so that a restored object equals the saved one)."""
+        return dict(step=self.step_dev.detach().clone())
+
+    def load_state_dict(self, state):
+        _copy_state("GridUpdateGraph", dict(step=self.step_dev), state)
 
     def step(self, n_iter: int):
         if n_iter % self.n:
@@ -829,6 +859,21 @@ class GridTrainRoundGraph:
                 self.iter += 1
         if n > 0:
             self._mark_stale()
+
+    def _state(self):
+        return dict(step=self.step_dev, lr=self.lr, loss_hist=self.loss_hist, counts_hist=self.counts_hist, skip_hist=self.skip_hist,
+                    last_loss=self.last_loss, n_marched=self.n_marched, counts=self.counts, pixel=self.pixel, skip=self.skip)
+
+    def state_dict(self):
+        """The device-resident state of the rounds: the step counter (the learning-rate table is indexed by it), the learning rate, the
+        loss / counts / skip history, last_loss, n_marched and the step's own outputs.  Reads the device (call it between runs)."""
+        return {k: t.detach().clone() for k, t in self._state().items()}
+
+    def load_state_dict(self, state):
+        """Copied into the static buffers - before or after the graphs are captured, they replay against the same addresses - and the
+        host's mirror of the counter set from the restored one."""
+        _copy_state("GridTrainRoundGraph", self._state(), state)
+        self.iter = int(torch.as_tensor(state["step"]))
 
     def history(self):
         """The device tensors the replays write, without synchronising."""
