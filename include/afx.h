@@ -268,6 +268,25 @@ int afx_composite_packed_backward(const float* pred, const int32_t* ray_indices,
                                   const float* t_ends, int64_t n, int64_t n_rays, const float* rgb_map,
                                   const float* d_rgb_map, float* d_pred, void* stream);
 
+/* get_ray_entropy(sigmas, rgb_map, threshold) with its gradient — nerf/nerf_helpers.py:125-135 and nerf/nerf_helpers_acc.py:33-43, for packed,
+ * ray-sorted samples (ray_indices ascending, every value in [0, n_rays)).  sigma_i = sigmoid(pred_i), eps = 1e-10, per ray:
+ *   D = sum sigma_i + eps, p_i = sigma_i / D, entropy[r] = -sum p_i log(p_i + eps) * [(1 - rgb_map[r]) > threshold]
+ * (the mask carries no gradient; rgb_map is an input, what afx_composite_packed wrote).  A ray without samples has entropy 0.
+ * ray_sums [n_rays,2] receives {D, sum_j p_j u_j}, u_i = log(p_i + eps) + p_i / (p_i + eps): what the backward needs per ray.
+ * One wavefront per ray, sums in a fixed order, no atomics: bit-reproducible. */
+int afx_ray_entropy_packed(const float* pred, const int32_t* ray_indices, int64_t n, const float* rgb_map, int64_t n_rays,
+                           float threshold, float* entropy, float* ray_sums /* [n_rays,2] */, void* stream);
+/* d_pred[i] (+)= d_entropy[r] * mask_r * (-(u_i - ray_sums[r][1]) / ray_sums[r][0]) * sigma_i (1 - sigma_i), r = ray_indices[i];
+ * accumulate != 0 adds to d_pred (e.g. onto afx_composite_packed_backward's output), 0 overwrites it. */
+int afx_ray_entropy_packed_backward(const float* pred, const int32_t* ray_indices, int64_t n, const float* rgb_map, float threshold,
+                                    const float* ray_sums, const float* d_entropy, int accumulate, float* d_pred, void* stream);
+/* The same for the dense layout raw[n_rays, n_samples] (nerf/nerf_helpers.py:119,125-135): the value afx_composite_dense writes to `entropy`,
+ * summed in another order, and its gradient d_raw[n_rays, n_samples]. */
+int afx_ray_entropy_dense(const float* raw, int64_t n_rays, int32_t n_samples, const float* rgb_map, float threshold,
+                          float* entropy, float* ray_sums /* [n_rays,2] */, void* stream);
+int afx_ray_entropy_dense_backward(const float* raw, int64_t n_rays, int32_t n_samples, const float* rgb_map, float threshold,
+                                   const float* ray_sums, const float* d_entropy, int accumulate, float* d_raw, void* stream);
+
 /* sample_pdf(bins, weights, N_samples) — nerf/nerf_helpers.py:197-222, with the uniform
  * draw u[R,n_fine] supplied by the caller; and the depth part of fine_sampling (:179-186):
  * bins = mid-points of z_coarse, weights = w_coarse[:,1:-1], output = sort(cat(z_coarse, samples)).

@@ -1235,6 +1235,52 @@ extern "C" int afx_composite_packed_backward(const float* pred, const int32_t* r
   return AFX_OK;
 }
 
+// ---- per-ray entropy of the density profile (get_ray_entropy, nerf/nerf_helpers.py:125-135, nerf/nerf_helpers_acc.py:33-43) and its gradient
+extern "C" int afx_ray_entropy_packed(const float* pred, const int32_t* ri, int64_t n, const float* rgb_map, int64_t n_rays, float threshold,
+                                      float* entropy, float* ray_sums, void* stream) {
+  if (n < 0 || n_rays < 0 || n_rays > INT32_MAX) return fail(AFX_E_INVALID, "afx_ray_entropy_packed: n and n_rays must be in 0..2^31-1");
+  if (n_rays == 0) return AFX_OK;
+  if (!rgb_map || !entropy || !ray_sums || (n > 0 && (!pred || !ri))) return fail(AFX_E_INVALID, "afx_ray_entropy_packed: null argument");
+  hipLaunchKernelGGL(k_ray_entropy_packed, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pred, ri, n, rgb_map, n_rays,
+                     threshold, entropy, ray_sums);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" int afx_ray_entropy_packed_backward(const float* pred, const int32_t* ri, int64_t n, const float* rgb_map, float threshold,
+                                               const float* ray_sums, const float* d_entropy, int accumulate, float* d_pred, void* stream) {
+  if (n < 0) return fail(AFX_E_INVALID, "afx_ray_entropy_packed_backward: n < 0");
+  if (n == 0) return AFX_OK;
+  if (!pred || !ri || !rgb_map || !ray_sums || !d_entropy || !d_pred) return fail(AFX_E_INVALID, "afx_ray_entropy_packed_backward: null argument");
+  hipLaunchKernelGGL(k_ray_entropy_packed_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred, ri, n, rgb_map,
+                     threshold, ray_sums, d_entropy, accumulate, d_pred);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" int afx_ray_entropy_dense(const float* raw, int64_t n_rays, int32_t n_samples, const float* rgb_map, float threshold, float* entropy,
+                                     float* ray_sums, void* stream) {
+  if (n_rays < 0 || n_samples < 1) return fail(AFX_E_INVALID, "afx_ray_entropy_dense: needs n_rays >= 0 and n_samples >= 1");
+  if (n_rays == 0) return AFX_OK;
+  if (!raw || !rgb_map || !entropy || !ray_sums) return fail(AFX_E_INVALID, "afx_ray_entropy_dense: null argument");
+  hipLaunchKernelGGL(k_ray_entropy_dense, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw, n_rays, n_samples, rgb_map,
+                     threshold, entropy, ray_sums);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
+extern "C" int afx_ray_entropy_dense_backward(const float* raw, int64_t n_rays, int32_t n_samples, const float* rgb_map, float threshold,
+                                              const float* ray_sums, const float* d_entropy, int accumulate, float* d_raw, void* stream) {
+  if (n_rays < 0 || n_samples < 1) return fail(AFX_E_INVALID, "afx_ray_entropy_dense_backward: needs n_rays >= 0 and n_samples >= 1");
+  if (n_rays == 0) return AFX_OK;
+  if (!raw || !rgb_map || !ray_sums || !d_entropy || !d_raw) return fail(AFX_E_INVALID, "afx_ray_entropy_dense_backward: null argument");
+  const int64_t n = n_rays * n_samples;
+  hipLaunchKernelGGL(k_ray_entropy_dense_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, raw, n_rays, n_samples,
+                     rgb_map, threshold, ray_sums, d_entropy, accumulate, d_raw);
+  HIPCHK(hipGetLastError());
+  return AFX_OK;
+}
+
 static int fine_depths_impl(const char* who, const float* z_coarse, int z_per_ray, const float* w_coarse, const float* tau, const float* u,
                             int64_t n_rays, int32_t n_coarse, int32_t n_fine, float* z_out, void* stream) {
   if (!z_coarse || (!w_coarse && !tau) || !u || !z_out) return fail(AFX_E_INVALID, "%s: null argument", who);

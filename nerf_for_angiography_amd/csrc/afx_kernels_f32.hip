@@ -976,6 +976,84 @@ __global__ void k_composite_packed_bwd(const float* pred, const int32_t* ri, con
   d_pred[i] = -(rgb_map[r] * d_rgb[r]) * __fsub_rn(te[i], ts[i]) * (sg * (1.f - sg));
 }
 
+// Per-ray entropy of the density profile with its gradient — get_ray_entropy, nerf/nerf_helpers.py:125-135 and
+// nerf/nerf_helpers_acc.py:33-43 (the term render_volume_density forms at nerf_helpers.py:119; the packed training loop leaves it out at
+// nerf_helpers_acc.py:60-61).  With sigma_i = sigmoid(x_i), eps = 1e-10 over the samples [lo, hi) of one ray:
+//   D = sum sigma_i + eps,  p_i = sigma_i / D,  E = -sum p_i log(p_i + eps),  entropy = E * [(1 - rgb_map) > threshold]
+//   u_i = log(p_i + eps) + p_i / (p_i + eps),  dE/dsigma_k = -(u_k - sum_j p_j u_j) / D       (the mask carries no gradient)
+// Forward: ONE WAVEFRONT PER RAY (4 rays per 256-thread block).  Lane l takes samples lo + l, lo + l + 64, ... in order and the 64 partial
+// sums meet in an xor butterfly (32, 16, .., 1): a fixed order of additions for a given segment length, no atomics, so two runs agree bit
+// for bit and every lane holds the same total.  Two passes over the segment: D first, then E and sum p u.  D and sum p u go to
+// ray_sums[r] = {D, sum_j p_j u_j}, which makes the backward one pass with one thread per sample.  An empty segment gives entropy 0.
+__device__ __forceinline__ float wave_sum64(float v) {
+  for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
+  return v;
+}
+__device__ __forceinline__ void ray_entropy_segment(const float* x, int64_t lo, int64_t hi, int lane, float T, float threshold,
+                                                    float* entropy_r, float* sums_r) {
+  float s = 0.f;
+  for (int64_t i = lo + lane; i < hi; i += 64) s = __fadd_rn(s, sigmoidf_(x[i]));
+  const float D = __fadd_rn(wave_sum64(s), 1e-10f);
+  float e = 0.f, su = 0.f;
+  for (int64_t i = lo + lane; i < hi; i += 64) {
+    const float p = sigmoidf_(x[i]) / D;
+    const float pe = __fadd_rn(p, 1e-10f);
+    const float lg = logf(pe);
+    e = __fadd_rn(e, __fmul_rn(p, lg));
+    su = __fadd_rn(su, __fmul_rn(p, __fadd_rn(lg, p / pe)));
+  }
+  e = wave_sum64(e);
+  su = wave_sum64(su);
+  if (lane == 0) {
+    *entropy_r = (1.f - T) > threshold ? 0.f - e : 0.f;
+    sums_r[0] = D;
+    sums_r[1] = su;
+  }
+}
+// d entropy[r] / d x_i times the incoming d_entropy[r]; 0 for a masked ray
+__device__ __forceinline__ float ray_entropy_grad(float x, float T, float threshold, const float* sums_r, float g) {
+  if (!((1.f - T) > threshold)) return 0.f;
+  const float sg = sigmoidf_(x);
+  const float D = sums_r[0];
+  const float p = sg / D;
+  const float pe = __fadd_rn(p, 1e-10f);
+  const float u = __fadd_rn(logf(pe), p / pe);
+  const float dE = -__fsub_rn(u, sums_r[1]) / D;
+  return __fmul_rn(__fmul_rn(g, dE), __fmul_rn(sg, __fsub_rn(1.f, sg)));
+}
+__global__ void __launch_bounds__(256) k_ray_entropy_packed(const float* pred, const int32_t* ri, int64_t n, const float* rgb_map, int64_t n_rays,
+                                                            float threshold, float* entropy, float* ray_sums) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (uniform per wavefront)
+  if (r >= n_rays) return;
+  const int64_t lo = lower_bound_i32(ri, n, (int32_t)r);
+  const int64_t hi = lower_bound_i32(ri, n, (int32_t)(r + 1));      // (n_rays <= INT32_MAX: checked by the entry point)
+  ray_entropy_segment(pred, lo, hi, threadIdx.x & 63, rgb_map[r], threshold, entropy + r, ray_sums + 2 * r);
+}
+__global__ void k_ray_entropy_packed_bwd(const float* pred, const int32_t* ri, int64_t n, const float* rgb_map, float threshold,
+                                         const float* ray_sums, const float* d_entropy, int accumulate, float* d_pred) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = ri[i];
+  const float v = ray_entropy_grad(pred[i], rgb_map[r], threshold, ray_sums + 2 * r, d_entropy[r]);
+  d_pred[i] = accumulate ? __fadd_rn(d_pred[i], v) : v;
+}
+// the same for raw[R,S] (every ray owns S consecutive samples).  k_composite_dense's `entropy` output is this value summed by one thread
+// in sample order; here 64 lanes sum strided partial sums, so the two differ by the summation order only.
+__global__ void __launch_bounds__(256) k_ray_entropy_dense(const float* raw, int64_t n_rays, int S, const float* rgb_map, float threshold,
+                                                           float* entropy, float* ray_sums) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_rays) return;
+  ray_entropy_segment(raw, r * S, (r + 1) * S, threadIdx.x & 63, rgb_map[r], threshold, entropy + r, ray_sums + 2 * r);
+}
+__global__ void k_ray_entropy_dense_bwd(const float* raw, int64_t n_rays, int S, const float* rgb_map, float threshold, const float* ray_sums,
+                                        const float* d_entropy, int accumulate, float* d_raw) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rays * S) return;
+  const int64_t r = i / S;
+  const float v = ray_entropy_grad(raw[i], rgb_map[r], threshold, ray_sums + 2 * r, d_entropy[r]);
+  d_raw[i] = accumulate ? __fadd_rn(d_raw[i], v) : v;
+}
+
 // Ground-truth X-ray projector over a voxel volume — ray_tracing, phantomdata/helpers.py:192-224.
 // mu(p) by trilinear interpolation on a regular grid with a constant fill value outside (scipy
 // RegularGridInterpolator(method='linear', bounds_error=False, fill_value)), float64 coordinates as upstream;

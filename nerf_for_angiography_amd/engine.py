@@ -617,6 +617,91 @@ def composite_packed_backward(pred, ray_indices, t_starts, t_ends, n_rays, rgb, 
     return d_pred
 
 
+# ---- per-ray entropy of the density profile (get_ray_entropy) with its gradient ---------------
+def _entropy_ray_indices(ray_indices, n, dev):
+    if not isinstance(ray_indices, torch.Tensor) or ray_indices.device != dev or ray_indices.dtype != torch.int32:
+        raise ValueError(f"ray_indices: expected an int32 tensor on {dev}")
+    if ray_indices.numel() != n:
+        raise ValueError(f"ray_indices: {ray_indices.numel()} entries for {n} samples")
+    return ray_indices if ray_indices.is_contiguous() else ray_indices.contiguous()
+
+
+def ray_entropy_packed(pred, ray_indices, rgb_map, n_rays, threshold=0.4):
+    """afx_ray_entropy_packed: pred[n] (before the sigmoid), ray_indices[n] int32 ascending, rgb_map[n_rays] -> (entropy[n_rays],
+    ray_sums[n_rays,2] for ray_entropy_packed_backward)."""
+    lib = _lib.load()
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise AfxError("ray_entropy_packed: tensors must live on the GPU; there is no CPU fallback")
+    dev, n_rays = pred.device, int(n_rays)
+    pred, rgb_map = _f32(pred.reshape(-1), "pred", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
+    ri = _entropy_ray_indices(ray_indices, pred.numel(), dev)
+    if rgb_map.numel() != n_rays:
+        raise ValueError(f"rgb_map: {rgb_map.numel()} entries for {n_rays} rays")
+    ent = torch.empty(n_rays, device=dev)
+    sums = torch.empty(n_rays, 2, device=dev)
+    _lib.check(lib.afx_ray_entropy_packed(_ptr(pred), _ptr(ri), pred.numel(), _ptr(rgb_map), n_rays, float(threshold), _ptr(ent), _ptr(sums),
+                                          Engine._stream(dev)), "afx_ray_entropy_packed")
+    return ent, sums
+
+
+def ray_entropy_packed_backward(pred, ray_indices, rgb_map, ray_sums, d_entropy, threshold=0.4, out=None):
+    """afx_ray_entropy_packed_backward -> d_pred[n].  `out`: a gradient buffer the result is ADDED to (the accumulate flag), e.g. the one
+    composite_packed_backward returned; without it a new tensor is written."""
+    lib = _lib.load()
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise AfxError("ray_entropy_packed_backward: tensors must live on the GPU; there is no CPU fallback")
+    dev = pred.device
+    pred, rgb_map = _f32(pred.reshape(-1), "pred", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
+    ri = _entropy_ray_indices(ray_indices, pred.numel(), dev)
+    ray_sums, d_entropy = _f32(ray_sums, "ray_sums", dev), _f32(d_entropy.reshape(-1), "d_entropy", dev)
+    if ray_sums.shape != (rgb_map.numel(), 2) or d_entropy.numel() != rgb_map.numel():
+        raise ValueError("ray_sums / d_entropy: expected [n_rays,2] and [n_rays]")
+    if out is not None and (_f32(out, "out", dev) is not out or out.numel() != pred.numel()):
+        raise ValueError("out: expected a contiguous tensor with one entry per sample")
+    d_pred = torch.empty_like(pred) if out is None else out
+    _lib.check(lib.afx_ray_entropy_packed_backward(_ptr(pred), _ptr(ri), pred.numel(), _ptr(rgb_map), float(threshold), _ptr(ray_sums),
+                                                   _ptr(d_entropy), int(out is not None), _ptr(d_pred), Engine._stream(dev)),
+               "afx_ray_entropy_packed_backward")
+    return d_pred
+
+
+def ray_entropy_dense(raw, rgb_map, threshold=0.4):
+    """afx_ray_entropy_dense: raw[R,S] (before the sigmoid), rgb_map[R] -> (entropy[R], ray_sums[R,2])."""
+    lib = _lib.load()
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
+        raise AfxError("ray_entropy_dense: tensors must live on the GPU; there is no CPU fallback")
+    dev = raw.device
+    raw, rgb_map = _f32(raw, "raw", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
+    if raw.dim() != 2 or raw.shape[1] < 1 or rgb_map.numel() != raw.shape[0]:
+        raise ValueError("ray_entropy_dense: expected raw[R,S] with S >= 1 and rgb_map[R]")
+    r, s = raw.shape
+    ent = torch.empty(r, device=dev)
+    sums = torch.empty(r, 2, device=dev)
+    _lib.check(lib.afx_ray_entropy_dense(_ptr(raw), r, s, _ptr(rgb_map), float(threshold), _ptr(ent), _ptr(sums), Engine._stream(dev)),
+               "afx_ray_entropy_dense")
+    return ent, sums
+
+
+def ray_entropy_dense_backward(raw, rgb_map, ray_sums, d_entropy, threshold=0.4, out=None):
+    """afx_ray_entropy_dense_backward -> d_raw[R,S]; `out` as in ray_entropy_packed_backward."""
+    lib = _lib.load()
+    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
+        raise AfxError("ray_entropy_dense_backward: tensors must live on the GPU; there is no CPU fallback")
+    dev = raw.device
+    raw, rgb_map = _f32(raw, "raw", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
+    ray_sums, d_entropy = _f32(ray_sums, "ray_sums", dev), _f32(d_entropy.reshape(-1), "d_entropy", dev)
+    if raw.dim() != 2 or raw.shape[1] < 1 or rgb_map.numel() != raw.shape[0] or ray_sums.shape != (raw.shape[0], 2) \
+            or d_entropy.numel() != raw.shape[0]:
+        raise ValueError("ray_entropy_dense_backward: expected raw[R,S], rgb_map[R], ray_sums[R,2], d_entropy[R]")
+    if out is not None and (_f32(out, "out", dev) is not out or out.shape != raw.shape):
+        raise ValueError("out: expected a contiguous [R,S] tensor")
+    d_raw = torch.empty_like(raw) if out is None else out
+    r, s = raw.shape
+    _lib.check(lib.afx_ray_entropy_dense_backward(_ptr(raw), r, s, _ptr(rgb_map), float(threshold), _ptr(ray_sums), _ptr(d_entropy),
+                                                  int(out is not None), _ptr(d_raw), Engine._stream(dev)), "afx_ray_entropy_dense_backward")
+    return d_raw
+
+
 def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None, dirs=None, poses=None, width=0, height=0,
                    focal=0.0, ray_ids=None, ray_id0=0, n_rays=None, type_ct=True):
     """afx_project_volume: X-ray projection of a voxel volume (trilinear lookup) along rays -> pixel[R]."""

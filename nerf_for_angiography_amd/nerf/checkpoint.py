@@ -57,6 +57,8 @@ def config_fingerprint(args, model_definition: dict, ray_table) -> dict:
     """The configuration a state file belongs to: `args` (the driver's namespace), the model definition (its `device` left out) and the
     training ray table (row count and checksum).  A flat dict of plain values; field names are what a mismatch reports."""
     fp = {name: _plain(getattr(args, name, None)) for name in _ARG_FIELDS}
+    if getattr(args, "entropy_weight", 0.0):      # (present only when the term is on: state files written without the flag keep their fingerprint)
+        fp["entropy_weight"] = float(args.entropy_weight)
     for k, v in sorted(model_definition.items()):
         if k != "device":
             fp[f"model.{k}"] = _plain(v)

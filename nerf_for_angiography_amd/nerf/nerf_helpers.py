@@ -63,6 +63,34 @@ def get_ray_entropy(sigmas, rgb_map, threshold=0.4):
     return entropy * ((1 - rgb_map) > threshold).detach()
 
 
+class _DenseEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, raw, rgb, threshold):
+        ent, sums = _engine.ray_entropy_dense(raw, rgb, threshold)
+        ctx.save_for_backward(raw, rgb, sums)
+        ctx.threshold = threshold
+        return ent
+
+    @staticmethod
+    def backward(ctx, d_ent):
+        raw, rgb, sums = ctx.saved_tensors
+        return _engine.ray_entropy_dense_backward(raw, rgb, sums, d_ent.contiguous(), ctx.threshold), None, None
+
+
+def ray_entropy(raw, rgb_map, threshold=0.4):
+    """The entropy render_volume_density forms (nerf/nerf_helpers.py:119, get_ray_entropy :125-135) from the model's one-channel output
+    raw [R,S] or [R,S,1] (before the sigmoid) and the rays' rgb_map [R] -> entropy[R], differentiable on the GPU (afx_ray_entropy_dense;
+    render_volume_density returns the same values detached).  The gradient flows to `raw` only; rgb_map only selects the rays."""
+    if not raw.is_cuda:
+        from .._lib import AfxError
+        raise AfxError("ray_entropy: tensors must live on the GPU; there is no CPU fallback")
+    if raw.dim() == 3:
+        if raw.shape[-1] != 1:
+            raise ValueError("ray_entropy: expected raw[R,S] or raw[R,S,1]")
+        raw = raw[..., 0]
+    return _DenseEntropyFn.apply(raw.float().contiguous(), rgb_map.detach().reshape(-1).float().contiguous(), float(threshold))
+
+
 def _render_volume_density_ops(radiance_field, ray_directions, depth_values):
     """The two branches of nerf/nerf_helpers.py:59-123 the reference's training path never takes, on PyTorch-ROCm operators
     (same device; kept for capability, not accelerated):

@@ -69,6 +69,34 @@ def acc_render_volume_density(predictions, ray_indices, t_starts, t_ends, n_rays
     return rgb, None
 
 
+class _PackedEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, ri, rgb, n_rays, threshold):
+        ent, sums = _engine.ray_entropy_packed(pred, ri, rgb, n_rays, threshold)
+        ctx.save_for_backward(pred, ri, rgb, sums)
+        ctx.threshold = threshold
+        return ent
+
+    @staticmethod
+    def backward(ctx, d_ent):
+        pred, ri, rgb, sums = ctx.saved_tensors
+        return _engine.ray_entropy_packed_backward(pred, ri, rgb, sums, d_ent.contiguous(), ctx.threshold), None, None, None, None
+
+
+def acc_ray_entropy(predictions, ray_indices, rgb_map, n_rays, threshold=0.4):
+    """get_ray_entropy (nerf/nerf_helpers_acc.py:33-43) for the packed, ray-sorted sample list of acc_render_volume_density - the term the
+    reference's packed loop leaves out (:60-61 `entropy = None`) -> entropy[n_rays], differentiable on the GPU (afx_ray_entropy_packed):
+    entropy[r] = -sum_i p_i log(p_i + 1e-10) * [(1 - rgb_map[r]) > threshold], p_i = sigmoid(pred_i) / (sum_{j in ray r} sigmoid(pred_j) + 1e-10).
+    The gradient flows to `predictions` only: rgb_map (the value acc_render_volume_density returned) only selects the rays, detached as
+    upstream.  A ray without samples has entropy 0."""
+    pred = predictions.reshape(-1).float()
+    if not pred.is_cuda:
+        from .._lib import AfxError
+        raise AfxError("acc_ray_entropy: tensors must live on the GPU; there is no CPU fallback (tests compare with a torch restatement)")
+    return _PackedEntropyFn.apply(pred.contiguous(), ray_indices.to(torch.int32).contiguous(),
+                                  rgb_map.detach().reshape(-1).float().contiguous(), int(n_rays), float(threshold))
+
+
 def acc_update_n_step(acc_grid, radiance_field, step, occ_thre=1e-2, inverse=False):
     """nerf/nerf_helpers_acc.py:65-78: refresh the occupancy grid every 16th step from sigmoid(MLP)."""
     if acc_grid is None:

@@ -19,6 +19,7 @@ included, from a HIP graph captured once (`render.GridTrainGraph`): the sizes st
 iterations with Adam and the learning-rate update - from one graph launch (`render.GridTrainRoundGraph`); same numbers, opt-in.
 `--single-eval` (with `grid`, f16s8, with or without `--graph`) evaluates the model once per iteration: the training step's forward half over
 the march's candidates doubles as the alpha pass.
+`--entropy_weight LAMBDA` (with `grid_ops`) adds LAMBDA times the batch's mean ray entropy (`acc_ray_entropy`) to the loss.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -43,7 +44,7 @@ from .. import engine as _engine
 from ..render import (render_rays, train_step_mse, march_train_step_mse, march_render, GridTrainGraph, GridUpdateGraph, GridTrainRoundGraph,
                       lr_decay_table)
 from .nerf_helpers import sample_pixel_rays, get_predictions
-from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_update_n_step
+from .nerf_helpers_acc import acc_ray_marching, acc_render_volume_density, acc_ray_entropy, acc_update_n_step
 from .occupancy import OccupancyGrid, ContractionType
 from . import checkpoint as _ckpt
 
@@ -106,6 +107,10 @@ def build_parser():
     p.add_argument('--resume', default=None, metavar='PATH',
                    help='continue from a training-state file (or the trainstate.pt in a directory) at its iteration, bit for bit; every '
                         'argument that changes the arithmetic must equal the saved run\'s (a mismatch names the fields)')
+    p.add_argument('--entropy_weight', type=float, default=0.0, metavar='LAMBDA',
+                   help='--march grid_ops: add LAMBDA * mean over the batch\'s rays of the per-ray entropy of the density profile to the loss '
+                        '(get_ray_entropy of the reference, the sparse-view regulariser its packed loop leaves out; acc_ray_entropy, '
+                        'afx_ray_entropy_packed); 0 (default): the MSE-only loop, and no `entropy` field in the log')
     p.add_argument('--log_dir', default='runs/afx')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out_bias_init', type=float, default=-5.0,
@@ -128,6 +133,11 @@ def check_args(args):
         raise ValueError("--graph-rounds: the batches are drawn inside the graph; --host_sampler draws them on the host")
 
 
+    if args.entropy_weight < 0:
+        raise ValueError("--entropy_weight: needs LAMBDA >= 0")
+    if args.entropy_weight > 0 and (args.march != 'grid_ops' or args.graph or args.graph_grid_update or args.graph_rounds or args.single_eval):
+        raise ValueError("--entropy_weight: needs --march grid_ops without the graph flags (the operator-sequence body, where the loss is built "
+                         "under autograd; --march dense, --march grid and the graphs are fused MSE steps)")
     if args.checkpoint_every < 0:
         raise ValueError("--checkpoint_every: needs N >= 0")
 
@@ -238,6 +248,7 @@ def main(argv=None):
     new_lr_coarse = coarse_lr
     loss_coarse = torch.tensor(float('nan'), device=device)
     n_marched = 0
+    entropy_mean = torch.tensor(float('nan'), device=device)      # (--entropy_weight: until the first iteration whose march keeps samples)
     train_graph = None
     round_graph = None
     if args.graph_rounds:      # whole refresh periods per graph launch: draw, refreshes, 16 iterations and their bookkeeping on the device
@@ -343,6 +354,9 @@ def main(argv=None):
                         pred, _ = acc_render_volume_density(predictions, ray_indices, t_starts, t_ends, img_sample_size,
                                                             depth_samples_per_ray_coarse)
                         loss_coarse = torch.nn.functional.mse_loss(pred, batch_pix_vals)
+                        if args.entropy_weight > 0:      # mse + lambda * mean entropy of the batch's rays (rays the march left empty count as 0)
+                            entropy_mean = acc_ray_entropy(predictions, ray_indices, pred, img_sample_size).mean()
+                            loss_coarse = loss_coarse + args.entropy_weight * entropy_mean
                         loss_coarse.backward()
                         n_marched += int(len(ray_indices))
             elif args.precision == 'f32':
@@ -393,6 +407,8 @@ def main(argv=None):
                        it_per_s=round(display_every / max(time.time() - t_last, 1e-9), 1) if n_iter else 0.0,
                        marched_samples_per_iter=(int(n_marched) // max(display_every, 1)) if args.march != 'dense' else
                        img_sample_size * depth_samples_per_ray_coarse)
+            if args.entropy_weight > 0:      # the last training batch's mean ray entropy (train_loss includes lambda times it)
+                rec['entropy'] = float(entropy_mean.detach())
             if eval_counts is not None:      # candidates : kept samples of the test-view march
                 rec['eval_candidates_per_kept'] = eval_counts[0] / eval_counts[1] if eval_counts[1] else None
             n_marched = 0 if train_graph is None and round_graph is None else n_marched.zero_()
