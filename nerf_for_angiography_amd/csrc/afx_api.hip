@@ -1283,9 +1283,10 @@ extern "C" int afx_ray_entropy_dense_backward(const float* raw, int64_t n_rays, 
 
 static int fine_depths_impl(const char* who, const float* z_coarse, int z_per_ray, const float* w_coarse, const float* tau, const float* u,
                             int64_t n_rays, int32_t n_coarse, int32_t n_fine, float* z_out, void* stream) {
-  if (!z_coarse || (!w_coarse && !tau) || !u || !z_out) return fail(AFX_E_INVALID, "%s: null argument", who);
+  // (the sizes first: an empty u[R,0] has a null pointer, and "n_fine must be in 1..512" is the message that names the mistake)
   if (n_coarse < 3 || n_coarse > AFX_MAX_COARSE) return fail(AFX_E_INVALID, "%s: n_coarse must be in 3..%d", who, AFX_MAX_COARSE);
   if (n_fine < 1 || n_fine > AFX_MAX_FINE) return fail(AFX_E_INVALID, "%s: n_fine must be in 1..%d", who, AFX_MAX_FINE);
+  if (!z_coarse || (!w_coarse && !tau) || !u || !z_out) return fail(AFX_E_INVALID, "%s: null argument", who);
   if (n_rays <= 0) return AFX_OK;
   hipLaunchKernelGGL(k_fine_depths, dim3((unsigned)((n_rays + 63) / 64)), dim3(64), 0, (hipStream_t)stream, z_coarse, z_per_ray,
                      w_coarse, tau, u, n_rays, n_coarse, n_fine, z_out, (float*)nullptr);

@@ -598,21 +598,56 @@ def composite_dense_backward(raw, dirs, z, rgb, d_rgb):
     return d_raw
 
 
+def _packed_args(fn, floats, ints):
+    """What the packed-sample wrappers hand to the library by pointer: `floats` {name: (tensor, entries)} must be float32 and come back
+    flattened and contiguous (_f32); `ints` {name: (tensor, dtype, entries)} must have exactly that dtype and be contiguous already; every
+    tensor on the one GPU of the first.  Nothing is converted: a violation raises AfxError naming the argument, before the library is
+    called (an int64 ray_indices or a float64 t_starts would otherwise be read as something else).  Types and sizes are checked before
+    the devices.  -> the float tensors in order."""
+    named = [(k, t, torch.float32, n) for k, (t, n) in floats.items()] + [(k, t, dt, n) for k, (t, dt, n) in ints.items()]
+    for name, t, dtype, n in named:
+        if not isinstance(t, torch.Tensor):
+            raise AfxError(f"{fn}: {name}: expected a tensor")
+        if t.dtype != dtype:
+            raise AfxError(f"{fn}: {name}: dtype {t.dtype}, expected {dtype}")
+        if n is not None and t.numel() != n:
+            raise AfxError(f"{fn}: {name}: {t.numel()} entries, expected {n}")
+    dev = named[0][1].device
+    for name, t, _, _ in named:
+        if not t.is_cuda:
+            raise AfxError(f"{fn}: {name} must live on the GPU; there is no CPU fallback")
+        if t.device != dev:
+            raise AfxError(f"{fn}: {name}: on {t.device}, expected {dev}")
+    for name, (t, _, _) in ints.items():
+        if not t.is_contiguous():
+            raise AfxError(f"{fn}: {name}: expected a contiguous tensor")
+    return [_f32(t.reshape(-1), name, dev) for name, (t, _) in floats.items()]
+
+
 def composite_packed(pred, ray_indices, t_starts, t_ends, n_rays):
+    """afx_composite_packed: pred[n] (before the sigmoid), ray_indices[n] int32 ascending, t_starts / t_ends [n] -> rgb_map[n_rays]."""
     lib = _lib.load()
+    n, n_rays = (pred.numel() if isinstance(pred, torch.Tensor) else None), int(n_rays)
+    pred, ts, te = _packed_args("composite_packed", {"pred": (pred, None), "t_starts": (t_starts, n), "t_ends": (t_ends, n)},
+                                {"ray_indices": (ray_indices, torch.int32, n)})
     dev = pred.device
     rgb = torch.empty(n_rays, device=dev)
-    _lib.check(lib.afx_composite_packed(_ptr(pred), _ptr(ray_indices), _ptr(t_starts), _ptr(t_ends), pred.numel(), n_rays,
+    _lib.check(lib.afx_composite_packed(_ptr(pred), _ptr(ray_indices), _ptr(ts), _ptr(te), n, n_rays,
                                         _ptr(rgb), Engine._stream(dev)), "afx_composite_packed")
     return rgb
 
 
 def composite_packed_backward(pred, ray_indices, t_starts, t_ends, n_rays, rgb, d_rgb):
+    """afx_composite_packed_backward: rgb = composite_packed's result, d_rgb[n_rays] -> d_pred, in pred's shape."""
     lib = _lib.load()
-    dev = pred.device
-    d_pred = torch.empty_like(pred)
-    _lib.check(lib.afx_composite_packed_backward(_ptr(pred), _ptr(ray_indices), _ptr(t_starts), _ptr(t_ends), pred.numel(),
-                                                 n_rays, _ptr(rgb), _ptr(_f32(d_rgb, "d_rgb", dev)), _ptr(d_pred),
+    n, n_rays = (pred.numel() if isinstance(pred, torch.Tensor) else None), int(n_rays)
+    flat, ts, te, rgb, d_rgb = _packed_args("composite_packed_backward",
+                                            {"pred": (pred, None), "t_starts": (t_starts, n), "t_ends": (t_ends, n), "rgb": (rgb, n_rays),
+                                             "d_rgb": (d_rgb, n_rays)}, {"ray_indices": (ray_indices, torch.int32, n)})
+    dev = flat.device
+    d_pred = torch.empty(pred.shape, device=dev)
+    _lib.check(lib.afx_composite_packed_backward(_ptr(flat), _ptr(ray_indices), _ptr(ts), _ptr(te), n,
+                                                 n_rays, _ptr(rgb), _ptr(d_rgb), _ptr(d_pred),
                                                  Engine._stream(dev)), "afx_composite_packed_backward")
     return d_pred
 
@@ -925,11 +960,17 @@ def march(origins, dirs, scene_aabb, near_plane, far_plane, step, grid_bits=None
 
 
 def march_visibility(raw, ts, te, offsets, early_stop_eps, alpha_thre, is_alpha=False, return_offsets=False):
-    """nerfacc render_visibility on the candidates' raw MLP outputs -> compacted (ray_indices, t_starts, t_ends)."""
+    """nerfacc render_visibility on the candidates' raw MLP outputs -> compacted (ray_indices, t_starts, t_ends).
+    raw / ts / te [n] float32, offsets int64 [n_rays + 1] are checked for type, size against each other and device; that offsets is
+    ascending with offsets[-1] == n is the caller's to keep (the march's own output does): checking it would cost a host read per call,
+    and the kernels index the samples by it."""
     lib = _lib.load()
-    dev = ts.device
+    n = raw.numel() if isinstance(raw, torch.Tensor) else None
+    raw, ts, te = _packed_args("march_visibility", {"raw": (raw, None), "ts": (ts, n), "te": (te, n)}, {"offsets": (offsets, torch.int64, None)})
+    dev = raw.device
     n_rays = offsets.numel() - 1
-    raw = _f32(raw.reshape(-1), "raw", dev)
+    if n_rays < 0:
+        raise AfxError("march_visibility: offsets: expected [n_rays + 1] entries")
     keep = torch.empty(ts.numel(), dtype=torch.uint8, device=dev)
     counts = torch.empty(n_rays, dtype=torch.int32, device=dev)
     st = Engine._stream(dev)
