@@ -649,6 +649,52 @@ int afx_ssim(const float* preds, const float* targets, int32_t n, int32_t h, int
 int afx_volume_grid(const float* vol, int32_t nx, int32_t ny, int32_t nz, const double origin[3], const double spacing[3], float fill_value,
                     double lo, double hi, int32_t n, float* out, void* stream);
 
+/* ---- Surface-distance scores of the 3-D reconstruction: the Dice of the vessel class, the average symmetric surface distance, the
+ * Hausdorff distance and its percentile (medpy.metric.binary dc / assd / hd / hd95 at unit spacing).  The rules above hold: device
+ * pointers, nothing allocated or synchronised, no floating-point atomics (integer atomics only, so every result is independent of the
+ * order of execution), hipGraph-capturable, the same bits on every run.
+ *
+ * afx_distance_transform_edt_3d: the exact Euclidean distance transform of a uint8 volume fg[n0][n1][n2] (row-major; non-zero =
+ * foreground).  d2 (uint32, required): the integer squared distance, in voxels, from every voxel to the nearest zero voxel - 0 at a zero
+ * voxel, AFX_EDT3D_NONE everywhere when the volume has no zero voxel.  dist (fp64, may be NULL): sqrt((double)d2), +inf for
+ * AFX_EDT3D_NONE (afx_distance_transform_edt's convention; scipy.ndimage.distance_transform_edt bit for bit wherever a zero voxel
+ * exists).  Three separable passes in integer arithmetic: the nearest zero along axis 2 (a wave per line), then along axis 1 and along
+ * axis 0 the exact lower envelope min over c' of g(c') + (c - c')^2, a workgroup taking a tile of 32 (lines of up to 512 voxels) or 16
+ * adjacent lines into LDS, so that the global loads and stores of the strided passes run along axis 2.
+ * AFX_E_INVALID: a null fg or d2, an axis outside 1..1024 (squared distances stay below 2^22, a tile of lines fits in 64 KiB of LDS;
+ * n0 n1 n2 <= 2^30 follows).  Workspace (afx_distance_transform_edt_3d_workspace_bytes; 0 for a refused shape): n0 n1 n2 uint16 (the
+ * distances of the first pass), rounded up to 256 bytes; AFX_E_WORKSPACE when smaller, with *workspace_needed (when not NULL) set.
+ *
+ * afx_surface_metrics_3d: pred and gt are fp32 volumes [n0][n1][n2];  A = pred >= thr_pred, B = gt >= thr_gt (a NaN is outside);
+ * S(M) = the voxels of M with at least one of the 6 face neighbours outside M, a neighbour beyond the grid counting as outside
+ * (M & ~scipy.ndimage.binary_erosion(M, generate_binary_structure(3, 1), border_value=0));  D_A->B = the multiset { EDT(~S(B))[v] :
+ * v in S(A) }, D_B->A likewise.  One fixed launch sequence (masks and counts, two EDTs, a gather with the first histogram, a scan, the
+ * second histogram, the finish) writes `record`, AFX_SURFACE_RECORD_SLOTS slots of 8 bytes on the device:
+ *   [0] |A|  [1] |B|  [2] |A & B|  [3] |S(A)|  [4] |S(B)|                                   uint64
+ *   [5] sum of D_A->B  [6] sum of D_B->A                                                   fp64: per-workgroup partials (a tree), summed
+ *                                                                                          strided per thread, then a tree - a fixed order
+ *   [7] max d^2 of D_A->B  [8] max d^2 of D_B->A                                           uint64 (squared voxel distances)
+ *   [9] [10] the d^2 at indices floor(v) and min(floor(v) + 1, M - 1) of the sorted merged multiset D_A->B + D_B->A, M = |S(A)| +
+ *            |S(B)|: the two values np.percentile(..., q) ('linear') interpolates between               uint64
+ *   [11] v = (M - 1) * (q / 100), the virtual index, computed in fp64 on the device                      fp64
+ *   [12] status: bit 1 (value 1) A is empty, bit 2 (value 2) B is empty                                  uint64
+ *   [13..15] zero
+ * With status != 0 no surface distance exists: [5], [6] and [11] are NaN, [7]..[10] are AFX_EDT3D_NONE.  The order statistics come
+ * from a radix select over the 22-bit keys (two passes of 11 bits, LDS histograms added to global ones with integer atomics, as
+ * afx_topk_indices does).  AFX_E_INVALID: a null pred, gt or record, an axis outside 1..1024, a NaN threshold, q outside [0, 100].
+ * Workspace (afx_surface_metrics_3d_workspace_bytes; 0 for a refused shape), each region rounded up to 256 bytes, N = n0 n1 n2: two
+ * uint8 [N] (~S(A), ~S(B)), uint16 [N] (the EDT's), two uint32 [N] (the squared distance fields), 2 x 2048 doubles (partial sums),
+ * 3 x 2048 uint32 (histograms) and 256 bytes of counters. */
+#define AFX_EDT3D_NONE 0xffffffffu
+#define AFX_EDT3D_MAX_SIDE 1024
+#define AFX_SURFACE_RECORD_SLOTS 16
+size_t afx_distance_transform_edt_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_distance_transform_edt_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, uint32_t* d2, double* dist, void* workspace,
+                                  size_t workspace_bytes, size_t* workspace_needed, void* stream);
+size_t afx_surface_metrics_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_surface_metrics_3d(const float* pred, const float* gt, int32_t n0, int32_t n1, int32_t n2, float thr_pred, float thr_gt, double q,
+                           void* record, void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -170,6 +170,12 @@ _SIGS = {
                            C.c_void_p]),
     "afx_volume_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_float,
                                   C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "afx_distance_transform_edt_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "afx_distance_transform_edt_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_surface_metrics_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "afx_surface_metrics_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
 }
 
 _libs = {}

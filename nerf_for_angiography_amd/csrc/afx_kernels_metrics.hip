@@ -138,7 +138,386 @@ __global__ void __launch_bounds__(GRID_BLOCK) k_volume_grid(const afx::VolArgs v
   }
 }
 
+// ---- The exact 3-D Euclidean distance transform and the surface-distance scores built on it (afx_distance_transform_edt_3d,
+// afx_surface_metrics_3d).  Integer arithmetic up to the final sqrt / sum, so nothing depends on the order of execution.
+constexpr uint32_t EDT3_NONE = AFX_EDT3D_NONE;        // no zero voxel (in the line so far / in the volume)
+constexpr uint16_t EDT3_NONE16 = 0xffffu;             // the same for the first pass's 1-D distances (<= 1023)
+constexpr int EDT3_BLOCK = 256;
+constexpr int SM_BINS = 2048;                         // 11 bits per pass of the radix select: squared distances are below 2^22
+constexpr int SM_MAX_PART = 2048;                     // workgroups of the gather = per-direction partial sums
+
+bool edt3_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
+  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
+}
+
+// First pass: g[c] = the distance from voxel c to the nearest zero voxel of its own line along axis 2 (EDT3_NONE16: the line has none).
+// A wave per line, 64 voxels at a time: the zero voxels of a chunk are one ballot, the nearest one at or below a lane the highest set
+// bit below it (or the last zero of the chunks before); the sweep back does the same from above.  Loads and stores are contiguous.
+__global__ void __launch_bounds__(EDT3_BLOCK) k_edt3_axis2(const uint8_t* __restrict__ fg, int64_t lines, int n2, uint16_t* __restrict__ g) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * EDT3_BLOCK + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * EDT3_BLOCK) >> 6;
+  for (int64_t line = wave; line < lines; line += n_waves) {
+    const uint8_t* v = fg + line * n2;
+    uint16_t* o = g + line * n2;
+    int last = -1;                                     // the last zero voxel before this chunk (the same in every lane)
+    for (int c0 = 0; c0 < n2; c0 += 64) {
+      const int c = c0 + lane;
+      const bool in = c < n2;
+      const unsigned long long m = __ballot(in && v[c] == 0);
+      const unsigned long long below = m & ((2ull << lane) - 1ull);                 // zero voxels of the chunk at lanes <= mine
+      const int l = below ? c0 + 63 - __builtin_clzll(below) : last;
+      if (in) o[c] = l < 0 ? EDT3_NONE16 : (uint16_t)(c - l);
+      if (m) last = c0 + 63 - __builtin_clzll(m);
+    }
+    int next = -1;                                     // the first zero voxel behind this chunk
+    for (int c0 = (n2 - 1) / 64 * 64; c0 >= 0; c0 -= 64) {
+      const int c = c0 + lane;
+      const bool in = c < n2;
+      const uint16_t cur = in ? o[c] : EDT3_NONE16;    // this lane's own store of the sweep forward
+      const unsigned long long m = __ballot(in && cur == 0);
+      const unsigned long long above = m & ~((1ull << lane) - 1ull);                 // zero voxels of the chunk at lanes >= mine
+      const int r = above ? c0 + __builtin_ctzll(above) : next;
+      if (in && r >= 0 && (uint32_t)(r - c) < (uint32_t)cur) o[c] = (uint16_t)(r - c);
+      if (m) next = c0 + __builtin_ctzll(m);
+    }
+  }
+}
+
+// Second and third pass: along an axis of `len` voxels whose neighbours lie `inner` elements apart (axis 1: inner = n2, one launch
+// block per (i, tile); axis 0: inner = n1 n2), out[c] = min over c' of g(c') + (c - c')^2 - the exact lower envelope, searched outwards
+// from c and stopped once (c - c')^2 alone reaches the best found, as k_edt_rows (afx_kernels_image.hip) does.  A workgroup takes `tw`
+// (16 or 32) ADJACENT lines, [len][tw] values in LDS: every global load and store is a run of tw consecutive elements, and the lanes of
+// a wave's half read tw distinct LDS banks.  In = uint16_t: g is the first pass's distance, squared here; uint32_t: squared already, and
+// the call may work in place (a workgroup has read its whole tile before it writes, and no other workgroup touches that tile).
+// grid: outer * tiles, dynamic LDS len * tw * 4 bytes
+template <class In>
+__global__ void __launch_bounds__(EDT3_BLOCK) k_edt3_lines(const In* g, int len, int64_t inner, int tw_shift, int tiles, uint32_t* d2,
+                                                           double* dist) {
+  extern __shared__ uint32_t col[];
+  const int tw = 1 << tw_shift;
+  const int64_t outer = blockIdx.x / tiles;
+  const int tile = (int)(blockIdx.x - outer * tiles);
+  const int64_t k0 = (int64_t)tile << tw_shift;
+  const int kw = inner - k0 < tw ? (int)(inner - k0) : tw;          // lines of this tile that exist
+  const int64_t base = outer * len * inner + k0;
+  const int cells = len << tw_shift;
+  for (int e = threadIdx.x; e < cells; e += EDT3_BLOCK) {
+    const int r = e >> tw_shift, k = e & (tw - 1);
+    uint32_t v = EDT3_NONE;
+    if (k < kw) {
+      const In x = g[base + (int64_t)r * inner + k];
+      if (sizeof(In) == 2) v = x == (In)EDT3_NONE16 ? EDT3_NONE : (uint32_t)x * (uint32_t)x;
+      else v = (uint32_t)x;
+    }
+    col[e] = v;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < cells; e += EDT3_BLOCK) {
+    const int r = e >> tw_shift, k = e & (tw - 1);
+    if (k >= kw) continue;
+    uint32_t best = EDT3_NONE;
+    for (int d = 0; d < len; ++d) {
+      const uint32_t dd = (uint32_t)d * (uint32_t)d;
+      if (dd >= best) break;
+      if (r - d >= 0) {
+        const uint32_t v = col[((r - d) << tw_shift) + k];
+        if (v != EDT3_NONE && v + dd < best) best = v + dd;
+      }
+      if (r + d < len) {
+        const uint32_t v = col[((r + d) << tw_shift) + k];
+        if (v != EDT3_NONE && v + dd < best) best = v + dd;
+      }
+    }
+    const int64_t at = base + (int64_t)r * inner + k;
+    d2[at] = best;
+    if (dist) dist[at] = best == EDT3_NONE ? (double)INFINITY : sqrt((double)best);
+  }
+}
+
+// tile width of k_edt3_lines as a shift: 32 lines while they fit in 64 KiB of LDS (len <= 512), else 16
+int edt3_tw_shift(int len) { return len <= 512 ? 5 : 4; }
+
+void launch_edt3(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, uint16_t* g16, uint32_t* d2, double* dist, hipStream_t st) {
+  const int64_t lines = (int64_t)n0 * n1, inner0 = (int64_t)n1 * n2;
+  const int64_t b1 = std::min<int64_t>((lines + 3) / 4, 1 << 16);                 // 4 waves = 4 lines per workgroup, then a stride
+  hipLaunchKernelGGL(k_edt3_axis2, dim3((unsigned)b1), dim3(EDT3_BLOCK), 0, st, fg, lines, (int)n2, g16);
+  const int s1 = edt3_tw_shift(n1), t1 = (n2 + (1 << s1) - 1) >> s1;
+  hipLaunchKernelGGL(k_edt3_lines<uint16_t>, dim3((unsigned)(n0 * t1)), dim3(EDT3_BLOCK), ((size_t)n1 << s1) * sizeof(uint32_t), st,
+                     (const uint16_t*)g16, (int)n1, (int64_t)n2, s1, t1, d2, (double*)nullptr);
+  const int s0 = edt3_tw_shift(n0), t0 = (int)((inner0 + (1 << s0) - 1) >> s0);
+  hipLaunchKernelGGL(k_edt3_lines<uint32_t>, dim3((unsigned)t0), dim3(EDT3_BLOCK), ((size_t)n0 << s0) * sizeof(uint32_t), st,
+                     (const uint32_t*)d2, (int)n0, inner0, s0, t0, d2, dist);
+}
+
+// Device-side state of afx_surface_metrics_3d between its launches (one 256-byte region of the workspace, zeroed by k_sm_init)
+struct SmState {
+  unsigned long long cnt[5];      // |A|, |B|, |A & B|, |S(A)|, |S(B)|
+  unsigned long long rem[2];      // rank of the two order statistics inside their first-pass bin
+  uint32_t bin[2];                // first-pass bin (the high 11 bits) of the two order statistics
+  uint32_t mx[2];                 // max d^2 of D_A->B, D_B->A
+  uint32_t status, pad;
+  double vidx;                    // the virtual index
+};
+static_assert(sizeof(SmState) <= 256, "SmState has 256 bytes of the workspace");
+
+__global__ void __launch_bounds__(256) k_sm_init(SmState* st, uint32_t* hist) {
+  if (threadIdx.x == 0) *st = SmState{};
+  for (int i = threadIdx.x; i < 3 * SM_BINS; i += 256) hist[i] = 0;
+}
+
+// Masks and counts: A = pred >= thr_pred, B = gt >= thr_gt; a voxel of M is on S(M) when one of its 6 face neighbours is outside M or
+// beyond the grid.  na[p] = 0 on S(A), 1 elsewhere (the EDT's foreground: the distance to S(A)); nb likewise.  Counts: integer atomics.
+__global__ void __launch_bounds__(256) k_sm_masks(const float* __restrict__ pred, const float* __restrict__ gt, int n0, int n1, int n2,
+                                                  float thr_pred, float thr_gt, uint8_t* __restrict__ na, uint8_t* __restrict__ nb,
+                                                  SmState* st) {
+  __shared__ unsigned int c[5];
+  if (threadIdx.x < 5) c[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t s0 = (int64_t)n1 * n2, total = s0 * n0;
+  unsigned int mine[5] = {0, 0, 0, 0, 0};
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
+    const int i = (int)(p / s0), r = (int)(p - i * s0), j = r / n2, k = r - j * n2;
+    const bool lo0 = i > 0, hi0 = i < n0 - 1, lo1 = j > 0, hi1 = j < n1 - 1, lo2 = k > 0, hi2 = k < n2 - 1;
+    const bool edge = !(lo0 && hi0 && lo1 && hi1 && lo2 && hi2);
+    auto surface = [&](const float* v, float thr) {      // v[p] is inside the mask
+      if (edge) return true;
+      return !(v[p - s0] >= thr && v[p + s0] >= thr && v[p - n2] >= thr && v[p + n2] >= thr && v[p - 1] >= thr && v[p + 1] >= thr);
+    };
+    const bool a = pred[p] >= thr_pred, b = gt[p] >= thr_gt;
+    const bool sa = a && surface(pred, thr_pred), sb = b && surface(gt, thr_gt);
+    na[p] = sa ? 0 : 1;
+    nb[p] = sb ? 0 : 1;
+    mine[0] += a; mine[1] += b; mine[2] += a && b; mine[3] += sa; mine[4] += sb;
+  }
+  for (int q = 0; q < 5; ++q)
+    if (mine[q]) atomicAdd(&c[q], mine[q]);
+  __syncthreads();
+  if (threadIdx.x < 5 && c[threadIdx.x]) atomicAdd(&st->cnt[threadIdx.x], (unsigned long long)c[threadIdx.x]);
+}
+
+// The two multisets, read where the masks mark a surface voxel: D_A->B = d2b at S(A) (na == 0), D_B->A = d2a at S(B).
+// PASS 1: the fp64 sums of sqrt(d^2) per direction as one partial per workgroup (a tree: a fixed order), the maxima, and the histogram
+// of the merged keys' high 11 bits.  PASS 2: the histograms of the low 11 bits of the keys in the bin of the lower order statistic
+// (hist[0..]) and of the upper one (hist[SM_BINS..]).  LDS histograms, added to the global ones with integer atomics.
+template <int PASS>
+__global__ void __launch_bounds__(256) k_sm_gather(const uint8_t* __restrict__ na, const uint8_t* __restrict__ nb, const uint32_t* __restrict__ d2a,
+                                                   const uint32_t* __restrict__ d2b, int64_t total, SmState* st, uint32_t* __restrict__ hist,
+                                                   double* __restrict__ partial) {
+  __shared__ uint32_t h[PASS == 1 ? 1 : 2][SM_BINS];
+  __shared__ double red[2][256];
+  __shared__ uint32_t smx[2];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < (PASS == 1 ? 1 : 2) * SM_BINS; i += 256) (&h[0][0])[i] = 0;
+  if (tid < 2) smx[tid] = 0;
+  __syncthreads();
+  const uint32_t bin0 = st->bin[0], bin1 = st->bin[1];
+  double sum[2] = {0.0, 0.0};
+  uint32_t mx[2] = {0, 0};
+  for (int64_t p = (int64_t)blockIdx.x * 256 + tid; p < total; p += (int64_t)gridDim.x * 256) {
+    const bool on[2] = {na[p] == 0, nb[p] == 0};
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir) {
+      if (!on[dir]) continue;
+      const uint32_t key = dir == 0 ? d2b[p] : d2a[p];
+      const uint32_t hi = key >> 11;
+      if (PASS == 1) {
+        sum[dir] += sqrt((double)key);
+        mx[dir] = key > mx[dir] ? key : mx[dir];
+        atomicAdd(&h[0][hi < SM_BINS ? hi : SM_BINS - 1], 1u);          // only the no-zero-voxel mark lies beyond: status != 0 then
+      } else {
+        if (hi == bin0) atomicAdd(&h[0][key & (SM_BINS - 1)], 1u);
+        if (hi == bin1) atomicAdd(&h[PASS == 1 ? 0 : 1][key & (SM_BINS - 1)], 1u);
+      }
+    }
+  }
+  if (PASS == 1) {
+    red[0][tid] = sum[0];
+    red[1][tid] = sum[1];
+    if (mx[0]) atomicMax(&smx[0], mx[0]);
+    if (mx[1]) atomicMax(&smx[1], mx[1]);
+  }
+  __syncthreads();
+  if (PASS == 1) {
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
+      __syncthreads();
+    }
+    if (tid < 2) {
+      partial[2 * (int64_t)blockIdx.x + tid] = red[tid][0];
+      if (smx[tid]) atomicMax(&st->mx[tid], smx[tid]);
+    }
+  }
+  for (int i = tid; i < (PASS == 1 ? 1 : 2) * SM_BINS; i += 256) {
+    const uint32_t v = (&h[0][0])[i];
+    if (v) atomicAdd(&hist[i], v);
+  }
+}
+
+// The bin of hist[SM_BINS] that holds rank r (0-based, ascending) and r's rank inside it; every thread of the 256 calls it and gets the
+// same answer (sh: 256 counts and the two results in LDS).  A rank beyond the histogram's total gives bin 0.
+struct SmFind { unsigned long long below[256]; unsigned long long rem; uint32_t bin; };
+__device__ void sm_find(const uint32_t* hist, unsigned long long r, SmFind* sh, uint32_t* bin, unsigned long long* rem) {
+  const int t = threadIdx.x;
+  uint32_t c[8];
+  unsigned long long s = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { c[j] = hist[8 * t + j]; s += c[j]; }
+  __syncthreads();                                     // the previous call's results have been read
+  sh->below[t] = s;
+  if (t == 0) { sh->bin = 0; sh->rem = 0; }
+  __syncthreads();
+  if (t == 0) {
+    unsigned long long run = 0;
+    for (int g = 0; g < 256; ++g) { const unsigned long long v = sh->below[g]; sh->below[g] = run; run += v; }
+  }
+  __syncthreads();
+  unsigned long long a = sh->below[t];
+  if (a <= r && r < a + s) {                           // exactly one group of 8 bins holds the rank
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (a <= r && r < a + c[j]) { sh->bin = (uint32_t)(8 * t + j); sh->rem = r - a; }
+      a += c[j];
+    }
+  }
+  __syncthreads();
+  *bin = sh->bin;
+  *rem = sh->rem;
+}
+
+// One workgroup, after the first histogram: the status, the virtual index v = (M - 1) quant in fp64 (np.percentile's 'linear' rule:
+// (n - 1) * (q / 100)), the two ranks floor(v) and min(floor(v) + 1, M - 1), and the first-pass bin of each.
+__global__ void __launch_bounds__(256) k_sm_scan(SmState* st, const uint32_t* hist, double quant) {
+  __shared__ SmFind sh;
+  const unsigned long long m = st->cnt[3] + st->cnt[4];
+  const uint32_t status = (st->cnt[0] == 0 ? 1u : 0u) | (st->cnt[1] == 0 ? 2u : 0u);
+  if (status) {                                        // the same in every thread
+    if (threadIdx.x == 0) { st->status = status; st->vidx = NAN; st->bin[0] = st->bin[1] = EDT3_NONE; }      // no key has this bin
+    return;
+  }
+  const double v = (double)(m - 1) * quant;
+  unsigned long long k0 = (unsigned long long)floor(v);
+  if (k0 > m - 1) k0 = m - 1;
+  const unsigned long long k1 = k0 + 1 < m ? k0 + 1 : m - 1;
+  uint32_t b0, b1;
+  unsigned long long r0, r1;
+  sm_find(hist, k0, &sh, &b0, &r0);
+  sm_find(hist, k1, &sh, &b1, &r1);
+  if (threadIdx.x == 0) { st->status = 0; st->vidx = v; st->bin[0] = b0; st->bin[1] = b1; st->rem[0] = r0; st->rem[1] = r1; }
+}
+
+// One workgroup: the record.  The sums: the gather's partials strided per thread, then a tree.  The order statistics: the rank left
+// inside the first-pass bin, looked up in the second histograms.
+__global__ void __launch_bounds__(256) k_sm_finish(const SmState* st, const uint32_t* hist2, const double* __restrict__ partial, int n_part,
+                                                   unsigned long long* __restrict__ record) {
+  __shared__ SmFind sh;
+  __shared__ double red[2][256];
+  const int tid = threadIdx.x;
+  double s0 = 0.0, s1 = 0.0;
+  for (int g = tid; g < n_part; g += 256) { s0 += partial[2 * g]; s1 += partial[2 * g + 1]; }
+  red[0][tid] = s0;
+  red[1][tid] = s1;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; }
+    __syncthreads();
+  }
+  const uint32_t status = st->status;
+  uint32_t lo[2] = {0, 0};
+  unsigned long long rem;
+  if (!status) {                                       // the same in every thread
+    sm_find(hist2, st->rem[0], &sh, &lo[0], &rem);
+    sm_find(hist2 + SM_BINS, st->rem[1], &sh, &lo[1], &rem);
+  }
+  if (tid != 0) return;
+  for (int q = 0; q < 5; ++q) record[q] = st->cnt[q];
+  const double nan = NAN;
+  record[5] = (unsigned long long)__double_as_longlong(status ? nan : red[0][0]);
+  record[6] = (unsigned long long)__double_as_longlong(status ? nan : red[1][0]);
+  record[7] = status ? EDT3_NONE : st->mx[0];
+  record[8] = status ? EDT3_NONE : st->mx[1];
+  record[9] = status ? EDT3_NONE : ((st->bin[0] << 11) | lo[0]);
+  record[10] = status ? EDT3_NONE : ((st->bin[1] << 11) | lo[1]);
+  record[11] = (unsigned long long)__double_as_longlong(st->vidx);
+  record[12] = status;
+  for (int q = 13; q < AFX_SURFACE_RECORD_SLOTS; ++q) record[q] = 0;
+}
+
+struct SurfaceBufs { uint8_t* na; uint8_t* nb; uint16_t* g16; uint32_t* d2a; uint32_t* d2b; double* partial; uint32_t* hist; SmState* st; };
+SurfaceBufs carve_surface(afx::Carve& c, int32_t n0, int32_t n1, int32_t n2) {
+  const size_t n = (size_t)n0 * n1 * n2;
+  SurfaceBufs b;
+  b.na = c.take<uint8_t>(n);
+  b.nb = c.take<uint8_t>(n);
+  b.g16 = c.take<uint16_t>(n * sizeof(uint16_t));
+  b.d2a = c.take<uint32_t>(n * sizeof(uint32_t));
+  b.d2b = c.take<uint32_t>(n * sizeof(uint32_t));
+  b.partial = c.take<double>((size_t)2 * SM_MAX_PART * sizeof(double));
+  b.hist = c.take<uint32_t>((size_t)3 * SM_BINS * sizeof(uint32_t));
+  b.st = c.take<SmState>(256);
+  return b;
+}
+
 }  // namespace
+
+extern "C" size_t afx_distance_transform_edt_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
+  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  afx::Carve c;
+  c.take<uint16_t>((size_t)n0 * n1 * n2 * sizeof(uint16_t));
+  return c.end;
+}
+
+extern "C" int afx_distance_transform_edt_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, uint32_t* d2, double* dist, void* workspace,
+                                             size_t workspace_bytes, size_t* workspace_needed, void* stream) {
+  const char* who = "afx_distance_transform_edt_3d";
+  if (!fg || !d2) return afx::set_error(AFX_E_INVALID, who, "null volume or squared-distance output");
+  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  const size_t need = afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2);
+  if (workspace_needed) *workspace_needed = need;
+  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_device(fg, "the volume", who)) return rc;
+  launch_edt3(fg, n0, n1, n2, (uint16_t*)workspace, d2, dist, (hipStream_t)stream);
+  return afx::launched(who);
+}
+
+extern "C" size_t afx_surface_metrics_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
+  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  afx::Carve c;
+  carve_surface(c, n0, n1, n2);
+  return c.end;
+}
+
+extern "C" int afx_surface_metrics_3d(const float* pred, const float* gt, int32_t n0, int32_t n1, int32_t n2, float thr_pred, float thr_gt,
+                                      double q, void* record, void* workspace, size_t workspace_bytes, size_t* workspace_needed,
+                                      void* stream) {
+  const char* who = "afx_surface_metrics_3d";
+  if (!pred || !gt || !record) return afx::set_error(AFX_E_INVALID, who, "null volume or record");
+  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need volumes of 1..1024 voxels along each axis");
+  if (thr_pred != thr_pred || thr_gt != thr_gt) return afx::set_error(AFX_E_INVALID, who, "a threshold is NaN");
+  if (!(q >= 0.0 && q <= 100.0)) return afx::set_error(AFX_E_INVALID, who, "the percentile q must lie in [0, 100]");
+  const size_t need = afx_surface_metrics_3d_workspace_bytes(n0, n1, n2);
+  if (workspace_needed) *workspace_needed = need;
+  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_device(pred, "pred", who)) return rc;
+  if (int rc = afx::check_device(gt, "gt", who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  afx::Carve c;
+  c.base = (uintptr_t)workspace;
+  const SurfaceBufs b = carve_surface(c, n0, n1, n2);
+  const int64_t total = (int64_t)n0 * n1 * n2;
+  const unsigned blocks = (unsigned)std::min<int64_t>((total + 2047) / 2048, SM_MAX_PART);      // ~8 voxels per thread, then a stride
+  hipLaunchKernelGGL(k_sm_init, dim3(1), dim3(256), 0, st, b.st, b.hist);
+  hipLaunchKernelGGL(k_sm_masks, dim3(blocks), dim3(256), 0, st, pred, gt, (int)n0, (int)n1, (int)n2, thr_pred, thr_gt, b.na, b.nb, b.st);
+  launch_edt3(b.na, n0, n1, n2, b.g16, b.d2a, nullptr, st);                  // the distance to S(A)
+  launch_edt3(b.nb, n0, n1, n2, b.g16, b.d2b, nullptr, st);                  // the distance to S(B)
+  hipLaunchKernelGGL(k_sm_gather<1>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)b.na, (const uint8_t*)b.nb, (const uint32_t*)b.d2a,
+                     (const uint32_t*)b.d2b, total, b.st, b.hist, b.partial);
+  hipLaunchKernelGGL(k_sm_scan, dim3(1), dim3(256), 0, st, b.st, (const uint32_t*)b.hist, q / 100.0);
+  hipLaunchKernelGGL(k_sm_gather<2>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)b.na, (const uint8_t*)b.nb, (const uint32_t*)b.d2a,
+                     (const uint32_t*)b.d2b, total, b.st, b.hist + SM_BINS, (double*)nullptr);
+  hipLaunchKernelGGL(k_sm_finish, dim3(1), dim3(256), 0, st, (const SmState*)b.st, (const uint32_t*)(b.hist + SM_BINS), (const double*)b.partial,
+                     (int)blocks, (unsigned long long*)record);
+  return afx::launched(who);
+}
 
 extern "C" size_t afx_ssim_workspace_bytes(int32_t n, int32_t h, int32_t w) {
   if (!ssim_shape_ok(n, h, w)) return 0;

@@ -1114,6 +1114,89 @@ def volume_grid(volume_values: torch.Tensor, origin, spacing, fill, lo: float, h
     return out
 
 
+def _volume_on_gpu(x, name: str, who: str) -> None:
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    if x.dim() != 3:
+        raise ValueError(f"{who}: {name} must have shape [n0, n1, n2], got {tuple(x.shape)}")
+
+
+def distance_transform_edt_3d(x: torch.Tensor, return_squared: bool = False):
+    """afx_distance_transform_edt_3d: the exact Euclidean distance transform of a [n0, n1, n2] device tensor (non-zero = foreground) -
+    float64 [n0, n1, n2], the distance in voxels from every voxel to the nearest zero voxel: scipy.ndimage.distance_transform_edt bit for
+    bit; +inf everywhere when there is no zero voxel.  return_squared: (distances, the exact integer squared distances as int64,
+    0xffffffff for 'no zero voxel')."""
+    lib = _lib.load()
+    _volume_on_gpu(x, "the volume", "distance_transform_edt_3d")
+    fg = (x != 0).to(torch.uint8).contiguous()
+    n0, n1, n2 = fg.shape
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    nbytes = int(lib.afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2))
+    d2 = torch.empty(fg.shape if nbytes else (1,), dtype=torch.int32, device=fg.device)
+    dist = torch.empty(fg.shape if nbytes else (1,), dtype=torch.float64, device=fg.device)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=fg.device)
+    _lib.check(lib.afx_distance_transform_edt_3d(_ptr(fg), n0, n1, n2, _ptr(d2), _ptr(dist), _ptr(ws), nbytes, None, Engine._stream(fg.device)),
+               "afx_distance_transform_edt_3d")
+    if not return_squared:
+        return dist
+    return dist, d2.to(torch.int64) & 0xffffffff      # the library's uint32 (held in an int32 tensor) as int64
+
+
+SURFACE_RECORD_SLOTS = 16
+
+
+def surface_metrics_record(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float, thr_gt: float, q: float = 95.0, record=None,
+                           workspace=None) -> torch.Tensor:
+    """afx_surface_metrics_3d: the 16-slot device record (int64 tensor; layout in include/afx.h) of two float32 [n0, n1, n2] device
+    volumes.  Launches only - nothing is read back, so the call can be captured in a graph (pass `record` and `workspace`, the latter of
+    afx_surface_metrics_3d_workspace_bytes bytes, to keep the capture free of allocations)."""
+    lib = _lib.load()
+    _volume_on_gpu(pred, "pred", "surface_metrics_3d")
+    _volume_on_gpu(gt, "gt", "surface_metrics_3d")
+    if pred.shape != gt.shape or pred.device != gt.device:
+        raise ValueError(f"surface_metrics_3d: pred {tuple(pred.shape)} on {pred.device}, gt {tuple(gt.shape)} on {gt.device}")
+    dev = pred.device
+    p, g = _f32(pred, "pred", dev), _f32(gt, "gt", dev)
+    n0, n1, n2 = p.shape
+    nbytes = int(lib.afx_surface_metrics_3d_workspace_bytes(n0, n1, n2))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.empty(SURFACE_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    _lib.check(lib.afx_surface_metrics_3d(_ptr(p), _ptr(g), n0, n1, n2, float(thr_pred), float(thr_gt), float(q), _ptr(record), _ptr(workspace),
+                                          workspace.numel(), None, Engine._stream(dev)), "afx_surface_metrics_3d")
+    return record
+
+
+def _lerp(a: float, b: float, t: float) -> float:
+    """numpy.lib._function_base_impl._lerp for scalars: a + (b - a) t, taken from b's side once t >= 0.5."""
+    diff = b - a
+    return b - diff * (1.0 - t) if t >= 0.5 else a + diff * t
+
+
+def surface_metrics_3d(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float, thr_gt: float, q: float = 95.0) -> dict:
+    """The surface-distance scores of A = pred >= thr_pred against B = gt >= thr_gt, in voxel units (medpy.metric.binary dc, assd, hd and
+    hd95 at unit spacing; definitions in include/afx.h): dice_vessel = 2 |A & B| / (|A| + |B|), assd = (mean D_A->B + mean D_B->A) / 2,
+    hd = the largest surface distance of either direction, hd_percentile = np.percentile(D_A->B + D_B->A, q) - the two order statistics
+    come from the device, NumPy's linear interpolation between them is finished here - and the counts n_pred, n_gt, n_overlap,
+    n_surface_pred, n_surface_gt.  One launch sequence and one read-back of 128 bytes.  ValueError: a threshold that leaves a volume
+    empty (no surface to measure from)."""
+    import math
+    import numpy as np
+    rec = surface_metrics_record(pred, gt, thr_pred, thr_gt, q).cpu().numpy()
+    f = rec.view(np.float64)
+    status = int(rec[12])
+    if status:
+        empty = [name for bit, name in ((1, "pred"), (2, "gt")) if status & bit]
+        raise ValueError(f"surface_metrics_3d: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has no surface distances")
+    n_a, n_b, n_ab, s_a, s_b = (int(v) for v in rec[:5])
+    v = float(f[11])
+    lo, hi = math.sqrt(float(rec[9])), math.sqrt(float(rec[10]))
+    return {"dice_vessel": 2.0 * n_ab / (n_a + n_b), "assd": (float(f[5]) / s_a + float(f[6]) / s_b) / 2.0,
+            "hd": math.sqrt(float(max(rec[7], rec[8]))), "hd_percentile": _lerp(lo, hi, v - math.floor(v)), "q": float(q),
+            "n_pred": n_a, "n_gt": n_b, "n_overlap": n_ab, "n_surface_pred": s_a, "n_surface_gt": s_b}
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

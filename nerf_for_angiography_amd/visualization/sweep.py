@@ -9,7 +9,11 @@ data range 1), SSIM (:411-417: torchmetrics' StructuralSimilarityIndexMeasure(da
 no network - every view in one `afx_ssim` call, in fp64), normalised DOT 2D (:440-450), DICE 2D on the binarised projections
 (:433-438; prediction binarised by zeroing densities below `binary_thresh`, :172,349-352), and the two whole-volume scores DICE 3D and
 DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against the ground-truth volume sampled at the same points
-(`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope."""
+(`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope.
+
+Beyond the reference: the surface-distance scores of `reconstruction_surface_metrics` (SURFACE_METRICS) - the Dice of the vessel class, the
+average symmetric surface distance, the Hausdorff distance and its 95th percentile between the two thresholded grids
+(`afx_surface_metrics_3d`: two exact 3-D distance transforms and a radix select on the GPU)."""
 from __future__ import annotations
 
 import itertools
@@ -24,6 +28,9 @@ from ..render import density_grid, march_render_projection, render_projection
 # the reference's metric columns in its order (visualization.py:455-495); LPIPS and DISTS need pretrained networks
 METRICS = ("PSNR", "SSIM", "LPIPS", "DISTS", "DICE 2D", "DOT 2D", "DICE 3D", "DOT 3D")
 _NETWORK_METRICS = ("LPIPS", "DISTS")
+# not in the reference: how far the reconstructed vessel surface lies from the true one (reconstruction_surface_metrics), tabulated
+# after the reference's columns
+SURFACE_METRICS = ("DICE 3D VESSEL", "ASSD 3D", "HD 3D", "HD95 3D")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -61,7 +68,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     in the reference's order (PSNR, SSIM, DICE 2D, DOT 2D, DICE 3D, DOT 3D); LPIPS and DISTS raise NotImplementedError.  DICE 2D needs
     binary_targets, DICE 3D / DOT 3D need `volume` (a VoxelVolume): `reconstruction_metrics(model, volume, volume_outside, volume_points)`,
     volume_points defaulting to depth_samples_per_ray + 1 as upstream (:102), its two scores repeated on every row (:490, :495).  The
-    arguments are checked before any work on the GPU."""
+    names of SURFACE_METRICS (DICE 3D VESSEL, ASSD 3D, HD 3D, HD95 3D) may be listed too: they need `volume` as well, come from one
+    `reconstruction_surface_metrics(model, volume, volume_outside, volume_points)` call (threshold mean(gt), q = 95, distances in world
+    units), follow the reference's columns and are repeated on every row.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -113,6 +122,11 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
         dice3d, dot3d, _, _ = reconstruction_metrics(model, volume, volume_outside, pts)
         scores["DICE 3D"], scores["DOT 3D"] = [dice3d] * n, [dot3d] * n
+    if any(m in want for m in SURFACE_METRICS):
+        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+        surf, _, _ = reconstruction_surface_metrics(model, volume, volume_outside, pts)
+        for name, key in zip(SURFACE_METRICS, ("dice_vessel", "assd", "hd", "hd_percentile")):
+            scores[name] = [surf[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -123,9 +137,9 @@ def _check_metrics(metrics, binary_targets, volume):
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS]
+    unknown = [m for m in metrics if m not in METRICS + SURFACE_METRICS]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + SURFACE_METRICS)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -134,7 +148,9 @@ def _check_metrics(metrics, binary_targets, volume):
         raise ValueError("evaluation_sweep: DICE 2D needs binary_targets")
     if ("DICE 3D" in metrics or "DOT 3D" in metrics) and volume is None:
         raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS if m in metrics]
+    if any(m in metrics for m in SURFACE_METRICS) and volume is None:
+        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in SURFACE_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS + SURFACE_METRICS if m in metrics]
 
 
 @torch.no_grad()
@@ -160,6 +176,28 @@ def reconstruction_metrics(model, volume, outside, n):
     dice = agree.double() / gt.numel()
     dot = torch.mean(pred * gt, dtype=torch.float64)
     return float(dice), float(dot), pred, gt
+
+
+@torch.no_grad()
+def reconstruction_surface_metrics(model, volume, outside, n, threshold=None, q=95.0):
+    """How far the reconstructed vessel lies from the true one -> (scores, predicted grid, ground-truth grid).
+
+    The two grids are those of `reconstruction_metrics` (n^3 points over [-outside, outside]^3); both are thresholded at `threshold`,
+    which defaults to mean(gt) in fp32 - the rule DICE 3D uses; pass e.g. the sweep's binary_thresh instead.  scores
+    (`engine.surface_metrics_3d`; medpy.metric.binary's dc / assd / hd / hd95 definitions): dice_vessel, the Dice of the vessel class
+    alone (DICE 3D counts the background, more than 99 % of the grid, as well); assd, hd and hd_percentile (the q-th percentile of the
+    surface distances of both directions) in WORLD units - the voxel distances times the grid step 2 outside / (n - 1), multiplied in fp64;
+    voxel_size, threshold, q and the counts.  ValueError when the threshold leaves either grid empty."""
+    from ..engine import surface_metrics_3d
+    pred = density_grid(model, outside, int(n) - 1)
+    gt = ground_truth_grid(volume, outside, n)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    scores = surface_metrics_3d(pred, gt, thr, thr, q)
+    voxel = 2.0 * float(outside) / (int(n) - 1)
+    for key in ("assd", "hd", "hd_percentile"):
+        scores[key] = scores[key] * voxel
+    scores["voxel_size"], scores["threshold"] = voxel, thr
+    return scores, pred, gt
 
 
 @torch.no_grad()
