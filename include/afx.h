@@ -695,6 +695,44 @@ size_t afx_surface_metrics_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2
 int afx_surface_metrics_3d(const float* pred, const float* gt, int32_t n0, int32_t n1, int32_t n2, float thr_pred, float thr_gt, double q,
                            void* record, void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
 
+/* ---- Connected components of a 3-D mask: how many pieces a thresholded reconstruction has, how large they are, and the mask without
+ * its specks (scipy.ndimage.label with generate_binary_structure(3, connectivity)).  The rules above hold: device pointers, nothing
+ * allocated or synchronised, integer atomics only, hipGraph-capturable, the same bits on every run.
+ *
+ * afx_label_components_3d: fg is a uint8 volume [n0][n1][n2] (row-major; non-zero = foreground); connectivity 1, 2 or 3 joins voxels
+ * that differ by 1 along at most that many axes (6, 18 or 26 neighbours); beyond the grid is background.  labels (int32 [n0][n1][n2],
+ * required): 0 on the background, 1..K on the components, numbered in the order of their smallest linear index (raster order of their
+ * first voxel) - exactly scipy.ndimage.label's numbering, a pure function of the input.  sizes (uint32 [n0 n1 n2], may be NULL):
+ * sizes[l - 1] = the voxels of component l; K <= n0 n1 n2 always, and the entries at and beyond K are written as 0.  record:
+ * AFX_COMPONENTS_RECORD_SLOTS uint64 slots on the device:
+ *   [0] foreground voxels  [1] K  [2] the size of the largest component  [3] its label (0 when K = 0; of equal sizes the smaller
+ *   label)  [4] its smallest linear index  [5..7] zero
+ * Union-find in global memory (Komura 2015; Playne & Hawick 2018) as one fixed launch sequence with no host loop and no read-back:
+ * init (parent[v] = v); merge (every voxel unites itself with the 3, 9 or 13 foreground neighbours before it in raster order:
+ * find both roots, atomicMin(&parent[larger], smaller), go on from the returned value if that was not the expected root - roots only
+ * ever link to smaller indices, so a component's final root is its smallest linear index); flatten (every voxel's root into `labels`,
+ * roots counted per chunk of 2048 voxels); scan (one workgroup); rank (label of a root = 1 + the roots before it); relabel (with the
+ * sizes: one integer add per distinct label in a wave, passes of one label combined); finish (the record).
+ * AFX_E_INVALID: a null fg, labels or record, an axis outside 1..AFX_EDT3D_MAX_SIDE (indices then fit int32), connectivity outside
+ * 1..3.  Workspace (afx_label_components_3d_workspace_bytes; 0 for a refused shape), each region rounded up to 256 bytes, N = n0 n1 n2:
+ * two uint32 [N] (the parent links; the sizes when the caller passes none - the query does not know whether the call will, and the
+ * record's largest component needs the sizes either way), uint32 [ceil(N / 2048)] (roots per chunk) and 256 bytes of state;
+ * AFX_E_WORKSPACE when smaller, with *workspace_needed (when not NULL) set.  Cost at the top of the shape range: the scan and the
+ * finish are one workgroup each, over N / 2048 chunk counts and over the K sizes - microseconds for a vessel mask, but K can reach
+ * N / 2 (a 6-neighbour checkerboard), about 2 GB read by one workgroup at 1024^3.
+ *
+ * afx_filter_components_3d: out[v] (uint8) = 1 where labels[v] != 0, sizes[labels[v] - 1] >= min_size and - when largest_only is
+ * non-zero - labels[v] is the record's largest label; 0 elsewhere.  labels, sizes and record are those afx_label_components_3d wrote
+ * (sizes required here); the record is read on the device, so label-then-filter needs no host round trip.  AFX_E_INVALID: a null
+ * pointer, a refused shape, min_size == 0. */
+#define AFX_COMPONENTS_RECORD_SLOTS 8
+size_t afx_label_components_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_label_components_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, int32_t connectivity, int32_t* labels,
+                            uint32_t* sizes /* [n0 n1 n2], may be NULL */, void* record, void* workspace, size_t workspace_bytes,
+                            size_t* workspace_needed, void* stream);
+int afx_filter_components_3d(const int32_t* labels, const uint32_t* sizes, const void* record, int32_t n0, int32_t n1, int32_t n2,
+                             int32_t largest_only, uint32_t min_size, uint8_t* out, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

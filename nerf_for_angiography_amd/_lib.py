@@ -176,6 +176,11 @@ _SIGS = {
     "afx_surface_metrics_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "afx_surface_metrics_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_double, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_label_components_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "afx_label_components_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_filter_components_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p]),
 }
 
 _libs = {}

@@ -1197,6 +1197,76 @@ def surface_metrics_3d(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float, th
             "n_pred": n_a, "n_gt": n_b, "n_overlap": n_ab, "n_surface_pred": s_a, "n_surface_gt": s_b}
 
 
+COMPONENTS_RECORD_SLOTS = 8
+
+
+def components_record(x: torch.Tensor, connectivity: int = 1, labels=None, sizes=None, record=None, workspace=None):
+    """afx_label_components_3d on a contiguous uint8 [n0, n1, n2] device mask (non-zero = foreground) -> (labels, sizes, record):
+    labels int32 [n0, n1, n2] (0 = background, 1..K in scipy.ndimage.label's order), sizes an int32 tensor of n0 n1 n2 entries holding
+    the library's uint32 counts (sizes[l - 1] = the voxels of component l, 0 from K on), record the 8-slot int64 device record (layout
+    in include/afx.h: foreground voxels, K, the largest component's size, label and first voxel).  Launches only - nothing is read
+    back, so the call can be captured in a graph (pass all four buffers, the workspace of afx_label_components_3d_workspace_bytes
+    bytes, to keep the capture free of allocations)."""
+    lib = _lib.load()
+    _volume_on_gpu(x, "the mask", "label_components_3d")
+    if x.dtype != torch.uint8 or not x.is_contiguous():
+        raise ValueError(f"components_record: the mask must be a contiguous uint8 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
+    dev = x.device
+    n0, n1, n2 = x.shape
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    nbytes = int(lib.afx_label_components_3d_workspace_bytes(n0, n1, n2))
+    if labels is None:
+        labels = torch.empty(x.shape if nbytes else (1,), dtype=torch.int32, device=dev)
+    if sizes is None:
+        sizes = torch.empty(x.numel() if nbytes else 1, dtype=torch.int32, device=dev)
+    if record is None:
+        record = torch.empty(COMPONENTS_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.afx_label_components_3d(_ptr(x), n0, n1, n2, int(connectivity), _ptr(labels), _ptr(sizes), _ptr(record), _ptr(workspace),
+                                           workspace.numel(), None, Engine._stream(dev)), "afx_label_components_3d")
+    return labels, sizes, record
+
+
+def label_components_3d(x: torch.Tensor, connectivity: int = 1, return_sizes: bool = False):
+    """The connected components of a [n0, n1, n2] device tensor (any dtype, non-zero = foreground; connectivity 1, 2, 3 = 6, 18, 26
+    neighbours, scipy.ndimage.generate_binary_structure(3, connectivity)) -> (labels int32 [n0, n1, n2], K): scipy.ndimage.label's
+    result exactly - 0 on the background, the components numbered 1..K in raster order of their first voxel.  return_sizes:
+    (labels, K, sizes int64 [K]), sizes[l - 1] = the voxels of component l.  One launch sequence and one read-back of 64 bytes."""
+    _volume_on_gpu(x, "the volume", "label_components_3d")
+    labels, sizes, record = components_record((x != 0).to(torch.uint8).contiguous(), connectivity)
+    k = int(record[1])
+    if not return_sizes:
+        return labels, k
+    return labels, k, sizes[:k].to(torch.int64) & 0xffffffff      # the library's uint32 (held in an int32 tensor) as int64
+
+
+def filter_components_3d(x: torch.Tensor, connectivity: int = 1, largest_only: bool = False, min_size: int = 1) -> torch.Tensor:
+    """The foreground of a [n0, n1, n2] device tensor (non-zero) without its small pieces -> bool [n0, n1, n2]: the voxels whose
+    component has at least `min_size` voxels and, with largest_only, is the largest one (of equal sizes the one that comes first in
+    raster order).  afx_label_components_3d + afx_filter_components_3d: the second reads the first's record on the device, nothing is
+    read back.  A volume without foreground gives an empty mask."""
+    _volume_on_gpu(x, "the volume", "filter_components_3d")
+    labels, sizes, record = components_record((x != 0).to(torch.uint8).contiguous(), connectivity)
+    return components_filter(labels, sizes, record, largest_only, min_size).bool()
+
+
+def components_filter(labels: torch.Tensor, sizes: torch.Tensor, record: torch.Tensor, largest_only: bool = False, min_size: int = 1,
+                      out=None) -> torch.Tensor:
+    """afx_filter_components_3d on what `components_record` returned -> uint8 [n0, n1, n2] (1 = kept).  Launches only; pass `out` to
+    keep a graph capture free of allocations."""
+    lib = _lib.load()
+    _volume_on_gpu(labels, "labels", "filter_components_3d")
+    if not 1 <= int(min_size) <= 0xffffffff:
+        raise ValueError(f"filter_components_3d: min_size must lie in 1..2^32 - 1, got {min_size}")
+    n0, n1, n2 = labels.shape
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    _lib.check(lib.afx_filter_components_3d(_ptr(labels), _ptr(sizes), _ptr(record), n0, n1, n2, int(bool(largest_only)), int(min_size),
+                                            _ptr(out), Engine._stream(labels.device)), "afx_filter_components_3d")
+    return out
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

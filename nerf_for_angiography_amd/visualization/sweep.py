@@ -13,7 +13,9 @@ DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against 
 
 Beyond the reference: the surface-distance scores of `reconstruction_surface_metrics` (SURFACE_METRICS) - the Dice of the vessel class, the
 average symmetric surface distance, the Hausdorff distance and its 95th percentile between the two thresholded grids
-(`afx_surface_metrics_3d`: two exact 3-D distance transforms and a radix select on the GPU)."""
+(`afx_surface_metrics_3d`: two exact 3-D distance transforms and a radix select on the GPU) - and the topology scores of
+`reconstruction_topology_metrics` (TOPOLOGY_METRICS): into how many connected pieces the thresholded reconstruction falls, which share of
+it its largest piece holds, and the vessel Dice of that piece alone (`afx_label_components_3d`: union-find labelling on the GPU)."""
 from __future__ import annotations
 
 import itertools
@@ -31,6 +33,10 @@ _NETWORK_METRICS = ("LPIPS", "DISTS")
 # not in the reference: how far the reconstructed vessel surface lies from the true one (reconstruction_surface_metrics), tabulated
 # after the reference's columns
 SURFACE_METRICS = ("DICE 3D VESSEL", "ASSD 3D", "HD 3D", "HD95 3D")
+# not in the reference either: whether the reconstruction is one vessel tree or a tree plus floaters (reconstruction_topology_metrics),
+# tabulated after the surface columns
+TOPOLOGY_METRICS = ("COMPONENTS 3D", "LCC FRACTION 3D", "DICE 3D LCC")
+_EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -70,7 +76,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     volume_points defaulting to depth_samples_per_ray + 1 as upstream (:102), its two scores repeated on every row (:490, :495).  The
     names of SURFACE_METRICS (DICE 3D VESSEL, ASSD 3D, HD 3D, HD95 3D) may be listed too: they need `volume` as well, come from one
     `reconstruction_surface_metrics(model, volume, volume_outside, volume_points)` call (threshold mean(gt), q = 95, distances in world
-    units), follow the reference's columns and are repeated on every row.  The arguments are checked before any work on the GPU."""
+    units), follow the reference's columns and are repeated on every row.  So are the names of TOPOLOGY_METRICS (COMPONENTS 3D, LCC
+    FRACTION 3D, DICE 3D LCC), from one `reconstruction_topology_metrics` call (threshold mean(gt), 26 neighbours), behind the surface
+    columns.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -118,15 +126,21 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
     if "SSIM" in want:
         scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
-    if "DICE 3D" in want or "DOT 3D" in want:
+    if any(m in want for m in ("DICE 3D", "DOT 3D") + _EXTRA_METRICS):
+        # the two n^3 grids are evaluated once and shared by the three families of whole-volume scores
         pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
-        dice3d, dot3d, _, _ = reconstruction_metrics(model, volume, volume_outside, pts)
+        grids = _reconstruction_grids(model, volume, volume_outside, pts)
+    if "DICE 3D" in want or "DOT 3D" in want:
+        dice3d, dot3d, _, _ = reconstruction_metrics(model, volume, volume_outside, pts, grids=grids)
         scores["DICE 3D"], scores["DOT 3D"] = [dice3d] * n, [dot3d] * n
     if any(m in want for m in SURFACE_METRICS):
-        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
-        surf, _, _ = reconstruction_surface_metrics(model, volume, volume_outside, pts)
+        surf, _, _ = reconstruction_surface_metrics(model, volume, volume_outside, pts, grids=grids)
         for name, key in zip(SURFACE_METRICS, ("dice_vessel", "assd", "hd", "hd_percentile")):
             scores[name] = [surf[key]] * n
+    if any(m in want for m in TOPOLOGY_METRICS):
+        topo = reconstruction_topology_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(TOPOLOGY_METRICS, ("n_components", "lcc_fraction", "dice_lcc")):
+            scores[name] = [topo[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -137,9 +151,9 @@ def _check_metrics(metrics, binary_targets, volume):
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS + SURFACE_METRICS]
+    unknown = [m for m in metrics if m not in METRICS + _EXTRA_METRICS]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + SURFACE_METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _EXTRA_METRICS)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -148,9 +162,9 @@ def _check_metrics(metrics, binary_targets, volume):
         raise ValueError("evaluation_sweep: DICE 2D needs binary_targets")
     if ("DICE 3D" in metrics or "DOT 3D" in metrics) and volume is None:
         raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
-    if any(m in metrics for m in SURFACE_METRICS) and volume is None:
-        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in SURFACE_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS + SURFACE_METRICS if m in metrics]
+    if any(m in metrics for m in _EXTRA_METRICS) and volume is None:
+        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _EXTRA_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS + _EXTRA_METRICS if m in metrics]
 
 
 @torch.no_grad()
@@ -162,15 +176,23 @@ def ground_truth_grid(volume, outside, n):
 
 
 @torch.no_grad()
-def reconstruction_metrics(model, volume, outside, n):
+def _reconstruction_grids(model, volume, outside, n, grids=None):
+    """(predicted grid, ground-truth grid) at the n^3 points of the whole-volume scores; `grids`, when given, is that pair already
+    evaluated (both are bit-reproducible, so sharing them between the scores changes nothing)."""
+    if grids is not None:
+        return grids
+    return density_grid(model, outside, int(n) - 1), ground_truth_grid(volume, outside, n)
+
+
+@torch.no_grad()
+def reconstruction_metrics(model, volume, outside, n, grids=None):
     """DICE 3D and DOT 3D of visualization.py:480-495 for 'ct' data -> (dice_3d, dot_3d, predicted grid, ground-truth grid).
 
     The predicted grid is the model's density at every one of the n^3 points (query_occ masks nothing there: `occ_pts >= 0` keeps them all,
     :216-219), `density_grid(model, outside, n - 1)`; the ground truth `ground_truth_grid(volume, outside, n)`.  thr = mean(gt) in fp32 as
     torch.mean gives it; DICE 3D is the fraction of points where (pred >= thr) == (gt >= thr) (Dice(average='micro') over both classes of a
     0/1 volume, as DICE 2D); DOT 3D = mean(pred * gt), the products in fp32, their mean accumulated in fp64."""
-    pred = density_grid(model, outside, int(n) - 1)
-    gt = ground_truth_grid(volume, outside, n)
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
     thr = torch.mean(gt)
     agree = ((pred >= thr) == (gt >= thr)).sum()
     dice = agree.double() / gt.numel()
@@ -179,7 +201,7 @@ def reconstruction_metrics(model, volume, outside, n):
 
 
 @torch.no_grad()
-def reconstruction_surface_metrics(model, volume, outside, n, threshold=None, q=95.0):
+def reconstruction_surface_metrics(model, volume, outside, n, threshold=None, q=95.0, largest_component=False, connectivity=3, grids=None):
     """How far the reconstructed vessel lies from the true one -> (scores, predicted grid, ground-truth grid).
 
     The two grids are those of `reconstruction_metrics` (n^3 points over [-outside, outside]^3); both are thresholded at `threshold`,
@@ -187,17 +209,55 @@ def reconstruction_surface_metrics(model, volume, outside, n, threshold=None, q=
     (`engine.surface_metrics_3d`; medpy.metric.binary's dc / assd / hd / hd95 definitions): dice_vessel, the Dice of the vessel class
     alone (DICE 3D counts the background, more than 99 % of the grid, as well); assd, hd and hd_percentile (the q-th percentile of the
     surface distances of both directions) in WORLD units - the voxel distances times the grid step 2 outside / (n - 1), multiplied in fp64;
-    voxel_size, threshold, q and the counts.  ValueError when the threshold leaves either grid empty."""
-    from ..engine import surface_metrics_3d
-    pred = density_grid(model, outside, int(n) - 1)
-    gt = ground_truth_grid(volume, outside, n)
+    voxel_size, threshold, q and the counts.  ValueError when the threshold leaves either grid empty.  largest_component: the scores of
+    the largest connected component of pred >= threshold alone (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) - the surface distances
+    without the floaters, one stray voxel of which sets HD; the returned predicted grid is the unfiltered one.  grids: the (predicted,
+    ground-truth) pair another of the reconstruction_* functions returned for the same points, to save evaluating them again."""
+    from ..engine import filter_components_3d, surface_metrics_3d
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
     thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    scores = surface_metrics_3d(pred, gt, thr, thr, q)
+    if largest_component:
+        lcc = filter_components_3d(pred >= torch.tensor(thr, dtype=torch.float32, device=pred.device), connectivity, largest_only=True)
+        scores = surface_metrics_3d(lcc.float(), gt, 0.5, thr, q)
+    else:
+        scores = surface_metrics_3d(pred, gt, thr, thr, q)
     voxel = 2.0 * float(outside) / (int(n) - 1)
     for key in ("assd", "hd", "hd_percentile"):
         scores[key] = scores[key] * voxel
     scores["voxel_size"], scores["threshold"] = voxel, thr
     return scores, pred, gt
+
+
+@torch.no_grad()
+def reconstruction_topology_metrics(model, volume, outside, n, threshold=None, connectivity=3, grids=None):
+    """Is the reconstruction one vessel tree, or a tree plus debris -> (scores, predicted grid, ground-truth grid, mask of the largest
+    component of the prediction [bool, n^3]).
+
+    A = pred >= threshold, B = gt >= threshold on the grids of `reconstruction_surface_metrics` (threshold: mean(gt) in fp32 unless
+    given); L = the largest connected component of A (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours; of equal sizes the first in raster
+    order).  scores: n_components = K(A) and n_components_gt = K(B), the number of connected components (`engine.label_components_3d`:
+    scipy.ndimage.label's result); n_pred = |A|, n_gt = |B|, n_largest = |L|; lcc_fraction = |L| / |A|, the share of the predicted vessel
+    class that hangs together; dice_lcc = 2 |L & B| / (|L| + |B|), the vessel Dice after the floaters are dropped; connectivity and
+    threshold.  Both ratios are formed in fp64 from integer counts.  ValueError when the threshold leaves either grid empty.  grids: as
+    in `reconstruction_surface_metrics`."""
+    from ..engine import components_filter, components_record
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
+    a, b = (pred >= t32), (gt >= t32)
+    labels, sizes, rec_a = components_record(a.to(torch.uint8).contiguous(), connectivity)
+    lcc = components_filter(labels, sizes, rec_a, largest_only=True).bool()
+    rec_b = components_record(b.to(torch.uint8).contiguous(), connectivity)[2]
+    n_a, k_a, n_l = (int(v) for v in rec_a[:3].cpu())
+    n_b, k_b = (int(v) for v in rec_b[:2].cpu())
+    if n_a == 0 or n_b == 0:
+        empty = [name for cnt, name in ((n_a, "pred"), (n_b, "gt")) if cnt == 0]
+        raise ValueError(f"reconstruction_topology_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has no "
+                         "components")
+    n_lb = int((lcc & b).sum())
+    scores = {"n_components": k_a, "n_components_gt": k_b, "n_pred": n_a, "n_gt": n_b, "n_largest": n_l, "lcc_fraction": n_l / n_a,
+              "dice_lcc": 2.0 * n_lb / (n_l + n_b), "connectivity": int(connectivity), "threshold": thr}
+    return scores, pred, gt, lcc
 
 
 @torch.no_grad()
