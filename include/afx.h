@@ -733,6 +733,48 @@ int afx_label_components_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n
 int afx_filter_components_3d(const int32_t* labels, const uint32_t* sizes, const void* record, int32_t n0, int32_t n1, int32_t n2,
                              int32_t largest_only, uint32_t min_size, uint8_t* out, void* stream);
 
+/* ---- The centreline of a 3-D mask: thinning to medial curves, the skeleton that clDice (Shit et al. 2021) scores a vessel tree by.
+ * 8-subfield parallel thinning after Bertrand & Aktouf (1995) with the (26, 6)-simple points of Malandain & Bertrand (1992), defined
+ * here so that every implementation gives the same voxels.  The foreground is 26-connected, the background 6-connected, beyond the
+ * grid is background.  Passes repeat until one deletes nothing:
+ *   1. B = the foreground voxels that have a background face neighbour at the start of the pass (so a pass takes one layer);
+ *   2. for s = 0..7 in this order, subfield s = (i0 & 1) * 4 + (i1 & 1) * 2 + (i2 & 1): every voxel of B in subfield s is deleted
+ *      when, in the mask as it stands when subfield s starts, it does NOT have exactly one foreground 26-neighbour (curve end points
+ *      stay) and is SIMPLE: the foreground of its 26-neighbourhood (centre excluded) is exactly one 26-connected component, and the
+ *      background of its 18-neighbourhood holds exactly one 6-connected component (joined inside the 18-neighbourhood) that is
+ *      6-adjacent to the centre.
+ * Two voxels of one subfield are never 26-neighbours, so deleting a subfield's voxels at once equals deleting them one after another
+ * in any order: the result is a pure function of the input, equal voxel for voxel to the sequential restatement, the same bits on
+ * every run.  Deleting simple points keeps the 26-components, the 6-cavities and the tunnels (the Euler characteristic); the result
+ * is a subset of the input and thinning it again changes nothing.  Which of several equally medial voxels stays depends on the order
+ * of the subfields (a solid cube thins to its main diagonal, a tube's end may keep a short spur): a property of the definition;
+ * nothing is pruned.
+ *
+ * afx_skeletonize_3d: fg and skel are uint8 volumes [n0][n1][n2] (row-major; fg: non-zero = foreground; skel: 1 on the skeleton, 0
+ * elsewhere; skel may be fg).  record: AFX_SKELETON_RECORD_SLOTS uint64 slots on the device:
+ *   [0] passes run (the one that deleted nothing included)  [1] voxels deleted  [2] converged: 1 once a pass has deleted nothing
+ *   [3] voxels that remain  [4] voxels the last pass run deleted  [5] foreground voxels of the input  [6..7] zero
+ * Launches, all on `stream`, one after another: reset, init (skel = fg != 0, counted), then per pass: mark (B as lists of voxel
+ * indices, one list per subfield), 8 subfield launches (each voxel of a list gathers its 26 neighbours into a word, applies the rule
+ * and clears itself with a plain store; deletions counted by an integer add per wave), advance (one lane rolls the record).  Every
+ * launch of a pass returns at once when the record says converged, so issuing more passes than needed changes nothing.
+ * sync_every = 0: exactly max_passes passes are issued, nothing is read back, allocated or synchronised - hipGraph-capturable; look
+ * at record[2].  sync_every > 0: after every sync_every passes, and after the last, the call copies record[2] to the host and waits
+ * for the stream; it returns at convergence, or after max_passes passes with converged = 0 - still AFX_OK, skel is the mask after
+ * that many passes, and afx_last_error() says that it stopped early.  Not capturable in this form.
+ * AFX_E_INVALID: a null fg, skel or record, an axis outside 1..AFX_EDT3D_MAX_SIDE, max_passes < 1, sync_every < 0.  Workspace
+ * (afx_skeletonize_3d_workspace_bytes; 0 for a refused shape): uint32 [8][ceil(n0 / 2) ceil(n1 / 2) ceil(n2 / 2)], rounded up to 256
+ * bytes, and 256 bytes of state; AFX_E_WORKSPACE when smaller.
+ *
+ * afx_simple_point_26: the predicate SIMPLE on the host, by the very function the kernels call.  nbr holds the 3 x 3 x 3
+ * neighbourhood, bit (d0 + 1) * 9 + (d1 + 1) * 3 + (d2 + 1) for the offset (d0, d1, d2); bit 13 (the centre) and bits 27..31 are
+ * ignored.  Returns 1 or 0; needs no device. */
+#define AFX_SKELETON_RECORD_SLOTS 8
+size_t afx_skeletonize_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, int32_t max_passes, int32_t sync_every, uint8_t* skel,
+                       void* record, void* workspace, size_t workspace_bytes, void* stream);
+int afx_simple_point_26(uint32_t nbr);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

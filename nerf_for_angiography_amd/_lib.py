@@ -181,6 +181,10 @@ _SIGS = {
                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "afx_filter_components_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                            C.c_void_p, C.c_void_p]),
+    "afx_skeletonize_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "afx_skeletonize_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_size_t, C.c_void_p]),
+    "afx_simple_point_26": (C.c_int, [C.c_uint32]),
 }
 
 _libs = {}

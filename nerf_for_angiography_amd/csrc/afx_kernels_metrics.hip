@@ -737,7 +737,246 @@ CcBufs carve_components(afx::Carve& c, int32_t n0, int32_t n1, int32_t n2) {
   return b;
 }
 
+// ---- 3-D thinning to medial curves (afx_skeletonize_3d): 8-subfield parallel thinning after Bertrand & Aktouf (1995) with Malandain &
+// Bertrand's (1992) (26, 6)-simple points; the definition stands in include/afx.h.  Two voxels of one subfield are never 26-neighbours, so
+// a subfield launch reads no voxel that the same launch writes, and deleting its voxels together equals deleting them one by one: the
+// result is a pure function of the input.  Per pass: mark (the border voxels, as index lists per subfield), 8 subfield launches, advance.
+//
+// A 3 x 3 x 3 neighbourhood is a 27-bit word, bit (d0 + 1) * 9 + (d1 + 1) * 3 + (d2 + 1); the words below are sets of positions.
+constexpr uint32_t sk_where(int axis, int value) {    // the positions whose coordinate (0, 1, 2) along `axis` is `value`
+  uint32_t m = 0;
+  for (int b = 0; b < 27; ++b) {
+    const int c[3] = {b / 9, b / 3 % 3, b % 3};
+    if (c[axis] == value) m |= 1u << b;
+  }
+  return m;
+}
+constexpr uint32_t sk_offsets(int lo, int hi) {       // the positions with lo..hi non-zero offsets
+  uint32_t m = 0;
+  for (int b = 0; b < 27; ++b) {
+    const int k = (b / 9 != 1) + (b / 3 % 3 != 1) + (b % 3 != 1);
+    if (k >= lo && k <= hi) m |= 1u << b;
+  }
+  return m;
+}
+constexpr uint32_t SK_N26 = sk_offsets(1, 3), SK_N18 = sk_offsets(1, 2), SK_N6 = sk_offsets(1, 1);
+constexpr uint32_t SK_LO0 = sk_where(0, 0), SK_HI0 = sk_where(0, 2), SK_LO1 = sk_where(1, 0), SK_HI1 = sk_where(1, 2),
+                   SK_LO2 = sk_where(2, 0), SK_HI2 = sk_where(2, 2);
+static_assert(SK_N26 == 0x7ffdfffu && SK_N6 == ((1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22)), "bit layout");
+static_assert(__builtin_popcount(SK_N18) == 18 && SK_LO0 == 0x1ffu && SK_HI0 == 0x1ffu << 18 && SK_LO2 == 0x1249249u, "bit layout");
+
+// One step along an axis in both directions: a position's bit moves to the positions next to it along that axis (stride 9, 3, 1); the
+// masks keep a bit from leaving its row.  The adjacency of all 27 positions at once - the word form of a per-position adjacency table.
+__host__ __device__ inline uint32_t sk_step0(uint32_t x) { return ((x & ~SK_HI0) << 9) | (x >> 9); }
+__host__ __device__ inline uint32_t sk_step1(uint32_t x) { return ((x & ~SK_HI1) << 3) | ((x & ~SK_LO1) >> 3); }
+__host__ __device__ inline uint32_t sk_step2(uint32_t x) { return ((x & ~SK_HI2) << 1) | ((x & ~SK_LO2) >> 1); }
+
+// The positions of `in` that `seed` reaches: a flood fill on the word, grown until it stops changing (at most 26 rounds; all in registers).
+// C26: through the 26 neighbours (a step along each axis in turn is the 3 x 3 x 3 box); else through the 6 face neighbours.
+template <bool C26>
+__host__ __device__ inline uint32_t sk_fill(uint32_t seed, uint32_t in) {
+  for (;;) {
+    uint32_t g = seed;
+    if (C26) {
+      g |= sk_step2(g);
+      g |= sk_step1(g);
+      g |= sk_step0(g);
+    } else {
+      g |= sk_step0(seed) | sk_step1(seed) | sk_step2(seed);
+    }
+    g &= in;
+    if (g == seed) return seed;
+    seed = g;
+  }
+}
+
+// (26, 6)-simple (Malandain & Bertrand): the foreground of the 26-neighbourhood is exactly one 26-component, and the background of the
+// 18-neighbourhood has exactly one 6-component (joined inside the 18-neighbourhood) that touches the centre by a face.  Bit 13, the
+// centre, and the bits from 27 up are ignored.  The one predicate of the device kernels and of afx_simple_point_26.
+__host__ __device__ inline bool sk_simple(uint32_t nbr) {
+  const uint32_t f = nbr & SK_N26;
+  if (f == 0 || sk_fill<true>(f & (0u - f), f) != f) return false;
+  const uint32_t bg = ~nbr & SK_N18, faces = bg & SK_N6;
+  if (faces == 0) return false;
+  return (faces & ~sk_fill<false>(faces & (0u - faces), bg)) == 0;
+}
+
+// Step 2 of a pass for a border voxel: it goes when it is not a curve end point (exactly one foreground 26-neighbour) and is simple.
+__host__ __device__ inline bool sk_deletable(uint32_t nbr) { return __builtin_popcount(nbr & SK_N26) != 1 && sk_simple(nbr); }
+
+constexpr int SK_BLOCK = 256;
+constexpr int SK_CHUNK = 2048;                        // consecutive voxels per workgroup of the init and mark launches
+constexpr int SK_ITERS = SK_CHUNK / SK_BLOCK;
+constexpr unsigned SK_MAX_GRID = 1024;                // workgroups of a subfield launch; they stride over the list
+enum { SK_PASSES = 0, SK_DELETED = 1, SK_CONVERGED = 2, SK_REMAINING = 3, SK_DELETED_LAST = 4, SK_INPUT = 5 };      // the record's slots
+
+struct SkState { uint32_t count[8]; uint32_t deleted; uint32_t input; };      // 256 bytes of the workspace: list lengths, counters
+
+__global__ void k_sk_reset(SkState* st, unsigned long long* record) {
+  for (int s = 0; s < 8; ++s) st->count[s] = 0;
+  st->deleted = st->input = 0;
+  for (int q = 0; q < AFX_SKELETON_RECORD_SLOTS; ++q) record[q] = 0;
+}
+
+// skel = (fg != 0) as 0 / 1 (skel may be fg: every thread reads and writes its own voxels), the foreground counted once per wave
+__global__ void __launch_bounds__(SK_BLOCK) k_sk_init(const uint8_t* fg, uint32_t total, uint8_t* skel, SkState* st) {
+  uint32_t n = 0;                                     // of this wave (the same in every lane)
+#pragma unroll
+  for (int i = 0; i < SK_ITERS; ++i) {
+    const uint32_t v = blockIdx.x * SK_CHUNK + i * SK_BLOCK + threadIdx.x;
+    const bool on = v < total && fg[v] != 0;
+    if (v < total) skel[v] = on ? 1 : 0;
+    n += (uint32_t)__popcll(__ballot(on));
+  }
+  if ((threadIdx.x & 63) == 0 && n) atomicAdd(&st->input, n);
+}
+
+// Mark: B, the foreground voxels with a background face neighbour (beyond the grid is background), appended to the list of their
+// subfield (i & 1) * 4 + (j & 1) * 2 + (k & 1): list[s * cap ..], cap = ceil(n0 / 2) ceil(n1 / 2) ceil(n2 / 2) >= the voxels of any
+// subfield.  A wave reserves its places with one integer add per subfield it holds; the order inside a list is left to the hardware and
+// does not matter, since a subfield's voxels are decided independently of each other.
+__global__ void __launch_bounds__(SK_BLOCK) k_sk_mark(const uint8_t* __restrict__ skel, int n0, int n1, int n2, uint32_t cap,
+                                                      const unsigned long long* __restrict__ record, SkState* st, uint32_t* __restrict__ list) {
+  if (record[SK_CONVERGED]) return;
+  const int s0 = n1 * n2, lane = threadIdx.x & 63;
+  const uint32_t total = (uint32_t)n0 * (uint32_t)s0;
+#pragma unroll 1
+  for (int it = 0; it < SK_ITERS; ++it) {
+    const uint32_t v = blockIdx.x * SK_CHUNK + it * SK_BLOCK + threadIdx.x;
+    bool is_border = false;
+    uint32_t sub = 0;
+    if (v < total && skel[v]) {
+      const int i = (int)(v / (uint32_t)s0), r = (int)(v - (uint32_t)i * (uint32_t)s0), j = r / n2, k = r - j * n2;
+      is_border = i == 0 || i == n0 - 1 || j == 0 || j == n1 - 1 || k == 0 || k == n2 - 1;      // checked first: the loads below stay inside
+      if (!is_border) is_border = !skel[v - s0] || !skel[v + s0] || !skel[v - n2] || !skel[v + n2] || !skel[v - 1] || !skel[v + 1];
+      sub = (uint32_t)((i & 1) * 4 + (j & 1) * 2 + (k & 1));
+    }
+    unsigned long long todo = __ballot(is_border);    // every pass clears at least its first lane's bit
+    while (todo) {
+      const int first = __builtin_ctzll(todo);
+      const uint32_t sx = __shfl(sub, first);
+      const unsigned long long m = __ballot(is_border && sub == sx);
+      uint32_t base = 0;
+      if (lane == first) base = atomicAdd(&st->count[sx], (uint32_t)__popcll(m));
+      base = __shfl(base, first);
+      if (is_border && sub == sx) list[(size_t)sx * cap + base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = v;
+      todo &= ~m;
+    }
+  }
+}
+
+// Subfield s: every listed voxel gathers its 26 neighbours from the byte mask (beyond the grid: background) and is cleared, with a plain
+// store, when the rule says so.  Its neighbours all lie in other subfields, so nothing read here is written by this launch.  (The gather
+// is 26 byte loads per border voxel, some 10^4 voxels of a vessel mask, served by L2; an LDS tile with halo would stage mostly voxels no
+// candidate needs.  Not measured against one.)
+__global__ void __launch_bounds__(SK_BLOCK) k_sk_subfield(uint8_t* skel, int n0, int n1, int n2, uint32_t cap, int s,
+                                                          const unsigned long long* __restrict__ record, SkState* st,
+                                                          const uint32_t* __restrict__ list) {
+  if (record[SK_CONVERGED]) return;
+  const uint32_t n = st->count[s];                    // <= cap
+  const int s0 = n1 * n2;
+  uint32_t gone = 0;
+  for (uint32_t q = blockIdx.x * SK_BLOCK + threadIdx.x; q < n; q += gridDim.x * SK_BLOCK) {
+    const uint32_t v = list[(size_t)s * cap + q];
+    const int i = (int)(v / (uint32_t)s0), r = (int)(v - (uint32_t)i * (uint32_t)s0), j = r / n2, k = r - j * n2;
+    uint32_t nbr = 0;
+#pragma unroll
+    for (int di = -1; di <= 1; ++di)
+#pragma unroll
+      for (int dj = -1; dj <= 1; ++dj)
+#pragma unroll
+        for (int dk = -1; dk <= 1; ++dk) {
+          if (di == 0 && dj == 0 && dk == 0) continue;
+          const bool inside = i + di >= 0 && i + di < n0 && j + dj >= 0 && j + dj < n1 && k + dk >= 0 && k + dk < n2;
+          if (inside && skel[(int)v + di * s0 + dj * n2 + dk]) nbr |= 1u << ((di + 1) * 9 + (dj + 1) * 3 + (dk + 1));
+        }
+    if (sk_deletable(nbr)) {
+      skel[v] = 0;
+      ++gone;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) gone += __shfl_xor(gone, d);
+  if ((threadIdx.x & 63) == 0 && gone) atomicAdd(&st->deleted, gone);
+}
+
+// One lane: the pass is over.  Rolls the record and empties the lists for the next pass; a pass that deleted nothing sets converged,
+// after which every launch of a later pass returns at once and the record stands.
+__global__ void k_sk_advance(SkState* st, unsigned long long* record) {
+  if (!record[SK_CONVERGED]) {
+    const unsigned long long d = st->deleted;
+    record[SK_PASSES] += 1;
+    record[SK_DELETED] += d;
+    record[SK_DELETED_LAST] = d;
+    record[SK_INPUT] = st->input;
+    record[SK_REMAINING] = st->input - record[SK_DELETED];
+    if (d == 0) record[SK_CONVERGED] = 1;
+  }
+  st->deleted = 0;
+  for (int s = 0; s < 8; ++s) st->count[s] = 0;
+}
+
+uint32_t sk_cap(int32_t n0, int32_t n1, int32_t n2) { return (uint32_t)((n0 + 1) / 2) * (uint32_t)((n1 + 1) / 2) * (uint32_t)((n2 + 1) / 2); }
+
+struct SkBufs { uint32_t* list; SkState* st; };
+SkBufs carve_skeleton(afx::Carve& c, int32_t n0, int32_t n1, int32_t n2) {
+  SkBufs b;
+  b.list = c.take<uint32_t>((size_t)8 * sk_cap(n0, n1, n2) * sizeof(uint32_t));
+  b.st = c.take<SkState>(256);
+  return b;
+}
+
 }  // namespace
+
+extern "C" int afx_simple_point_26(uint32_t nbr) { return sk_simple(nbr) ? 1 : 0; }
+
+extern "C" size_t afx_skeletonize_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
+  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  afx::Carve c;
+  carve_skeleton(c, n0, n1, n2);
+  return c.end;
+}
+
+extern "C" int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, int32_t max_passes, int32_t sync_every, uint8_t* skel,
+                                  void* record, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "afx_skeletonize_3d";
+  if (!fg || !skel || !record) return afx::set_error(AFX_E_INVALID, who, "null volume, skeleton or record");
+  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (max_passes < 1) return afx::set_error(AFX_E_INVALID, who, "max_passes must be at least 1");
+  if (sync_every < 0) return afx::set_error(AFX_E_INVALID, who, "sync_every must be 0 (no read-back) or the passes between two read-backs");
+  const size_t need = afx_skeletonize_3d_workspace_bytes(n0, n1, n2);
+  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_device(fg, "the volume", who)) return rc;
+  if (int rc = afx::check_device(skel, "the skeleton", who)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  afx::Carve c;
+  c.base = (uintptr_t)workspace;
+  const SkBufs b = carve_skeleton(c, n0, n1, n2);
+  unsigned long long* rec = (unsigned long long*)record;
+  const uint32_t total = (uint32_t)n0 * (uint32_t)n1 * (uint32_t)n2, cap = sk_cap(n0, n1, n2);      // total <= 2^30
+  const unsigned chunks = (total + SK_CHUNK - 1) / SK_CHUNK, grid = std::min((cap + SK_BLOCK - 1) / SK_BLOCK, SK_MAX_GRID);
+  hipLaunchKernelGGL(k_sk_reset, dim3(1), dim3(1), 0, st, b.st, rec);
+  hipLaunchKernelGGL(k_sk_init, dim3(chunks), dim3(SK_BLOCK), 0, st, fg, total, skel, b.st);
+  for (int32_t p = 1; p <= max_passes; ++p) {
+    hipLaunchKernelGGL(k_sk_mark, dim3(chunks), dim3(SK_BLOCK), 0, st, (const uint8_t*)skel, (int)n0, (int)n1, (int)n2, cap,
+                       (const unsigned long long*)rec, b.st, b.list);
+    for (int s = 0; s < 8; ++s)
+      hipLaunchKernelGGL(k_sk_subfield, dim3(grid), dim3(SK_BLOCK), 0, st, skel, (int)n0, (int)n1, (int)n2, cap, s,
+                         (const unsigned long long*)rec, b.st, (const uint32_t*)b.list);
+    hipLaunchKernelGGL(k_sk_advance, dim3(1), dim3(1), 0, st, b.st, rec);
+    if (sync_every > 0 && (p % sync_every == 0 || p == max_passes)) {
+      if (int rc = afx::launched(who)) return rc;
+      unsigned long long converged = 0;
+      hipError_t e = hipMemcpyAsync(&converged, rec + SK_CONVERGED, sizeof converged, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return afx::set_error(AFX_E_HIP, who, hipGetErrorString(e));
+      if (converged) return AFX_OK;
+    }
+  }
+  if (sync_every > 0)                                 // not a failure: the mask after max_passes passes and a record that says converged = 0
+    return afx::set_error(AFX_OK, who, "stopped at max_passes before a pass deleted nothing: the record's converged slot is 0");
+  return afx::launched(who);
+}
 
 extern "C" size_t afx_label_components_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
   if (!edt3_shape_ok(n0, n1, n2)) return 0;

@@ -1267,6 +1267,52 @@ def components_filter(labels: torch.Tensor, sizes: torch.Tensor, record: torch.T
     return out
 
 
+SKELETON_RECORD_SLOTS = 8
+
+
+def skeleton_record(x: torch.Tensor, max_passes: int, sync_every: int = 0, skel=None, record=None, workspace=None):
+    """afx_skeletonize_3d on a contiguous uint8 [n0, n1, n2] device mask (non-zero = foreground) -> (skel, record): skel uint8
+    [n0, n1, n2] (1 on the medial curves; pass skel=x to thin in place), record the 8-slot int64 device record (layout in include/afx.h:
+    passes, deleted, converged, remaining, deleted by the last pass, input voxels).  sync_every = 0 issues exactly `max_passes` passes
+    and reads nothing back, so the call can be captured in a graph (pass all three buffers, the workspace of
+    afx_skeletonize_3d_workspace_bytes bytes, to keep the capture free of allocations; passes beyond convergence change nothing);
+    sync_every > 0 lets the library look at the record every so many passes and stop at convergence."""
+    lib = _lib.load()
+    _volume_on_gpu(x, "the mask", "skeletonize_3d")
+    if x.dtype != torch.uint8 or not x.is_contiguous():
+        raise ValueError(f"skeleton_record: the mask must be a contiguous uint8 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
+    dev = x.device
+    n0, n1, n2 = x.shape
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    nbytes = int(lib.afx_skeletonize_3d_workspace_bytes(n0, n1, n2))
+    if skel is None:
+        skel = torch.empty(x.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.empty(SKELETON_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.afx_skeletonize_3d(_ptr(x), n0, n1, n2, int(max_passes), int(sync_every), _ptr(skel), _ptr(record), _ptr(workspace),
+                                      workspace.numel(), Engine._stream(dev)), "afx_skeletonize_3d")
+    return skel, record
+
+
+def skeletonize_3d(x: torch.Tensor, max_passes=None, return_record: bool = False):
+    """The medial curves of a [n0, n1, n2] device tensor (any dtype, non-zero = foreground) -> bool [n0, n1, n2]: 8-subfield parallel
+    thinning with (26, 6)-simple points, curve end points kept (the definition in include/afx.h) - the same 26-components, cavities and
+    tunnels as the input, a subset of it, a pure function of it.  max_passes: stop after that many passes (None: run until a pass
+    deletes nothing; the library looks at its record every 4 passes).  return_record: (skeleton, record) with record = {"passes",
+    "deleted", "converged", "remaining", "deleted_last", "input"}; converged is 0 when max_passes came first."""
+    _volume_on_gpu(x, "the volume", "skeletonize_3d")
+    fg = (x != 0).to(torch.uint8).contiguous()
+    if max_passes is None:
+        max_passes = min(fg.numel() + 1, 2 ** 31 - 1)      # every pass but the last deletes a voxel: never reached
+    skel, record = skeleton_record(fg, max_passes, sync_every=4, skel=fg)
+    if not return_record:
+        return skel.bool()
+    r = record.cpu().tolist()
+    return skel.bool(), dict(zip(("passes", "deleted", "converged", "remaining", "deleted_last", "input"), r))
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

@@ -15,7 +15,9 @@ Beyond the reference: the surface-distance scores of `reconstruction_surface_met
 average symmetric surface distance, the Hausdorff distance and its 95th percentile between the two thresholded grids
 (`afx_surface_metrics_3d`: two exact 3-D distance transforms and a radix select on the GPU) - and the topology scores of
 `reconstruction_topology_metrics` (TOPOLOGY_METRICS): into how many connected pieces the thresholded reconstruction falls, which share of
-it its largest piece holds, and the vessel Dice of that piece alone (`afx_label_components_3d`: union-find labelling on the GPU)."""
+it its largest piece holds, and the vessel Dice of that piece alone (`afx_label_components_3d`: union-find labelling on the GPU) - and the
+centreline scores of `reconstruction_centreline_metrics` (CENTRELINE_METRICS): clDice and its two halves, topology precision and
+sensitivity, from the medial curves of both masks (`afx_skeletonize_3d`: parallel thinning on the GPU)."""
 from __future__ import annotations
 
 import itertools
@@ -36,7 +38,10 @@ SURFACE_METRICS = ("DICE 3D VESSEL", "ASSD 3D", "HD 3D", "HD95 3D")
 # not in the reference either: whether the reconstruction is one vessel tree or a tree plus floaters (reconstruction_topology_metrics),
 # tabulated after the surface columns
 TOPOLOGY_METRICS = ("COMPONENTS 3D", "LCC FRACTION 3D", "DICE 3D LCC")
-_EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS
+# and whether the reconstruction follows the true vessel tree's centrelines (reconstruction_centreline_metrics; clDice, Shit et al. 2021),
+# tabulated after the topology columns
+CENTRELINE_METRICS = ("CLDICE 3D", "TPREC 3D", "TSENS 3D")
+_EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -78,7 +83,8 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     `reconstruction_surface_metrics(model, volume, volume_outside, volume_points)` call (threshold mean(gt), q = 95, distances in world
     units), follow the reference's columns and are repeated on every row.  So are the names of TOPOLOGY_METRICS (COMPONENTS 3D, LCC
     FRACTION 3D, DICE 3D LCC), from one `reconstruction_topology_metrics` call (threshold mean(gt), 26 neighbours), behind the surface
-    columns.  The arguments are checked before any work on the GPU."""
+    columns, and the names of CENTRELINE_METRICS (CLDICE 3D, TPREC 3D, TSENS 3D), from one `reconstruction_centreline_metrics` call (threshold
+    mean(gt)), behind the topology columns.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -141,6 +147,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         topo = reconstruction_topology_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(TOPOLOGY_METRICS, ("n_components", "lcc_fraction", "dice_lcc")):
             scores[name] = [topo[key]] * n
+    if any(m in want for m in CENTRELINE_METRICS):
+        line = reconstruction_centreline_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(CENTRELINE_METRICS, ("cldice", "tprec", "tsens")):
+            scores[name] = [line[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -258,6 +268,64 @@ def reconstruction_topology_metrics(model, volume, outside, n, threshold=None, c
     scores = {"n_components": k_a, "n_components_gt": k_b, "n_pred": n_a, "n_gt": n_b, "n_largest": n_l, "lcc_fraction": n_l / n_a,
               "dice_lcc": 2.0 * n_lb / (n_l + n_b), "connectivity": int(connectivity), "threshold": thr}
     return scores, pred, gt, lcc
+
+
+def cldice_scores(vp, vl, sp, sl):
+    """clDice (Shit et al. 2021) of two bool masks V_P, V_L and their skeletons S_P, S_L (tensors of one shape, on any device) ->
+    {"cldice", "tprec", "tsens", "n_skeleton", "n_skeleton_gt"}: tprec = |S_P & V_L| / |S_P|, tsens = |S_L & V_P| / |S_L|, cldice their
+    harmonic mean (0 when both are 0); integer counts, the ratios in fp64.  ValueError on an empty skeleton."""
+    n_sp, n_sl = int(sp.sum()), int(sl.sum())
+    if n_sp == 0 or n_sl == 0:
+        empty = [name for cnt, name in ((n_sp, "pred"), (n_sl, "gt")) if cnt == 0]
+        raise ValueError(f"cldice_scores: the skeleton of {' or '.join(empty)} is empty")
+    tprec, tsens = int((sp & vl).sum()) / n_sp, int((sl & vp).sum()) / n_sl
+    return {"cldice": 2.0 * tprec * tsens / (tprec + tsens) if tprec + tsens > 0 else 0.0, "tprec": tprec, "tsens": tsens,
+            "n_skeleton": n_sp, "n_skeleton_gt": n_sl}
+
+
+@torch.no_grad()
+def reconstruction_centreline_metrics(model, volume, outside, n, threshold=None, largest_component=False, grids=None):
+    """Does the reconstruction follow the centrelines of the true vessel tree -> (scores, predicted grid, ground-truth grid, skeleton of
+    the prediction, skeleton of the ground truth [bool, n^3 each]).
+
+    V_P = pred >= threshold, V_L = gt >= threshold on the grids of `reconstruction_topology_metrics` (threshold: mean(gt) in fp32 unless
+    given); S_P, S_L = their medial curves (`engine.skeletonize_3d`; largest_component: S_P is thinned from the largest 26-connected
+    component of V_P alone, `filter_components_3d(..., largest_only=True)`, the skeleton without the floaters; V_P itself stays whole).
+    clDice of Shit et al. (2021): tprec = |S_P & V_L| / |S_P|, tsens = |S_L & V_P| / |S_L|, cldice = 2 tprec tsens / (tprec + tsens)
+    (0 when both are 0), formed in fp64 from integer counts.  A thin branch the reconstruction loses costs tsens its whole length,
+    however few voxels it had.  Also: n_skeleton, n_skeleton_gt = |S_P|, |S_L|; n_end_points, n_end_points_gt, the skeleton voxels
+    with exactly one 26-neighbour in the skeleton; mean_radius, mean_radius_gt, the mean over the skeleton voxels of the mask's exact
+    distance transform (`engine.distance_transform_edt_3d` of the mask that was thinned: the vessel radius along the centreline), in
+    WORLD units - voxels times the grid step 2 outside / (n - 1), summed and multiplied in fp64; n_pred, n_gt, passes, passes_gt,
+    voxel_size and threshold.  ValueError when the threshold leaves either mask, or either skeleton, empty.  grids: as in
+    `reconstruction_surface_metrics`."""
+    from ..engine import distance_transform_edt_3d, filter_components_3d, skeletonize_3d
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
+    vp, vl = (pred >= t32), (gt >= t32)
+    n_p, n_l = int(vp.sum()), int(vl.sum())
+    if n_p == 0 or n_l == 0:
+        empty = [name for cnt, name in ((n_p, "pred"), (n_l, "gt")) if cnt == 0]
+        raise ValueError(f"reconstruction_centreline_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has "
+                         "no centreline")
+    body = filter_components_3d(vp, 3, largest_only=True) if largest_component else vp
+    sp, rec_p = skeletonize_3d(body, return_record=True)
+    sl, rec_l = skeletonize_3d(vl, return_record=True)
+    scores = cldice_scores(vp, vl, sp, sl)                      # (thinning keeps every component: only an empty mask has an empty skeleton)
+    n_sp, n_sl = scores["n_skeleton"], scores["n_skeleton_gt"]
+    voxel = 2.0 * float(outside) / (int(n) - 1)
+
+    def ends(s):                                              # skeleton voxels with exactly one 26-neighbour: 2 voxels in their 3 x 3 x 3 box
+        p = torch.nn.functional.pad(s.to(torch.int32), (1, 1, 1, 1, 1, 1))
+        box = sum(p[a:a + s.shape[0], b:b + s.shape[1], c:c + s.shape[2]] for a, b, c in itertools.product(range(3), repeat=3))
+        return int((s & (box == 2)).sum())
+
+    scores.update({"n_end_points": ends(sp), "n_end_points_gt": ends(sl),
+                   "mean_radius": float(distance_transform_edt_3d(body)[sp].sum()) / n_sp * voxel,
+                   "mean_radius_gt": float(distance_transform_edt_3d(vl)[sl].sum()) / n_sl * voxel,
+                   "n_pred": n_p, "n_gt": n_l, "passes": rec_p["passes"], "passes_gt": rec_l["passes"], "voxel_size": voxel, "threshold": thr})
+    return scores, pred, gt, sp, sl
 
 
 @torch.no_grad()
