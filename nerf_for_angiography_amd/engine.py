@@ -29,6 +29,33 @@ def _f32(t: torch.Tensor, name: str, device) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def ray_window(who: str, n_proj: int, width: int, height: int, ray_id0: int = 0, n_rays=None, ray_ids=None) -> int:
+    """The rays a pose-mode call asks for, out of the [n_proj, height, width] ray table -> their number.  `ray_ids` (any integer tensor)
+    names them one by one; otherwise they are ray_id0 .. ray_id0 + n_rays, n_rays defaulting to the rest of the table.  Anything outside
+    the table is refused here: the kernels index `poses` by ray id / (height width) without a check of their own."""
+    table = int(n_proj) * int(width) * int(height)
+    shape = f"the {int(n_proj)} x {int(height)} x {int(width)} table"
+    if int(n_proj) < 0 or int(width) < 0 or int(height) < 0:
+        raise ValueError(f"{who}: n_proj, height and width must be >= 0, got {shape}")
+    if ray_ids is not None:
+        if ray_ids.is_floating_point() or ray_ids.dtype == torch.bool:
+            raise ValueError(f"{who}: ray_ids: dtype {ray_ids.dtype}, expected an integer type")
+        n_rays = ray_ids.numel() if n_rays is None else int(n_rays)
+        if n_rays < 0 or n_rays > ray_ids.numel():
+            raise ValueError(f"{who}: n_rays = {n_rays} with {ray_ids.numel()} ray_ids")
+        if n_rays:
+            lo, hi = int(ray_ids.reshape(-1)[:n_rays].min()), int(ray_ids.reshape(-1)[:n_rays].max())
+            if lo < 0 or hi >= table:
+                raise ValueError(f"{who}: ray_ids {lo} .. {hi} outside {shape} (0 .. {table - 1})")
+        return n_rays
+    ray_id0 = int(ray_id0)
+    n_rays = table - ray_id0 if n_rays is None else int(n_rays)
+    if ray_id0 < 0 or n_rays < 0 or ray_id0 + n_rays > table:
+        what = "ray_id0" if ray_id0 < 0 or ray_id0 > table else "n_rays"
+        raise ValueError(f"{who}: {what}: rays {ray_id0} .. {ray_id0 + n_rays} outside {shape} (0 .. {table})")
+    return n_rays
+
+
 @dataclass
 class RenderSpec:
     """One ray batch for the fused renderer.
@@ -439,10 +466,7 @@ class Engine:
             if poses.device != dev or poses.dtype != torch.float64:
                 raise ValueError(f"march_render: poses must be float64 on {dev}")
             poses = poses[:, :3, :].contiguous()
-            if n_rays is None:
-                n_rays = poses.shape[0] * int(width) * int(height) - int(ray_id0)
-            if int(ray_id0) < 0 or int(ray_id0) + int(n_rays) > poses.shape[0] * int(width) * int(height):
-                raise ValueError(f"march_render: rays {ray_id0} .. {int(ray_id0) + int(n_rays)} outside the {poses.shape[0]} x {height} x {width} table")
+            n_rays = ray_window("march_render", poses.shape[0], width, height, ray_id0, n_rays)
             o = d = None
         else:
             o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
@@ -739,7 +763,9 @@ def ray_entropy_dense_backward(raw, rgb_map, ray_sums, d_entropy, threshold=0.4,
 
 def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None, dirs=None, poses=None, width=0, height=0,
                    focal=0.0, ray_ids=None, ray_id0=0, n_rays=None, type_ct=True):
-    """afx_project_volume: X-ray projection of a voxel volume (trilinear lookup) along rays -> pixel[R]."""
+    """afx_project_volume: X-ray projection of a voxel volume (trilinear lookup) along rays -> pixel[R].  Rays: origins / dirs [R,3]
+    float32, or poses [n_proj,3 or 4,4] + width / height / focal, generated in fp64 in the kernel: the rays `ray_ids` (any integer tensor)
+    of the [n_proj, H, W] table, or ray_id0 .. ray_id0 + n_rays of it (n_rays defaults to the rest).  Rays outside the table raise."""
     lib = _lib.load()
     dev = vol.device
     if not vol.is_cuda:
@@ -751,12 +777,16 @@ def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None,
     a = RenderArgs()
     keep = [vol, z]
     if poses is not None:
+        if poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] != 4:
+            raise ValueError(f"project_volume: poses: expected [n_proj, 3 or 4, 4], got {tuple(poses.shape)}")
+        n = ray_window("project_volume", poses.shape[0], width, height, ray_id0, n_rays, ray_ids)
         poses = poses[:, :3, :].to(dev, torch.float64).contiguous().reshape(-1, 12)
         keep.append(poses)
-        n = n_rays if n_rays is not None else (ray_ids.numel() if ray_ids is not None else poses.shape[0] * width * height - ray_id0)
         a.ray_mode, a.poses = _lib.RAYS_POSE, poses.data_ptr()
         if ray_ids is not None:
-            ray_ids = ray_ids.to(dev, torch.int32).contiguous()
+            if poses.shape[0] * int(width) * int(height) > 2 ** 31 - 1:
+                raise ValueError("project_volume: ray_ids are int32: the ray table must hold fewer than 2^31 rays")
+            ray_ids = ray_ids.reshape(-1).to(dev, torch.int32).contiguous()
             keep.append(ray_ids)
             a.ray_ids = ray_ids.data_ptr()
         a.ray_id0, a.width, a.height, a.focal = int(ray_id0), int(width), int(height), float(focal)
@@ -764,6 +794,8 @@ def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None,
         o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
         keep += [o, d]
         n = o.shape[0]
+        if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
+            raise ValueError(f"project_volume: origins/dirs: expected two [n_rays, 3] tensors, got {tuple(o.shape)} and {tuple(d.shape)}")
         a.ray_mode, a.origins, a.dirs = _lib.RAYS_ARRAYS, o.data_ptr(), d.data_ptr()
     pixel = torch.empty(int(n), dtype=torch.float32, device=dev)
     a.n_rays, a.n_samples, a.depth_mode, a.z, a.pixel = int(n), int(z.numel()), _lib.DEPTH_SHARED_Z, z.data_ptr(), pixel.data_ptr()

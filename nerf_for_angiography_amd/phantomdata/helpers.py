@@ -102,12 +102,16 @@ class VoxelVolume:
 
     def __init__(self, points_x, points_y, points_z, values, fill_value=None, device="cuda:0"):
         self.axes = [np.asarray(a, dtype=np.float64) for a in (points_x, points_y, points_z)]
-        for a in self.axes:
-            if len(a) < 2 or not np.allclose(np.diff(a), a[1] - a[0], rtol=1e-9, atol=1e-12):
-                raise ValueError("VoxelVolume: the grid must be regular (uniform spacing) along every axis")
+        for name, a in zip(("points_x", "points_y", "points_z"), self.axes):
+            if a.ndim != 1 or len(a) < 2:
+                raise ValueError(f"VoxelVolume: {name} needs at least 2 points along one dimension, got shape {a.shape}")
+            if not (np.diff(a) > 0).all():      # (origin + spacing * index with spacing > 0 is all the kernels know)
+                raise ValueError(f"VoxelVolume: {name} must be strictly ascending")
+            if not np.allclose(np.diff(a), a[1] - a[0], rtol=1e-9, atol=1e-12):
+                raise ValueError(f"VoxelVolume: {name}: the grid must be regular (uniform spacing) along every axis")
         v = np.asarray(values, dtype=np.float32)
         if v.shape != tuple(len(a) for a in self.axes):
-            raise ValueError("VoxelVolume: values shape does not match the axes")
+            raise ValueError(f"VoxelVolume: values has shape {v.shape}, the axes have {tuple(len(a) for a in self.axes)} points")
         self.fill_value = float(np.min(v)) if fill_value is None else float(fill_value)
         self.values = torch.from_numpy(np.ascontiguousarray(v)).to(device)
         self.origin = [float(a[0]) for a in self.axes]
