@@ -775,6 +775,70 @@ int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int32_t n2, in
                        void* record, void* workspace, size_t workspace_bytes, void* stream);
 int afx_simple_point_26(uint32_t nbr);
 
+/* ---- The reconstructed vessel as a surface: an indexed triangle mesh of the level set f = iso of a 3-D volume, and its area and
+ * enclosed volume.  Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cube, defined here so that every implementation
+ * gives the same mesh.  The rules above hold: device pointers, nothing allocated or synchronised, no atomics at all,
+ * hipGraph-capturable, the same bits on every run.
+ *
+ * The volume f is fp32 [n0][n1][n2], row-major; a voxel is INSIDE when f >= iso (afx_surface_metrics_3d's rule).  Values must be
+ * finite: a NaN voxel is outside, and the vertices on the edges that lead to it are NaN.  Every cube of eight neighbouring voxels is
+ * split into six tetrahedra, one per permutation p of the axes, numbered 0..5 in lexicographic order - (0,1,2) (0,2,1) (1,0,2) (1,2,0)
+ * (2,0,1) (2,1,0) - with the corners c0 = the cube's base, c1 = c0 + e[p0], c2 = c1 + e[p1], c3 = c0 + (1,1,1).  The split is the
+ * same in every cube, so neighbouring cubes agree on the diagonal of their common face: the surface is that of the continuous
+ * piecewise-linear interpolant of f on this triangulation, and no case is ambiguous.
+ *   Vertices: one per crossed edge of the triangulation (one end inside, one outside).  An edge belongs to its lexicographically smaller
+ *     end a and has one of seven directions d = 0..6: (0,0,1) (0,1,0) (0,1,1) (1,0,0) (1,0,1) (1,1,0) (1,1,1); b = a + direction.  The
+ *     vertex ids 0..V-1 increase with the key linear_index(a) * 7 + d: the mesh is welded and its numbering canonical.  Position, every
+ *     operation in fp64 and rounded on its own: t = ((double)iso - (double)f[a]) / ((double)f[b] - (double)f[a]); q[x] = (double)a[x] + t
+ *     on the axes where b differs from a, (double)a[x] on the others; w[r] = ((o[r] + m[r][0] q[0]) + m[r][1] q[1]) + m[r][2] q[2] with
+ *     index_to_world = { m[0][0], m[0][1], m[0][2], o[0], m[1][0], ... o[2] } (12 doubles on the host); w is rounded to fp32.
+ *   Triangles: by cube in raster order of its base, then by tetrahedron p = 0..5.  A tetrahedron with one corner L on one side and
+ *     X < Y < Z (in the order c0..c3) on the other gives one triangle, of the vertices on L-X, L-Y, L-Z; one with the corners A < B
+ *     inside and C < D outside gives two, (AC, AD, BD) and (AC, BD, BC) - the quadrilateral AC, AD, BD, BC cut along AC-BD.  Winding:
+ *     the right-hand-rule normal of (v0, v1, v2) in WORLD space points from inside to outside; where that asks for the other
+ *     orientation the last two vertices of the triangle are exchanged ((LX, LZ, LY); (AC, BD, AD) and (AC, BC, BD)).  The winding is
+ *     therefore reversed when det(m) < 0 (an index_to_world that exchanges two axes, as the density grid's meshgrid 'xy' layout asks).
+ *     Voxels exactly equal to iso are inside; the mesh stays combinatorially closed, some of its triangles degenerate to a point or a
+ *     line.
+ *
+ * afx_isosurface_3d: vertices is fp32 [max_vertices][3], triangles int32 [max_triangles][3]; record, AFX_ISOSURFACE_RECORD_SLOTS uint64
+ * slots on the device:
+ *   [0] V  [1] T  [2] E, the edges of the mesh  [3] B, its boundary edges (edges with one triangle: on the faces of the grid, where the
+ *   surface leaves it)  [4] the tetrahedra cut two and two  [5] status: bit 1 (value 1) V exceeds max_vertices, bit 2 (value 2) T exceeds
+ *   max_triangles  [6..7] zero
+ * The counts are the true ones whatever the capacities; nothing is written at or beyond a capacity (vertices and triangles below it are
+ * the same as in a call with room for all; with status bit 1 set, a triangle may name a vertex that was not written).  Both capacities
+ * 0 (the arrays may then be NULL) is the counting call.  E and B come from the classification, not from matching edges: every crossed
+ * triangular face of the triangulation carries exactly one mesh edge and every two-and-two tetrahedron one more, its diagonal: E = crossed
+ * faces + [4], B = the crossed faces in the six outer planes of the grid.  V - E + T is the Euler characteristic of the surface - of the
+ * interpolant's level set: the Kuhn split joins a voxel to 14 neighbours, so it is not the Euler number of a 6- or 26-connected mask.
+ * An axis of one voxel has no cube: the mesh is empty, every count 0.  Launches: classify (one thread per grid point: its edge mask, the
+ * triangles of its cube, the faces it owns, prefixes inside chunks of 1024 points, the chunk sums), scan (one workgroup: the chunk
+ * offsets, the record), emit (skipped by the counting call).
+ * AFX_E_INVALID: a null f, record or index_to_world; an axis outside 1..AFX_EDT3D_MAX_SIDE; a NaN iso; a capacity below 0 or above
+ * 2^31 - 1, or above 0 with a null array; a non-finite entry of index_to_world or det(m) = m00 (m11 m22 - m12 m21) - m01 (m10 m22 -
+ * m12 m20) + m02 (m10 m21 - m11 m20) equal to 0 or not finite.  Workspace (afx_isosurface_3d_workspace_bytes; 0 for a refused shape),
+ * each region rounded up to 256 bytes, N = n0 n1 n2, C = ceil(N / 1024): uint8 [N] (edge masks), two uint16 [N] (the vertex and triangle
+ * prefixes inside a chunk), five uint32 [C] (chunk sums) and two uint64 [C] (chunk offsets: 7 N vertices do not fit 32 bits);
+ * AFX_E_WORKSPACE when smaller, with *workspace_needed (when not NULL) set.
+ *
+ * afx_mesh_measures: out[0] (fp64, device) = the surface area, the sum over the triangles of |(v1 - v0) x (v2 - v0)| / 2; out[1] = the
+ * enclosed volume, the sum of (v0 - r) . ((v1 - r) x (v2 - r)) / 6 - positive for a closed mesh wound as above; r = ref_point (3
+ * doubles on the host; NULL = the origin), best chosen inside the mesh: the terms then cancel less.  fp64 from the fp32 vertices, no
+ * contraction; per-workgroup partial sums (strided per thread, then a tree) and one finishing workgroup: a fixed order for a given
+ * max_triangles.  V and T are read from `record` on the device (slots [0] and [1] of afx_isosurface_3d's record, cut to max_vertices
+ * and max_triangles), so extract-then-measure needs no host round trip; a triangle that names a vertex outside 0..V-1 adds nothing.
+ * AFX_E_INVALID: a null record or out, a capacity below 0 or above 2^31 - 1, or above 0 with a null array, a non-finite ref_point.
+ * Workspace (afx_mesh_measures_workspace_bytes): 2 x 2048 doubles; AFX_E_WORKSPACE when smaller. */
+#define AFX_ISOSURFACE_RECORD_SLOTS 8
+size_t afx_isosurface_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_isosurface_3d(const float* f, int32_t n0, int32_t n1, int32_t n2, float iso, const double index_to_world[12], float* vertices,
+                      int64_t max_vertices, int32_t* triangles, int64_t max_triangles, void* record, void* workspace, size_t workspace_bytes,
+                      size_t* workspace_needed, void* stream);
+size_t afx_mesh_measures_workspace_bytes(void);
+int afx_mesh_measures(const float* vertices, int64_t max_vertices, const int32_t* triangles, int64_t max_triangles, const void* record,
+                      const double ref_point[3], double* out, void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

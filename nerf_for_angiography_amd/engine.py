@@ -1345,6 +1345,118 @@ def skeletonize_3d(x: torch.Tensor, max_passes=None, return_record: bool = False
     return skel.bool(), dict(zip(("passes", "deleted", "converged", "remaining", "deleted_last", "input"), r))
 
 
+ISOSURFACE_RECORD_SLOTS = 8
+_IDENTITY_AFFINE = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _affine12(index_to_world, who: str):
+    """index_to_world as 12 doubles: rows m[r][0..2], o[r] (a [3, 4] array, a flat sequence of 12, None = the identity)."""
+    import numpy as np
+    a = np.asarray(_IDENTITY_AFFINE if index_to_world is None else index_to_world, dtype=np.float64).reshape(-1)
+    if a.size != 12:
+        raise ValueError(f"{who}: index_to_world must hold 12 numbers (a 3 x 4 matrix: rows m[r][0..2], o[r]), got {a.size}")
+    return a
+
+
+def isosurface_record(x: torch.Tensor, iso: float, index_to_world=None, max_vertices: int = 0, max_triangles: int = 0, vertices=None,
+                      triangles=None, record=None, workspace=None):
+    """afx_isosurface_3d on a float32 [n0, n1, n2] device volume -> (vertices float32 [max_vertices, 3], triangles int32
+    [max_triangles, 3], record): marching tetrahedra on the Kuhn split, the mesh of {x >= iso} in the canonical order of include/afx.h;
+    record the 8-slot int64 device record (V, T, E, B, the tetrahedra cut two and two, status bit 1: V > max_vertices, bit 2:
+    T > max_triangles).  The counts are the true ones whatever the capacities, and nothing is written beyond them: both capacities 0
+    is the counting call.  Launches only - nothing is read back, so the call can be captured in a graph (pass all four buffers, the
+    workspace of afx_isosurface_3d_workspace_bytes bytes, to keep the capture free of allocations)."""
+    lib = _lib.load()
+    _volume_on_gpu(x, "the volume", "isosurface_record")
+    dev = x.device
+    f = _f32(x, "the volume", dev)
+    n0, n1, n2 = f.shape
+    aff = (C.c_double * 12)(*_affine12(index_to_world, "isosurface_record"))
+    max_vertices, max_triangles = int(max_vertices), int(max_triangles)
+    # a capacity the library refuses gets a one-element buffer: the call reports the range instead of the allocator failing first
+    if vertices is None:
+        vertices = torch.empty((max_vertices if 0 <= max_vertices < 2 ** 31 else 1, 3), dtype=torch.float32, device=dev)
+    if triangles is None:
+        triangles = torch.empty((max_triangles if 0 <= max_triangles < 2 ** 31 else 1, 3), dtype=torch.int32, device=dev)
+    nbytes = int(lib.afx_isosurface_3d_workspace_bytes(n0, n1, n2))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.empty(ISOSURFACE_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    _lib.check(lib.afx_isosurface_3d(_ptr(f), n0, n1, n2, float(iso), aff, _ptr(vertices) if max_vertices else None, max_vertices,
+                                     _ptr(triangles) if max_triangles else None, max_triangles, _ptr(record), _ptr(workspace),
+                                     workspace.numel(), None, Engine._stream(dev)), "afx_isosurface_3d")
+    return vertices, triangles, record
+
+
+def extract_isosurface(x: torch.Tensor, iso: float, index_to_world=None, cap: bool = True, fill: float = 0.0):
+    """The surface {x = iso} of a [n0, n1, n2] device volume as an indexed triangle mesh -> (vertices float32 [V, 3], triangles int32
+    [T, 3], info): a voxel is inside when x >= iso, the vertices are welded and canonically numbered, the triangles wound so that
+    their normals point from inside to outside in the coordinates of index_to_world (12 numbers, rows m[r][0..2], o[r]; None = index
+    coordinates).  info = {"V", "T", "E", "B", "n22", "euler"}: vertices, triangles, edges, boundary edges, tetrahedra cut two and two,
+    and V - E + T.  The counting call, one read-back of the record (64 bytes), an exact allocation, the emitting call.
+    cap: one layer of `fill` is put around the volume first (the affine moves by one index, so the positions do not), which closes the
+    surface where the vessel leaves the grid: B = 0.  ValueError when fill >= iso (the cap would be inside)."""
+    _volume_on_gpu(x, "the volume", "extract_isosurface")
+    dev = x.device
+    f = _f32(x, "the volume", dev)
+    aff = _affine12(index_to_world, "extract_isosurface").reshape(3, 4)
+    if cap:
+        if not float(fill) < float(iso):
+            raise ValueError(f"extract_isosurface: fill = {fill} must lie below iso = {iso}: the cap has to be outside")
+        f = torch.nn.functional.pad(f, (1, 1, 1, 1, 1, 1), value=float(fill))
+        aff = aff.copy()
+        aff[:, 3] = aff[:, 3] - aff[:, :3] @ [1.0, 1.0, 1.0]
+    nbytes = int(_lib.load().afx_isosurface_3d_workspace_bytes(*f.shape))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    rec = isosurface_record(f, iso, aff, workspace=ws)[2].cpu().tolist()
+    v, t = rec[0], rec[1]
+    if v > 2 ** 31 - 1 or t > 2 ** 31 - 1:
+        raise ValueError(f"extract_isosurface: the mesh has {v} vertices and {t} triangles, more than 2^31 - 1")
+    vertices, triangles, record = isosurface_record(f, iso, aff, v, t, workspace=ws)
+    info = {"V": v, "T": t, "E": rec[2], "B": rec[3], "n22": rec[4], "euler": v - rec[2] + t}
+    return vertices, triangles, info
+
+
+def mesh_measures_record(vertices: torch.Tensor, triangles: torch.Tensor, record: torch.Tensor, ref_point=None, out=None, workspace=None):
+    """afx_mesh_measures on what `isosurface_record` returned -> float64 [2] on the device: the surface area and the enclosed volume
+    about ref_point (3 numbers; None = the origin).  V and T are read from the record on the device.  Launches only; pass `out` and
+    the workspace of afx_mesh_measures_workspace_bytes bytes to keep a graph capture free of allocations."""
+    lib = _lib.load()
+    for t, name in ((vertices, "vertices"), (triangles, "triangles"), (record, "the record")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"mesh_measures: {name} must be a tensor on a GPU; there is no CPU path")
+    if vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or not triangles.is_contiguous():
+        raise ValueError("mesh_measures: vertices must be contiguous float32 [V, 3], triangles contiguous int32 [T, 3]")
+    dev = vertices.device
+    nbytes = int(lib.afx_mesh_measures_workspace_bytes())
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+    ref = (C.c_double * 3)(*[float(r) for r in (ref_point if ref_point is not None else (0.0, 0.0, 0.0))])
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    _lib.check(lib.afx_mesh_measures(_ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None, nt, _ptr(record), ref, _ptr(out),
+                                     _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_mesh_measures")
+    return out
+
+
+def mesh_measures(vertices: torch.Tensor, triangles: torch.Tensor, ref_point=None) -> dict:
+    """{"area", "volume"} of an indexed triangle mesh on the device (float32 [V, 3], int32 [T, 3]): the sum of the triangles' areas and
+    the enclosed volume, sum of (v0 - r) . ((v1 - r) x (v2 - r)) / 6, in fp64 in a fixed order - positive for a closed mesh whose
+    normals point outwards.  ref_point r: None = the mean of the vertices' bounding box (the terms then cancel least)."""
+    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"mesh_measures: {name} must be a tensor on a GPU; there is no CPU path")
+    v = vertices.to(torch.float32).contiguous().view(-1, 3)
+    t = triangles.to(torch.int32).contiguous().view(-1, 3)
+    if ref_point is None:
+        ref_point = ((v.min(0).values.double() + v.max(0).values.double()) / 2).cpu().tolist() if v.shape[0] else (0.0, 0.0, 0.0)
+    record = torch.tensor([v.shape[0], t.shape[0]] + [0] * (ISOSURFACE_RECORD_SLOTS - 2), dtype=torch.int64, device=v.device)
+    out = mesh_measures_record(v, t, record, ref_point).cpu().tolist()
+    return {"area": out[0], "volume": out[1]}
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

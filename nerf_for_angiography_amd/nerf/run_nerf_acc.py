@@ -111,6 +111,12 @@ def build_parser():
                    help='--march grid_ops: add LAMBDA * mean over the batch\'s rays of the per-ray entropy of the density profile to the loss '
                         '(get_ray_entropy of the reference, the sparse-view regulariser its packed loop leaves out; acc_ray_entropy, '
                         'afx_ray_entropy_packed); 0 (default): the MSE-only loop, and no `entropy` field in the log')
+    p.add_argument('--save_mesh', default=None, metavar='PATH',
+                   help='after training, write the final model\'s vessel surface to PATH (.stl: binary STL, .vtk: legacy VTK POLYDATA): the '
+                        'density grid at depth_samples + 1 points per axis, meshed at --mesh_threshold by marching tetrahedra on the GPU '
+                        '(afx_isosurface_3d), capped where it leaves the grid, in world coordinates; without the flag nothing changes')
+    p.add_argument('--mesh_threshold', type=float, default=0.05, metavar='SIGMA',
+                   help='--save_mesh: the density at which the surface is taken (default: the evaluation sweep\'s binary_thresh)')
     p.add_argument('--log_dir', default='runs/afx')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out_bias_init', type=float, default=-5.0,
@@ -140,6 +146,11 @@ def check_args(args):
                          "under autograd; --march dense, --march grid and the graphs are fused MSE steps)")
     if args.checkpoint_every < 0:
         raise ValueError("--checkpoint_every: needs N >= 0")
+    if args.save_mesh is not None:
+        if os.path.splitext(args.save_mesh)[1].lower() not in ('.stl', '.vtk'):
+            raise ValueError("--save_mesh: PATH must end in .stl or .vtk")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0 (the surface is capped with zero density around the grid)")
 
 
 def checkpoint_interval(checkpoint_every: int, graph_rounds: bool, round_len: int = 16) -> int:
@@ -440,9 +451,24 @@ def main(argv=None):
         if ckpt_every and (n_iter + 1) % ckpt_every == 0:
             last_state = write_state(n_iter + 1)
     log.close()
-    return dict(history=history, best_psnr=highest_psnr, best_iter=highest_iter, model=coarse_model,
-                optimizer=coarse_optimizer, test_image=test_img, log_dir=args.log_dir, acc_grid=acc_grid,
-                vessel_acc_grid=vessel_acc_grid)
+    result = dict(history=history, best_psnr=highest_psnr, best_iter=highest_iter, model=coarse_model,
+                  optimizer=coarse_optimizer, test_image=test_img, log_dir=args.log_dir, acc_grid=acc_grid,
+                  vessel_acc_grid=vessel_acc_grid)
+    if args.save_mesh is not None:
+        result['mesh_info'] = save_mesh(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_mesh)
+    return result
+
+
+def save_mesh(model, outside, n, threshold, path):
+    """--save_mesh: the surface {sigma = threshold} of the model's density grid (n points per axis over [-outside, outside]^3), capped, in
+    world coordinates, written by the file name's extension -> its info (V, T, E, B, euler, area, volume, threshold, path)."""
+    from ..render import density_grid
+    from ..visualization.mesh_io import write_mesh
+    from ..visualization.sweep import _grid_mesh
+    vertices, triangles, info = _grid_mesh(density_grid(model, outside, int(n) - 1), float(threshold), outside, n)
+    info.update(threshold=float(threshold), path=write_mesh(path, vertices, triangles))
+    print('mesh', {k: info[k] for k in ('V', 'T', 'euler', 'area', 'volume', 'path')}, flush=True)
+    return info
 
 
 if __name__ == "__main__":

@@ -17,7 +17,10 @@ average symmetric surface distance, the Hausdorff distance and its 95th percenti
 `reconstruction_topology_metrics` (TOPOLOGY_METRICS): into how many connected pieces the thresholded reconstruction falls, which share of
 it its largest piece holds, and the vessel Dice of that piece alone (`afx_label_components_3d`: union-find labelling on the GPU) - and the
 centreline scores of `reconstruction_centreline_metrics` (CENTRELINE_METRICS): clDice and its two halves, topology precision and
-sensitivity, from the medial curves of both masks (`afx_skeletonize_3d`: parallel thinning on the GPU)."""
+sensitivity, from the medial curves of both masks (`afx_skeletonize_3d`: parallel thinning on the GPU) - and the vessel itself as a
+surface: `reconstruction_mesh` (the triangle mesh of the thresholded reconstruction in world coordinates, `afx_isosurface_3d`: marching
+tetrahedra on the GPU; visualization/mesh_io.py writes it as STL or VTK) and the scores of `reconstruction_mesh_metrics` (MESH_METRICS):
+the enclosed volume and the surface area of the reconstruction over those of the truth, and the Euler characteristic of its surface."""
 from __future__ import annotations
 
 import itertools
@@ -41,7 +44,9 @@ TOPOLOGY_METRICS = ("COMPONENTS 3D", "LCC FRACTION 3D", "DICE 3D LCC")
 # and whether the reconstruction follows the true vessel tree's centrelines (reconstruction_centreline_metrics; clDice, Shit et al. 2021),
 # tabulated after the topology columns
 CENTRELINE_METRICS = ("CLDICE 3D", "TPREC 3D", "TSENS 3D")
-_EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS
+# and the reconstructed vessel measured as a surface (reconstruction_mesh_metrics), tabulated after the centreline columns
+MESH_METRICS = ("VOLUME RATIO 3D", "AREA RATIO 3D", "EULER 3D")
+_EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS + MESH_METRICS
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -84,7 +89,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     units), follow the reference's columns and are repeated on every row.  So are the names of TOPOLOGY_METRICS (COMPONENTS 3D, LCC
     FRACTION 3D, DICE 3D LCC), from one `reconstruction_topology_metrics` call (threshold mean(gt), 26 neighbours), behind the surface
     columns, and the names of CENTRELINE_METRICS (CLDICE 3D, TPREC 3D, TSENS 3D), from one `reconstruction_centreline_metrics` call (threshold
-    mean(gt)), behind the topology columns.  The arguments are checked before any work on the GPU."""
+    mean(gt)), behind the topology columns, and the names of MESH_METRICS (VOLUME RATIO 3D, AREA RATIO 3D, EULER 3D), from one
+    `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns.  The arguments are checked
+    before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -151,6 +158,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         line = reconstruction_centreline_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(CENTRELINE_METRICS, ("cldice", "tprec", "tsens")):
             scores[name] = [line[key]] * n
+    if any(m in want for m in MESH_METRICS):
+        mesh = reconstruction_mesh_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(MESH_METRICS, ("volume_ratio", "area_ratio", "euler")):
+            scores[name] = [mesh[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -326,6 +337,73 @@ def reconstruction_centreline_metrics(model, volume, outside, n, threshold=None,
                    "mean_radius_gt": float(distance_transform_edt_3d(vl)[sl].sum()) / n_sl * voxel,
                    "n_pred": n_p, "n_gt": n_l, "passes": rec_p["passes"], "passes_gt": rec_l["passes"], "voxel_size": voxel, "threshold": thr})
     return scores, pred, gt, sp, sl
+
+
+def grid_index_to_world(outside, n):
+    """The index-to-world map of the n^3 evaluation grids (density_grid, ground_truth_grid) as afx_isosurface_3d takes it, 12 numbers
+    (rows m[r][0..2], o[r]): index (i0, i1, i2) lies at (t[i1], t[i0], t[i2]), t[m] = m * (2 outside / (n - 1)) - outside (np.meshgrid's
+    'xy' order).  The first two axes are exchanged: det(m) < 0."""
+    step, lo = 2.0 * float(outside) / (int(n) - 1), -float(outside)
+    return (0.0, step, 0.0, lo, step, 0.0, 0.0, lo, 0.0, 0.0, step, lo)
+
+
+def _grid_mesh(x, iso, outside, n):
+    """(vertices, triangles, info) of the capped surface {x = iso} of an n^3 evaluation grid in world coordinates; info with its area
+    and enclosed volume (fp64, about the middle of the mesh's bounding box)."""
+    from ..engine import extract_isosurface, mesh_measures
+    vertices, triangles, info = extract_isosurface(x, iso, grid_index_to_world(outside, n), cap=True, fill=0.0)
+    if info["T"]:
+        info.update(mesh_measures(vertices, triangles))
+    else:
+        info.update(area=0.0, volume=0.0)
+    return vertices, triangles, info
+
+
+@torch.no_grad()
+def reconstruction_mesh(model, volume, outside, n, threshold=None, largest_component=False, connectivity=3, grids=None):
+    """The reconstructed vessel as a surface -> (vertices float32 [V, 3], triangles int32 [T, 3], info, predicted grid, ground-truth grid).
+
+    The mesh of {pred >= threshold} on the n^3 grid of `reconstruction_metrics`, in WORLD coordinates (`grid_index_to_world`), welded,
+    canonically numbered and wound so that the normals point out of the vessel (`engine.extract_isosurface`: marching tetrahedra on
+    the Kuhn split).  threshold: mean(gt) in fp32 unless given; it must be positive - the surface is capped with one layer of zero
+    density around the grid, so it is closed where the vessel leaves the grid.  largest_component: the mesh of the largest connected
+    component alone (`filter_components_3d`'s mask, `connectivity` 1, 2, 3 = 6, 18, 26 neighbours, meshed at 0.5: its surface runs
+    half-way between the voxels).  info: V, T, E, B, n22, euler = V - E + T, area and volume (world units, fp64), threshold.  The surface
+    is that of the piecewise-linear interpolant, which joins a voxel to 14 neighbours: euler is not the Euler number of the
+    26-connected mask.  An empty mesh (nothing reaches the threshold) has V = T = 0.  grids: as in `reconstruction_surface_metrics`."""
+    from ..engine import filter_components_3d
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    if largest_component:
+        lcc = filter_components_3d(pred >= torch.tensor(thr, dtype=torch.float32, device=pred.device), connectivity, largest_only=True)
+        vertices, triangles, info = _grid_mesh(lcc.float(), 0.5, outside, n)
+    else:
+        vertices, triangles, info = _grid_mesh(pred, thr, outside, n)
+    info["threshold"] = thr
+    return vertices, triangles, info, pred, gt
+
+
+@torch.no_grad()
+def reconstruction_mesh_metrics(model, volume, outside, n, threshold=None, largest_component=False, connectivity=3, grids=None):
+    """The reconstruction and the truth measured as surfaces -> (scores, predicted grid, ground-truth grid).
+
+    Both grids are meshed at `threshold` as in `reconstruction_mesh` (largest_component filters the prediction only).  scores: area,
+    volume (world units, fp64), euler, n_vertices, n_triangles, n_edges of the prediction, the same with the suffix _gt of the truth,
+    volume_ratio = volume / volume_gt and area_ratio = area / area_gt (fp64), threshold and voxel_size.  ValueError when either mesh
+    is empty."""
+    vertices, triangles, info, pred, gt = reconstruction_mesh(model, volume, outside, n, threshold, largest_component, connectivity, grids)
+    thr = info["threshold"]
+    info_gt = _grid_mesh(gt, thr, outside, n)[2]
+    if info["T"] == 0 or info_gt["T"] == 0:
+        empty = [name for i, name in ((info, "pred"), (info_gt, "gt")) if i["T"] == 0]
+        raise ValueError(f"reconstruction_mesh_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty mesh has no measures")
+    scores = {}
+    for suffix, i in (("", info), ("_gt", info_gt)):
+        scores.update({"area" + suffix: i["area"], "volume" + suffix: i["volume"], "euler" + suffix: i["euler"], "n_vertices" + suffix: i["V"],
+                       "n_triangles" + suffix: i["T"], "n_edges" + suffix: i["E"]})
+    scores.update(volume_ratio=scores["volume"] / scores["volume_gt"], area_ratio=scores["area"] / scores["area_gt"], threshold=thr,
+                  voxel_size=2.0 * float(outside) / (int(n) - 1))
+    return scores, pred, gt
 
 
 @torch.no_grad()
