@@ -254,6 +254,22 @@ __global__ void k_grid_select(const uint32_t* bits, int64_t n_cells, int64_t n_w
 }
 
 // --- ray marching (nerfacc.ray_marching, fixed-step lattice, AABB contraction) ----------------------------------------
+// Every operation of the lattice t_min + k dt, of the mid-points and of the position a step is decided at is rounded on its own (add_rn, sub_rn,
+// mul_rn below).  HIP's __fadd_rn / __fmul_rn are plain operators inside header functions that allow contraction, and hipcc fused
+// t_min + k dt and o + d m into one fma each: the lattice then differed by an ulp from the oracle's and from the one the host's
+// afx_march_max_steps walks, and a ray starting at max(0, near) could keep one step more than that bound.
+__device__ __forceinline__ float add_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+__device__ __forceinline__ float sub_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x - y;
+}
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
 struct MarchArgs {
   const float* org; const float* dir;      // [R,3]
   int64_t n_rays;
@@ -273,7 +289,7 @@ __device__ __forceinline__ void march_range(const MarchArgs& a, int64_t r, float
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       const float inv = __fdiv_rn(1.0f, d[q] == 0.f ? 1e-12f : d[q]);
-      const float t0 = __fmul_rn(__fsub_rn(a.aabb[q], o[q]), inv), t1 = __fmul_rn(__fsub_rn(a.aabb[3 + q], o[q]), inv);
+      const float t0 = mul_rn(sub_rn(a.aabb[q], o[q]), inv), t1 = mul_rn(sub_rn(a.aabb[3 + q], o[q]), inv);
       lo = fmaxf(lo, fminf(t0, t1));
       hi = fminf(hi, fmaxf(t0, t1));
     }
@@ -283,12 +299,12 @@ __device__ __forceinline__ void march_range(const MarchArgs& a, int64_t r, float
   }
   if (a.has_near) t_min = fmaxf(t_min, a.near_plane);
   if (a.has_far) t_max = fminf(t_max, a.far_plane);
-  float ns = ceilf(__fdiv_rn(__fsub_rn(t_max, t_min), a.dt));
+  float ns = ceilf(__fdiv_rn(sub_rn(t_max, t_min), a.dt));
   if (!(ns > 0.f)) ns = 0.f;
   n_steps = t_min >= 1e10f ? 0 : (ns > 2.0e9f ? 2000000000 : (int)ns);
   // nerfacc marches `while (t_mid < far)`: a step belongs to the ray when its MID-POINT lies before t_max (not its start), so the
   // ceil() above is corrected by the step(s) at the end whose mid-point falls outside / inside - same fp32 expressions as the loops below
-  auto mid_of = [&](int k) { const float ts = __fadd_rn(t_min, __fmul_rn((float)k, a.dt)); return __fmul_rn(__fadd_rn(ts, __fadd_rn(ts, a.dt)), 0.5f); };
+  auto mid_of = [&](int k) { const float ts = add_rn(t_min, mul_rn((float)k, a.dt)); return mul_rn(add_rn(ts, add_rn(ts, a.dt)), 0.5f); };
   if (n_steps < 2000000000) {
     while (n_steps > 0 && !(mid_of(n_steps - 1) < t_max)) --n_steps;
     for (int i = 0; i < 2 && t_min < 1e10f && mid_of(n_steps) < t_max; ++i) ++n_steps;
@@ -297,9 +313,9 @@ __device__ __forceinline__ void march_range(const MarchArgs& a, int64_t r, float
 }
 __device__ __forceinline__ bool march_keep(const MarchArgs& a, const float o[3], const float d[3], float ts, float te) {
   if (!a.bits) return true;
-  const float m = __fmul_rn(__fadd_rn(ts, te), 0.5f);
+  const float m = mul_rn(add_rn(ts, te), 0.5f);
   int64_t idx;
-  if (!grid_cell(a.g, __fadd_rn(o[0], __fmul_rn(d[0], m)), __fadd_rn(o[1], __fmul_rn(d[1], m)), __fadd_rn(o[2], __fmul_rn(d[2], m)), idx)) return false;
+  if (!grid_cell(a.g, add_rn(o[0], mul_rn(d[0], m)), add_rn(o[1], mul_rn(d[1], m)), add_rn(o[2], mul_rn(d[2], m)), idx)) return false;
   return (a.bits[idx >> 5] >> (idx & 31)) & 1u;
 }
 // The five per-ray kernels below run ONE WAVEFRONT PER RAY (blocks of 256 threads = 4 rays): the 64 lanes take 64 consecutive steps /
@@ -322,7 +338,7 @@ __global__ void __launch_bounds__(256) k_march_count(const MarchArgs a, int32_t*
     const int k = k0 + lane;
     bool keep = false;
     if (k < ns) {
-      const float ts = __fadd_rn(tmin, __fmul_rn((float)k, a.dt)), te = __fadd_rn(ts, a.dt);
+      const float ts = add_rn(tmin, mul_rn((float)k, a.dt)), te = add_rn(ts, a.dt);
       keep = march_keep(a, o, d, ts, te);
     }
     c += __popcll(__ballot(keep));
@@ -342,8 +358,8 @@ __global__ void __launch_bounds__(256) k_march_write(const MarchArgs a, const in
     bool keep = false;
     float ts = 0.f, te = 0.f;
     if (k < ns) {
-      ts = __fadd_rn(tmin, __fmul_rn((float)k, a.dt));
-      te = __fadd_rn(ts, a.dt);
+      ts = add_rn(tmin, mul_rn((float)k, a.dt));
+      te = add_rn(ts, a.dt);
       keep = march_keep(a, o, d, ts, te);
     }
     const uint64_t bal = __ballot(keep);
@@ -352,9 +368,9 @@ __global__ void __launch_bounds__(256) k_march_write(const MarchArgs a, const in
       ray_indices[w] = (int32_t)r; t_starts[w] = ts; t_ends[w] = te;
       if (mid_pts) {
         // positions = o + d * (t_s + t_e) / 2.0   (alpha_fn, nerf_helpers_acc.py:13-15)
-        const float sm = __fadd_rn(ts, te);
+        const float sm = add_rn(ts, te);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) mid_pts[3 * w + q] = __fadd_rn(o[q], __fdiv_rn(__fmul_rn(d[q], sm), 2.0f));
+        for (int q = 0; q < 3; ++q) mid_pts[3 * w + q] = add_rn(o[q], __fdiv_rn(mul_rn(d[q], sm), 2.0f));
       }
     }
     base += __popcll(bal);

@@ -962,18 +962,38 @@ def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits
         m.has_far, m.far_plane = 1, float(far_plane)
     m.step = float(step)
     if grid_bits is not None:
+        # k_march_count / k_march_write read grid_bits[cell >> 5] without a check of their own
+        if grid_aabb is None or grid_res is None:
+            raise ValueError("march: grid_bits needs grid_aabb and grid_res")
+        if not isinstance(grid_bits, torch.Tensor) or grid_bits.dtype != torch.int32 or not grid_bits.is_contiguous():
+            raise ValueError("march: grid_bits: expected a contiguous int32 tensor (32 cells per word)")
+        if o is not None and grid_bits.device != o.device:
+            raise ValueError(f"march: grid_bits on {grid_bits.device}, expected {o.device}")
+        res = [int(x) for x in grid_res]
+        if len(res) != 3 or min(res) <= 0 or len(list(grid_aabb)) != 6:
+            raise ValueError("march: grid_res must be three positive sizes and grid_aabb six numbers")
+        words = (res[0] * res[1] * res[2] + 31) // 32
+        if grid_bits.numel() < words:
+            raise ValueError(f"march: grid_bits has {grid_bits.numel()} words, the {res[0]} x {res[1]} x {res[2]} grid needs {words}")
         m.grid_bits = grid_bits.data_ptr()
         m.grid = _grid_desc(grid_aabb, grid_res)
 
 
 def march(origins, dirs, scene_aabb, near_plane, far_plane, step, grid_bits=None, grid_aabb=None, grid_res=None, want_points=True):
     """Grid-skipping fixed-step march -> packed (ray_indices int32 [n], t_starts [n], t_ends [n], mid-points [n,3] | None,
-    offsets int64 [R+1])."""
+    offsets int64 [R+1]).  Refused before any launch: rays that are not two equal [R, 3] arrays, a step <= 0, a march that neither a scene
+    box nor a far plane bounds, and a grid_bits that is not int32, on another device, without box and resolution, or shorter than the grid."""
     lib = _lib.load()
     dev = origins.device
     if dev.type != "cuda":
         raise AfxError("march: rays must live on a GPU; there is no CPU fallback")
     o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
+    if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"march: origins {tuple(o.shape)} and dirs {tuple(d.shape)}: expected [R, 3] both")
+    if not float(step) > 0:
+        raise ValueError(f"march: step {step} must be > 0")
+    if scene_aabb is None and far_plane is None:
+        raise ValueError("march: neither a scene box nor a far plane bounds the rays")
     m = _lib.MarchArgs()
     _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
     st = Engine._stream(dev)
