@@ -839,6 +839,69 @@ size_t afx_mesh_measures_workspace_bytes(void);
 int afx_mesh_measures(const float* vertices, int64_t max_vertices, const int32_t* triangles, int64_t max_triangles, const void* record,
                       const double ref_point[3], double* out, void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
 
+/* ---- A triangle mesh back into a volume: the signed distance field of an indexed triangle mesh on a regular grid, and the unsigned
+ * distance of arbitrary points to a mesh.  Defined here operation by operation, so that every implementation gives the same distance and
+ * the same nearest triangle.  The rules above hold: device pointers, nothing allocated or synchronised, no floating-point atomics (the
+ * record's 64-bit counters are integer atomics), hipGraph-capturable, the same bits on every run.
+ *
+ * Inputs: vertices fp32 [V][3] in world coordinates, triangles int32 [T][3].  Every coordinate is widened to fp64 first; all that follows
+ * is fp64, every operation rounded on its own (no contraction), dot(u, v) = (u0 v0 + u1 v1) + u2 v2, cross(u, v) = (u1 v2 - u2 v1,
+ * u2 v0 - u0 v2, u0 v1 - u1 v0).  Grid point (i0, i1, i2) lies at p[r] = ((o[r] + m[r][0] i0) + m[r][1] i1) + m[r][2] i2, index_to_world =
+ * { m[0][0], m[0][1], m[0][2], o[0], m[1][0], ... o[2] } as for afx_isosurface_3d, and is NOT rounded to fp32.  A triangle that names a
+ * vertex outside 0..V-1, or a vertex with a non-finite coordinate (afx_isosurface_3d emits NaN vertices next to NaN voxels), is SKIPPED:
+ * it takes part in nothing and is counted in the record.  Points (afx_mesh_point_distance) must be finite.
+ *   Distance.  d2(p, triangle a b c) = the minimum of
+ *     seg(p, a, b), seg(p, b, c), seg(p, c, a), with seg(p, a, b): e = b - a, w = p - a, den = dot(e, e), t = dot(w, e) / den when
+ *       den > 0, else 0; t below 0 becomes 0, above 1 becomes 1; q = a + t e (per component), g = p - q; seg = dot(g, g);
+ *     and, only when nn = dot(n, n) > 0 for n = cross(b - a, c - a) and the three edge functions dot(cross(b - a, p - a), n),
+ *       dot(cross(c - b, p - b), n), dot(cross(a - c, p - c), n) are all > 0: the plane term (h h) / nn, h = dot(p - a, n).
+ *     Nothing divides 0 by 0 on a triangle that degenerates to a line or a point (capped isosurface meshes contain such).
+ *   d2(p) = the minimum over the triangles that are not skipped, nearest(p) = the smallest index that attains it, d = sqrt(d2).  Without
+ *     such a triangle d = +inf and nearest = -1.  A minimum is exact: it does not depend on the order or on which other triangles were
+ *     looked at, which is what the culling below rests on.
+ *   Sign: the generalised winding number, robust on soups, degenerate triangles and meshes that leave the grid.  Per triangle, with
+ *     A = a - p, B = b - p, C = c - p, lA = sqrt(dot(A, A)) (lB, lC alike): term = 2 atan2(dot(A, cross(B, C)), (((lA lB) lC +
+ *     dot(A, B) lC) + dot(B, C) lA) + dot(C, A) lB); w(p) = (the terms added in triangle-index order, starting from 0) / (4 pi), 4 pi
+ *     rounded to fp64.  p is inside when w(p) >= 0.5.  The value written is fp32: -d inside and +d outside, rounded from fp64; d = 0 gives
+ *     +0.0.  (Negative inside is the reference's convention: rev_sigmoid(x, c1 = 2) is about 1 for negative x.)  The library's atan2 need
+ *     not equal another one to the bit: only the comparison with 0.5 and winding_out depend on it.
+ *
+ * afx_mesh_sdf_3d: sdf_out fp32 [n0][n1][n2]; nearest_out int32 [n0][n1][n2] or NULL; winding_out fp64 [n0][n1][n2] or NULL (w at every
+ * grid point).  flags: AFX_MESH_SDF_BRUTE switches the culling off (every point against every triangle: the comparator of the culled
+ * path, which must give the same bits); AFX_MESH_SDF_CLOSED is the caller's promise that the mesh has no boundary (true for a capped
+ * isosurface, record slot B = 0): w is then constant on any region the surface does not enter, so a brick no triangle comes near is
+ * evaluated once, at its centre, and the value shared - on a closed mesh this cannot change a sign.  A request for winding_out forces
+ * the per-point sum.  record, AFX_MESH_SDF_RECORD_SLOTS uint64 slots on the device:
+ *   [0] valid triangles  [1] skipped triangles  [2] bricks classed as clear (0 without AFX_MESH_SDF_CLOSED)  [3] point-triangle pairs the
+ *   distance pass evaluated (N T' without culling, T' = [0]: what the culling saved)  [4..7] zero
+ * Launches: zero the record; prepare (one thread per triangle: valid or not, the nine coordinates as fp64, the bounding sphere about the
+ * middle of its bounding box; skipped when T = 0); the grid kernel, one workgroup of 512 threads per brick of 8 x 8 x 8 neighbouring grid
+ * points.  It finds the exact distance dc of the brick's centre to the mesh, then walks the triangles in tiles of AFX_MESH_SDF_TILE
+ * through LDS: each thread tests one triangle's sphere against the ball of radius dc + 2 R about the centre (R = the farthest of the
+ * brick's eight world-space corners; a triangle beyond it is farther from every point of the brick than the nearest one), padded by a
+ * relative 1e-12 and 1e-12 of the coordinates' magnitude against the rounding of all those quantities; the survivors are compacted in
+ * index order and every thread walks them, skipping a survivor whose sphere lies beyond the nearest distance the thread has found so far
+ * (padded alike) and evaluating the exact distance of the others; [3] counts those evaluations.  T = 0 is valid: every distance +inf, every nearest -1.
+ * AFX_E_INVALID: a null sdf_out, record or index_to_world; a count below 0 or above 2^31 - 1, or above 0 with a null array; an axis
+ * outside 1..AFX_EDT3D_MAX_SIDE; a non-finite entry of index_to_world or det(m) (as for afx_isosurface_3d) 0 or not finite; unknown flag
+ * bits.  Workspace (afx_mesh_sdf_3d_workspace_bytes(T); 0 for a refused count), each region rounded up to 256 bytes, T' = max(T, 1):
+ * double [9][T'] and double [4][T']; AFX_E_WORKSPACE when smaller, with *workspace_needed (when not NULL) set.
+ *
+ * afx_mesh_point_distance: dist_out[i] (fp32, rounded from fp64) = d of point i of points fp32 [P][3], nearest_out int32 [P] or NULL; all
+ * pairs, one launch, no workspace: P T is small where it is used (the vertices of one mesh against the triangles of another).  record:
+ * the same slots, [2] = 0, [3] = P [0].  AFX_E_INVALID: a null record; a count below 0 or above 2^31 - 1; P > 0 with null points or
+ * dist_out; V or T above 0 with a null array. */
+#define AFX_MESH_SDF_RECORD_SLOTS 8
+#define AFX_MESH_SDF_TILE 512
+#define AFX_MESH_SDF_BRUTE 1u
+#define AFX_MESH_SDF_CLOSED 2u
+size_t afx_mesh_sdf_3d_workspace_bytes(int64_t n_triangles);
+int afx_mesh_sdf_3d(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, int32_t n0, int32_t n1, int32_t n2,
+                    const double index_to_world[12], uint32_t flags, float* sdf_out, int32_t* nearest_out, double* winding_out, void* record,
+                    void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
+int afx_mesh_point_distance(const float* points, int64_t n_points, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                            int64_t n_triangles, float* dist_out, int32_t* nearest_out, void* record, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -191,6 +191,11 @@ _SIGS = {
     "afx_mesh_measures_workspace_bytes": (C.c_size_t, []),
     "afx_mesh_measures": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_mesh_sdf_3d_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "afx_mesh_sdf_3d": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_mesh_point_distance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
 }
 
 _libs = {}

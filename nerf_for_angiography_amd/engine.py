@@ -1477,6 +1477,121 @@ def mesh_measures(vertices: torch.Tensor, triangles: torch.Tensor, ref_point=Non
     return {"area": out[0], "volume": out[1]}
 
 
+MESH_SDF_RECORD_SLOTS = 8
+MESH_SDF_TILE = 512          # AFX_MESH_SDF_TILE: triangles per LDS tile of the grid kernel
+MESH_SDF_BRUTE, MESH_SDF_CLOSED = 1, 2
+_MESH_SDF_RECORD_KEYS = ("valid_triangles", "skipped_triangles", "clear_bricks", "pairs_evaluated")
+
+
+def _mesh_on_gpu(vertices, triangles, who: str):
+    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    if vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or not triangles.is_contiguous() \
+            or vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError(f"{who}: vertices must be contiguous float32 [V, 3], triangles contiguous int32 [T, 3]")
+    if triangles.device != vertices.device:
+        raise ValueError(f"{who}: vertices and triangles live on different devices")
+
+
+def _as_mesh(vertices, triangles, who: str):
+    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    return vertices.to(torch.float32).contiguous().view(-1, 3), triangles.to(torch.int32).contiguous().view(-1, 3)
+
+
+def mesh_sdf_record(vertices: torch.Tensor, triangles: torch.Tensor, shape, index_to_world=None, flags: int = 0, sdf=None, nearest=None,
+                    winding=None, record=None, workspace=None):
+    """afx_mesh_sdf_3d on a mesh on the device (float32 [V, 3], int32 [T, 3]) -> (sdf float32 [n0, n1, n2], record): the signed distance
+    (negative inside) of every point of the grid `shape` whose point (i0, i1, i2) lies at index_to_world (12 numbers, rows m[r][0..2],
+    o[r]; None = index coordinates), as include/afx.h defines it.  flags: MESH_SDF_BRUTE | MESH_SDF_CLOSED.  nearest (int32 [n0, n1,
+    n2]) and winding (float64 [n0, n1, n2]) are filled when given.  record: the 8-slot int64 device record (valid triangles, skipped
+    triangles, clear bricks, pairs the distance pass evaluated).  Launches only - nothing is read back, so the call can be captured in
+    a graph (pass sdf, record and the workspace of afx_mesh_sdf_3d_workspace_bytes(T) bytes to keep the capture free of allocations)."""
+    lib = _lib.load()
+    _mesh_on_gpu(vertices, triangles, "mesh_sdf_record")
+    dev = vertices.device
+    n0, n1, n2 = (int(n) for n in shape)
+    aff = (C.c_double * 12)(*_affine12(index_to_world, "mesh_sdf_record"))
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    ok = all(1 <= n <= 1024 for n in (n0, n1, n2))
+    if sdf is None:
+        sdf = torch.empty((n0, n1, n2) if ok else (1,), dtype=torch.float32, device=dev)
+    for t, name, dtype in ((sdf, "sdf", torch.float32), (nearest, "nearest", torch.int32), (winding, "winding", torch.float64)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or (ok and t.numel() != n0 * n1 * n2)):
+            raise ValueError(f"mesh_sdf_record: {name} must be a contiguous {dtype} tensor of {n0 * n1 * n2} elements on {dev}")
+    nbytes = int(lib.afx_mesh_sdf_3d_workspace_bytes(nt))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.empty(MESH_SDF_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    _lib.check(lib.afx_mesh_sdf_3d(_ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None, nt, n0, n1, n2, aff, int(flags),
+                                   _ptr(sdf), _ptr(nearest) if nearest is not None else None, _ptr(winding) if winding is not None else None,
+                                   _ptr(record), _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_mesh_sdf_3d")
+    return sdf, record
+
+
+def mesh_signed_distance(vertices: torch.Tensor, triangles: torch.Tensor, shape, index_to_world=None, closed: bool = False, brute: bool = False,
+                         return_nearest: bool = False, return_winding: bool = False, return_record: bool = False):
+    """The signed distance field of a triangle mesh on the device (vertices [V, 3], triangles [T, 3]) on the regular grid `shape` ->
+    float32 [n0, n1, n2], negative inside: the exact distance to the nearest triangle, signed by the generalised winding number (robust
+    on soups, degenerate triangles, meshes that leave the grid).  closed: the promise that the mesh has no boundary (a capped
+    isosurface), which lets bricks the surface does not come near share one winding number.  brute: no culling (the comparator; the
+    same bits).  Further results follow in the order nearest (int32, the index of the nearest triangle, -1 without any), winding
+    (float64, which forces the per-point sum), record ({"valid_triangles", "skipped_triangles", "clear_bricks", "pairs_evaluated"})."""
+    v, t = _as_mesh(vertices, triangles, "mesh_signed_distance")
+    n0, n1, n2 = (int(n) for n in shape)
+    ok = all(1 <= n <= 1024 for n in (n0, n1, n2))
+    nearest = torch.empty((n0, n1, n2), dtype=torch.int32, device=v.device) if return_nearest and ok else None
+    winding = torch.empty((n0, n1, n2), dtype=torch.float64, device=v.device) if return_winding and ok else None
+    flags = (MESH_SDF_BRUTE if brute else 0) | (MESH_SDF_CLOSED if closed else 0)
+    sdf, record = mesh_sdf_record(v, t, (n0, n1, n2), index_to_world, flags, nearest=nearest, winding=winding)
+    out = [sdf] + ([nearest] if return_nearest else []) + ([winding] if return_winding else [])
+    if return_record:
+        out.append(dict(zip(_MESH_SDF_RECORD_KEYS, record.cpu().tolist())))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def mesh_point_distance_record(points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, dist=None, nearest=None, record=None):
+    """afx_mesh_point_distance: the unsigned distance of points (float32 [P, 3], device) to a mesh on the device -> (dist float32 [P],
+    record); nearest (int32 [P]) is filled when given.  All pairs, one launch, no workspace; nothing is read back (pass dist and record
+    to keep a graph capture free of allocations)."""
+    lib = _lib.load()
+    _mesh_on_gpu(vertices, triangles, "mesh_point_distance_record")
+    if not isinstance(points, torch.Tensor) or points.device.type != "cuda":
+        raise AfxError("mesh_point_distance_record: points must be a tensor on a GPU; there is no CPU path")
+    dev = vertices.device
+    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.device != dev:
+        raise ValueError(f"mesh_point_distance_record: points must be contiguous float32 [P, 3] on {dev}")
+    n = points.shape[0]
+    if dist is None:
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+    for t, name, dtype in ((dist, "dist", torch.float32), (nearest, "nearest", torch.int32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n):
+            raise ValueError(f"mesh_point_distance_record: {name} must be a contiguous {dtype} tensor of {n} elements on {dev}")
+    if record is None:
+        record = torch.empty(MESH_SDF_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    nv, nt = vertices.shape[0], triangles.shape[0]
+    _lib.check(lib.afx_mesh_point_distance(_ptr(points) if n else None, n, _ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None,
+                                           nt, _ptr(dist) if n else None, _ptr(nearest) if nearest is not None and n else None, _ptr(record),
+                                           Engine._stream(dev)), "afx_mesh_point_distance")
+    return dist, record
+
+
+def mesh_point_distance(points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, return_nearest: bool = False):
+    """The distance of every point ([P, 3], device) to the nearest triangle of a mesh on the device -> float32 [P] (+inf without a valid
+    triangle); with return_nearest also the index of that triangle (int32, the smallest one on a tie, -1 without any)."""
+    if not isinstance(points, torch.Tensor) or points.device.type != "cuda":
+        raise AfxError("mesh_point_distance: points must be a tensor on a GPU; there is no CPU path")
+    v, t = _as_mesh(vertices, triangles, "mesh_point_distance")
+    p = points.to(torch.float32).contiguous().view(-1, 3)
+    nearest = torch.empty(p.shape[0], dtype=torch.int32, device=v.device) if return_nearest else None
+    dist, _ = mesh_point_distance_record(p, v, t, nearest=nearest)
+    return (dist, nearest) if return_nearest else dist
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

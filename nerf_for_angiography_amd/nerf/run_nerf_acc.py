@@ -117,6 +117,12 @@ def build_parser():
                         '(afx_isosurface_3d), capped where it leaves the grid, in world coordinates; without the flag nothing changes')
     p.add_argument('--mesh_threshold', type=float, default=0.05, metavar='SIGMA',
                    help='--save_mesh: the density at which the surface is taken (default: the evaluation sweep\'s binary_thresh)')
+    p.add_argument('--phantom_mesh', default=None, metavar='PATH',
+                   help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
+                        'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
+                        'reference\'s sdftoray.py does; the mesh is centred and scaled to fill the scene.  Without the flag nothing changes')
+    p.add_argument('--phantom_points', type=int, default=201, metavar='N',
+                   help='--phantom_mesh: grid points along the longest side of the mesh (default 201)')
     p.add_argument('--log_dir', default='runs/afx')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--out_bias_init', type=float, default=-5.0,
@@ -146,6 +152,13 @@ def check_args(args):
                          "under autograd; --march dense, --march grid and the graphs are fused MSE steps)")
     if args.checkpoint_every < 0:
         raise ValueError("--checkpoint_every: needs N >= 0")
+    if args.phantom_mesh is not None:
+        if not args.synthetic:
+            raise ValueError("--phantom_mesh: needs --synthetic (the phantom replaces the capsule tree of the synthetic dataset)")
+        if os.path.splitext(args.phantom_mesh)[1].lower() not in ('.stl', '.vtk'):
+            raise ValueError("--phantom_mesh: PATH must end in .stl or .vtk")
+        if args.phantom_points < 2:
+            raise ValueError("--phantom_points: needs N >= 2")
     if args.save_mesh is not None:
         if os.path.splitext(args.save_mesh)[1].lower() not in ('.stl', '.vtk'):
             raise ValueError("--save_mesh: PATH must end in .stl or .vtk")
@@ -179,7 +192,13 @@ def main(argv=None):
     outside = 100
     file_name = f'limited-sparse-{limited_size}-{number_angles}-{center_point}' if binary else \
         f'background-{limited_size}-{number_angles}-{center_point}'
-    if args.synthetic:
+    if args.synthetic and args.phantom_mesh is not None:
+        proj_df, ray_df = ds.make_synthetic_dataset(ds.angle_grid(limited_size, int(number_angles), center_point),
+                                                    img_size=args.img_size, sampling_strategy=sampling_strategy,
+                                                    device=device, seed=args.seed, binary=binary,
+                                                    phantom=mesh_phantom(args.phantom_mesh, args.phantom_points, outside, device),
+                                                    projection_type='sdf')
+    elif args.synthetic:
         proj_df, ray_df = ds.make_synthetic_dataset(ds.angle_grid(limited_size, int(number_angles), center_point),
                                                     img_size=args.img_size, sampling_strategy=sampling_strategy,
                                                     device=device, seed=args.seed, binary=binary)
@@ -457,6 +476,20 @@ def main(argv=None):
     if args.save_mesh is not None:
         result['mesh_info'] = save_mesh(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_mesh)
     return result
+
+
+def mesh_phantom(path, n, outside, device):
+    """--phantom_mesh: the mesh in `path` as a VoxelVolume - centred, scaled so that its longest side takes three quarters of the scene
+    [-outside, outside]^3, its signed distance field on n points along that side passed through rev_sigmoid(., 2)."""
+    from ..phantomdata.helpers import voxel_volume_from_mesh
+    from ..visualization.mesh_io import read_mesh
+    vertices, triangles = read_mesh(path)
+    if len(triangles) == 0:
+        raise ValueError(f"--phantom_mesh: {path} holds no triangle")
+    longest = float((vertices.max(axis=0).astype(np.float64) - vertices.min(axis=0)).max())
+    if not longest > 0:
+        raise ValueError(f"--phantom_mesh: {path}: the mesh is a single point")
+    return voxel_volume_from_mesh(vertices, triangles, n=n, margin=0.1, vol_scale=1.5 * float(outside) / longest, device=device)
 
 
 def save_mesh(model, outside, n, threshold, path):

@@ -21,7 +21,8 @@ import pandas as pd
 import torch
 from scipy.ndimage import distance_transform_edt
 
-from .helpers import capsule_mu, capsule_tree, get_depth_values, get_ray_values, ray_tracing_fn as ray_tracing
+from .helpers import (VoxelVolume, capsule_mu, capsule_tree, get_depth_values, get_ray_values, ray_tracing as volume_ray_tracing,
+                      ray_tracing_fn as ray_tracing)
 
 PROJ_COLUMNS = ["image_id", "theta", "phi", "larm", "theta_shift", "phi_shift", "larm_shift", "translation_x",
                 "translation_y", "translation_z", "tform_cam2world", "unshifted_tform_cam2world", "image_data",
@@ -94,22 +95,32 @@ def angle_grid(limited_size: float, number_angles: int, center_point=(90, 0)):
 
 def make_synthetic_dataset(angles, img_size: int = 64, depth_samples_per_ray: int = 160, outside: float = 100.0,
                            src_z: float = 1500.0, sampling_strategy: str = "segmentation", device="cpu", seed: int = 0,
-                           binary: bool = True):
+                           binary: bool = True, phantom=None, projection_type: str = "ct"):
     """(proj_df, ray_df) for a capsule-tree phantom seen from `angles` = [(theta, phi), ...]; larm = 0, no shifts.
+    phantom: a `VoxelVolume` (e.g. `voxel_volume_from_mesh` of an STL vessel) that replaces the capsule tree; it is projected by
+    `helpers.ray_tracing` with type=projection_type ('ct', or 'sdf' as the reference's sdftoray.py projects a distance field).  None:
+    the capsule tree, as before.
     sampling_strategy 'frangi' computes the weights of all views with one sampling_weights_device call (`binary` False: with
     cttoray's percentile pre-step) and needs a GPU `device`; 'segmentation' and 'random' run the host sampling_weights per view."""
     w = h = int(img_size)
     focal = 13.0 * w                       # same field of view as the reference's f=1300 @ 100 px (SURVEY §8d)
     src_pt = np.array([0.0, 0.0, src_z])
     near, far = src_z - outside, src_z + outside
-    caps = capsule_tree(levels=5, seed=seed)
+    if phantom is not None and not isinstance(phantom, VoxelVolume):
+        raise ValueError(f"make_synthetic_dataset: phantom must be a VoxelVolume, got {type(phantom).__name__}")
+    if projection_type not in ("ct", "sdf"):
+        raise ValueError(f"make_synthetic_dataset: projection_type must be 'ct' or 'sdf', got {projection_type!r}")
+    caps = capsule_tree(levels=5, seed=seed) if phantom is None else None
     views = []
     for theta, phi in angles:
         o, d, mat, ii, jj = get_ray_values(theta, phi, 0.0, src_pt, w, h, focal, device)
         z = get_depth_values(near, far, depth_samples_per_ray, device, stratified=False)
         with torch.no_grad():
-            img = ray_tracing(lambda p: capsule_mu(p, caps), o.reshape(-1, 3).float(), d.reshape(-1, 3).float(),
-                              z.float(), batch_rays=8192).reshape(h, w).cpu()
+            if phantom is not None:
+                img = volume_ray_tracing(phantom, None, o, d, z, w, h, ii, jj, None, device, type=projection_type).reshape(h, w).cpu()
+            else:
+                img = ray_tracing(lambda p: capsule_mu(p, caps), o.reshape(-1, 3).float(), d.reshape(-1, 3).float(),
+                                  z.float(), batch_rays=8192).reshape(h, w).cpu()
         views.append((theta, phi, o, d, mat, ii, jj, z, img.numpy().astype(np.float64)))
     if sampling_strategy == "frangi":
         if torch.device(device).type != "cuda":

@@ -118,6 +118,50 @@ class VoxelVolume:
         self.spacing = [float(a[1] - a[0]) for a in self.axes]
 
 
+def voxel_volume_from_mesh(vertices, triangles, n=201, margin=0.1, vol_scale=1.0, centre=True, c1=2.0, closed=False, device="cuda:0",
+                           return_sdf=False):
+    """A triangle mesh (e.g. `visualization.mesh_io.read_mesh` of an STL vessel) as a `VoxelVolume` phantom: get_interpolator_from_vol_sdf
+    (helpers.py:72-100) on a signed distance field computed here (`engine.mesh_signed_distance`) instead of read from a file.
+
+    The mesh is scaled by vol_scale and (centre) the middle of its bounding box moved to the origin; a regular grid is laid over the box
+    grown on every side by `margin` times its longest side: n points along the longest side, the same spacing on the other axes (as many
+    points as cover them, at least 2), centred on the box.  values = rev_sigmoid(sdf, c1) - about 1 inside the vessel, where the distance is
+    negative - in fp64, stored as fp32; the fill value is their minimum.  closed: the promise that the mesh has no boundary
+    (`mesh_signed_distance`).  vertices [V, 3] / triangles [T, 3]: arrays or tensors.  return_sdf: (volume, sdf float32 [nx, ny, nz] on the
+    device)."""
+    from ..engine import mesh_signed_distance
+    if int(n) < 2 or not margin >= 0 or not vol_scale > 0:
+        raise ValueError(f"voxel_volume_from_mesh: need n >= 2, margin >= 0 and vol_scale > 0, got {n}, {margin}, {vol_scale}")
+    v = torch.as_tensor(np.asarray(vertices) if not isinstance(vertices, torch.Tensor) else vertices).to(device, torch.float64).reshape(-1, 3)
+    t = torch.as_tensor(np.asarray(triangles) if not isinstance(triangles, torch.Tensor) else triangles).to(device, torch.int32).reshape(-1, 3)
+    if v.shape[0] == 0 or not bool(torch.isfinite(v).all()):
+        raise ValueError("voxel_volume_from_mesh: the mesh needs vertices, all of them finite")
+    v = v * float(vol_scale)
+    lo, hi = v.min(0).values, v.max(0).values
+    if centre:
+        mid = (lo + hi) / 2
+        v, lo, hi = v - mid, lo - mid, hi - mid
+    lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
+    longest = float((hi - lo).max())
+    if not longest > 0:
+        raise ValueError("voxel_volume_from_mesh: the mesh is a single point")
+    pad = float(margin) * longest
+    h = (longest + 2 * pad) / (int(n) - 1)
+    axes = []
+    for k in range(3):
+        side = float(hi[k] - lo[k]) + 2 * pad
+        nk = max(2, int(np.ceil(side / h - 1e-9)) + 1)
+        axes.append((lo[k] + hi[k]) / 2 - h * (nk - 1) / 2 + h * np.arange(nk, dtype=np.float64))
+    # the field is sampled exactly where the volume says its samples are: origin + spacing * index, per axis
+    vol = VoxelVolume(axes[0], axes[1], axes[2], np.zeros(tuple(len(a) for a in axes), dtype=np.float32), fill_value=0.0, device=device)
+    (o0, o1, o2), (s0, s1, s2) = vol.origin, vol.spacing
+    sdf = mesh_signed_distance(v.to(torch.float32).contiguous(), t.contiguous(), tuple(vol.values.shape),
+                               (s0, 0.0, 0.0, o0, 0.0, s1, 0.0, o1, 0.0, 0.0, s2, o2), closed=closed)
+    vol.values = (1.0 / (1.0 + torch.exp(float(c1) * sdf.double()))).to(torch.float32)          # rev_sigmoid(sdf, c1) in fp64, as upstream
+    vol.fill_value = float(vol.values.min())
+    return (vol, sdf) if return_sdf else vol
+
+
 def ray_tracing(interpolator, angles, ray_origins, ray_directions, depth_values, img_width, img_height, ii, jj, batch_size,
                 device, proj_folder_name=None, type='ct', invert=False):
     """Upstream signature (helpers.py:192).  `interpolator`: a VoxelVolume (fused HIP projector; the tiling by

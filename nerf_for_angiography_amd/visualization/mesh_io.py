@@ -1,5 +1,8 @@
 """Triangle meshes on disk: binary STL (what the LCA phantom comes as) and legacy VTK POLYDATA (what the reference's viewer reads).
 
+`read_stl` / `read_vtk_polydata` / `read_mesh` read them back (STL also as ASCII): a mesh from disk becomes a phantom through
+`phantomdata.helpers.voxel_volume_from_mesh`.
+
 Host plumbing: the arrays are what `engine.extract_isosurface` / `sweep.reconstruction_mesh` return (tensors on any device, or arrays).
 Both writers write atomically, as nerf/checkpoint.py does: to a temporary name in the same directory, flushed, then os.replace - a
 write that fails half-way leaves no partial file and keeps a previous file as it was."""
@@ -91,3 +94,115 @@ def write_mesh(path, vertices, triangles):
     if ext == ".vtk":
         return write_vtk_polydata(path, vertices, triangles)
     raise ValueError(f"write_mesh: {path}: the name must end in .stl or .vtk")
+
+
+def _weld(corners):
+    """float32 [T, 3, 3] -> (vertices [V, 3], triangles [T, 3]): corners with the same bits become one vertex (-0.0 and 0.0 stay
+    apart), numbered in the order of their first appearance."""
+    flat = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 3)
+    if not len(flat):
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+    keys = flat.view(np.dtype((np.void, 12))).reshape(-1)
+    _, first, inverse = np.unique(keys, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                      # unique() sorts by bytes: back to the order of first appearance
+    rank = np.empty(len(order), dtype=np.int64)
+    rank[order] = np.arange(len(order))
+    return flat[first[order]].copy(), rank[inverse.reshape(-1)].reshape(-1, 3).astype(np.int32)
+
+
+def _stl_is_binary(raw):
+    """A binary STL is exactly 84 + 50 T bytes long; anything else has to parse as ASCII ('solid' in the header proves nothing)."""
+    return len(raw) >= 84 and len(raw) == 84 + 50 * int(np.frombuffer(raw, dtype="<u4", count=1, offset=80)[0])
+
+
+def read_stl(path, weld: bool = True):
+    """An STL file, binary or ASCII -> (vertices float32 [V, 3], triangles int32 [T, 3]).  STL is a triangle soup: weld=True merges
+    corners with identical bits into one vertex, numbered in the order of first appearance; weld=False keeps three vertices per
+    triangle.  The facet normals are not read: the winding carries the orientation.  ValueError on a truncated or malformed file."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if _stl_is_binary(raw):
+        rec = np.frombuffer(raw, dtype=np.dtype([("normal", "<f4", 3), ("corners", "<f4", (3, 3)), ("attr", "<u2")]), offset=84)
+        corners = rec["corners"].astype(np.float32)
+    else:
+        try:
+            tok = raw.decode("ascii").split()
+        except UnicodeDecodeError:
+            tok = []
+        if not tok or tok[0].lower() != "solid":
+            raise ValueError(f"read_stl: {path}: neither a binary STL of 84 + 50 T bytes (truncated?) nor an ASCII STL")
+        low = [t.lower() for t in tok]
+        if "endsolid" not in low:
+            raise ValueError(f"read_stl: {path}: the ASCII STL has no 'endsolid' (truncated?)")
+        at = [k for k, t in enumerate(low) if t == "vertex"]
+        facets, closed = low.count("facet"), low.count("endfacet")
+        if len(at) != 3 * facets or closed != facets or (at and at[-1] + 3 >= len(tok)):
+            raise ValueError(f"read_stl: {path}: {facets} facets, {closed} closed, {len(at)} vertices (truncated?)")
+        try:
+            corners = np.array([[float(tok[k + 1]), float(tok[k + 2]), float(tok[k + 3])] for k in at], dtype=np.float64)
+        except ValueError as e:
+            raise ValueError(f"read_stl: {path}: a vertex is not three numbers ({e})") from None
+        corners = corners.astype(np.float32).reshape(-1, 3, 3)
+    if weld:
+        return _weld(corners)
+    return corners.reshape(-1, 3).copy(), np.arange(3 * len(corners), dtype=np.int32).reshape(-1, 3)
+
+
+def read_vtk_polydata(path):
+    """The legacy VTK POLYDATA this module writes (POINTS as float, POLYGONS of triangles), binary or ASCII -> (vertices float32
+    [V, 3], triangles int32 [T, 3]), the arrays as they were written.  ValueError on anything else or on a truncated file."""
+    with open(path, "rb") as f:
+        raw = f.read()
+
+    def bad(why):
+        return ValueError(f"read_vtk_polydata: {path}: {why}")
+    lines = raw.split(b"\n", 5)
+    if len(lines) < 6 or not lines[0].startswith(b"# vtk DataFile Version") or lines[3].strip() != b"DATASET POLYDATA":
+        raise bad("not a legacy VTK POLYDATA file")
+    mode = lines[2].strip()
+    if mode not in (b"BINARY", b"ASCII"):
+        raise bad(f"neither BINARY nor ASCII: {mode!r}")
+    head = lines[4].split()
+    if len(head) != 3 or head[0] != b"POINTS" or head[2] != b"float" or not head[1].isdigit():
+        raise bad(f"expected 'POINTS n float', got {lines[4]!r}")
+    n, body = int(head[1]), lines[5]
+    if mode == b"BINARY":
+        if len(body) < 12 * n:
+            raise bad("the points are cut short")
+        pts = np.frombuffer(body, dtype=">f4", count=3 * n).reshape(n, 3).astype(np.float32)
+        rest = body[12 * n:].lstrip(b"\n").split(b"\n", 1)
+        poly = rest[0].split()
+        if len(rest) != 2 or len(poly) != 3 or poly[0] != b"POLYGONS" or not poly[1].isdigit() or not poly[2].isdigit():
+            raise bad("no 'POLYGONS t size' behind the points (truncated?)")
+        t, size = int(poly[1]), int(poly[2])
+        if size != 4 * t or len(rest[1]) < 4 * size:
+            raise bad("the polygons are not triangles or are cut short")
+        cells = np.frombuffer(rest[1], dtype=">i4", count=size).reshape(t, 4).astype(np.int64)
+    else:
+        tok = body.split()
+        if len(tok) < 3 * n + 3:
+            raise bad("the points are cut short")
+        try:
+            pts = np.array([float(x) for x in tok[:3 * n]], dtype=np.float64).astype(np.float32).reshape(n, 3)
+            kw, t, size = tok[3 * n], int(tok[3 * n + 1]), int(tok[3 * n + 2])
+            if kw != b"POLYGONS" or size != 4 * t or len(tok) < 3 * n + 3 + size:
+                raise bad("the polygons are not triangles or are cut short")
+            cells = np.array([int(x) for x in tok[3 * n + 3:3 * n + 3 + size]], dtype=np.int64).reshape(t, 4)
+        except ValueError as e:
+            raise bad(f"malformed number ({e})") from None
+    if len(cells) and (cells[:, 0] != 3).any():
+        raise bad("a polygon is not a triangle")
+    tri = cells[:, 1:]
+    if tri.size and (tri.min() < 0 or tri.max() >= n):
+        raise bad(f"a triangle names a vertex outside 0..{n - 1}")
+    return pts, tri.astype(np.int32)
+
+
+def read_mesh(path):
+    """By the file name: .stl -> read_stl (welded), .vtk -> read_vtk_polydata."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".stl":
+        return read_stl(path)
+    if ext == ".vtk":
+        return read_vtk_polydata(path)
+    raise ValueError(f"read_mesh: {path}: the name must end in .stl or .vtk")

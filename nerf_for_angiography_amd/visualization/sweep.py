@@ -20,7 +20,10 @@ centreline scores of `reconstruction_centreline_metrics` (CENTRELINE_METRICS): c
 sensitivity, from the medial curves of both masks (`afx_skeletonize_3d`: parallel thinning on the GPU) - and the vessel itself as a
 surface: `reconstruction_mesh` (the triangle mesh of the thresholded reconstruction in world coordinates, `afx_isosurface_3d`: marching
 tetrahedra on the GPU; visualization/mesh_io.py writes it as STL or VTK) and the scores of `reconstruction_mesh_metrics` (MESH_METRICS):
-the enclosed volume and the surface area of the reconstruction over those of the truth, and the Euler characteristic of its surface."""
+the enclosed volume and the surface area of the reconstruction over those of the truth, and the Euler characteristic of its surface -
+and how far the two surfaces lie apart, measured on the meshes themselves: `reconstruction_mesh_distance_metrics`
+(MESH_DISTANCE_METRICS), each mesh's vertices against the other's triangles (`afx_mesh_point_distance`), the surface-distance scores
+at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid."""
 from __future__ import annotations
 
 import itertools
@@ -47,6 +50,9 @@ CENTRELINE_METRICS = ("CLDICE 3D", "TPREC 3D", "TSENS 3D")
 # and the reconstructed vessel measured as a surface (reconstruction_mesh_metrics), tabulated after the centreline columns
 MESH_METRICS = ("VOLUME RATIO 3D", "AREA RATIO 3D", "EULER 3D")
 _EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS + MESH_METRICS
+# and the distance between the two surfaces as meshes (reconstruction_mesh_distance_metrics), tabulated after the mesh columns
+MESH_DISTANCE_METRICS = ("ASSD MESH", "HD MESH", "HD95 MESH")
+_VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS          # every family of columns that needs the ground-truth volume
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -90,8 +96,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     FRACTION 3D, DICE 3D LCC), from one `reconstruction_topology_metrics` call (threshold mean(gt), 26 neighbours), behind the surface
     columns, and the names of CENTRELINE_METRICS (CLDICE 3D, TPREC 3D, TSENS 3D), from one `reconstruction_centreline_metrics` call (threshold
     mean(gt)), behind the topology columns, and the names of MESH_METRICS (VOLUME RATIO 3D, AREA RATIO 3D, EULER 3D), from one
-    `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns.  The arguments are checked
-    before any work on the GPU."""
+    `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns, and the names of
+    MESH_DISTANCE_METRICS (ASSD MESH, HD MESH, HD95 MESH), from one `reconstruction_mesh_distance_metrics` call (threshold mean(gt),
+    q = 95; NaN when either mesh is empty), behind the mesh columns.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -139,7 +146,7 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
     if "SSIM" in want:
         scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
-    if any(m in want for m in ("DICE 3D", "DOT 3D") + _EXTRA_METRICS):
+    if any(m in want for m in ("DICE 3D", "DOT 3D") + _VOLUME_METRICS):
         # the two n^3 grids are evaluated once and shared by the three families of whole-volume scores
         pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
         grids = _reconstruction_grids(model, volume, volume_outside, pts)
@@ -162,6 +169,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         mesh = reconstruction_mesh_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(MESH_METRICS, ("volume_ratio", "area_ratio", "euler")):
             scores[name] = [mesh[key]] * n
+    if any(m in want for m in MESH_DISTANCE_METRICS):
+        apart = reconstruction_mesh_distance_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(MESH_DISTANCE_METRICS, ("assd", "hd", "hd_percentile")):
+            scores[name] = [apart[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -172,9 +183,9 @@ def _check_metrics(metrics, binary_targets, volume):
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS + _EXTRA_METRICS]
+    unknown = [m for m in metrics if m not in METRICS + _VOLUME_METRICS]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _EXTRA_METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _VOLUME_METRICS)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -183,9 +194,9 @@ def _check_metrics(metrics, binary_targets, volume):
         raise ValueError("evaluation_sweep: DICE 2D needs binary_targets")
     if ("DICE 3D" in metrics or "DOT 3D" in metrics) and volume is None:
         raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
-    if any(m in metrics for m in _EXTRA_METRICS) and volume is None:
-        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _EXTRA_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS + _EXTRA_METRICS if m in metrics]
+    if any(m in metrics for m in _VOLUME_METRICS) and volume is None:
+        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _VOLUME_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS + _VOLUME_METRICS if m in metrics]
 
 
 @torch.no_grad()
@@ -403,6 +414,33 @@ def reconstruction_mesh_metrics(model, volume, outside, n, threshold=None, large
                        "n_triangles" + suffix: i["T"], "n_edges" + suffix: i["E"]})
     scores.update(volume_ratio=scores["volume"] / scores["volume_gt"], area_ratio=scores["area"] / scores["area_gt"], threshold=thr,
                   voxel_size=2.0 * float(outside) / (int(n) - 1))
+    return scores, pred, gt
+
+
+@torch.no_grad()
+def reconstruction_mesh_distance_metrics(model, volume, outside, n, threshold=None, q=95.0, largest_component=False, grids=None):
+    """How far the reconstructed surface lies from the true one, measured on the meshes -> (scores, predicted grid, ground-truth grid).
+
+    Both grids are meshed as `reconstruction_mesh` meshes them, the truth at the same threshold (largest_component filters the
+    prediction only); each mesh's vertices are measured against the other's triangles (`engine.mesh_point_distance`: the exact
+    point-to-triangle distance, fp32 in world units).  scores, by medpy's formulas: assd = the mean of the two directed means, hd =
+    the maximum of the two directed maxima, hd_percentile = the q-th percentile of the two directed sets together (sums and the
+    percentile in fp64); n_vertices, n_vertices_gt, threshold, q.  An empty mesh on either side gives NaN scores, as the voxel scores
+    do."""
+    from ..engine import mesh_point_distance
+    if not 0.0 <= float(q) <= 100.0:
+        raise ValueError(f"reconstruction_mesh_distance_metrics: q = {q} must lie in [0, 100]")
+    vertices, triangles, info, pred, gt = reconstruction_mesh(model, volume, outside, n, threshold, largest_component, grids=grids)
+    thr = info["threshold"]
+    vertices_gt, triangles_gt, info_gt = _grid_mesh(gt, thr, outside, n)
+    scores = {"assd": float("nan"), "hd": float("nan"), "hd_percentile": float("nan"), "n_vertices": info["V"], "n_vertices_gt": info_gt["V"],
+              "threshold": thr, "q": float(q)}
+    if info["T"] and info_gt["T"]:
+        there = mesh_point_distance(vertices, vertices_gt, triangles_gt).double()
+        back = mesh_point_distance(vertices_gt, vertices, triangles).double()
+        scores["assd"] = float((there.mean() + back.mean()) / 2.0)
+        scores["hd"] = float(torch.maximum(there.max(), back.max()))
+        scores["hd_percentile"] = float(torch.quantile(torch.cat([there, back]), float(q) / 100.0))
     return scores, pred, gt
 
 
