@@ -902,6 +902,92 @@ int afx_mesh_sdf_3d(const float* vertices, int64_t n_vertices, const int32_t* tr
 int afx_mesh_point_distance(const float* points, int64_t n_points, const float* vertices, int64_t n_vertices, const int32_t* triangles,
                             int64_t n_triangles, float* dist_out, int32_t* nearest_out, void* record, void* stream);
 
+/* ---- The centreline read as a graph: junction nodes, branches in path order, lengths, radii along the branch, and spur pruning.
+ * Defined here so that every implementation gives the same result.  The rules above hold: device pointers, nothing allocated or
+ * synchronised, integer atomics only, hipGraph-capturable, the same bits on every run.
+ *
+ * Input: skel, a uint8 volume [n0][n1][n2] (row-major; non-zero = on) - ANY mask, not only afx_skeletonize_3d's output; beyond the grid
+ * is off; every axis in 1..AFX_EDT3D_MAX_SIDE.  d2 (uint32 [n0][n1][n2], may be NULL for the graph): the squared EDT of the mask that was
+ * thinned, as afx_distance_transform_edt_3d writes it.
+ *   deg(v) = the on voxels among v's 26 neighbours.  J = the on voxels with deg >= 3, P = those with deg <= 2.
+ *   Junction nodes = the 26-components of J, labelled 1..K_J; branches = the 26-components of P, labelled 1..B; both in the order of
+ *     their smallest linear index (afx_label_components_3d at connectivity 3).  A P voxel has at most 2 on neighbours, so a branch is a
+ *     simple path, a single voxel or a closed cycle.  An EXTREME is a P voxel with fewer than 2 P-neighbours; a cycle has none, and none
+ *     of its voxels touches J.
+ *   Path order: a path starts at its extreme with the smaller linear index; a cycle starts at its smallest linear index and steps first
+ *     to that voxel's P-neighbour with the smaller linear index.  path_voxels = the linear indices of all P voxels, branch after branch
+ *     in label order, each in path order; a branch's offset into it is the exclusive prefix sum of the branch sizes.
+ *   Attachments: an extreme is attached to the junction node of each J voxel among its neighbours - at most one per extreme of a path of
+ *     >= 2 voxels; a single-voxel branch has at most two: the J neighbour with the smaller linear index is its start side, the other its
+ *     end side.  Free ends of a branch = (0 for a cycle, else 2) - attachments; over the volume they sum to (voxels with deg 1) +
+ *     2 (voxels with deg 0).  A SPUR is a branch with exactly one free end and exactly one attachment.
+ *   Steps: every step between consecutive path voxels, the closing step of a cycle and the link from an attached extreme to its J voxel
+ *     has a direction class: with code(d) = (d0 + 1) * 9 + (d1 + 1) * 3 + (d2 + 1), c = code - 14 of whichever of +-offset has
+ *     code > 13: 13 classes, c = 0 for (0,0,1) .. c = 12 for (1,1,1).  A branch carries the 13 integer counts n_c; its length is
+ *     (((n_0 L_0) + n_1 L_1) + ...) + n_12 L_12 in fp64, every product and sum rounded on its own (no contraction), L = step_lengths[13]
+ *     (host, fp64, finite and >= 0; NULL = unit voxels: 1, sqrt 2, sqrt 3 by the number of non-zero components; for a world-space
+ *     length pass |A d_c| for the index_to_world matrix A).  The volume's total length is the same formula on the summed counts: no
+ *     floating-point sum depends on an order the hardware chooses.
+ *   Radii (only with d2): per branch the min and max d2 along the path, the path position of the first minimum, the sum of
+ *     sqrt((double)d2) added one after another in path order starting from 0.0 (each sqrt and sum rounded on its own), and the d2 at the
+ *     attached J voxel of each side (0 for a free side).
+ *   Pruning: one round deletes, together, the voxels of every spur b with len(b) <= factor * sqrt((double)d2[u]) - len the branch's
+ *     length with unit step lengths, u the J voxel it is attached to, the product and the comparison in fp64 as above.  J voxels are
+ *     never deleted, so the 26-components, cavities and tunnels of the input stay.  The graph is rebuilt and rounds repeat until one
+ *     deletes nothing (that round is counted).  The result is a subset of the input; pruning it again changes nothing.
+ *
+ * afx_centreline_graph: node_labels, branch_labels (int32 [n0][n1][n2]: 0, or the node / branch of the voxel) and path_voxels (int32
+ * [n0 n1 n2]: the first record[2] entries are written) are required.  branches: max_branches rows of AFX_GRAPH_BRANCH_SLOTS 8-byte
+ * slots (row b - 1 for branch b; may be NULL with max_branches 0); lo / hi = the low / high 32 bits of a slot:
+ *   [0] lo voxels, hi offset into path_voxels   [1] lo flags: bit 0 cycle, bit 1 spur, bits 8..9 free ends, bits 16..17 attachments;
+ *   hi the path position of the first d2 minimum   [2] lo the node of the start side, hi of the end side (0 = free)
+ *   [3] lo min d2, hi max d2 along the path (0 without d2)   [4] lo d2 at the start side's J voxel, hi at the end side's (0 = free)
+ *   [5..11] the step counts, n_2q in lo and n_2q+1 in hi of slot 5 + q (hi of slot 11 is 0)   [12] length, fp64
+ *   [13] the sum of radii, fp64 (0.0 without d2)   [14] lo the path's first voxel, hi its last   [15] zero
+ * record: AFX_GRAPH_RECORD_SLOTS uint64 slots on the device:
+ *   [0] on voxels  [1] J voxels  [2] P voxels  [3] K_J  [4] B  [5] voxels with deg 0  [6] with deg 1  [7] free ends = [6] + 2 [5]
+ *   [8] cycles  [9] spurs  [10] total length, fp64  [11] status: bit 1 (value 1) B exceeds max_branches: rows 1..max_branches are
+ *   written, everything else is complete, the call returns AFX_OK  [12] the smallest d2 on any branch (AFX_EDT3D_NONE without d2 or
+ *   without a P voxel)  [13..15] zero
+ * Launches: reset; classify (degrees, the J and P byte masks, counts by one integer add per wave); afx_label_components_3d on J, then
+ * on P with its sizes; terminals (per branch, by integer atomicMin, the smallest extreme, or for a cycle the smallest voxel); offsets
+ * (the exclusive scan of the sizes: chunk sums, one workgroup over them, the entries); walk (one lane per branch takes exactly
+ * sizes[b] steps of 26 neighbour loads each: path order, step counts, radii, attachments, the row); finish (the record).  No loop
+ * depends on a value another thread writes.  Cost at the top of the shape range: besides the labelling's own, the walk of one very
+ * long branch is sequential, roughly a microsecond per voxel - a vessel tree's branches are a few hundred voxels, but a single curve
+ * that fills a 1024^3 volume (2^28 voxels and more) would take minutes in one lane.
+ * AFX_E_INVALID (before any HIP call): a null skel, node_labels, branch_labels, path_voxels or record; an axis outside
+ * 1..AFX_EDT3D_MAX_SIDE; max_branches below 0, above 2^31 - 1, or above 0 with a null table; a step length that is negative or not
+ * finite.  Workspace (afx_centreline_graph_workspace_bytes; 0 for a refused shape), each region rounded up to 256 bytes, N = n0 n1 n2:
+ * two uint8 [N] (the J and P masks), uint32 [N] (branch sizes), max(afx_label_components_3d_workspace_bytes, two uint32 [N]) (the
+ * labelling's workspace, afterwards the branch starts and offsets), uint32 [ceil(N / 2048)], and three times 256 bytes (the two
+ * labelling records, counters); AFX_E_WORKSPACE when smaller, with *workspace_needed (when not NULL) set.
+ *
+ * afx_prune_spurs: out (uint8, 1 / 0; may be skel) = skel after the rounds above; d2 is required.  record: AFX_PRUNE_RECORD_SLOTS uint64
+ * slots on the device:
+ *   [0] rounds run (the one that deleted nothing included)  [1] branches deleted  [2] voxels deleted  [3] converged: 1 once a round has
+ *   deleted nothing  [4] voxels that remain  [5] on voxels of the input  [6] voxels the last round run deleted  [7] zero
+ * Per round: the graph's launches on `out` (the walk also marks the spurs the rule takes), delete, advance (one lane rolls the record).
+ * Once the record says converged, later rounds find the same graph, mark nothing and leave mask and record as they are.  sync_every
+ * has afx_skeletonize_3d's meaning: 0 issues exactly max_rounds rounds and reads nothing back (capturable; look at record[3]);
+ * sync_every > 0 copies record[3] to the host after every sync_every rounds and after the last, and returns at convergence, or after
+ * max_rounds rounds with converged = 0 - still AFX_OK, afx_last_error() says that it stopped early.
+ * AFX_E_INVALID (before any HIP call): a null skel, d2, out or record; a refused shape; a factor that is negative, NaN or infinite;
+ * max_rounds < 1; sync_every < 0.  Workspace (afx_prune_spurs_workspace_bytes): the graph's, then three int32 [N] (node labels, branch
+ * labels, path voxels), uint8 [N] (marks) and 256 bytes (the graph record); AFX_E_WORKSPACE when smaller, *workspace_needed set. */
+#define AFX_GRAPH_RECORD_SLOTS 16
+#define AFX_GRAPH_BRANCH_SLOTS 16
+#define AFX_PRUNE_RECORD_SLOTS 8
+size_t afx_centreline_graph_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_centreline_graph(const uint8_t* skel, const uint32_t* d2 /* may be NULL */, int32_t n0, int32_t n1, int32_t n2,
+                         const double* step_lengths /* [13] on the host, may be NULL */, int32_t* node_labels, int32_t* branch_labels,
+                         int32_t* path_voxels, void* branches, int64_t max_branches, void* record, void* workspace, size_t workspace_bytes,
+                         size_t* workspace_needed, void* stream);
+size_t afx_prune_spurs_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_prune_spurs(const uint8_t* skel, const uint32_t* d2, int32_t n0, int32_t n1, int32_t n2, double factor, int32_t max_rounds,
+                    int32_t sync_every, uint8_t* out, void* record, void* workspace, size_t workspace_bytes, size_t* workspace_needed,
+                    void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -1592,6 +1592,192 @@ def mesh_point_distance(points: torch.Tensor, vertices: torch.Tensor, triangles:
     return (dist, nearest) if return_nearest else dist
 
 
+GRAPH_RECORD_SLOTS = 16
+GRAPH_BRANCH_SLOTS = 16
+PRUNE_RECORD_SLOTS = 8
+_GRAPH_RECORD_NAMES = ("n_on", "n_junction_voxels", "n_path_voxels", "n_nodes", "n_branches", "n_deg0", "n_deg1", "n_free_ends", "n_cycles",
+                       "n_spurs")
+
+
+def _step_class_offsets():
+    """The offset of each of the 13 step classes: class c has code c + 14 = (d0 + 1) * 9 + (d1 + 1) * 3 + (d2 + 1)."""
+    return [((c + 14) // 9 - 1, (c + 14) // 3 % 3 - 1, (c + 14) % 3 - 1) for c in range(13)]
+
+
+def graph_step_lengths(index_to_world=None):
+    """step_lengths of afx_centreline_graph for an index_to_world ([3, 4] or 12 numbers; None = unit voxels): |A d_c| in fp64 on the host,
+    A its 3 x 3 matrix, d_c the offset of step class c."""
+    import numpy as np
+    if index_to_world is None:
+        return None
+    a = _affine12(index_to_world, "centreline_graph").reshape(3, 4)[:, :3]
+    return [float(np.sqrt(((a @ np.asarray(d, np.float64)) ** 2).sum())) for d in _step_class_offsets()]
+
+
+def _d2_u32(d2, like: torch.Tensor, who: str):
+    """The squared EDT as the library's uint32, held in an int32 tensor (distance_transform_edt_3d returns it as int64)."""
+    if d2 is None:
+        return None
+    _volume_on_gpu(d2, "d2", who)
+    if d2.shape != like.shape or d2.device != like.device:
+        raise ValueError(f"{who}: d2 {tuple(d2.shape)} on {d2.device}, the mask {tuple(like.shape)} on {like.device}")
+    if d2.dtype == torch.int32:
+        return d2.contiguous()
+    d = d2.to(torch.int64)
+    return torch.where(d >= 2 ** 31, d - 2 ** 32, d).to(torch.int32).contiguous()
+
+
+def centreline_graph_record(skel: torch.Tensor, d2=None, step_lengths=None, max_branches: int = 0, node_labels=None, branch_labels=None,
+                            path_voxels=None, branches=None, record=None, workspace=None):
+    """afx_centreline_graph on a contiguous uint8 [n0, n1, n2] device mask (non-zero = on; d2: int32 tensor holding the uint32 squared EDT,
+    or None) -> (node_labels, branch_labels, path_voxels, branches, record): int32 volumes, int32 [N], int64 [max_branches, 16] rows and
+    the 16-slot int64 device record (layouts in include/afx.h).  Launches only - nothing is read back, so the call can be captured in a
+    graph (pass every buffer, the workspace of afx_centreline_graph_workspace_bytes bytes, to keep the capture free of allocations)."""
+    import ctypes as C
+    lib = _lib.load()
+    _volume_on_gpu(skel, "the mask", "centreline_graph")
+    if skel.dtype != torch.uint8 or not skel.is_contiguous():
+        raise ValueError(f"centreline_graph_record: the mask must be a contiguous uint8 tensor, got {skel.dtype}, contiguous = {skel.is_contiguous()}")
+    if d2 is not None and (d2.dtype != torch.int32 or not d2.is_contiguous() or d2.shape != skel.shape):
+        raise ValueError("centreline_graph_record: d2 must be a contiguous int32 tensor of the mask's shape")
+    dev = skel.device
+    n0, n1, n2 = skel.shape
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    nbytes = int(lib.afx_centreline_graph_workspace_bytes(n0, n1, n2))
+    if node_labels is None:
+        node_labels = torch.empty(skel.shape if nbytes else (1,), dtype=torch.int32, device=dev)
+    if branch_labels is None:
+        branch_labels = torch.empty(skel.shape if nbytes else (1,), dtype=torch.int32, device=dev)
+    if path_voxels is None:
+        path_voxels = torch.empty(skel.numel() if nbytes else 1, dtype=torch.int32, device=dev)
+    if branches is None:
+        branches = torch.empty((max(int(max_branches), 0), GRAPH_BRANCH_SLOTS), dtype=torch.int64, device=dev)
+    if record is None:
+        record = torch.empty(GRAPH_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    L = None if step_lengths is None else (C.c_double * 13)(*[float(x) for x in step_lengths])
+    _lib.check(lib.afx_centreline_graph(_ptr(skel), _ptr(d2), n0, n1, n2, L, _ptr(node_labels), _ptr(branch_labels), _ptr(path_voxels),
+                                        _ptr(branches) if int(max_branches) > 0 else None, int(max_branches), _ptr(record), _ptr(workspace),
+                                        workspace.numel(), None, Engine._stream(dev)), "afx_centreline_graph")
+    return node_labels, branch_labels, path_voxels, branches, record
+
+
+def _unpack_branch_rows(rows: torch.Tensor) -> dict:
+    """The fields of [B, 16] int64 branch rows (include/afx.h) as tensors; device-independent."""
+    lo = lambda x: x & 0xffffffff
+    hi = lambda x: (x >> 32) & 0xffffffff
+    out = {"branch_size": lo(rows[:, 0]), "path_offset": hi(rows[:, 0]), "is_cycle": (rows[:, 1] & 1).bool(), "is_spur": ((rows[:, 1] >> 1) & 1).bool(),
+           "free_ends": (rows[:, 1] >> 8) & 3, "attachments": (rows[:, 1] >> 16) & 3, "d2_argmin": hi(rows[:, 1]),
+           "node_start": lo(rows[:, 2]), "node_end": hi(rows[:, 2]), "d2_min": lo(rows[:, 3]), "d2_max": hi(rows[:, 3]),
+           "d2_start": lo(rows[:, 4]), "d2_end": hi(rows[:, 4]),
+           "step_counts": torch.stack([f(rows[:, 5 + q]) for q in range(7) for f in (lo, hi)][:13], dim=1) if rows.shape[0] else
+           torch.zeros((0, 13), dtype=torch.int64, device=rows.device),
+           "length": rows[:, 12].contiguous().view(torch.float64), "radius_sum": rows[:, 13].contiguous().view(torch.float64),
+           "first_voxel": lo(rows[:, 14]), "last_voxel": hi(rows[:, 14])}
+    return out
+
+
+def centreline_graph(skel: torch.Tensor, d2=None, index_to_world=None) -> dict:
+    """The centreline of a [n0, n1, n2] device mask (any dtype, non-zero = on; ANY mask, a skeleton is the usual one) read as a graph
+    (definitions in include/afx.h): junction nodes = the 26-components of the voxels with 3 or more neighbours, branches = those of the
+    voxels with at most 2, each a path, a single voxel or a cycle.  d2: the squared EDT of the mask that was thinned
+    (distance_transform_edt_3d(..., return_squared=True)[1]) for the radii; index_to_world ([3, 4]) for lengths in world units (None: voxels).
+    -> dict: node_labels, branch_labels (int32 volumes), path_voxels (int64 [P]: the linear indices branch after branch in path order),
+    per-branch tensors of B entries (branch_size, path_offset, is_cycle, is_spur, free_ends, attachments, node_start, node_end, step_counts
+    [B, 13], length, and with d2: d2_min, d2_max, d2_argmin, d2_start, d2_end, radius_sum), and the integers n_on, n_junction_voxels,
+    n_path_voxels, n_nodes, n_branches, n_deg0, n_deg1, n_free_ends, n_cycles, n_spurs, total_length (float), d2_min_all (None without
+    d2 or without a branch).  One launch sequence and one read-back of 128 bytes; a second one when more than 1024 branches were found."""
+    import numpy as np
+    _volume_on_gpu(skel, "the mask", "centreline_graph")
+    s = (skel != 0).to(torch.uint8).contiguous()
+    d = _d2_u32(d2, s, "centreline_graph")
+    L = graph_step_lengths(index_to_world)
+    cap = 1024
+    nl, bl, pv, rows, record = centreline_graph_record(s, d, L, cap)
+    rec = record.cpu().numpy()
+    if int(rec[11]) & 1:                                  # the table was too small: once more with the reported B
+        nl, bl, pv, rows, record = centreline_graph_record(s, d, L, int(rec[4]))
+        rec = record.cpu().numpy()
+    nb = int(rec[4])
+    out = {"node_labels": nl, "branch_labels": bl, "path_voxels": pv[:int(rec[2])].to(torch.int64), "shape": tuple(s.shape), "has_d2": d is not None}
+    out.update(_unpack_branch_rows(rows[:nb]))
+    out.update({k: int(v) for k, v in zip(_GRAPH_RECORD_NAMES, rec[:10])})
+    out["total_length"] = float(rec.view(np.float64)[10])
+    d2_min = int(rec[12]) & 0xffffffff
+    out["d2_min_all"] = None if d is None or nb == 0 else d2_min
+    return out
+
+
+def prune_record(skel: torch.Tensor, d2: torch.Tensor, factor: float, max_rounds: int, sync_every: int = 0, out=None, record=None, workspace=None):
+    """afx_prune_spurs on a contiguous uint8 [n0, n1, n2] device mask and its int32-held uint32 squared EDT -> (out, record): out uint8
+    (1 / 0; pass out=skel to prune in place), record the 8-slot int64 device record (rounds, branches deleted, voxels deleted, converged,
+    remaining, input, deleted by the last round).  sync_every = 0 issues exactly max_rounds rounds and reads nothing back (capturable:
+    pass all three buffers); sync_every > 0 lets the library look at the record every so many rounds and stop at convergence."""
+    lib = _lib.load()
+    _volume_on_gpu(skel, "the mask", "prune_spurs")
+    if skel.dtype != torch.uint8 or not skel.is_contiguous():
+        raise ValueError(f"prune_record: the mask must be a contiguous uint8 tensor, got {skel.dtype}, contiguous = {skel.is_contiguous()}")
+    if not isinstance(d2, torch.Tensor) or d2.dtype != torch.int32 or not d2.is_contiguous() or d2.shape != skel.shape or d2.device != skel.device:
+        raise ValueError("prune_record: d2 must be a contiguous int32 tensor of the mask's shape on its device")
+    dev = skel.device
+    n0, n1, n2 = skel.shape
+    nbytes = int(lib.afx_prune_spurs_workspace_bytes(n0, n1, n2))
+    if out is None:
+        out = torch.empty(skel.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.empty(PRUNE_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.afx_prune_spurs(_ptr(skel), _ptr(d2), n0, n1, n2, float(factor), int(max_rounds), int(sync_every), _ptr(out), _ptr(record),
+                                   _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_prune_spurs")
+    return out, record
+
+
+def prune_spurs(skel: torch.Tensor, d2: torch.Tensor, factor: float = 1.0, max_rounds=None, return_record: bool = False):
+    """A [n0, n1, n2] device mask without its spurs -> bool [n0, n1, n2]: round after round, every branch with one free end and one
+    junction whose length (in voxels) is at most factor x the radius sqrt(d2) at the junction voxel it hangs on is deleted, until a round
+    deletes nothing (include/afx.h).  Junction voxels stay, so components, cavities and tunnels are kept.  max_rounds: stop after that
+    many rounds (None: until convergence).  return_record: (mask, record) with record = {"rounds", "branches", "voxels", "converged",
+    "remaining", "input", "last"}."""
+    _volume_on_gpu(skel, "the mask", "prune_spurs")
+    s = (skel != 0).to(torch.uint8).contiguous()
+    d = _d2_u32(d2, s, "prune_spurs")
+    if d is None:
+        raise ValueError("prune_spurs: d2 (the squared EDT of the mask that was thinned) is required")
+    if max_rounds is None:
+        max_rounds = min(s.numel() + 1, 2 ** 31 - 1)      # every round but the last deletes a voxel: never reached
+    out, record = prune_record(s, d, factor, max_rounds, sync_every=1, out=s)
+    if not return_record:
+        return out.bool()
+    r = record.cpu().tolist()
+    return out.bool(), dict(zip(("rounds", "branches", "voxels", "converged", "remaining", "input", "last"), r))
+
+
+def centreline_branch_profile(graph: dict, d2: torch.Tensor, b: int, voxel_size=1.0) -> dict:
+    """Arc length and radius along branch b (1-based) of a `centreline_graph` result: {"voxels" (int64 [n] linear indices in path order),
+    "arc_length" (float64 [n], 0 at the path's first voxel, the Euclidean steps added up), "radius" (float64 [n]: voxel_size x sqrt(d2),
+    an isotropic scalar or the geometric reading along the smallest axis is the caller's choice), "r_min", "r_median", "stenosis" =
+    1 - r_min / median(r)}.  voxel_size: a scalar or one size per axis (arc lengths use the per-axis sizes, radii the smallest).  Plain
+    torch operations on whatever device the graph lives on."""
+    nb = int(graph["n_branches"])
+    if not 1 <= int(b) <= nb:
+        raise ValueError(f"centreline_branch_profile: branch {b} outside 1..{nb}")
+    off, n = int(graph["path_offset"][b - 1]), int(graph["branch_size"][b - 1])
+    vox = graph["path_voxels"][off:off + n].to(torch.int64)
+    n0, n1, n2 = graph["shape"]
+    vs = torch.as_tensor(voxel_size, dtype=torch.float64, device=vox.device).reshape(-1)
+    vs = vs.expand(3) if vs.numel() == 1 else vs
+    ijk = torch.stack([vox // (n1 * n2), vox // n2 % n1, vox % n2], dim=1).to(torch.float64) * vs
+    steps = (ijk[1:] - ijk[:-1]).pow(2).sum(1).sqrt()
+    arc = torch.cat([torch.zeros(1, dtype=torch.float64, device=vox.device), torch.cumsum(steps, 0)])
+    dd = d2.reshape(-1)[vox.to(d2.device)].to(torch.int64) & 0xffffffff
+    radius = dd.to(torch.float64).sqrt().to(vox.device) * vs.min()
+    r_min, r_med = float(radius.min()), float(radius.median())
+    return {"voxels": vox, "arc_length": arc, "radius": radius, "r_min": r_min, "r_median": r_med,
+            "stenosis": 1.0 - r_min / r_med if r_med > 0 else 0.0}
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

@@ -117,6 +117,11 @@ def build_parser():
                         '(afx_isosurface_3d), capped where it leaves the grid, in world coordinates; without the flag nothing changes')
     p.add_argument('--mesh_threshold', type=float, default=0.05, metavar='SIGMA',
                    help='--save_mesh: the density at which the surface is taken (default: the evaluation sweep\'s binary_thresh)')
+    p.add_argument('--save_centreline', default=None, metavar='PATH',
+                   help='after training, write the final model\'s vessel centreline to PATH (.vtk: legacy VTK POLYDATA LINES with the radius '
+                        'per point): the density grid at depth_samples + 1 points per axis, thresholded at --mesh_threshold, thinned '
+                        '(afx_skeletonize_3d), its spurs pruned (afx_prune_spurs, factor 1) and read as a graph (afx_centreline_graph), one '
+                        'polyline per branch in world coordinates; without the flag nothing changes')
     p.add_argument('--phantom_mesh', default=None, metavar='PATH',
                    help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
                         'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
@@ -164,6 +169,11 @@ def check_args(args):
             raise ValueError("--save_mesh: PATH must end in .stl or .vtk")
         if not args.mesh_threshold > 0:
             raise ValueError("--mesh_threshold: needs SIGMA > 0 (the surface is capped with zero density around the grid)")
+    if args.save_centreline is not None:
+        if os.path.splitext(args.save_centreline)[1].lower() != '.vtk':
+            raise ValueError("--save_centreline: PATH must end in .vtk")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
 
 
 def checkpoint_interval(checkpoint_every: int, graph_rounds: bool, round_len: int = 16) -> int:
@@ -475,6 +485,9 @@ def main(argv=None):
                   vessel_acc_grid=vessel_acc_grid)
     if args.save_mesh is not None:
         result['mesh_info'] = save_mesh(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_mesh)
+    if args.save_centreline is not None:
+        result['centreline_info'] = save_centreline(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold,
+                                                    args.save_centreline)
     return result
 
 
@@ -501,6 +514,28 @@ def save_mesh(model, outside, n, threshold, path):
     vertices, triangles, info = _grid_mesh(density_grid(model, outside, int(n) - 1), float(threshold), outside, n)
     info.update(threshold=float(threshold), path=write_mesh(path, vertices, triangles))
     print('mesh', {k: info[k] for k in ('V', 'T', 'euler', 'area', 'volume', 'path')}, flush=True)
+    return info
+
+
+def save_centreline(model, outside, n, threshold, path, prune_factor=1.0):
+    """--save_centreline: the pruned centreline of {sigma >= threshold} on the model's density grid (n points per axis over [-outside,
+    outside]^3), one polyline per branch in world coordinates with the radius per point -> its info (branches, nodes, free ends, spurs
+    removed, length, threshold, path).  An empty mask writes a file without lines."""
+    import torch
+    from ..engine import centreline_graph, distance_transform_edt_3d, prune_spurs, skeletonize_3d
+    from ..render import density_grid
+    from ..visualization.mesh_io import write_vtk_polylines
+    from ..visualization.sweep import centreline_polylines, grid_index_to_world
+    mask = density_grid(model, outside, int(n) - 1) >= torch.tensor(float(threshold), dtype=torch.float32, device=model.flat_params.device)
+    d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
+    pruned, rec = prune_spurs(skeletonize_3d(mask), d2, prune_factor, return_record=True)
+    a = grid_index_to_world(outside, n)
+    graph = centreline_graph(pruned, d2, a)
+    voxel = 2.0 * float(outside) / (int(n) - 1)
+    points, offsets, radius = centreline_polylines(graph, d2, a, voxel)
+    info = dict(n_branches=graph['n_branches'], n_nodes=graph['n_nodes'], n_free_ends=graph['n_free_ends'], n_spurs_removed=rec['branches'],
+                length=graph['total_length'], threshold=float(threshold), path=write_vtk_polylines(path, points, offsets, {'radius': radius}))
+    print('centreline', info, flush=True)
     return info
 
 

@@ -4,7 +4,9 @@
 `phantomdata.helpers.voxel_volume_from_mesh`.
 
 Host plumbing: the arrays are what `engine.extract_isosurface` / `sweep.reconstruction_mesh` return (tensors on any device, or arrays).
-Both writers write atomically, as nerf/checkpoint.py does: to a temporary name in the same directory, flushed, then os.replace - a
+`write_vtk_polylines` writes a centreline (`engine.centreline_graph`'s paths) as POLYDATA LINES with a per-point radius.
+
+The writers write atomically, as nerf/checkpoint.py does: to a temporary name in the same directory, flushed, then os.replace - a
 write that fails half-way leaves no partial file and keeps a previous file as it was."""
 from __future__ import annotations
 
@@ -84,6 +86,40 @@ def write_vtk_polydata(path, vertices, triangles, binary: bool = True, title: st
                    f"POLYGONS {len(t)} {4 * len(t)}\n".encode("ascii"),
                    "".join(f"3 {c[1]} {c[2]} {c[3]}\n" for c in cells).encode("ascii")]
     return _write_atomically(path, chunks)
+
+
+def write_vtk_polylines(path, points, offsets, point_data=None, title: str = "nerf_for_angiography_amd centreline"):
+    """Legacy VTK (version 3.0, ASCII) POLYDATA with LINES: polyline b runs over points[offsets[b]:offsets[b + 1]] (offsets has one entry
+    more than there are lines and ends at len(points); a line of one point is written as such).  point_data: {name: [P] values} written as
+    POINT_DATA SCALARS double, e.g. the radius along the centreline.  Written atomically, as the mesh writers do."""
+    def host(x):
+        return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    pts = np.ascontiguousarray(host(points), dtype=np.float64)
+    off = np.ascontiguousarray(host(offsets), dtype=np.int64).reshape(-1)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError(f"write_vtk_polylines: points must have shape [P, 3], got {pts.shape}")
+    if len(off) < 1 or off[0] != 0 or off[-1] != len(pts) or (np.diff(off) < 1).any():
+        raise ValueError("write_vtk_polylines: offsets must rise from 0 to the number of points, every line holding at least one point")
+    if not np.isfinite(pts).all():
+        raise ValueError("write_vtk_polylines: a point is not finite")
+    data = {}
+    for name, values in (point_data or {}).items():
+        a = np.ascontiguousarray(host(values), dtype=np.float64).reshape(-1)
+        if len(a) != len(pts) or not str(name) or any(ch.isspace() for ch in str(name)):
+            raise ValueError(f"write_vtk_polylines: point_data[{name!r}] needs a name without blanks and one value per point")
+        data[str(name)] = a
+    n_lines = len(off) - 1
+    title = title.replace("\n", " ")[:255]
+    text = [f"# vtk DataFile Version 3.0\n{title}\nASCII\nDATASET POLYDATA\nPOINTS {len(pts)} double\n"]
+    text += [f"{float(p[0])!r} {float(p[1])!r} {float(p[2])!r}\n" for p in pts]
+    text.append(f"LINES {n_lines} {n_lines + len(pts)}\n")
+    text += [f"{off[b + 1] - off[b]} {' '.join(str(i) for i in range(off[b], off[b + 1]))}\n" for b in range(n_lines)]
+    if data:
+        text.append(f"POINT_DATA {len(pts)}\n")
+        for name, a in data.items():
+            text.append(f"SCALARS {name} double 1\nLOOKUP_TABLE default\n")
+            text += [f"{float(x)!r}\n" for x in a]
+    return _write_atomically(path, ["".join(text).encode("ascii")])
 
 
 def write_mesh(path, vertices, triangles):

@@ -23,7 +23,10 @@ tetrahedra on the GPU; visualization/mesh_io.py writes it as STL or VTK) and the
 the enclosed volume and the surface area of the reconstruction over those of the truth, and the Euler characteristic of its surface -
 and how far the two surfaces lie apart, measured on the meshes themselves: `reconstruction_mesh_distance_metrics`
 (MESH_DISTANCE_METRICS), each mesh's vertices against the other's triangles (`afx_mesh_point_distance`), the surface-distance scores
-at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid."""
+at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid - and the centreline read as a graph:
+`reconstruction_graph_metrics` (GRAPH_METRICS) prunes the thinning spurs of both skeletons (`afx_prune_spurs`) and counts the branches,
+junction nodes and free ends that are left, the centreline's length in world units and the narrowest radius along any branch
+(`afx_centreline_graph`)."""
 from __future__ import annotations
 
 import itertools
@@ -52,7 +55,10 @@ MESH_METRICS = ("VOLUME RATIO 3D", "AREA RATIO 3D", "EULER 3D")
 _EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS + MESH_METRICS
 # and the distance between the two surfaces as meshes (reconstruction_mesh_distance_metrics), tabulated after the mesh columns
 MESH_DISTANCE_METRICS = ("ASSD MESH", "HD MESH", "HD95 MESH")
-_VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS          # every family of columns that needs the ground-truth volume
+# and the centreline read as a graph (reconstruction_graph_metrics): branches and junctions of the pruned predicted centreline, and its
+# length over the true one's, tabulated after the mesh-distance columns
+GRAPH_METRICS = ("BRANCHES 3D", "JUNCTIONS 3D", "LENGTH RATIO 3D")
+_VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS + GRAPH_METRICS          # every family of columns that needs the ground-truth volume
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -98,7 +104,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     mean(gt)), behind the topology columns, and the names of MESH_METRICS (VOLUME RATIO 3D, AREA RATIO 3D, EULER 3D), from one
     `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns, and the names of
     MESH_DISTANCE_METRICS (ASSD MESH, HD MESH, HD95 MESH), from one `reconstruction_mesh_distance_metrics` call (threshold mean(gt),
-    q = 95; NaN when either mesh is empty), behind the mesh columns.  The arguments are checked before any work on the GPU."""
+    q = 95; NaN when either mesh is empty), behind the mesh columns, and the names of GRAPH_METRICS (BRANCHES 3D, JUNCTIONS 3D, LENGTH
+    RATIO 3D), from one `reconstruction_graph_metrics` call (threshold mean(gt), prune factor 1), behind the mesh-distance columns.  The
+    arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -173,6 +181,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         apart = reconstruction_mesh_distance_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(MESH_DISTANCE_METRICS, ("assd", "hd", "hd_percentile")):
             scores[name] = [apart[key]] * n
+    if any(m in want for m in GRAPH_METRICS):
+        tree = reconstruction_graph_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(GRAPH_METRICS, ("n_branches", "n_nodes", "length_ratio")):
+            scores[name] = [tree[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -348,6 +360,61 @@ def reconstruction_centreline_metrics(model, volume, outside, n, threshold=None,
                    "mean_radius_gt": float(distance_transform_edt_3d(vl)[sl].sum()) / n_sl * voxel,
                    "n_pred": n_p, "n_gt": n_l, "passes": rec_p["passes"], "passes_gt": rec_l["passes"], "voxel_size": voxel, "threshold": thr})
     return scores, pred, gt, sp, sl
+
+
+def graph_scores(graph_p, graph_l, rec_p, rec_l, voxel):
+    """The scores of `reconstruction_graph_metrics` from two `engine.centreline_graph` results of the pruned centrelines (lengths in world
+    units), the two pruning records and the voxel size: plain Python on integers and fp64."""
+    out = {}
+    for sfx, g, r in (("", graph_p, rec_p), ("_gt", graph_l, rec_l)):
+        out.update({"n_branches" + sfx: g["n_branches"], "n_nodes" + sfx: g["n_nodes"], "n_free_ends" + sfx: g["n_free_ends"],
+                    "n_spurs_removed" + sfx: r["branches"], "prune_rounds" + sfx: r["rounds"], "length" + sfx: g["total_length"],
+                    "min_radius" + sfx: float("nan") if g["d2_min_all"] is None else float(g["d2_min_all"]) ** 0.5 * voxel})
+    out["length_ratio"] = out["length"] / out["length_gt"] if out["length_gt"] > 0 else float("nan")
+    return out
+
+
+@torch.no_grad()
+def reconstruction_graph_metrics(model, volume, outside, n, threshold=None, largest_component=False, prune_factor=1.0, grids=None):
+    """The two centrelines read as graphs -> (scores, pruned predicted centreline, pruned true centreline, graph of the prediction, graph of
+    the ground truth).
+
+    The masks and skeletons are those of `reconstruction_centreline_metrics` (same threshold, same largest_component).  Both skeletons are
+    pruned (`engine.prune_spurs` at `prune_factor`, with the squared distance transform of the mask that was thinned: a spur no longer than
+    prune_factor x the vessel radius at the junction it hangs on is a thinning artefact) and read with `engine.centreline_graph` at the
+    grid's index_to_world.  Scores, for the prediction and with the suffix _gt for the ground truth, AFTER pruning: n_branches, n_nodes
+    (junction nodes), n_free_ends, n_spurs_removed, prune_rounds, length (the total centreline length in WORLD units) and min_radius
+    (the smallest radius along any branch, world units: voxels times the grid step; NaN without a branch); length_ratio = length /
+    length_gt in fp64 (NaN when the true centreline has no step); voxel_size and threshold."""
+    from ..engine import centreline_graph, distance_transform_edt_3d, filter_components_3d, prune_spurs
+    line, pred, gt, sp, sl = reconstruction_centreline_metrics(model, volume, outside, n, threshold, largest_component, grids)
+    t32 = torch.tensor(line["threshold"], dtype=torch.float32, device=pred.device)
+    vp, vl = (pred >= t32), (gt >= t32)
+    body = filter_components_3d(vp, 3, largest_only=True) if largest_component else vp
+    a = grid_index_to_world(outside, n)
+    res = []
+    for mask, skel in ((body, sp), (vl, sl)):
+        d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
+        pruned, rec = prune_spurs(skel, d2, prune_factor, return_record=True)
+        res.append((pruned, rec, centreline_graph(pruned, d2, a)))
+    scores = graph_scores(res[0][2], res[1][2], res[0][1], res[1][1], line["voxel_size"])
+    scores.update(voxel_size=line["voxel_size"], threshold=line["threshold"])
+    return scores, res[0][0], res[1][0], res[0][2], res[1][2]
+
+
+def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
+    """An `engine.centreline_graph` result as polylines -> (points float64 [P, 3] in world coordinates, offsets int64 [B + 1], radius
+    float64 [P] = voxel_size x sqrt(d2)): branch b is points[offsets[b]:offsets[b + 1]] in path order; what `mesh_io.write_vtk_polylines`
+    takes.  Junction voxels belong to no branch and are not listed.  Host arithmetic in fp64."""
+    a = np.asarray(index_to_world, np.float64).reshape(3, 4)
+    vox = graph["path_voxels"].cpu().numpy().astype(np.int64)
+    n0, n1, n2 = graph["shape"]
+    ijk = np.stack([vox // (n1 * n2), vox // n2 % n1, vox % n2], axis=1).astype(np.float64)
+    points = ijk @ a[:, :3].T + a[:, 3]
+    sizes = graph["branch_size"].cpu().numpy().astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    dd = (d2.reshape(-1).cpu().numpy().astype(np.int64) & 0xffffffff)[vox]
+    return points, offsets, np.sqrt(dd.astype(np.float64)) * float(voxel_size)
 
 
 def grid_index_to_world(outside, n):
