@@ -988,6 +988,43 @@ int afx_prune_spurs(const uint8_t* skel, const uint32_t* d2, int32_t n0, int32_t
                     int32_t sync_every, uint8_t* out, void* record, void* workspace, size_t workspace_bytes, size_t* workspace_needed,
                     void* stream);
 
+/* ---- 3-D Frangi vesselness of a density volume (Frangi et al. 1998): is a bright voxel part of a tube, or of a blob or a plate?
+ * Defined here so that every implementation gives the same result; tests/frangi3d_reference.py restates it in NumPy / SciPy.  The rules
+ * above hold: device pointers, nothing allocated or synchronised, integer atomics only, hipGraph-capturable, the same bits on every run.
+ * fp64 throughout, every expression evaluated operation by operation (no contraction).
+ *
+ * afx_frangi_3d: x is a volume [n0][n1][n2] (row-major; fp64 when x_is_f64 != 0, else fp32, converted to fp64 on load); sigma in voxels
+ * (isotropic unit spacing).  For each sigma s in sigmas[n_sigmas] (1..16 values, each > 0 with int(4 s + 0.5) <= 1000), one after another:
+ *   1. black_ridges != 0: x <- 1 - x.  (0 is the default of the Python layer: a density volume has BRIGHT vessels - the opposite of
+ *      afx_frangi's projections.)
+ *   2. G = scipy.ndimage.gaussian_filter(x, s): separable, axes 0, 1, 2 in that order, radius r = int(4 s + 0.5), weights
+ *      exp(-j^2 / 2 s^2) normalised by NumPy's pairwise sum, mode 'reflect' (period 2n, also for r >= n); each pass sums x[i] w_0 first,
+ *      then the pairs (x[i - j] + x[i + j]) w_j from j = r down to 1
+ *   3. g_a = np.gradient(G, axis=a) and H_ab = (s * s) * np.gradient(g_a, axis=b) for a <= b (unit spacing, central differences inside,
+ *      one-sided at the two ends of a line): six entries, each multiplied by the one product s * s
+ *   4. the eigenvalues of H by 5 cyclic Jacobi sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the third index.  A pair with
+ *      a_pq == 0 is skipped; otherwise theta = (a_qq - a_pp) / (2 a_pq), t = (theta < 0 ? -1 : 1) / (|theta| + sqrt(theta theta + 1)),
+ *      c = 1 / sqrt(t t + 1), s_ = t c, tau = s_ / (1 + c); a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, and from the old values
+ *      a_rp' = a_rp - s_ (a_rq + tau a_rp), a_rq' = a_rq + s_ (a_rp - tau a_rq).  Only + - * / and sqrt: correctly rounded on the host and
+ *      on the device alike.  (4 sweeps reach their floor, at most 6.6 eps ||H||_F from LAPACK's eigvalsh over 12 decades; the fifth is spare.)
+ *   5. the diagonal ordered by |lambda| ascending, stable (a tie: the earlier diagonal position first): l1, l2, l3
+ *   6. ra = (|l2| / d3)^2, d3 = |l3| (1e-10 where 0); rb = (|l1| / d23)^2, d23 = sqrt(|l2 l3|) (1e-10 where 0); S = l1 l1 + l2 l2 + l3 l3;
+ *      v = (1 - exp(-ra / (2 alpha^2))) exp(-rb / (2 beta^2)) (1 - exp(-S / (2 gamma_s^2))); v = 0 where l2 > 0 or l3 > 0
+ *      gamma <= 0: gamma_s = sqrt(max over the volume of S at this scale) / 2, or 1 where that is 0 (the density scale of a trained model is
+ *      arbitrary: a fixed gamma means nothing on it); gamma > 0: that value at every scale
+ *   7. out = max over the scales of v (a NaN propagates, as np.max); scale_index (uint8 [n0][n1][n2], may be NULL) = the first scale that
+ *      attains it (np.argmax over the scale axis)
+ * AFX_E_INVALID (before any HIP call): a null x, out or sigmas; a side < 2 (np.gradient needs two points); n0 n1 n2 >= 2^31; n_sigmas
+ * outside 1..16; a bad sigma; alpha or beta not finite and > 0; gamma NaN or +inf.  Workspace (afx_frangi_3d_workspace_bytes; 0 for
+ * arguments the call refuses), each region rounded up to 256 bytes, N = n0 n1 n2 - independent of n_sigmas: two fp64 [N] (the passes'
+ * volumes), fp64 [3][N] (the eigenvalues of the current scale, which gamma_s needs complete before any v), 16 x 8 bytes (the bit patterns
+ * of max S per scale: S >= 0, so an integer atomicMax on them is exact); AFX_E_WORKSPACE when smaller, with *workspace_needed (when not
+ * NULL) set.  Launches: one memset, then per scale three Gaussian passes, eigen, vessel. */
+size_t afx_frangi_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2, int32_t n_sigmas);
+int afx_frangi_3d(const void* x, int32_t x_is_f64, int32_t n0, int32_t n1, int32_t n2, const double* sigmas, int32_t n_sigmas, double alpha,
+                  double beta, double gamma /* <= 0: per-scale */, int32_t black_ridges, double* out, uint8_t* scale_index /* may be NULL */,
+                  void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -202,6 +202,9 @@ _SIGS = {
     "afx_prune_spurs_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "afx_prune_spurs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_frangi_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "afx_frangi_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double,
+                                C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
 }
 
 _libs = {}

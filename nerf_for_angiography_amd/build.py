@@ -11,11 +11,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
+DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_frangi3d.hip", "afx_image_common.h", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
         "afx_internal.h", os.path.join("..", "..", "include", "afx.h")]
 VARIANTS = {"": [], "safe": ["-DAFX_SAFE_WAITS"],
             "h6": ["-DAFX_H6=1"],      # the 6-bit (bf6 + block scales) H stash: 12.5 % fewer stash bytes, no faster; tests/ compare it with the default
             "stamp": ["-DAFX_STAMP", "-DAFX_SINGLE_TU"],
+            "f3drc": ["-DAFX_FRANGI3D_RECOMPUTE", "-DAFX_SINGLE_TU"],      # measurement: afx_frangi_3d takes the eigenvalues twice instead of keeping them
             "stamp128": ["-DAFX_STAMP", "-DAFX_STAMP_F=128", "-DAFX_SINGLE_TU"]}      # ... of the width-128 kernels      # diagnostic: per-phase cycle stamps of the backward chain kernel (one translation unit)
 
 
@@ -35,6 +36,7 @@ def _units():
             out.append((f"chain16_w{f}_{('fwd', 'bwd', 'phases')[bwd]}", "afx_inst_chain16.hip", [f"-DAFX_INST_F={f}", f"-DAFX_INST_BWD={bwd}"]))
     # linked last: the units above keep the order, and so the code-object registration order, they had before this unit existed
     out.append(("graph", "afx_kernels_graph.hip", []))
+    out.append(("frangi3d", "afx_kernels_frangi3d.hip", []))
     return out
 
 
@@ -69,7 +71,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", jobs: i
         return obj
 
     jobs = jobs or min(8, os.cpu_count() or 1)
-    units = [u for u in _units() if u[0] in ("api", "image", "metrics", "mesh", "sdf", "graph")] if "-DAFX_SINGLE_TU" in VARIANTS[variant] else _units()
+    units = [u for u in _units() if u[0] in ("api", "image", "metrics", "mesh", "sdf", "graph", "frangi3d")] if "-DAFX_SINGLE_TU" in VARIANTS[variant] else _units()
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         objs = list(ex.map(compile_one, units))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs

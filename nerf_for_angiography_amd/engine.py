@@ -1778,6 +1778,49 @@ def centreline_branch_profile(graph: dict, d2: torch.Tensor, b: int, voxel_size=
             "stenosis": 1.0 - r_min / r_med if r_med > 0 else 0.0}
 
 
+def frangi_3d_record(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta: float = 0.5, gamma=None, black_ridges: bool = False, out=None,
+                     scale_index=None, workspace=None, want_scale: bool = True):
+    """afx_frangi_3d on a contiguous float32 or float64 [n0, n1, n2] device volume -> (out float64 [n0, n1, n2], scale_index uint8
+    [n0, n1, n2] or None): the 3-D Frangi vesselness defined in include/afx.h and the index of the first scale that attains it.  Reads
+    nothing back and, with all three buffers passed (the workspace of afx_frangi_3d_workspace_bytes bytes), allocates nothing: the call can
+    be captured in a graph.  gamma None: per scale sqrt(max S) / 2.  want_scale False (and no scale_index buffer): no index is written."""
+    lib = _lib.load()
+    _volume_on_gpu(x, "the volume", "frangi_3d")
+    if x.dtype not in (torch.float32, torch.float64) or not x.is_contiguous():
+        raise ValueError(f"frangi_3d_record: the volume must be a contiguous float32 or float64 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
+    if gamma is not None and not float(gamma) > 0.0:
+        raise ValueError(f"frangi_3d: gamma must be None (per-scale) or > 0, got {gamma!r}")
+    dev = x.device
+    n0, n1, n2 = x.shape
+    sg, ns = _sigma_array(sigmas)
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    nbytes = int(lib.afx_frangi_3d_workspace_bytes(n0, n1, n2, ns))
+    if out is None:
+        out = torch.empty(x.shape if nbytes else (1,), dtype=torch.float64, device=dev)
+    if scale_index is None and want_scale:
+        scale_index = torch.empty(x.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.afx_frangi_3d(_ptr(x), int(x.dtype == torch.float64), n0, n1, n2, sg, ns, float(alpha), float(beta),
+                                 0.0 if gamma is None else float(gamma), int(bool(black_ridges)), _ptr(out), _ptr(scale_index), _ptr(workspace),
+                                 workspace.numel(), None, Engine._stream(dev)), "afx_frangi_3d")
+    return out, scale_index
+
+
+def frangi_3d(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta: float = 0.5, gamma=None, black_ridges: bool = False,
+              return_scale: bool = False):
+    """The 3-D Frangi vesselness (Frangi et al. 1998; the definition in include/afx.h) of a float32 or float64 [n0, n1, n2] device volume ->
+    float64 [n0, n1, n2] in [0, 1): near 1 on bright tubes of a radius near one of `sigmas` (in voxels), near 0 on blobs, plates and
+    background.  black_ridges=False is the default (a density volume has bright vessels; the 2-D `frangi` defaults to dark ones).
+    gamma None: per scale sqrt(max S) / 2, so the result does not depend on the volume's density scale; a float fixes it for all scales.
+    return_scale: (vesselness, uint8 index into `sigmas` of the first scale that attains it)."""
+    _volume_on_gpu(x, "the volume", "frangi_3d")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"frangi_3d: the volume must be float32 or float64, got {x.dtype}")
+    out, idx = frangi_3d_record(x.contiguous(), sigmas, alpha, beta, gamma, black_ridges, want_scale=return_scale)
+    return (out, idx) if return_scale else out
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

@@ -26,7 +26,9 @@ and how far the two surfaces lie apart, measured on the meshes themselves: `reco
 at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid - and the centreline read as a graph:
 `reconstruction_graph_metrics` (GRAPH_METRICS) prunes the thinning spurs of both skeletons (`afx_prune_spurs`) and counts the branches,
 junction nodes and free ends that are left, the centreline's length in world units and the narrowest radius along any branch
-(`afx_centreline_graph`)."""
+(`afx_centreline_graph`) - and whether the bright voxels are tube-shaped in the first place: `reconstruction_vesselness_metrics`
+(VESSELNESS_METRICS) runs the 3-D Frangi filter (`afx_frangi_3d`) over both grids and scores the share of the thresholded reconstruction
+that is tubular, the Dice of the two tubular masks and the ratio of the mean selected scales."""
 from __future__ import annotations
 
 import itertools
@@ -59,6 +61,10 @@ MESH_DISTANCE_METRICS = ("ASSD MESH", "HD MESH", "HD95 MESH")
 # length over the true one's, tabulated after the mesh-distance columns
 GRAPH_METRICS = ("BRANCHES 3D", "JUNCTIONS 3D", "LENGTH RATIO 3D")
 _VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS + GRAPH_METRICS          # every family of columns that needs the ground-truth volume
+# and whether the thresholded reconstruction is tube-shaped at all (reconstruction_vesselness_metrics: the 3-D Frangi filter), a tuple of
+# its own, tabulated after the graph columns; it needs the ground-truth volume as well
+VESSELNESS_METRICS = ("TUBULAR FRACTION 3D", "DICE 3D TUBULAR", "SCALE RATIO 3D")
+_ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -105,8 +111,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns, and the names of
     MESH_DISTANCE_METRICS (ASSD MESH, HD MESH, HD95 MESH), from one `reconstruction_mesh_distance_metrics` call (threshold mean(gt),
     q = 95; NaN when either mesh is empty), behind the mesh columns, and the names of GRAPH_METRICS (BRANCHES 3D, JUNCTIONS 3D, LENGTH
-    RATIO 3D), from one `reconstruction_graph_metrics` call (threshold mean(gt), prune factor 1), behind the mesh-distance columns.  The
-    arguments are checked before any work on the GPU."""
+    RATIO 3D), from one `reconstruction_graph_metrics` call (threshold mean(gt), prune factor 1), behind the mesh-distance columns, and the
+    names of VESSELNESS_METRICS (TUBULAR FRACTION 3D, DICE 3D TUBULAR, SCALE RATIO 3D), from one `reconstruction_vesselness_metrics` call
+    (threshold mean(gt), sigmas (1, 2, 3), v_min 0.1), behind the graph columns.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -154,7 +161,7 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
     if "SSIM" in want:
         scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
-    if any(m in want for m in ("DICE 3D", "DOT 3D") + _VOLUME_METRICS):
+    if any(m in want for m in ("DICE 3D", "DOT 3D") + _ALL_VOLUME_METRICS):
         # the two n^3 grids are evaluated once and shared by the three families of whole-volume scores
         pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
         grids = _reconstruction_grids(model, volume, volume_outside, pts)
@@ -185,6 +192,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         tree = reconstruction_graph_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(GRAPH_METRICS, ("n_branches", "n_nodes", "length_ratio")):
             scores[name] = [tree[key]] * n
+    if any(m in want for m in VESSELNESS_METRICS):
+        tube = reconstruction_vesselness_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(VESSELNESS_METRICS, ("tubular_fraction", "dice_tubular", "scale_ratio")):
+            scores[name] = [tube[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -195,9 +206,9 @@ def _check_metrics(metrics, binary_targets, volume):
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS + _VOLUME_METRICS]
+    unknown = [m for m in metrics if m not in METRICS + _ALL_VOLUME_METRICS]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _VOLUME_METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _ALL_VOLUME_METRICS)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -206,9 +217,9 @@ def _check_metrics(metrics, binary_targets, volume):
         raise ValueError("evaluation_sweep: DICE 2D needs binary_targets")
     if ("DICE 3D" in metrics or "DOT 3D" in metrics) and volume is None:
         raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
-    if any(m in metrics for m in _VOLUME_METRICS) and volume is None:
-        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _VOLUME_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS + _VOLUME_METRICS if m in metrics]
+    if any(m in metrics for m in _ALL_VOLUME_METRICS) and volume is None:
+        raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _ALL_VOLUME_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS + _ALL_VOLUME_METRICS if m in metrics]
 
 
 @torch.no_grad()
@@ -400,6 +411,57 @@ def reconstruction_graph_metrics(model, volume, outside, n, threshold=None, larg
     scores = graph_scores(res[0][2], res[1][2], res[0][1], res[1][1], line["voxel_size"])
     scores.update(voxel_size=line["voxel_size"], threshold=line["threshold"])
     return scores, res[0][0], res[1][0], res[0][2], res[1][2]
+
+
+def vesselness_scores(a, b, vp, vg, ip, ig, sigmas, v_min):
+    """The scores of `reconstruction_vesselness_metrics` from the two thresholded masks A, B (bool), the two vesselness volumes (float64),
+    the two scale-index volumes (uint8) - tensors of one shape on any device - the sigmas and v_min -> (scores, A' = A & (Vp >= v_min)).
+    Integer counts and fp64 sums; a ratio whose divisor is 0 is NaN."""
+    ta, tb = a & (vp >= v_min), b & (vg >= v_min)
+    n_a, n_b, n_ta, n_tb, n_both = (int(v) for v in (a.sum(), b.sum(), ta.sum(), tb.sum(), (ta & tb).sum()))
+    sg = torch.tensor([float(v) for v in sigmas], dtype=torch.float64, device=a.device)
+    sum_a, sum_b = float(sg[ip[ta].long()].sum()), float(sg[ig[tb].long()].sum())
+    nan = float("nan")
+    mean_a, mean_b = (sum_a / n_ta if n_ta else nan), (sum_b / n_tb if n_tb else nan)
+    scores = {"tubular_fraction": n_ta / n_a if n_a else nan, "tubular_fraction_gt": n_tb / n_b if n_b else nan,
+              "dice_tubular": 2.0 * n_both / (n_ta + n_tb) if n_ta + n_tb else nan,
+              "scale_ratio": mean_a / mean_b if n_ta and n_tb and mean_b != 0 else nan, "mean_scale": mean_a, "mean_scale_gt": mean_b,
+              "n_pred": n_a, "n_gt": n_b, "n_tubular": n_ta, "n_tubular_gt": n_tb, "n_tubular_both": n_both,
+              "sigmas": tuple(float(v) for v in sigmas), "v_min": float(v_min)}
+    return scores, ta
+
+
+@torch.no_grad()
+def reconstruction_vesselness_metrics(model, volume, outside, n, threshold=None, sigmas=(1, 2, 3), v_min=0.1, grids=None):
+    """Are the bright voxels of the reconstruction tube-shaped -> (scores, predicted grid, ground-truth grid, tubular mask of the prediction
+    [bool, n^3]).
+
+    A = pred >= threshold, B = gt >= threshold on the grids of `reconstruction_topology_metrics` (threshold: mean(gt) in fp32 unless
+    given).  Vp, Vg = `engine.frangi_3d` of the two grids (the 3-D Frangi vesselness of include/afx.h: bright ridges, `sigmas` in voxels,
+    gamma per scale, so neither depends on the density scale) with the index of the scale each voxel selects.  A' = A & (Vp >= v_min),
+    B' = B & (Vg >= v_min): a floater is blob-like and back-projection haze plate-like - both pass the threshold and fail the filter.
+    scores: tubular_fraction = |A'| / |A|; tubular_fraction_gt = |B'| / |B|, what a perfect reconstruction would score (the wall voxels
+    of a true tube fail the filter as well); dice_tubular = 2 |A' & B'| / (|A'| + |B'|); scale_ratio = the mean selected sigma over A'
+    divided by the mean over B', a coarse ratio of the vessel radii (mean_scale, mean_scale_gt); the counts n_pred, n_gt, n_tubular,
+    n_tubular_gt, n_tubular_both; sigmas, v_min and threshold.  The ratios are formed in fp64 from integer counts and fp64 sums; an
+    empty A' or B' gives NaN for the ratios that divide by it.  ValueError when the threshold leaves A or B empty.  v_min = 0.1 is a
+    default, not a validated operating point.  The mask can be fed to the component, skeleton and surface functions.
+    grids: as in `reconstruction_surface_metrics`."""
+    from ..engine import frangi_3d
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
+    a, b = (pred >= t32), (gt >= t32)
+    n_a, n_b = int(a.sum()), int(b.sum())
+    if n_a == 0 or n_b == 0:
+        empty = [name for cnt, name in ((n_a, "pred"), (n_b, "gt")) if cnt == 0]
+        raise ValueError(f"reconstruction_vesselness_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has "
+                         "no tubular share")
+    vp, ip = frangi_3d(pred, sigmas, return_scale=True)
+    vg, ig = frangi_3d(gt, sigmas, return_scale=True)
+    scores, tubular = vesselness_scores(a, b, vp, vg, ip, ig, sigmas, v_min)
+    scores["threshold"] = thr
+    return scores, pred, gt, tubular
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
