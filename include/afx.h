@@ -1025,6 +1025,52 @@ int afx_frangi_3d(const void* x, int32_t x_is_f64, int32_t n0, int32_t n1, int32
                   double beta, double gamma /* <= 0: per-scale */, int32_t black_ridges, double* out, uint8_t* scale_index /* may be NULL */,
                   void* workspace, size_t workspace_bytes, size_t* workspace_needed, void* stream);
 
+/* ---- Lumen cross-sections along a centreline: how wide is the vessel at each centreline point, below the voxel?  Defined here so that
+ * every implementation gives the same result; tests/lumen_reference.py restates it in NumPy.  The rules above hold: device pointers,
+ * nothing allocated or synchronised, no atomics, hipGraph-capturable, the same bits on every run.  fp64 throughout, only + - * / sqrt,
+ * floor and comparisons, every product and sum rounded on its own (no contraction).
+ *
+ * afx_lumen_profile: vol is a volume [n0][n1][n2] (row-major; fp64 when vol_is_f64 != 0, else fp32, converted to fp64 on load), every
+ * side >= 2, N = n0 n1 n2 < 2^31.  world_to_index W[3][4] (12 doubles on the host, rows W[a][0..2] and the offset W[a][3]).  points:
+ * double [P][3], world coordinates, device.  seg_first, seg_last: int32 [P], device: the first and last point index of the polyline that
+ * point k belongs to.  ray_cs: 2 R doubles on the host, cos(2 pi j / R) at [2 j] and sin(2 pi j / R) at [2 j + 1]; area_coef =
+ * sin(2 pi / R) / 2; both reach the kernel in its arguments, no copy is issued.  R = n_rays in {8, 16, 32, 64}, h = half_window >= 1,
+ * ds = step > 0 in world units, M = max_steps in 1..4096.  Per point k:
+ *   1. Tangent.  a = max(k - h, seg_first[k]), b = min(k + h, seg_last[k]), both then clamped into [0, P - 1].  t = points[b] - points[a];
+ *      n2 = (t0 t0 + t1 t1) + t2 t2.  b <= a or n2 == 0: flag NO_TANGENT.  Otherwise t <- t / sqrt(n2), component by component.  A cycle is
+ *      an open path: no wrap-around.
+ *   2. Frame.  e = the unit axis of the first component with the smallest |t_a|; u = t x e (each component two products and one
+ *      subtraction: u0 = t1 e2 - t2 e1, u1 = t2 e0 - t0 e2, u2 = t0 e1 - t1 e0), normalised as in step 1; v = t x u.
+ *   3. Directions.  d_j,a = (cs_j u_a) + (sn_j v_a).
+ *   4. Lookup f(x).  q_a = ((W[a][0] x0 + W[a][1] x1) + W[a][2] x2) + W[a][3].  x is inside iff q_a >= 0 && q_a <= n_a - 1 on all three
+ *      axes (a NaN or a huge q is outside); nothing is converted to an integer and nothing is loaded before the test passes.  Outside:
+ *      0.0.  Inside: i_a = min(floor(q_a), n_a - 2), tau_a = q_a - i_a; the eight voxels i + {0, 1}^3 converted to fp64;
+ *      lerp(p, q, tau) = p + (q - p) tau along axis 2 (four times), then axis 1 (twice), then axis 0.
+ *   5. Centre.  f_0 = f(points[k]); !(f_0 >= iso): flag CENTRE_OUTSIDE.
+ *   6. March, ray j: for m = 1..M, s_m = m ds (m as a double), x_a = c_a + s_m d_j,a, f_m = f(x).  The crossing is the first m with
+ *      f_m < iso: r_j = ds ((m - 1) + (f_{m-1} - iso) / (f_{m-1} - f_m)), the divisor > 0 as f_{m-1} >= iso > f_m.  No crossing within M
+ *      steps: r_j = M ds and the ray is OPEN.
+ *   7. Reductions, the order part of the definition.  The pairwise tree s(0)_j = r_j r_{(j+1) mod R}, s(l+1)_j = s(l)_2j + s(l)_2j+1,
+ *      area = area_coef s(log2 R)_0 - the area of the star-shaped polygon of the crossings about the point, which need not lie on the
+ *      axis.  r_mean = the same tree over r_j, divided by R.  r_min, r_max over j.  d_min, d_max over j < R / 2 of r_j + r_{j + R/2}.
+ *   8. Outputs.  profile: double [P][AFX_LUMEN_PROFILE_SLOTS] = (area, r_mean, r_min, r_max, d_min, d_max, f_0, 0).  flags: int32 [P]:
+ *      bit 0 AFX_LUMEN_NO_TANGENT, bit 1 AFX_LUMEN_CENTRE_OUTSIDE, bits 8..15 the number of open rays.  radii: double [P][R], or NULL:
+ *      not written.  With bit 0 or bit 1 set the row is zeros but for f_0 in slot 6, the radii are zeros and the open count is 0.
+ * One launch: a lane per ray, 64 / R points per wavefront, 4 wavefronts per workgroup; the reductions are xor-butterflies over the lane
+ * distances 1, 2, 4, .. < R (exactly the tree above in every lane).  No lane waits for another and the march count is fixed before
+ * entry: the kernel ends on any input.  NaN voxels are out of scope.  There is no workspace: a wavefront owns its points.
+ * AFX_E_INVALID, the message naming the argument, before any HIP call: a null vol, world_to_index or ray_cs; a side < 2 or N >= 2^31;
+ * n_points < 0 or > 2^31 - 1; n_rays outside the set; half_window < 1; a non-finite iso, world_to_index, ray_cs or area_coef; step not
+ * finite or not > 0; max_steps outside 1..4096; and, with n_points > 0, a null points, seg_first, seg_last, profile or flags.
+ * n_points == 0 returns AFX_OK without a launch. */
+#define AFX_LUMEN_PROFILE_SLOTS 8
+#define AFX_LUMEN_NO_TANGENT 1
+#define AFX_LUMEN_CENTRE_OUTSIDE 2
+int afx_lumen_profile(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t n1, int32_t n2, const double* world_to_index /* [12], host */,
+                      const double* points, const int32_t* seg_first, const int32_t* seg_last, int64_t n_points, int32_t half_window,
+                      int32_t n_rays, const double* ray_cs /* [2 n_rays], host */, double area_coef, double iso, double step,
+                      int32_t max_steps, double* profile, int32_t* flags, double* radii /* may be NULL */, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -205,6 +205,9 @@ _SIGS = {
     "afx_frangi_3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "afx_frangi_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_double,
                                 C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "afx_lumen_profile": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _libs = {}

@@ -11,12 +11,13 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_frangi3d.hip", "afx_image_common.h", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
+DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_frangi3d.hip", "afx_kernels_lumen.hip", "afx_image_common.h", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
         "afx_internal.h", os.path.join("..", "..", "include", "afx.h")]
 VARIANTS = {"": [], "safe": ["-DAFX_SAFE_WAITS"],
             "h6": ["-DAFX_H6=1"],      # the 6-bit (bf6 + block scales) H stash: 12.5 % fewer stash bytes, no faster; tests/ compare it with the default
             "stamp": ["-DAFX_STAMP", "-DAFX_SINGLE_TU"],
             "f3drc": ["-DAFX_FRANGI3D_RECOMPUTE", "-DAFX_SINGLE_TU"],      # measurement: afx_frangi_3d takes the eigenvalues twice instead of keeping them
+            "lumidle": ["-DAFX_LUMEN_IDLE_LANES", "-DAFX_SINGLE_TU"],      # measurement: afx_lumen_profile with one point per wave at every ray count
             "stamp128": ["-DAFX_STAMP", "-DAFX_STAMP_F=128", "-DAFX_SINGLE_TU"]}      # ... of the width-128 kernels      # diagnostic: per-phase cycle stamps of the backward chain kernel (one translation unit)
 
 
@@ -37,6 +38,7 @@ def _units():
     # linked last: the units above keep the order, and so the code-object registration order, they had before this unit existed
     out.append(("graph", "afx_kernels_graph.hip", []))
     out.append(("frangi3d", "afx_kernels_frangi3d.hip", []))
+    out.append(("lumen", "afx_kernels_lumen.hip", []))
     return out
 
 
@@ -71,7 +73,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", jobs: i
         return obj
 
     jobs = jobs or min(8, os.cpu_count() or 1)
-    units = [u for u in _units() if u[0] in ("api", "image", "metrics", "mesh", "sdf", "graph", "frangi3d")] if "-DAFX_SINGLE_TU" in VARIANTS[variant] else _units()
+    units = [u for u in _units() if u[0] in ("api", "image", "metrics", "mesh", "sdf", "graph", "frangi3d", "lumen")] if "-DAFX_SINGLE_TU" in VARIANTS[variant] else _units()
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         objs = list(ex.map(compile_one, units))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs

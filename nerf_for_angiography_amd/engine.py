@@ -1759,7 +1759,9 @@ def centreline_branch_profile(graph: dict, d2: torch.Tensor, b: int, voxel_size=
     "arc_length" (float64 [n], 0 at the path's first voxel, the Euclidean steps added up), "radius" (float64 [n]: voxel_size x sqrt(d2),
     an isotropic scalar or the geometric reading along the smallest axis is the caller's choice), "r_min", "r_median", "stenosis" =
     1 - r_min / median(r)}.  voxel_size: a scalar or one size per axis (arc lengths use the per-axis sizes, radii the smallest).  Plain
-    torch operations on whatever device the graph lives on."""
+    torch operations on whatever device the graph lives on.  The radius is the inscribed-sphere radius of the thresholded mask, quantised
+    to whole voxels; `centreline_lumen_profile` and `lumen_branch_summary` measure the cross-section's area, diameters and the percent
+    stenosis below the voxel, on the density itself."""
     nb = int(graph["n_branches"])
     if not 1 <= int(b) <= nb:
         raise ValueError(f"centreline_branch_profile: branch {b} outside 1..{nb}")
@@ -1776,6 +1778,212 @@ def centreline_branch_profile(graph: dict, d2: torch.Tensor, b: int, voxel_size=
     r_min, r_med = float(radius.min()), float(radius.median())
     return {"voxels": vox, "arc_length": arc, "radius": radius, "r_min": r_min, "r_median": r_med,
             "stenosis": 1.0 - r_min / r_med if r_med > 0 else 0.0}
+
+
+LUMEN_PROFILE_SLOTS = 8
+LUMEN_NO_TANGENT, LUMEN_CENTRE_OUTSIDE = 1, 2
+_LUMEN_COLUMNS = ("area", "r_mean", "r_min", "r_max", "d_min", "d_max", "centre_value")
+
+
+def lumen_world_to_index(index_to_world=None):
+    """world_to_index of afx_lumen_profile, 12 doubles (rows W[a][0..2], W[a][3]): the inverse of index_to_world ([3, 4] or 12 numbers;
+    None = the identity, exactly) taken in fp64 on the host - W = inv(A), offset -(W o).  The library and the NumPy restatement get this
+    array alike."""
+    import numpy as np
+    if index_to_world is None:
+        return np.asarray(_IDENTITY_AFFINE, np.float64).reshape(-1).copy()
+    a = _affine12(index_to_world, "lumen_profile").reshape(3, 4)
+    w = np.linalg.inv(a[:, :3])
+    return np.concatenate([w, -(w @ a[:, 3])[:, None]], axis=1).reshape(-1)
+
+
+def lumen_ray_table(n_rays: int):
+    """(ray_cs float64 [2 R]: cos(2 pi j / R) at [2 j] and sin(2 pi j / R) at [2 j + 1]; area_coef = sin(2 pi / R) / 2) of afx_lumen_profile,
+    made with NumPy on the host."""
+    import numpy as np
+    r = int(n_rays)
+    if r not in (8, 16, 32, 64):
+        raise ValueError(f"lumen_profile: n_rays must be 8, 16, 32 or 64, got {n_rays!r}")
+    ang = 2.0 * np.pi * np.arange(r, dtype=np.float64) / r
+    cs = np.empty(2 * r, np.float64)
+    cs[0::2], cs[1::2] = np.cos(ang), np.sin(ang)
+    return cs, float(0.5 * np.sin(2.0 * np.pi / r))
+
+
+def lumen_default_step(index_to_world=None) -> float:
+    """The default march step of lumen_profile: half the smallest |A d| over the three axis steps d of index_to_world's matrix A."""
+    import numpy as np
+    a = _affine12(index_to_world, "lumen_profile").reshape(3, 4)[:, :3]
+    return 0.5 * float(np.sqrt((a * a).sum(axis=0)).min())
+
+
+def lumen_profile_record(volume: torch.Tensor, points: torch.Tensor, seg_first: torch.Tensor, seg_last: torch.Tensor, world_to_index, iso: float,
+                         n_rays: int, step: float, max_steps: int, half_window: int = 3, ray_cs=None, area_coef=None, profile=None, flags=None,
+                         radii=None, want_radii: bool = False):
+    """afx_lumen_profile on a contiguous float32 or float64 [n0, n1, n2] device volume, points float64 [P, 3] (world) and seg_first /
+    seg_last int32 [P] on its device -> (profile float64 [P, 8], flags int32 [P], radii float64 [P, n_rays] or None); the definition, the
+    row layout and the flag bits stand in include/afx.h.  world_to_index: 12 host numbers (`lumen_world_to_index`); ray_cs, area_coef:
+    `lumen_ray_table(n_rays)` unless given.  Launches only: nothing is read back, and with profile, flags (and radii) passed nothing is
+    allocated - the call can be captured in a graph."""
+    import numpy as np
+    lib = _lib.load()
+    _volume_on_gpu(volume, "the volume", "lumen_profile")
+    if volume.dtype not in (torch.float32, torch.float64) or not volume.is_contiguous():
+        raise ValueError(f"lumen_profile_record: the volume must be a contiguous float32 or float64 tensor, got {volume.dtype}, "
+                         f"contiguous = {volume.is_contiguous()}")
+    dev = volume.device
+    for t, name in ((points, "points"), (seg_first, "seg_first"), (seg_last, "seg_last")):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"lumen_profile_record: {name} must be a tensor on a GPU; there is no CPU path")
+    if points.dtype != torch.float64 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.device != dev:
+        raise ValueError(f"lumen_profile_record: points must be contiguous float64 [P, 3] on {dev}")
+    n = points.shape[0]
+    for t, name in ((seg_first, "seg_first"), (seg_last, "seg_last")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n or t.device != dev:
+            raise ValueError(f"lumen_profile_record: {name} must be a contiguous int32 tensor of {n} elements on {dev}")
+    r = int(n_rays)
+    if ray_cs is None or area_coef is None:
+        ray_cs, area_coef = lumen_ray_table(r)
+    cs = np.ascontiguousarray(ray_cs, np.float64).reshape(-1)
+    w = np.ascontiguousarray(world_to_index, np.float64).reshape(-1)
+    if w.size != 12 or cs.size != 2 * max(r, 0):
+        raise ValueError(f"lumen_profile_record: world_to_index must hold 12 numbers and ray_cs 2 x n_rays, got {w.size} and {cs.size}")
+    if profile is None:
+        profile = torch.empty((n, LUMEN_PROFILE_SLOTS), dtype=torch.float64, device=dev)
+    if flags is None:
+        flags = torch.empty(n, dtype=torch.int32, device=dev)
+    if radii is None and want_radii:
+        radii = torch.empty((n, max(r, 0)), dtype=torch.float64, device=dev)
+    for t, name, dtype, count in ((profile, "profile", torch.float64, n * LUMEN_PROFILE_SLOTS), (flags, "flags", torch.int32, n),
+                                  (radii, "radii", torch.float64, n * max(r, 0))):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != count):
+            raise ValueError(f"lumen_profile_record: {name} must be a contiguous {dtype} tensor of {count} elements on {dev}")
+    n0, n1, n2 = volume.shape
+    dp = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
+    _lib.check(lib.afx_lumen_profile(_ptr(volume), int(volume.dtype == torch.float64), n0, n1, n2, dp(w), _ptr(points) if n else None,
+                                     _ptr(seg_first) if n else None, _ptr(seg_last) if n else None, n, int(half_window), r, dp(cs),
+                                     float(area_coef), float(iso), float(step), int(max_steps), _ptr(profile) if n else None,
+                                     _ptr(flags) if n else None, _ptr(radii) if radii is not None and n else None, Engine._stream(dev)),
+               "afx_lumen_profile")
+    return profile, flags, radii
+
+
+def lumen_profile(volume: torch.Tensor, points, seg_first, seg_last, index_to_world=None, iso: float = 0.5, n_rays: int = 64, step=None,
+                  r_max=None, half_window: int = 3, return_radii: bool = False) -> dict:
+    """The lumen cross-section at every centreline point (include/afx.h: afx_lumen_profile): a fan of n_rays rays in the plane normal to the
+    centreline is marched in steps of `step` (world units) through the trilinearly interpolated float32 / float64 [n0, n1, n2] device volume
+    until it falls below `iso`; the crossing radii, interpolated below the step, give the area of the cross-section and its diameters.
+    points [P, 3] world coordinates (index (i0, i1, i2) lies at index_to_world, [3, 4]; None: the identity); seg_first / seg_last [P]: the
+    first and last point index of the polyline a point belongs to (the tangent window of +-half_window points stops there).  step: half
+    the smallest voxel step unless given; r_max: how far a ray goes, 32 steps unless given (max_steps = ceil(r_max / step), at most 4096).
+    -> dict of device tensors [P]: area, r_mean, r_min, r_max, d_min, d_max (world units), centre_value (the volume at the point), flags
+    (bit 0: no tangent, bit 1: the point is not inside the lumen, bits 8..15: rays that found no crossing), n_open, valid (flags == 0), and
+    seg_first; with return_radii also radii [P, n_rays].  A flagged point's numbers are zeros."""
+    import math
+    _volume_on_gpu(volume, "the volume", "lumen_profile")
+    if volume.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"lumen_profile: the volume must be float32 or float64, got {volume.dtype}")
+    dev = volume.device
+    pts = torch.as_tensor(points, dtype=torch.float64).to(dev).reshape(-1, 3).contiguous()
+    sf = torch.as_tensor(seg_first).to(dev, torch.int32).reshape(-1).contiguous()
+    sl = torch.as_tensor(seg_last).to(dev, torch.int32).reshape(-1).contiguous()
+    if step is None:
+        step = lumen_default_step(index_to_world)
+    step = float(step)
+    if not (step > 0.0 and math.isfinite(step)):
+        raise ValueError(f"lumen_profile: step must be finite and > 0, got {step!r}")
+    max_steps = 32 if r_max is None else int(math.ceil(float(r_max) / step))
+    profile, flags, radii = lumen_profile_record(volume.contiguous(), pts, sf, sl, lumen_world_to_index(index_to_world), iso, n_rays, step,
+                                                 max_steps, half_window, want_radii=return_radii)
+    out = {name: profile[:, q] for q, name in enumerate(_LUMEN_COLUMNS)}
+    out.update(flags=flags, n_open=(flags >> 8) & 0xff, valid=flags == 0, seg_first=sf, step=step, max_steps=max_steps)
+    if return_radii:
+        out["radii"] = radii
+    return out
+
+
+def centreline_world_points(graph: dict, index_to_world):
+    """The path voxels of a `centreline_graph` result in world coordinates -> (points float64 [P, 3], offsets int64 [B + 1]): branch b
+    (1-based) is points[offsets[b - 1]:offsets[b]] in path order.  Host arithmetic in fp64 (NumPy): the one place that forms these points
+    (`visualization.sweep.centreline_polylines`, `centreline_lumen_profile`)."""
+    import numpy as np
+    a = np.asarray(index_to_world, np.float64).reshape(3, 4)
+    vox = graph["path_voxels"].cpu().numpy().astype(np.int64)
+    n0, n1, n2 = graph["shape"]
+    ijk = np.stack([vox // (n1 * n2), vox // n2 % n1, vox % n2], axis=1).astype(np.float64)
+    points = ijk @ a[:, :3].T + a[:, 3]
+    sizes = graph["branch_size"].cpu().numpy().astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return points, offsets
+
+
+def centreline_segments(points, offsets):
+    """(seg_first int32 [P], seg_last int32 [P], branch int64 [P] 1-based, arc_length float64 [P]) of polylines given as points [P, 3] and
+    offsets [B + 1]: arc_length is 0 at a branch's first point and adds the Euclidean steps, sqrt((dx dx + dy dy) + dz dz), one after
+    another.  NumPy on the host."""
+    import numpy as np
+    offsets = np.asarray(offsets, np.int64)
+    sizes = offsets[1:] - offsets[:-1]
+    p = int(offsets[-1]) if offsets.size else 0
+    branch = np.repeat(np.arange(1, sizes.size + 1, dtype=np.int64), sizes)
+    seg_first = np.repeat(offsets[:-1], sizes).astype(np.int32)
+    seg_last = np.repeat(offsets[1:] - 1, sizes).astype(np.int32)
+    arc = np.zeros(p, np.float64)
+    pts = np.asarray(points, np.float64).reshape(-1, 3)
+    for b in range(sizes.size):
+        lo, hi = int(offsets[b]), int(offsets[b + 1])
+        d = pts[lo + 1:hi] - pts[lo:hi - 1]
+        steps = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        for q in range(steps.size):
+            arc[lo + 1 + q] = arc[lo + q] + steps[q]
+    return seg_first, seg_last, branch, arc
+
+
+def centreline_lumen_profile(graph: dict, volume: torch.Tensor, index_to_world, iso: float, **kw) -> dict:
+    """`lumen_profile` along every branch of a `centreline_graph` result: the points are the path voxels in world coordinates
+    (`centreline_world_points`; junction voxels belong to no branch), each branch a polyline of its own.  -> the dict of `lumen_profile`
+    plus points (float64 [P, 3]), branch (int64 [P], 1-based) and arc_length (float64 [P], 0 at a branch's first point), on the volume's
+    device; `lumen_branch_summary` reads the narrowing per branch from it."""
+    _volume_on_gpu(volume, "the volume", "centreline_lumen_profile")
+    a = _affine12(index_to_world, "centreline_lumen_profile")
+    points, offsets = centreline_world_points(graph, a)
+    seg_first, seg_last, branch, arc = centreline_segments(points, offsets)
+    out = lumen_profile(volume, points, seg_first, seg_last, a, iso, **kw)
+    dev = volume.device
+    out.update(points=torch.from_numpy(points).to(dev), branch=torch.from_numpy(branch).to(dev), arc_length=torch.from_numpy(arc).to(dev))
+    return out
+
+
+def lumen_branch_summary(profile: dict, min_points: int = 5) -> dict:
+    """The narrowing of every branch of a lumen profile (`centreline_lumen_profile`; or `lumen_profile`, its polylines numbered from 1 in
+    the order of their first points) -> dict of NumPy arrays, one entry per branch: branch (the ids, ascending), n_valid, and for a
+    branch with at least min_points valid points (flags == 0): area_min, argmin (the position within the branch's points of the first
+    minimum), area_ref = the LOWER median sorted[(n_valid - 1) // 2] of the valid areas, area_stenosis = 1 - area_min / area_ref and
+    diameter_stenosis = 1 - sqrt(area_min / area_ref); NaN (argmin -1) for the other branches.  Host arithmetic on the read-back arrays."""
+    import numpy as np
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    area, flags = host(profile["area"]).astype(np.float64), host(profile["flags"])
+    if "branch" in profile:
+        branch = host(profile["branch"]).astype(np.int64)
+    else:
+        branch = np.unique(host(profile["seg_first"]), return_inverse=True)[1].astype(np.int64).reshape(-1) + 1
+    ids = np.unique(branch)
+    out = {"branch": ids, "n_valid": np.zeros(ids.size, np.int64), "argmin": np.full(ids.size, -1, np.int64)}
+    for name in ("area_min", "area_ref", "area_stenosis", "diameter_stenosis"):
+        out[name] = np.full(ids.size, np.nan)
+    for q, b in enumerate(ids):
+        mine = np.flatnonzero(branch == b)
+        ok = mine[flags[mine] == 0]
+        out["n_valid"][q] = ok.size
+        if ok.size < max(int(min_points), 1):
+            continue
+        a = area[ok]
+        first = int(np.argmin(a))
+        ref = np.sort(a)[(ok.size - 1) // 2]
+        out["area_min"][q], out["argmin"][q], out["area_ref"][q] = a[first], ok[first] - mine[0], ref
+        ratio = a[first] / ref
+        out["area_stenosis"][q], out["diameter_stenosis"][q] = 1.0 - ratio, 1.0 - np.sqrt(ratio)
+    return out
 
 
 def frangi_3d_record(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta: float = 0.5, gamma=None, black_ridges: bool = False, out=None,

@@ -122,6 +122,11 @@ def build_parser():
                         'per point): the density grid at depth_samples + 1 points per axis, thresholded at --mesh_threshold, thinned '
                         '(afx_skeletonize_3d), its spurs pruned (afx_prune_spurs, factor 1) and read as a graph (afx_centreline_graph), one '
                         'polyline per branch in world coordinates; without the flag nothing changes')
+    p.add_argument('--save_lumen', default=None, metavar='PATH',
+                   help='after training, write the lumen cross-sections along the final model\'s vessel centreline to PATH (.csv): the pruned '
+                        'centreline of --save_centreline at --mesh_threshold, and at each of its points the area and the diameters of the '
+                        'cross-section of the density grid at that level (afx_lumen_profile: 64 rays in the plane normal to the centreline, '
+                        'crossings interpolated below the voxel), one row per point; without the flag nothing changes')
     p.add_argument('--phantom_mesh', default=None, metavar='PATH',
                    help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
                         'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
@@ -172,6 +177,11 @@ def check_args(args):
     if args.save_centreline is not None:
         if os.path.splitext(args.save_centreline)[1].lower() != '.vtk':
             raise ValueError("--save_centreline: PATH must end in .vtk")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
+    if args.save_lumen is not None:
+        if os.path.splitext(args.save_lumen)[1].lower() != '.csv':
+            raise ValueError("--save_lumen: PATH must end in .csv")
         if not args.mesh_threshold > 0:
             raise ValueError("--mesh_threshold: needs SIGMA > 0")
 
@@ -488,6 +498,8 @@ def main(argv=None):
     if args.save_centreline is not None:
         result['centreline_info'] = save_centreline(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold,
                                                     args.save_centreline)
+    if args.save_lumen is not None:
+        result['lumen_info'] = save_lumen(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_lumen)
     return result
 
 
@@ -536,6 +548,53 @@ def save_centreline(model, outside, n, threshold, path, prune_factor=1.0):
     info = dict(n_branches=graph['n_branches'], n_nodes=graph['n_nodes'], n_free_ends=graph['n_free_ends'], n_spurs_removed=rec['branches'],
                 length=graph['total_length'], threshold=float(threshold), path=write_vtk_polylines(path, points, offsets, {'radius': radius}))
     print('centreline', info, flush=True)
+    return info
+
+
+LUMEN_CSV_COLUMNS = ('branch', 'index', 'x', 'y', 'z', 'arc_length', 'area', 'd_min', 'd_max', 'r_mean', 'flags')
+
+
+def save_lumen(model, outside, n, threshold, path, prune_factor=1.0):
+    """--save_lumen: the cross-sections of the model's density grid (n points per axis over [-outside, outside]^3) at the level `threshold`
+    along the pruned centreline of {sigma >= threshold} (that of --save_centreline), one CSV row per centreline point (LUMEN_CSV_COLUMNS;
+    index = the point's position within its branch, lengths in world units, numbers written with repr) -> its info (path, n_points,
+    n_valid, max_area_stenosis and its branch - NaN and -1 without a branch of 5 valid points - and threshold).  An empty mask writes the
+    header alone."""
+    import torch
+    from ..engine import centreline_graph, centreline_lumen_profile, distance_transform_edt_3d, lumen_branch_summary, prune_spurs, skeletonize_3d
+    from ..render import density_grid
+    from ..visualization.sweep import grid_index_to_world
+    grid = density_grid(model, outside, int(n) - 1)
+    t32 = torch.tensor(float(threshold), dtype=torch.float32, device=model.flat_params.device)
+    threshold = float(t32)                                # the level the mask was cut at is the level the rays look for
+    mask = grid >= t32
+    d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
+    pruned = prune_spurs(skeletonize_3d(mask), d2, prune_factor)
+    a = grid_index_to_world(outside, n)
+    graph = centreline_graph(pruned, d2, a)
+    prof = centreline_lumen_profile(graph, grid, a, float(threshold))
+    host = {k: v.cpu().numpy() for k, v in prof.items() if isinstance(v, torch.Tensor)}
+    n_points = int(host['flags'].size)
+    summary = lumen_branch_summary(host)
+    worst = float('nan'), -1
+    known = ~np.isnan(summary['area_stenosis'])
+    if known.any():
+        q = int(np.flatnonzero(known)[np.argmax(summary['area_stenosis'][known])])
+        worst = float(summary['area_stenosis'][q]), int(summary['branch'][q])
+    first = {}
+    tmp = f'{path}.tmp.{os.getpid()}'
+    with open(tmp, 'w') as f:
+        f.write(','.join(LUMEN_CSV_COLUMNS) + '\n')
+        for k in range(n_points):
+            b = int(host['branch'][k])
+            first.setdefault(b, k)
+            row = [b, k - first[b]] + [repr(float(v)) for v in host['points'][k]] + \
+                  [repr(float(host[name][k])) for name in ('arc_length', 'area', 'd_min', 'd_max', 'r_mean')] + [int(host['flags'][k])]
+            f.write(','.join(str(v) for v in row) + '\n')
+    os.replace(tmp, path)
+    info = dict(path=str(path), n_points=n_points, n_valid=int((host['flags'] == 0).sum()), max_area_stenosis=worst[0], branch=worst[1],
+                threshold=float(threshold))
+    print('lumen', info, flush=True)
     return info
 
 

@@ -28,7 +28,9 @@ at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid - and th
 junction nodes and free ends that are left, the centreline's length in world units and the narrowest radius along any branch
 (`afx_centreline_graph`) - and whether the bright voxels are tube-shaped in the first place: `reconstruction_vesselness_metrics`
 (VESSELNESS_METRICS) runs the 3-D Frangi filter (`afx_frangi_3d`) over both grids and scores the share of the thresholded reconstruction
-that is tubular, the Dice of the two tubular masks and the ratio of the mean selected scales."""
+that is tubular, the Dice of the two tubular masks and the ratio of the mean selected scales - and how wide the lumen is:
+`reconstruction_lumen_metrics` (LUMEN_METRICS) measures the cross-sections of both grids along the true centreline below the voxel
+(`afx_lumen_profile`) and scores the area error, the minimal lumen area and the percent stenosis."""
 from __future__ import annotations
 
 import itertools
@@ -64,7 +66,10 @@ _VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS + GRAPH_METRICS        
 # and whether the thresholded reconstruction is tube-shaped at all (reconstruction_vesselness_metrics: the 3-D Frangi filter), a tuple of
 # its own, tabulated after the graph columns; it needs the ground-truth volume as well
 VESSELNESS_METRICS = ("TUBULAR FRACTION 3D", "DICE 3D TUBULAR", "SCALE RATIO 3D")
-_ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS
+# and how wide the reconstructed lumen is along the TRUE centreline, below the voxel (reconstruction_lumen_metrics: cross-sections by
+# afx_lumen_profile), a tuple of its own, tabulated after the vesselness columns; it needs the ground-truth volume as well
+LUMEN_METRICS = ("LUMEN AREA ERR 3D", "MLA RATIO 3D", "STENOSIS ERR 3D")
+_ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS + LUMEN_METRICS
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -113,7 +118,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     q = 95; NaN when either mesh is empty), behind the mesh columns, and the names of GRAPH_METRICS (BRANCHES 3D, JUNCTIONS 3D, LENGTH
     RATIO 3D), from one `reconstruction_graph_metrics` call (threshold mean(gt), prune factor 1), behind the mesh-distance columns, and the
     names of VESSELNESS_METRICS (TUBULAR FRACTION 3D, DICE 3D TUBULAR, SCALE RATIO 3D), from one `reconstruction_vesselness_metrics` call
-    (threshold mean(gt), sigmas (1, 2, 3), v_min 0.1), behind the graph columns.  The arguments are checked before any work on the GPU."""
+    (threshold mean(gt), sigmas (1, 2, 3), v_min 0.1), behind the graph columns, and the names of LUMEN_METRICS (LUMEN AREA ERR 3D, MLA
+    RATIO 3D, STENOSIS ERR 3D), from one `reconstruction_lumen_metrics` call (threshold mean(gt), prune factor 1, 64 rays), behind the
+    vesselness columns.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume)
     dev = model.flat_params.device
@@ -196,6 +203,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         tube = reconstruction_vesselness_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(VESSELNESS_METRICS, ("tubular_fraction", "dice_tubular", "scale_ratio")):
             scores[name] = [tube[key]] * n
+    if any(m in want for m in LUMEN_METRICS):
+        lumen = reconstruction_lumen_metrics(model, volume, volume_outside, pts, grids=grids)[0]
+        for name, key in zip(LUMEN_METRICS, ("lumen_area_err", "mla_ratio", "stenosis_err")):
+            scores[name] = [lumen[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -464,17 +475,63 @@ def reconstruction_vesselness_metrics(model, volume, outside, n, threshold=None,
     return scores, pred, gt, tubular
 
 
+def lumen_scores(prof_p, prof_g, sum_p, sum_g):
+    """The scores of `reconstruction_lumen_metrics` from the two profiles along one centreline (read back: NumPy arrays `area` and `flags`
+    of P points each) and their `engine.lumen_branch_summary` results: NumPy fp64 on the host, NaN where a divisor or a set is empty."""
+    nan = float("nan")
+    ap, ag = np.asarray(prof_p["area"], np.float64), np.asarray(prof_g["area"], np.float64)
+    ok_g = np.asarray(prof_g["flags"]) == 0
+    both = ok_g & (np.asarray(prof_p["flags"]) == 0)
+    n_g, n_b = int(ok_g.sum()), int(both.sum())
+    out = {"n_points": int(ag.size), "n_valid_gt": n_g, "n_valid_both": n_b, "centreline_coverage": n_b / n_g if n_g else nan}
+    out["lumen_area_err"] = float(np.mean(np.abs(ap[both] - ag[both]) / ag[both])) if n_b else nan
+    out["mla"], out["mla_gt"] = (float(ap[both].min()), float(ag[both].min())) if n_b else (nan, nan)
+    out["mla_ratio"] = out["mla"] / out["mla_gt"] if n_b and out["mla_gt"] != 0 else nan
+    sp, sg = np.asarray(sum_p["area_stenosis"], np.float64), np.asarray(sum_g["area_stenosis"], np.float64)
+    out["max_stenosis"] = float(sp[~np.isnan(sp)].max()) if (~np.isnan(sp)).any() else nan
+    out["max_stenosis_gt"] = float(sg[~np.isnan(sg)].max()) if (~np.isnan(sg)).any() else nan
+    pair = ~np.isnan(sp) & ~np.isnan(sg)
+    out["stenosis_err"] = float(np.abs(sp[pair] - sg[pair]).max()) if pair.any() else nan
+    return out
+
+
+@torch.no_grad()
+def reconstruction_lumen_metrics(model, volume, outside, n, threshold=None, prune_factor=1.0, grids=None, **profile_kw):
+    """How wide is the reconstructed lumen along the TRUE centreline -> (scores, profile of the prediction, profile of the ground truth).
+
+    The centreline is the pruned true one of `reconstruction_graph_metrics` (same threshold, prune_factor), so no branch of one graph has
+    to be matched with a branch of the other.  `engine.centreline_lumen_profile` (afx_lumen_profile: include/afx.h) measures the
+    ground-truth grid and the predicted grid along it at iso = threshold with `grid_index_to_world(outside, n)`; profile_kw goes to it
+    (n_rays, step, r_max, half_window).  Both profiles are read back (NumPy arrays per key) and scored on the host in fp64
+    (`lumen_scores`): n_points, n_valid_gt, n_valid_both (points whose cross-section is closed in both grids),
+    centreline_coverage = n_valid_both / n_valid_gt, the share of the true centreline that lies inside the predicted lumen;
+    lumen_area_err = the mean over the both-valid points of |A_p - A_g| / A_g; mla, mla_gt, mla_ratio: the minimal lumen areas over those
+    points and their ratio; max_stenosis, max_stenosis_gt: the largest area_stenosis of `engine.lumen_branch_summary` over the branches;
+    stenosis_err = the largest |S_p,b - S_g,b| over the branches with a summary on both sides; threshold.  NaN where a divisor or a set
+    is empty; ValueError only when the true centreline has no point.  Near a bifurcation rays leak into the sibling branch: the median
+    and the minimum are robust to it.  grids: as in `reconstruction_surface_metrics`."""
+    from ..engine import centreline_lumen_profile, lumen_branch_summary
+    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    tree, _, _, _, graph_l = reconstruction_graph_metrics(model, volume, outside, n, threshold, False, prune_factor, (pred, gt))
+    if int(graph_l["path_voxels"].numel()) == 0:
+        raise ValueError("reconstruction_lumen_metrics: the true centreline has no point at this threshold")
+    a, thr = grid_index_to_world(outside, n), tree["threshold"]
+    profiles = []
+    for x in (pred, gt):
+        prof = centreline_lumen_profile(graph_l, x, a, thr, **profile_kw)
+        profiles.append({k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in prof.items()})
+    scores = lumen_scores(profiles[0], profiles[1], lumen_branch_summary(profiles[0]), lumen_branch_summary(profiles[1]))
+    scores["threshold"] = thr
+    return scores, profiles[0], profiles[1]
+
+
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
     """An `engine.centreline_graph` result as polylines -> (points float64 [P, 3] in world coordinates, offsets int64 [B + 1], radius
     float64 [P] = voxel_size x sqrt(d2)): branch b is points[offsets[b]:offsets[b + 1]] in path order; what `mesh_io.write_vtk_polylines`
     takes.  Junction voxels belong to no branch and are not listed.  Host arithmetic in fp64."""
-    a = np.asarray(index_to_world, np.float64).reshape(3, 4)
+    from ..engine import centreline_world_points
+    points, offsets = centreline_world_points(graph, index_to_world)
     vox = graph["path_voxels"].cpu().numpy().astype(np.int64)
-    n0, n1, n2 = graph["shape"]
-    ijk = np.stack([vox // (n1 * n2), vox // n2 % n1, vox % n2], axis=1).astype(np.float64)
-    points = ijk @ a[:, :3].T + a[:, 3]
-    sizes = graph["branch_size"].cpu().numpy().astype(np.int64)
-    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     dd = (d2.reshape(-1).cpu().numpy().astype(np.int64) & 0xffffffff)[vox]
     return points, offsets, np.sqrt(dd.astype(np.float64)) * float(voxel_size)
 
