@@ -1071,6 +1071,45 @@ int afx_lumen_profile(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t n
                       int32_t n_rays, const double* ray_cs /* [2 n_rays], host */, double area_coef, double iso, double step,
                       int32_t max_steps, double* profile, int32_t* flags, double* radii /* may be NULL */, void* stream);
 
+/* ---- The visual hull of the training views (space carving).  On vessel-only data a point whose projection misses the vessel silhouette
+ * of some view is empty; the votes of all views over a lattice of points are two counts per point.  All arithmetic is fp64, every
+ * operation rounded on its own (no contraction), only + - * / sqrt floor and comparisons: tests/hull_reference.py restates it in NumPy
+ * and the device equals the restatement exactly.
+ *   Lattice.  Point p = (i n1 + j) n2 + k, x_a = ((A[a][0] i + A[a][1] j) + A[a][2] k) + A[a][3], A = index_to_world (12 doubles, host:
+ *      rows A[a][0..2], A[a][3]; i, j, k as doubles).  rho = radius >= 0, in world units: the ball about x the votes speak for (a grid
+ *      cell: half its diagonal).
+ *   Views.  views: double [n_views][AFX_HULL_VIEW_DOUBLES] on the device: R[r][n] at [3 r + n] (the rotation of the pose cam2world =
+ *      [R | c]: camera looks down -z, y up), c at [9..11], the focal length f at [12], [13..15] unused.  width W, height H and the margin
+ *      m = margin_px >= 0 (pixels) are common to all views.  dist: double [n_views][H][W], D_v = the distance from each pixel to the
+ *      nearest mask pixel (0 on the mask) - the caller refuses a view with an empty mask.
+ *   Per point and view, in this order:
+ *      e = x - c;  q_n = (R[0][n] e0 + R[1][n] e1) + R[2][n] e2, n = 0, 1, 2;  d = -q_2.
+ *      !(d - rho > 0): the view neither sees nor rejects the point; next view.
+ *      u = W / 2 + (f q_0) / d;  w = H / 2 - (f q_1) / d      (the inverse of the ray model: pixel centres at the integers)
+ *      l = sqrt(q_0 q_0 + q_1 q_1);  r = ((f rho) (d + l)) / (d (d - rho)) + m
+ *      dx = max(max(0, -u), u - (W - 1));  dy = max(max(0, -w), w - (H - 1));  delta = sqrt(dx dx + dy dy)
+ *      seen iff dx <= r && dy <= r
+ *      iu = min(max(floor(u + 0.5), 0), W - 1);  iw = min(max(floor(w + 0.5), 0), H - 1)
+ *      reject iff seen && D_v[iw][iu] > (r + sqrt(0.5)) + delta           (sqrt(0.5) rounded to fp64)
+ *   Output.  seen, rejects: uint16 [n0 n1 n2], the counts over the views.  The hull is rejects <= max_rejects && seen >= min_seen.
+ *   Guarantees (proofs in DESIGN 1.13; R orthonormal).  For |x' - x| <= rho the projection moves by at most
+ *      f rho (d + l) / (d (d - rho)) pixels.  G1: if some point within rho of x projects within m of a mask pixel centre of view v,
+ *      v does not reject x.  G2: if some point within rho of x projects within m of any pixel centre of v's detector, v sees x.
+ * One launch, a lane per point, k fastest; the view records are read through wave-uniform addresses; no LDS, atomics, workspace or
+ * synchronisation: the call can be captured in a graph.  AFX_E_INVALID before any launch, the message naming the argument: a null
+ * pointer; n_views outside 1..65535; a non-positive extent, width or height; n0 n1 n2 >= 2^31; a non-finite index_to_world; radius or
+ * margin_px negative or not finite; views, dist, seen or rejects not memory of the current device. */
+#define AFX_HULL_VIEW_DOUBLES 16
+int afx_visual_hull(int32_t n0, int32_t n1, int32_t n2, const double* index_to_world /* [12], host */, double radius,
+                    const double* views /* device */, int32_t n_views, int32_t width, int32_t height, double margin_px, const double* dist,
+                    uint16_t* seen, uint16_t* rejects, void* stream);
+
+/* Carving an occupancy grid: where the byte mask[c] == 0, occs[c] = 0 (occs may be NULL) and binary[c] = 0; bits, the packed bitfield
+ * the march reads, is rewritten from the result (bit b of word w = binary[32 w + b] != 0; the spare bits of the last word are 0).
+ * In place, one launch, a lane per cell, no atomics, workspace or synchronisation: capturable.  AFX_E_INVALID: a null grid, mask,
+ * binary or bits; a resolution outside 1..2048. */
+int afx_grid_apply_mask(const afx_grid_desc* grid, const uint8_t* mask, float* occs, uint8_t* binary, uint32_t* bits, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -2029,6 +2029,141 @@ def frangi_3d(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta: float
     return (out, idx) if return_scale else out
 
 
+# ---- the visual hull of the training views (afx_visual_hull) and the mask that carves a grid with it (afx_grid_apply_mask) ----
+HULL_VIEW_DOUBLES = 16
+
+
+def hull_view_records(poses, focal):
+    """The view records of afx_visual_hull, float64 [V, 16] on the host: R row-major at [0..8], c at [9..11], f at [12] of each pose
+    cam2world = [R | c] ([V, 4, 4] or [V, 3, 4]; focal: a number, or one per view)."""
+    import numpy as np
+    p = np.asarray(poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else poses, dtype=np.float64)
+    if p.ndim != 3 or p.shape[1] not in (3, 4) or p.shape[2] != 4:
+        raise ValueError(f"visual_hull_views: poses must be [V, 4, 4] or [V, 3, 4], got {p.shape}")
+    v = p.shape[0]
+    if not 1 <= v <= 65535:
+        raise ValueError(f"visual_hull_views: 1 to 65535 views, got {v}")
+    f = np.asarray(focal.detach().cpu().numpy() if isinstance(focal, torch.Tensor) else focal, dtype=np.float64).reshape(-1)
+    if f.size not in (1, v):
+        raise ValueError(f"visual_hull_views: focal must be one number or one per view ({v}), got {f.size}")
+    f = np.broadcast_to(f, (v,))
+    if not (np.isfinite(p).all() and np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError("visual_hull_views: poses and focal must be finite, focal > 0")
+    rot = p[:, :3, :3]
+    if not np.allclose(rot @ rot.transpose(0, 2, 1), np.eye(3), atol=1e-9):
+        raise ValueError("visual_hull_views: the rotation of a pose is not orthonormal (the hull's bound needs |R^T e| = |e|)")
+    rec = np.zeros((v, HULL_VIEW_DOUBLES), np.float64)
+    rec[:, 0:9] = rot.reshape(v, 9)
+    rec[:, 9:12] = p[:, :3, 3]
+    rec[:, 12] = f
+    return rec
+
+
+def visual_hull_views(poses, masks: torch.Tensor, focal, margin_px: float = 1.0) -> dict:
+    """The training views of a visual hull: poses [V, 4, 4] or [V, 3, 4] (cam2world, the project's own pose), masks [V, H, W] on the GPU
+    (bool or 0/1: the vessel silhouette of each view), focal (a number, or one per view), margin_px (pixels added to every view's
+    tolerance).  Builds the stack of distance images D_v (`distance_transform_edt` of the complement of each mask: 0 on the mask) and the
+    device copy of the view records.  A view with an empty mask is refused (ValueError): it would reject everything it sees.
+    -> dict(records float64 [V, 16] and dist float64 [V, H, W] on the device, n_views, width, height, margin_px)."""
+    import math
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 3:
+        raise ValueError(f"visual_hull_views: masks must be a [V, H, W] tensor, got {type(masks).__name__}"
+                         f"{tuple(masks.shape) if isinstance(masks, torch.Tensor) else ''}")
+    rec = hull_view_records(poses, focal)
+    v, h, w = masks.shape
+    if v != rec.shape[0]:
+        raise ValueError(f"visual_hull_views: {rec.shape[0]} poses but {v} masks")
+    if not (margin_px >= 0 and math.isfinite(margin_px)):
+        raise ValueError(f"visual_hull_views: margin_px must be finite and >= 0, got {margin_px!r}")
+    on = masks != 0
+    empty = torch.nonzero(~on.reshape(v, -1).any(dim=1)).flatten().tolist()
+    if empty:
+        raise ValueError(f"visual_hull_views: the mask of view {empty[0]} is empty ({len(empty)} such view(s)): it would reject every point it sees")
+    if masks.device.type != "cuda":
+        raise AfxError("visual_hull_views: the masks must live on a GPU; there is no CPU path")
+    dist = distance_transform_edt((~on).to(torch.float64))
+    return dict(records=torch.from_numpy(rec).to(masks.device), dist=dist, n_views=v, width=int(w), height=int(h), margin_px=float(margin_px))
+
+
+def hull_default_radius(index_to_world=None) -> float:
+    """Half the longest diagonal of the lattice cell spanned by the three axis steps of index_to_world (12 numbers; None: the identity):
+    every point of the cell about a lattice point lies within it."""
+    import numpy as np
+    a = _affine12(index_to_world, "visual_hull").reshape(3, 4)[:, :3]
+    return 0.5 * max(float(np.sqrt(((a[:, 0] + s1 * a[:, 1] + s2 * a[:, 2]) ** 2).sum())) for s1 in (-1.0, 1.0) for s2 in (-1.0, 1.0))
+
+
+def grid_cell_lattice(roi_aabb, resolution):
+    """(index_to_world 12 doubles, radius) of an occupancy grid's cell centres: cell size s_a = (hi_a - lo_a) / res_a, centre
+    lo_a + s_a / 2 + s_a i_a, radius = half the cell diagonal - formed in fp64 from the grid's float32 box."""
+    import numpy as np
+    box = np.asarray([float(x) for x in roi_aabb], np.float32).astype(np.float64)
+    res = [int(x) for x in resolution]
+    s = (box[3:] - box[:3]) / np.asarray(res, np.float64)
+    o = box[:3] + 0.5 * s
+    a = np.array([s[0], 0, 0, o[0], 0, s[1], 0, o[1], 0, 0, s[2], o[2]], np.float64)
+    return a, 0.5 * float(np.sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]))
+
+
+def visual_hull_record(views: dict, shape, index_to_world, radius: float, seen=None, rejects=None):
+    """afx_visual_hull, the launch alone: the votes of `views` (visual_hull_views) over the lattice x = index_to_world (i, j, k, 1) of
+    `shape` = (n0, n1, n2), each point speaking for the ball of `radius` about it -> (seen, rejects) uint16 [n0, n1, n2] on the views'
+    device.  Nothing is read back and, with seen and rejects passed, nothing is allocated: the call can be captured in a graph."""
+    import numpy as np
+    lib = _lib.load()
+    rec, dist = views["records"], views["dist"]
+    dev = dist.device
+    if dev.type != "cuda":
+        raise AfxError("visual_hull_record: the views must live on a GPU; there is no CPU path")
+    n0, n1, n2 = (int(s) for s in shape)
+    v, w, h = int(views["n_views"]), int(views["width"]), int(views["height"])
+    if rec.dtype != torch.float64 or not rec.is_contiguous() or tuple(rec.shape) != (v, HULL_VIEW_DOUBLES) or rec.device != dev:
+        raise ValueError(f"visual_hull_record: records must be contiguous float64 [{v}, {HULL_VIEW_DOUBLES}] on {dev}")
+    if dist.dtype != torch.float64 or not dist.is_contiguous() or tuple(dist.shape) != (v, h, w):
+        raise ValueError(f"visual_hull_record: dist must be contiguous float64 [{v}, {h}, {w}]")
+    a = np.ascontiguousarray(_affine12(index_to_world, "visual_hull_record"))
+    n = max(n0, 0) * max(n1, 0) * max(n2, 0)
+    if seen is None:
+        seen = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev)
+    if rejects is None:
+        rejects = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev)
+    for t, name in ((seen, "seen"), (rejects, "rejects")):
+        if t.dtype != torch.uint16 or not t.is_contiguous() or t.device != dev or t.numel() != n:
+            raise ValueError(f"visual_hull_record: {name} must be a contiguous uint16 tensor of {n} elements on {dev}")
+    _lib.check(lib.afx_visual_hull(n0, n1, n2, a.ctypes.data_as(C.POINTER(C.c_double)), float(radius), _ptr(rec), v, w, h,
+                                   float(views["margin_px"]), _ptr(dist), _ptr(seen), _ptr(rejects), Engine._stream(dev)), "afx_visual_hull")
+    return seen, rejects
+
+
+def visual_hull(views: dict, shape, index_to_world=None, radius=None, max_rejects: int = 0, min_seen: int = 1, return_counts: bool = False):
+    """The visual hull of the training views over a lattice (include/afx.h: afx_visual_hull): bool [n0, n1, n2], True where at most
+    max_rejects views reject the point and at least min_seen views see it.  A view rejects a point when the whole ball of `radius` about
+    it (default: half the lattice cell's diagonal, so a point speaks for its cell) projects further than the views' margin from every
+    mask pixel.  return_counts: (hull, seen, rejects), the uint16 votes."""
+    if radius is None:
+        radius = hull_default_radius(index_to_world)
+    seen, rejects = visual_hull_record(views, shape, index_to_world, radius)
+    hull = (rejects.to(torch.int32) <= int(max_rejects)) & (seen.to(torch.int32) >= int(min_seen))
+    return (hull, seen, rejects) if return_counts else hull
+
+
+def grid_apply_mask(roi_aabb, resolution, mask_u8, occs, binary_u8, bits):
+    """afx_grid_apply_mask: occs[c] = 0 (occs may be None) and binary_u8[c] = 0 where mask_u8[c] == 0, and the march's bitfield rewritten
+    from the result; in place, one launch."""
+    lib = _lib.load()
+    dev = binary_u8.device
+    if dev.type != "cuda":
+        raise AfxError("grid_apply_mask: the occupancy grid lives on a GPU; there is no CPU fallback")
+    g = _grid_desc(roi_aabb, resolution)
+    n = g.resolution[0] * g.resolution[1] * g.resolution[2]
+    for t, name, dtype, count in ((mask_u8, "mask", torch.uint8, n), (binary_u8, "binary", torch.uint8, n), (occs, "occs", torch.float32, n),
+                                  (bits, "bits", torch.int32, (n + 31) // 32)):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != count):
+            raise ValueError(f"grid_apply_mask: {name} must be a contiguous {dtype} tensor of {count} elements on {dev}")
+    _lib.check(lib.afx_grid_apply_mask(C.byref(g), _ptr(mask_u8), _ptr(occs), _ptr(binary_u8), _ptr(bits), Engine._stream(dev)),
+               "afx_grid_apply_mask")
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

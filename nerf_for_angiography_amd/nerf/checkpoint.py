@@ -59,6 +59,10 @@ def config_fingerprint(args, model_definition: dict, ray_table) -> dict:
     fp = {name: _plain(getattr(args, name, None)) for name in _ARG_FIELDS}
     if getattr(args, "entropy_weight", 0.0):      # (present only when the term is on: state files written without the flag keep their fingerprint)
         fp["entropy_weight"] = float(args.entropy_weight)
+    if getattr(args, "grid_init", None):          # (likewise: --grid_init hull and its three parameters are named only when set)
+        fp["grid_init"] = str(args.grid_init)
+        for name in ("hull_margin", "hull_max_rejects", "hull_threshold"):
+            fp[name] = _plain(getattr(args, name, None))
     for k, v in sorted(model_definition.items()):
         if k != "device":
             fp[f"model.{k}"] = _plain(v)

@@ -61,6 +61,7 @@ class OccupancyGrid(torch.nn.Module):
         self._res_host = [int(x) for x in res]
         self.contraction_type = contraction_type
         self.seed = int(seed)
+        self._carve_u8 = None                         # carve(): a persistent byte mask, the ceiling of `binary` (a plain attribute: not in state_dict)
 
     @property
     def roi_aabb(self):
@@ -100,8 +101,11 @@ class OccupancyGrid(torch.nn.Module):
     def training_state(self):
         """What a resumed run needs of the grid: the EMA `occs`, the mask, the seed of its draws and its shape.  The grid keeps no step or
         warm-up counter of its own: every_n_step / refresh take the training step from the caller, who saves it."""
-        return dict(occs=self.occs.detach().cpu(), binary=self._binary_u8.detach().cpu(), seed=self.seed, resolution=list(self._res_host),
-                    aabb=list(self._aabb_host))
+        state = dict(occs=self.occs.detach().cpu(), binary=self._binary_u8.detach().cpu(), seed=self.seed, resolution=list(self._res_host),
+                     aabb=list(self._aabb_host))
+        if self._carve_u8 is not None:      # only a carved grid carries the entry: the state of every other grid is what it was
+            state["carve"] = self._carve_u8.detach().cpu()
+        return state
 
     @torch.no_grad()
     def load_training_state(self, state):
@@ -112,9 +116,15 @@ class OccupancyGrid(torch.nn.Module):
                              f"is not this one (resolution {self._res_host}, seed {self.seed}, box {self._aabb_host})")
         self.occs.copy_(state["occs"])
         self.set_binary(state["binary"])
+        if state.get("carve") is not None:
+            self._install_carve(state["carve"])
+        elif self._carve_u8 is not None:
+            self._carve_u8 = None
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
+        if self._carve_u8 is not None:
+            self._carve_u8 = fn(self._carve_u8)
         if getattr(self, "_bits_stale", False) and self._binary_u8.is_cuda:
             _engine.grid_pack(self._aabb_host, self._res_host, self._binary_u8, self._bits)
             self._bits_stale = False
@@ -152,6 +162,7 @@ class OccupancyGrid(torch.nn.Module):
         occ = occ_eval_fn(x).reshape(-1).float().contiguous()
         _engine.grid_update(self._aabb_host, self._res_host, self.occs, indices, occ, ema_decay, self._scratch)
         _engine.grid_binarize(self._aabb_host, self._res_host, self.occs, occ_thre, self._binary_u8, self._bits, self._partial)
+        self._apply_carve()
 
     @torch.no_grad()
     def every_n_step(self, step, occ_eval_fn, occ_thre=1e-2, ema_decay=0.95, warmup_steps=256, n=16):
@@ -195,6 +206,49 @@ class OccupancyGrid(torch.nn.Module):
         ws = self._refresh_workspace(_engine.grid_refresh_workspace_bytes(self._aabb_host, self._res_host, n_draw, all_cells))
         _engine.grid_refresh(eng, prepared, prec, self._aabb_host, self._res_host, self.occs, self._binary_u8, self.bits, n_draw, all_cells,
                              self.seed, step, occ_thre, ema_decay, ws)
+        self._apply_carve()
+
+    # ---- carving: a persistent mask (the visual hull of the training views) that the grid never grows out of ----
+    def _apply_carve(self):
+        """The one launch a carved grid adds to every update (afx_grid_apply_mask); nothing when no mask is installed."""
+        if self._carve_u8 is not None:
+            _engine.grid_apply_mask(self._aabb_host, self._res_host, self._carve_u8, self.occs, self._binary_u8, self._bits)
+
+    def _install_carve(self, mask):
+        mask = torch.as_tensor(mask)
+        if mask.numel() != self.num_cells:
+            raise ValueError(f"carve: {mask.numel()} cells, expected {self.num_cells} = {self._res_host}")
+        m = (mask.reshape(-1) != 0).to(device=self.occs.device, dtype=torch.uint8).contiguous()
+        if self._carve_u8 is not None and self._carve_u8.device == m.device:
+            self._carve_u8.copy_(m)                   # a graph captured over the carved grid keeps reading this address
+        else:
+            self._carve_u8 = m
+
+    @torch.no_grad()
+    def carve(self, mask):
+        """Install a persistent mask [res, res, res] (or flat; bool or 0/1): cells where it is 0 are emptied now (occs = 0, binary = 0, the
+        march's bitfield rewritten) and again at the end of every later update (every_n_step, refresh and the graphs captured over them), by
+        one afx_grid_apply_mask launch.  Call it before any graph is captured over the grid: a graph captured earlier does not contain the
+        launch.  carve(None) removes the mask (the emptied cells refill at the next updates); a grid that was never carved launches nothing
+        extra and updates exactly as before.  Side effect: a later update takes mean(occs) over the zeroed cells too, so the threshold
+        min(mean(occs), occ_thre) of a carved grid is lower than that of the same grid uncarved whenever the mean is the smaller one."""
+        if mask is None:
+            self._carve_u8 = None
+            return
+        self._require_gpu()
+        self._install_carve(mask)
+        self._apply_carve()
+
+    @torch.no_grad()
+    def carve_from_views(self, views, max_rejects: int = 0, min_seen: int = 1, return_counts: bool = False):
+        """Carve the grid with the visual hull of `views` (engine.visual_hull_views) taken over the cell centres, each centre speaking for
+        its cell (radius: half the cell diagonal): a cell stays when at most max_rejects views reject it and at least min_seen see it.
+        -> the hull, bool [res, res, res] (return_counts: (hull, seen, rejects))."""
+        self._require_gpu()
+        a, rho = _engine.grid_cell_lattice(self._aabb_host, self._res_host)
+        hull, seen, rejects = _engine.visual_hull(views, self._res_host, a, rho, max_rejects, min_seen, return_counts=True)
+        self.carve(hull)
+        return (hull, seen, rejects) if return_counts else hull
 
     @torch.no_grad()
     def query_occ(self, samples):

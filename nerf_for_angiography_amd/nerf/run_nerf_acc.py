@@ -20,6 +20,8 @@ iterations with Adam and the learning-rate update - from one graph launch (`rend
 `--single-eval` (with `grid`, f16s8, with or without `--graph`) evaluates the model once per iteration: the training step's forward half over
 the march's candidates doubles as the alpha pass.
 `--entropy_weight LAMBDA` (with `grid_ops`) adds LAMBDA times the batch's mean ray entropy (`acc_ray_entropy`) to the loss.
+`--grid_init hull` (with `grid` or `grid_ops`, `--binary True`) carves both occupancy grids with the visual hull of the training views
+before training and keeps it as the ceiling of every grid update (`OccupancyGrid.carve_from_views`, `afx_visual_hull`).
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -127,6 +129,21 @@ def build_parser():
                         'centreline of --save_centreline at --mesh_threshold, and at each of its points the area and the diameters of the '
                         'cross-section of the density grid at that level (afx_lumen_profile: 64 rays in the plane normal to the centreline, '
                         'crossings interpolated below the voxel), one row per point; without the flag nothing changes')
+    p.add_argument('--grid_init', default=None, choices=['hull'],
+                   help='hull (--march grid or grid_ops, --binary True): before training, carve both occupancy grids with the visual hull of '
+                        'the training views - a cell stays only where no training view\'s vessel silhouette (pixel_value < --hull_threshold) '
+                        'rules it out and at least one view sees it (afx_visual_hull over the cell centres) - and keep that mask as the '
+                        'ceiling of every later grid update (OccupancyGrid.carve).  On data with background the tissue outside the vessel '
+                        'attenuates too, so the flag is refused there.  Without the flag nothing changes')
+    p.add_argument('--hull_margin', type=float, default=1.0, metavar='PIXELS',
+                   help='--grid_init hull: pixels added to every view\'s tolerance (1: a vessel point may project up to one pixel from the '
+                        'nearest silhouette pixel centre)')
+    p.add_argument('--hull_max_rejects', type=int, default=0, metavar='N', help='--grid_init hull: a cell stays when at most N views reject it')
+    p.add_argument('--hull_threshold', type=float, default=1.0, metavar='T',
+                   help='--grid_init hull: a training pixel belongs to the silhouette when pixel_value < T (1.0: any attenuation at all)')
+    p.add_argument('--save_hull', default=None, metavar='PATH',
+                   help='--grid_init hull: write the vote volumes to PATH (.npy): uint16 [2, 128, 128, 128], the views that see each cell and '
+                        'the views that reject it')
     p.add_argument('--phantom_mesh', default=None, metavar='PATH',
                    help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
                         'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
@@ -162,6 +179,21 @@ def check_args(args):
                          "under autograd; --march dense, --march grid and the graphs are fused MSE steps)")
     if args.checkpoint_every < 0:
         raise ValueError("--checkpoint_every: needs N >= 0")
+    if getattr(args, 'grid_init', None) == 'hull':
+        if args.binary != 'True':
+            raise ValueError("--grid_init hull: needs --binary True (vessel-only data: on data with background the tissue outside the vessel "
+                             "attenuates too, every pixel would belong to the silhouette, and carving by it would be wrong)")
+        if args.march == 'dense':
+            raise ValueError("--grid_init hull: needs --march grid or grid_ops (the dense march has no occupancy grid to carve)")
+        if not (args.hull_margin >= 0 and np.isfinite(args.hull_margin)):
+            raise ValueError("--hull_margin: needs PIXELS >= 0")
+        if args.hull_max_rejects < 0:
+            raise ValueError("--hull_max_rejects: needs N >= 0")
+    if getattr(args, 'save_hull', None) is not None:
+        if getattr(args, 'grid_init', None) != 'hull':
+            raise ValueError("--save_hull: needs --grid_init hull")
+        if os.path.splitext(args.save_hull)[1].lower() != '.npy':
+            raise ValueError("--save_hull: PATH must end in .npy")
     if args.phantom_mesh is not None:
         if not args.synthetic:
             raise ValueError("--phantom_mesh: needs --synthetic (the phantom replaces the capsule tree of the synthetic dataset)")
@@ -289,6 +321,10 @@ def main(argv=None):
         if args.march != 'dense' else None
     packed_step = args.march == 'grid' and args.precision == 'f16s8'      # else the operator sequence
     batch_size = 131072
+    hull_info = None
+    if args.grid_init == 'hull':      # before any graph is captured over the grids: a carved grid ends every update with the mask's launch
+        hull_info = carve_grids_with_hull([acc_grid, vessel_acc_grid], proj_df, train_ray_df, test_proj_id, args.hull_threshold,
+                                          args.hull_margin, args.hull_max_rejects, device, save_path=args.save_hull, log_dir=args.log_dir)
 
     os.makedirs(args.log_dir, exist_ok=True)
     log = open(os.path.join(args.log_dir, 'train_log.jsonl'), 'a')
@@ -459,6 +495,8 @@ def main(argv=None):
                        img_sample_size * depth_samples_per_ray_coarse)
             if args.entropy_weight > 0:      # the last training batch's mean ray entropy (train_loss includes lambda times it)
                 rec['entropy'] = float(entropy_mean.detach())
+            if hull_info is not None:      # --grid_init hull: the hull's share of the grid and the fewest views that see a kept cell
+                rec['hull'] = dict(share=hull_info['share'], min_seen=hull_info['min_seen'], n_views=hull_info['n_views'])
             if eval_counts is not None:      # candidates : kept samples of the test-view march
                 rec['eval_candidates_per_kept'] = eval_counts[0] / eval_counts[1] if eval_counts[1] else None
             n_marched = 0 if train_graph is None and round_graph is None else n_marched.zero_()
@@ -493,6 +531,8 @@ def main(argv=None):
     result = dict(history=history, best_psnr=highest_psnr, best_iter=highest_iter, model=coarse_model,
                   optimizer=coarse_optimizer, test_image=test_img, log_dir=args.log_dir, acc_grid=acc_grid,
                   vessel_acc_grid=vessel_acc_grid)
+    if hull_info is not None:
+        result['hull_info'] = hull_info
     if args.save_mesh is not None:
         result['mesh_info'] = save_mesh(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_mesh)
     if args.save_centreline is not None:
@@ -501,6 +541,52 @@ def main(argv=None):
     if args.save_lumen is not None:
         result['lumen_info'] = save_lumen(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_lumen)
     return result
+
+
+def training_view_masks(proj_df, train_ray_df, test_proj_id, threshold, device):
+    """The vessel silhouettes of the training views from the training rays alone: pixel (y_position, x_position) of view image_id belongs
+    to the silhouette when pixel_value < threshold; the held-out view is left out -> (poses float64 [V, 4, 4], masks bool [V, H, W] on
+    `device`, focal float64 [V]), the views in the order of proj_df."""
+    ids = [i for i in proj_df.index if i != test_proj_id]
+    if not ids:
+        raise ValueError("--grid_init hull: there is no training view")
+    w, h = int(proj_df['org_img_width'].iloc[0]), int(proj_df['org_img_height'].iloc[0])
+    slot = {image_id: v for v, image_id in enumerate(ids)}
+    image = train_ray_df['image_id'].map(slot)
+    if image.isna().any():
+        raise ValueError("--grid_init hull: a training ray belongs to no training view of the projection frame")
+    inside = torch.from_numpy((train_ray_df['pixel_value'].to_numpy() < float(threshold)))
+    masks = torch.zeros((len(ids), h, w), dtype=torch.bool)
+    masks[torch.from_numpy(image.to_numpy().astype('int64')), torch.from_numpy(train_ray_df['y_position'].to_numpy().astype('int64')),
+          torch.from_numpy(train_ray_df['x_position'].to_numpy().astype('int64'))] = inside
+    poses = np.asarray([proj_df.loc[i, 'tform_cam2world'] for i in ids], dtype=np.float64)
+    focal = np.asarray([proj_df.loc[i, 'focal_length'] for i in ids], dtype=np.float64)
+    return poses, masks.to(device), focal
+
+
+def carve_grids_with_hull(grids, proj_df, train_ray_df, test_proj_id, threshold, margin, max_rejects, device, save_path=None, log_dir=None):
+    """--grid_init hull: the visual hull of the training views over the cell centres of each grid (the grids share their box: computed
+    once per distinct shape), installed as the grids' persistent mask -> its info (share of the grid, fewest views that see a kept cell,
+    views, margin); LOG_DIR/hull.npy keeps the hull as the grid masks are kept, --save_hull the two vote volumes."""
+    poses, masks, focal = training_view_masks(proj_df, train_ray_df, test_proj_id, threshold, device)
+    views = _engine.visual_hull_views(poses, masks, focal, margin_px=margin)
+    hull, seen, rejects = grids[0].carve_from_views(views, max_rejects=max_rejects, min_seen=1, return_counts=True)
+    for g in grids[1:]:
+        if g._res_host == grids[0]._res_host and g._aabb_host == grids[0]._aabb_host:
+            g.carve(hull)
+        else:
+            g.carve_from_views(views, max_rejects=max_rejects, min_seen=1)
+    n_kept = int(hull.sum())
+    info = dict(share=n_kept / hull.numel(), cells=n_kept, n_views=int(views['n_views']), margin=float(margin), max_rejects=int(max_rejects),
+                min_seen=int(seen.to(torch.int32)[hull].min()) if n_kept else 0)
+    if log_dir is not None:
+        os.makedirs(log_dir, exist_ok=True)
+        np.save(os.path.join(log_dir, 'hull.npy'), hull.cpu().numpy())
+    if save_path is not None:
+        np.save(save_path, np.stack([seen.cpu().numpy(), rejects.cpu().numpy()]))
+        info['path'] = str(save_path)
+    print('hull', {k: info[k] for k in ('share', 'cells', 'n_views', 'min_seen', 'margin')}, flush=True)
+    return info
 
 
 def mesh_phantom(path, n, outside, device):

@@ -30,7 +30,10 @@ junction nodes and free ends that are left, the centreline's length in world uni
 (VESSELNESS_METRICS) runs the 3-D Frangi filter (`afx_frangi_3d`) over both grids and scores the share of the thresholded reconstruction
 that is tubular, the Dice of the two tubular masks and the ratio of the mean selected scales - and how wide the lumen is:
 `reconstruction_lumen_metrics` (LUMEN_METRICS) measures the cross-sections of both grids along the true centreline below the voxel
-(`afx_lumen_profile`) and scores the area error, the minimal lumen area and the percent stenosis."""
+(`afx_lumen_profile`) and scores the area error, the minimal lumen area and the percent stenosis - and whether the reconstruction agrees
+with the training images themselves: `reconstruction_hull_metrics` (HULL_METRICS) takes the visual hull of the training views over the
+grid (`afx_visual_hull`) and scores the share of the reconstructed vessel outside it, which needs no ground truth, and the hull's own
+Dice against the truth, the baseline silhouettes alone achieve."""
 from __future__ import annotations
 
 import itertools
@@ -70,6 +73,9 @@ VESSELNESS_METRICS = ("TUBULAR FRACTION 3D", "DICE 3D TUBULAR", "SCALE RATIO 3D"
 # afx_lumen_profile), a tuple of its own, tabulated after the vesselness columns; it needs the ground-truth volume as well
 LUMEN_METRICS = ("LUMEN AREA ERR 3D", "MLA RATIO 3D", "STENOSIS ERR 3D")
 _ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS + LUMEN_METRICS
+# and how the reconstruction stands against the visual hull of the training views (reconstruction_hull_metrics: afx_visual_hull), a tuple
+# of its own, tabulated last; it needs the views (hull_views=engine.visual_hull_views(...)) and the ground-truth volume
+HULL_METRICS = ("OUTSIDE HULL 3D", "DICE 3D HULL", "HULL RATIO 3D")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -91,7 +97,7 @@ def _poses(angles, src_pt, translation, device):
 def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length, src_pt, near_thresh, far_thresh,
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
                      views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3, metrics=None, volume=None,
-                     volume_outside=100.0, volume_points=None):
+                     volume_outside=100.0, volume_points=None, hull_views=None):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
 
     grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
@@ -120,9 +126,11 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     names of VESSELNESS_METRICS (TUBULAR FRACTION 3D, DICE 3D TUBULAR, SCALE RATIO 3D), from one `reconstruction_vesselness_metrics` call
     (threshold mean(gt), sigmas (1, 2, 3), v_min 0.1), behind the graph columns, and the names of LUMEN_METRICS (LUMEN AREA ERR 3D, MLA
     RATIO 3D, STENOSIS ERR 3D), from one `reconstruction_lumen_metrics` call (threshold mean(gt), prune factor 1, 64 rays), behind the
-    vesselness columns.  The arguments are checked before any work on the GPU."""
+    vesselness columns, and the names of HULL_METRICS (OUTSIDE HULL 3D, DICE 3D HULL, HULL RATIO 3D), from one
+    `reconstruction_hull_metrics` call (threshold mean(gt), the hull of `hull_views` = engine.visual_hull_views(...) of the training views,
+    which they need besides `volume`), last.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
-    want = _check_metrics(metrics, binary_targets, volume)
+    want = _check_metrics(metrics, binary_targets, volume, hull_views)
     dev = model.flat_params.device
     n = len(angles)
     poses = _poses(angles, src_pt, translation, dev)
@@ -168,7 +176,7 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
     if "SSIM" in want:
         scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
-    if any(m in want for m in ("DICE 3D", "DOT 3D") + _ALL_VOLUME_METRICS):
+    if any(m in want for m in ("DICE 3D", "DOT 3D") + _ALL_VOLUME_METRICS + HULL_METRICS):
         # the two n^3 grids are evaluated once and shared by the three families of whole-volume scores
         pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
         grids = _reconstruction_grids(model, volume, volume_outside, pts)
@@ -207,19 +215,23 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         lumen = reconstruction_lumen_metrics(model, volume, volume_outside, pts, grids=grids)[0]
         for name, key in zip(LUMEN_METRICS, ("lumen_area_err", "mla_ratio", "stenosis_err")):
             scores[name] = [lumen[key]] * n
+    if any(m in want for m in HULL_METRICS):
+        carved = reconstruction_hull_metrics(model, volume, volume_outside, pts, hull_views, grids=grids)[0]
+        for name, key in zip(HULL_METRICS, ("outside_hull", "dice_hull", "hull_ratio")):
+            scores[name] = [carved[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
 
 
-def _check_metrics(metrics, binary_targets, volume):
+def _check_metrics(metrics, binary_targets, volume, hull_views=None):
     """The metric columns evaluation_sweep fills, in order; raises on a request it cannot serve (before any GPU work)."""
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS + _ALL_VOLUME_METRICS]
+    unknown = [m for m in metrics if m not in METRICS + _ALL_VOLUME_METRICS + HULL_METRICS]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _ALL_VOLUME_METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _ALL_VOLUME_METRICS + HULL_METRICS)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -230,7 +242,12 @@ def _check_metrics(metrics, binary_targets, volume):
         raise ValueError("evaluation_sweep: DICE 3D and DOT 3D need the ground-truth volume (volume=VoxelVolume)")
     if any(m in metrics for m in _ALL_VOLUME_METRICS) and volume is None:
         raise ValueError(f"evaluation_sweep: {[m for m in metrics if m in _ALL_VOLUME_METRICS]} need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS + _ALL_VOLUME_METRICS if m in metrics]
+    hull = [m for m in metrics if m in HULL_METRICS]
+    if hull and hull_views is None:
+        raise ValueError(f"evaluation_sweep: {hull} need the training views (hull_views=engine.visual_hull_views(poses, masks, focal))")
+    if hull and volume is None:
+        raise ValueError(f"evaluation_sweep: {hull} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in METRICS + _ALL_VOLUME_METRICS + HULL_METRICS if m in metrics]
 
 
 @torch.no_grad()
@@ -523,6 +540,45 @@ def reconstruction_lumen_metrics(model, volume, outside, n, threshold=None, prun
     scores = lumen_scores(profiles[0], profiles[1], lumen_branch_summary(profiles[0]), lumen_branch_summary(profiles[1]))
     scores["threshold"] = thr
     return scores, profiles[0], profiles[1]
+
+
+def hull_scores(n_pred, n_pred_outside, n_hull, n_gt, n_both):
+    """The scores of `reconstruction_hull_metrics` from five voxel counts, fp64 on the host, NaN where a divisor is 0: outside_hull =
+    n_pred_outside / n_pred; dice_hull = 2 n_both / (n_hull + n_gt); hull_ratio = n_hull / n_gt."""
+    nan = float("nan")
+    return dict(outside_hull=float(n_pred_outside) / float(n_pred) if n_pred else nan,
+                dice_hull=2.0 * float(n_both) / float(n_hull + n_gt) if n_hull + n_gt else nan,
+                hull_ratio=float(n_hull) / float(n_gt) if n_gt else nan)
+
+
+@torch.no_grad()
+def reconstruction_hull_metrics(model, volume, outside, n, views, threshold=None, grids=None):
+    """How the reconstruction stands against the visual hull of the training views -> (scores, hull mask [bool, n^3], predicted grid,
+    ground-truth grid).
+
+    The hull (`engine.visual_hull`: include/afx.h, afx_visual_hull) is taken over the n^3 points of the evaluation grids
+    (`grid_index_to_world(outside, n)`), each point speaking for its voxel (radius: half the voxel diagonal), from `views` =
+    engine.visual_hull_views(poses, masks, focal) of the TRAINING views.  A = pred >= threshold, B = gt >= threshold (threshold: mean(gt)
+    in fp32 unless given), H = the hull.  scores (`hull_scores`, fp64 on the host from device counts): outside_hull = |A and not H| / |A|, the
+    share of the reconstructed vessel that contradicts a training image - it needs no ground truth (volume=None with `threshold` given
+    leaves the other two NaN); dice_hull = the vessel Dice of H against B, what silhouettes alone achieve - the reconstruction should
+    beat it; hull_ratio = |H| / |B|; and the counts n_pred, n_pred_outside, n_hull, n_gt, n_hull_gt, threshold."""
+    from ..engine import visual_hull
+    if volume is None and grids is None:
+        if threshold is None:
+            raise ValueError("reconstruction_hull_metrics: without the ground-truth volume the threshold must be given")
+        pred, gt = density_grid(model, outside, int(n) - 1), None
+    else:
+        pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
+    hull = visual_hull(views, tuple(pred.shape), grid_index_to_world(outside, n))
+    a = pred >= t32
+    n_pred, n_out, n_hull = int(a.sum()), int((a & ~hull).sum()), int(hull.sum())
+    n_gt, n_both = (int((gt >= t32).sum()), int(((gt >= t32) & hull).sum())) if gt is not None else (0, 0)
+    scores = hull_scores(n_pred, n_out, n_hull if gt is not None else 0, n_gt, n_both)
+    scores.update(n_pred=n_pred, n_pred_outside=n_out, n_hull=n_hull, n_gt=n_gt, n_hull_gt=n_both, threshold=thr)
+    return scores, hull, pred, gt
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
