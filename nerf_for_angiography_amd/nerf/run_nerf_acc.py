@@ -533,13 +533,14 @@ def main(argv=None):
                   vessel_acc_grid=vessel_acc_grid)
     if hull_info is not None:
         result['hull_info'] = hull_info
-    if args.save_mesh is not None:
-        result['mesh_info'] = save_mesh(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_mesh)
-    if args.save_centreline is not None:
-        result['centreline_info'] = save_centreline(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold,
-                                                    args.save_centreline)
-    if args.save_lumen is not None:
-        result['lumen_info'] = save_lumen(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_lumen)
+    exports = (('mesh_info', save_mesh, args.save_mesh), ('centreline_info', save_centreline, args.save_centreline),
+               ('lumen_info', save_lumen, args.save_lumen))
+    exports = [e for e in exports if e[2] is not None]
+    if exports:      # the density grid the exports read, evaluated once
+        from ..render import density_grid
+        grid = density_grid(coarse_model, outside, depth_samples_per_ray_coarse)
+    for key, save, path in exports:
+        result[key] = save(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, path, grid=grid)
     return result
 
 
@@ -603,36 +604,44 @@ def mesh_phantom(path, n, outside, device):
     return voxel_volume_from_mesh(vertices, triangles, n=n, margin=0.1, vol_scale=1.5 * float(outside) / longest, device=device)
 
 
-def save_mesh(model, outside, n, threshold, path):
-    """--save_mesh: the surface {sigma = threshold} of the model's density grid (n points per axis over [-outside, outside]^3), capped, in
-    world coordinates, written by the file name's extension -> its info (V, T, E, B, euler, area, volume, threshold, path)."""
+def _export_grid(model, outside, n, grid):
+    """The density grid the --save_* exports read (n points per axis over [-outside, outside]^3): `grid` when the caller has evaluated it."""
     from ..render import density_grid
+    return density_grid(model, outside, int(n) - 1) if grid is None else grid
+
+
+def _export_tree(grid, outside, n, threshold, prune_factor):
+    """The pruned centreline of {grid >= threshold}, the level rounded to fp32 as the grid is -> (`sweep.centreline_tree`'s result, the
+    grid's index_to_world)."""
+    from ..visualization.sweep import centreline_tree, grid_index_to_world
+    a = grid_index_to_world(outside, n)
+    return centreline_tree(grid >= torch.tensor(float(threshold), dtype=torch.float32, device=grid.device), a, prune_factor), a
+
+
+def save_mesh(model, outside, n, threshold, path, grid=None):
+    """--save_mesh: the surface {sigma = threshold} of the model's density grid (n points per axis over [-outside, outside]^3), capped, in
+    world coordinates, written by the file name's extension -> its info (V, T, E, B, euler, area, volume, threshold, path).  grid: that
+    density grid, when it has been evaluated already."""
     from ..visualization.mesh_io import write_mesh
     from ..visualization.sweep import _grid_mesh
-    vertices, triangles, info = _grid_mesh(density_grid(model, outside, int(n) - 1), float(threshold), outside, n)
+    vertices, triangles, info = _grid_mesh(_export_grid(model, outside, n, grid), float(threshold), outside, n)
     info.update(threshold=float(threshold), path=write_mesh(path, vertices, triangles))
     print('mesh', {k: info[k] for k in ('V', 'T', 'euler', 'area', 'volume', 'path')}, flush=True)
     return info
 
 
-def save_centreline(model, outside, n, threshold, path, prune_factor=1.0):
+def save_centreline(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
     """--save_centreline: the pruned centreline of {sigma >= threshold} on the model's density grid (n points per axis over [-outside,
     outside]^3), one polyline per branch in world coordinates with the radius per point -> its info (branches, nodes, free ends, spurs
-    removed, length, threshold, path).  An empty mask writes a file without lines."""
-    import torch
-    from ..engine import centreline_graph, distance_transform_edt_3d, prune_spurs, skeletonize_3d
-    from ..render import density_grid
+    removed, length, threshold, path).  An empty mask writes a file without lines.  grid: as in `save_mesh`."""
     from ..visualization.mesh_io import write_vtk_polylines
-    from ..visualization.sweep import centreline_polylines, grid_index_to_world
-    mask = density_grid(model, outside, int(n) - 1) >= torch.tensor(float(threshold), dtype=torch.float32, device=model.flat_params.device)
-    d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
-    pruned, rec = prune_spurs(skeletonize_3d(mask), d2, prune_factor, return_record=True)
-    a = grid_index_to_world(outside, n)
-    graph = centreline_graph(pruned, d2, a)
-    voxel = 2.0 * float(outside) / (int(n) - 1)
-    points, offsets, radius = centreline_polylines(graph, d2, a, voxel)
-    info = dict(n_branches=graph['n_branches'], n_nodes=graph['n_nodes'], n_free_ends=graph['n_free_ends'], n_spurs_removed=rec['branches'],
-                length=graph['total_length'], threshold=float(threshold), path=write_vtk_polylines(path, points, offsets, {'radius': radius}))
+    from ..visualization.sweep import centreline_polylines
+    tree, a = _export_tree(_export_grid(model, outside, n, grid), outside, n, threshold, prune_factor)
+    graph = tree['graph']
+    points, offsets, radius = centreline_polylines(graph, tree['d2'], a, 2.0 * float(outside) / (int(n) - 1))
+    info = dict(n_branches=graph['n_branches'], n_nodes=graph['n_nodes'], n_free_ends=graph['n_free_ends'],
+                n_spurs_removed=tree['prune_record']['branches'], length=graph['total_length'], threshold=float(threshold),
+                path=write_vtk_polylines(path, points, offsets, {'radius': radius}))
     print('centreline', info, flush=True)
     return info
 
@@ -640,25 +649,17 @@ def save_centreline(model, outside, n, threshold, path, prune_factor=1.0):
 LUMEN_CSV_COLUMNS = ('branch', 'index', 'x', 'y', 'z', 'arc_length', 'area', 'd_min', 'd_max', 'r_mean', 'flags')
 
 
-def save_lumen(model, outside, n, threshold, path, prune_factor=1.0):
+def save_lumen(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
     """--save_lumen: the cross-sections of the model's density grid (n points per axis over [-outside, outside]^3) at the level `threshold`
     along the pruned centreline of {sigma >= threshold} (that of --save_centreline), one CSV row per centreline point (LUMEN_CSV_COLUMNS;
     index = the point's position within its branch, lengths in world units, numbers written with repr) -> its info (path, n_points,
     n_valid, max_area_stenosis and its branch - NaN and -1 without a branch of 5 valid points - and threshold).  An empty mask writes the
-    header alone."""
-    import torch
-    from ..engine import centreline_graph, centreline_lumen_profile, distance_transform_edt_3d, lumen_branch_summary, prune_spurs, skeletonize_3d
-    from ..render import density_grid
-    from ..visualization.sweep import grid_index_to_world
-    grid = density_grid(model, outside, int(n) - 1)
-    t32 = torch.tensor(float(threshold), dtype=torch.float32, device=model.flat_params.device)
-    threshold = float(t32)                                # the level the mask was cut at is the level the rays look for
-    mask = grid >= t32
-    d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
-    pruned = prune_spurs(skeletonize_3d(mask), d2, prune_factor)
-    a = grid_index_to_world(outside, n)
-    graph = centreline_graph(pruned, d2, a)
-    prof = centreline_lumen_profile(graph, grid, a, float(threshold))
+    header alone.  grid: as in `save_mesh`."""
+    from ..engine import centreline_lumen_profile, lumen_branch_summary
+    grid = _export_grid(model, outside, n, grid)
+    threshold = float(torch.tensor(float(threshold), dtype=torch.float32))      # the level the mask is cut at is the level the rays look for
+    tree, a = _export_tree(grid, outside, n, threshold, prune_factor)
+    prof = centreline_lumen_profile(tree['graph'], grid, a, threshold)
     host = {k: v.cpu().numpy() for k, v in prof.items() if isinstance(v, torch.Tensor)}
     n_points = int(host['flags'].size)
     summary = lumen_branch_summary(host)

@@ -11,29 +11,15 @@ no network - every view in one `afx_ssim` call, in fp64), normalised DOT 2D (:44
 DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against the ground-truth volume sampled at the same points
 (`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope.
 
-Beyond the reference: the surface-distance scores of `reconstruction_surface_metrics` (SURFACE_METRICS) - the Dice of the vessel class, the
-average symmetric surface distance, the Hausdorff distance and its 95th percentile between the two thresholded grids
-(`afx_surface_metrics_3d`: two exact 3-D distance transforms and a radix select on the GPU) - and the topology scores of
-`reconstruction_topology_metrics` (TOPOLOGY_METRICS): into how many connected pieces the thresholded reconstruction falls, which share of
-it its largest piece holds, and the vessel Dice of that piece alone (`afx_label_components_3d`: union-find labelling on the GPU) - and the
-centreline scores of `reconstruction_centreline_metrics` (CENTRELINE_METRICS): clDice and its two halves, topology precision and
-sensitivity, from the medial curves of both masks (`afx_skeletonize_3d`: parallel thinning on the GPU) - and the vessel itself as a
-surface: `reconstruction_mesh` (the triangle mesh of the thresholded reconstruction in world coordinates, `afx_isosurface_3d`: marching
-tetrahedra on the GPU; visualization/mesh_io.py writes it as STL or VTK) and the scores of `reconstruction_mesh_metrics` (MESH_METRICS):
-the enclosed volume and the surface area of the reconstruction over those of the truth, and the Euler characteristic of its surface -
-and how far the two surfaces lie apart, measured on the meshes themselves: `reconstruction_mesh_distance_metrics`
-(MESH_DISTANCE_METRICS), each mesh's vertices against the other's triangles (`afx_mesh_point_distance`), the surface-distance scores
-at sub-voxel resolution where ASSD 3D / HD 3D are quantised to the grid - and the centreline read as a graph:
-`reconstruction_graph_metrics` (GRAPH_METRICS) prunes the thinning spurs of both skeletons (`afx_prune_spurs`) and counts the branches,
-junction nodes and free ends that are left, the centreline's length in world units and the narrowest radius along any branch
-(`afx_centreline_graph`) - and whether the bright voxels are tube-shaped in the first place: `reconstruction_vesselness_metrics`
-(VESSELNESS_METRICS) runs the 3-D Frangi filter (`afx_frangi_3d`) over both grids and scores the share of the thresholded reconstruction
-that is tubular, the Dice of the two tubular masks and the ratio of the mean selected scales - and how wide the lumen is:
-`reconstruction_lumen_metrics` (LUMEN_METRICS) measures the cross-sections of both grids along the true centreline below the voxel
-(`afx_lumen_profile`) and scores the area error, the minimal lumen area and the percent stenosis - and whether the reconstruction agrees
-with the training images themselves: `reconstruction_hull_metrics` (HULL_METRICS) takes the visual hull of the training views over the
-grid (`afx_visual_hull`) and scores the share of the reconstructed vessel outside it, which needs no ground truth, and the hull's own
-Dice against the truth, the baseline silhouettes alone achieve."""
+Beyond the reference: nine more families of whole-volume scores on the same two grids, each a reconstruction_* function with a tuple of
+column names, listed in table order in _VOLUME_FAMILIES at the end of this file; what a family scores is in its function's docstring.
+The surface distances between the two thresholded grids (`afx_surface_metrics_3d`), the connected pieces of the reconstruction
+(`afx_label_components_3d`), clDice on the medial curves (`afx_skeletonize_3d`), the vessel as a capped triangle mesh
+(`reconstruction_mesh`, `afx_isosurface_3d`; visualization/mesh_io.py writes it) with its measures and the distance between the two
+meshes (`afx_mesh_point_distance`), the pruned centreline read as a graph (`afx_prune_spurs`, `afx_centreline_graph`), the tubular
+share by the 3-D Frangi filter (`afx_frangi_3d`), the lumen's cross-sections along the true centreline (`afx_lumen_profile`) and the
+visual hull of the training views (`afx_visual_hull`).  The families share what they derive from the grids through one `GridAnalysis`;
+the chain mask -> distance transform -> skeleton -> pruned skeleton -> graph is `centreline_tree`."""
 from __future__ import annotations
 
 import itertools
@@ -48,33 +34,20 @@ from ..render import density_grid, march_render_projection, render_projection
 # the reference's metric columns in its order (visualization.py:455-495); LPIPS and DISTS need pretrained networks
 METRICS = ("PSNR", "SSIM", "LPIPS", "DISTS", "DICE 2D", "DOT 2D", "DICE 3D", "DOT 3D")
 _NETWORK_METRICS = ("LPIPS", "DISTS")
-# not in the reference: how far the reconstructed vessel surface lies from the true one (reconstruction_surface_metrics), tabulated
-# after the reference's columns
-SURFACE_METRICS = ("DICE 3D VESSEL", "ASSD 3D", "HD 3D", "HD95 3D")
-# not in the reference either: whether the reconstruction is one vessel tree or a tree plus floaters (reconstruction_topology_metrics),
-# tabulated after the surface columns
-TOPOLOGY_METRICS = ("COMPONENTS 3D", "LCC FRACTION 3D", "DICE 3D LCC")
-# and whether the reconstruction follows the true vessel tree's centrelines (reconstruction_centreline_metrics; clDice, Shit et al. 2021),
-# tabulated after the topology columns
-CENTRELINE_METRICS = ("CLDICE 3D", "TPREC 3D", "TSENS 3D")
-# and the reconstructed vessel measured as a surface (reconstruction_mesh_metrics), tabulated after the centreline columns
-MESH_METRICS = ("VOLUME RATIO 3D", "AREA RATIO 3D", "EULER 3D")
+# not in the reference: one tuple of columns per family of whole-volume scores, tabulated behind the reference's columns in this order
+# (_VOLUME_FAMILIES pairs each with its reconstruction_* function); all need the ground-truth volume
+SURFACE_METRICS = ("DICE 3D VESSEL", "ASSD 3D", "HD 3D", "HD95 3D")                  # how far the two vessel surfaces lie apart, on the grid
+TOPOLOGY_METRICS = ("COMPONENTS 3D", "LCC FRACTION 3D", "DICE 3D LCC")               # one vessel tree, or a tree plus floaters
+CENTRELINE_METRICS = ("CLDICE 3D", "TPREC 3D", "TSENS 3D")                           # clDice (Shit et al. 2021)
+MESH_METRICS = ("VOLUME RATIO 3D", "AREA RATIO 3D", "EULER 3D")                      # the vessel measured as a surface
 _EXTRA_METRICS = SURFACE_METRICS + TOPOLOGY_METRICS + CENTRELINE_METRICS + MESH_METRICS
-# and the distance between the two surfaces as meshes (reconstruction_mesh_distance_metrics), tabulated after the mesh columns
-MESH_DISTANCE_METRICS = ("ASSD MESH", "HD MESH", "HD95 MESH")
-# and the centreline read as a graph (reconstruction_graph_metrics): branches and junctions of the pruned predicted centreline, and its
-# length over the true one's, tabulated after the mesh-distance columns
-GRAPH_METRICS = ("BRANCHES 3D", "JUNCTIONS 3D", "LENGTH RATIO 3D")
-_VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS + GRAPH_METRICS          # every family of columns that needs the ground-truth volume
-# and whether the thresholded reconstruction is tube-shaped at all (reconstruction_vesselness_metrics: the 3-D Frangi filter), a tuple of
-# its own, tabulated after the graph columns; it needs the ground-truth volume as well
-VESSELNESS_METRICS = ("TUBULAR FRACTION 3D", "DICE 3D TUBULAR", "SCALE RATIO 3D")
-# and how wide the reconstructed lumen is along the TRUE centreline, below the voxel (reconstruction_lumen_metrics: cross-sections by
-# afx_lumen_profile), a tuple of its own, tabulated after the vesselness columns; it needs the ground-truth volume as well
-LUMEN_METRICS = ("LUMEN AREA ERR 3D", "MLA RATIO 3D", "STENOSIS ERR 3D")
+MESH_DISTANCE_METRICS = ("ASSD MESH", "HD MESH", "HD95 MESH")                        # how far the two meshes lie apart, below the voxel
+GRAPH_METRICS = ("BRANCHES 3D", "JUNCTIONS 3D", "LENGTH RATIO 3D")                   # the pruned centreline read as a graph
+_VOLUME_METRICS = _EXTRA_METRICS + MESH_DISTANCE_METRICS + GRAPH_METRICS
+VESSELNESS_METRICS = ("TUBULAR FRACTION 3D", "DICE 3D TUBULAR", "SCALE RATIO 3D")    # is the thresholded reconstruction tube-shaped at all
+LUMEN_METRICS = ("LUMEN AREA ERR 3D", "MLA RATIO 3D", "STENOSIS ERR 3D")             # the lumen's width along the TRUE centreline
 _ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS + LUMEN_METRICS
-# and how the reconstruction stands against the visual hull of the training views (reconstruction_hull_metrics: afx_visual_hull), a tuple
-# of its own, tabulated last; it needs the views (hull_views=engine.visual_hull_views(...)) and the ground-truth volume
+# against the visual hull of the training views: needs the views (hull_views=engine.visual_hull_views(...)) besides the volume
 HULL_METRICS = ("OUTSIDE HULL 3D", "DICE 3D HULL", "HULL RATIO 3D")
 
 
@@ -111,24 +84,14 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
 
     metrics=None: the metric columns PSNR, DOT 2D[, DICE 2D when binary_targets are given].  Otherwise a list drawn from METRICS, tabulated
     in the reference's order (PSNR, SSIM, DICE 2D, DOT 2D, DICE 3D, DOT 3D); LPIPS and DISTS raise NotImplementedError.  DICE 2D needs
-    binary_targets, DICE 3D / DOT 3D need `volume` (a VoxelVolume): `reconstruction_metrics(model, volume, volume_outside, volume_points)`,
-    volume_points defaulting to depth_samples_per_ray + 1 as upstream (:102), its two scores repeated on every row (:490, :495).  The
-    names of SURFACE_METRICS (DICE 3D VESSEL, ASSD 3D, HD 3D, HD95 3D) may be listed too: they need `volume` as well, come from one
-    `reconstruction_surface_metrics(model, volume, volume_outside, volume_points)` call (threshold mean(gt), q = 95, distances in world
-    units), follow the reference's columns and are repeated on every row.  So are the names of TOPOLOGY_METRICS (COMPONENTS 3D, LCC
-    FRACTION 3D, DICE 3D LCC), from one `reconstruction_topology_metrics` call (threshold mean(gt), 26 neighbours), behind the surface
-    columns, and the names of CENTRELINE_METRICS (CLDICE 3D, TPREC 3D, TSENS 3D), from one `reconstruction_centreline_metrics` call (threshold
-    mean(gt)), behind the topology columns, and the names of MESH_METRICS (VOLUME RATIO 3D, AREA RATIO 3D, EULER 3D), from one
-    `reconstruction_mesh_metrics` call (threshold mean(gt), capped meshes), behind the centreline columns, and the names of
-    MESH_DISTANCE_METRICS (ASSD MESH, HD MESH, HD95 MESH), from one `reconstruction_mesh_distance_metrics` call (threshold mean(gt),
-    q = 95; NaN when either mesh is empty), behind the mesh columns, and the names of GRAPH_METRICS (BRANCHES 3D, JUNCTIONS 3D, LENGTH
-    RATIO 3D), from one `reconstruction_graph_metrics` call (threshold mean(gt), prune factor 1), behind the mesh-distance columns, and the
-    names of VESSELNESS_METRICS (TUBULAR FRACTION 3D, DICE 3D TUBULAR, SCALE RATIO 3D), from one `reconstruction_vesselness_metrics` call
-    (threshold mean(gt), sigmas (1, 2, 3), v_min 0.1), behind the graph columns, and the names of LUMEN_METRICS (LUMEN AREA ERR 3D, MLA
-    RATIO 3D, STENOSIS ERR 3D), from one `reconstruction_lumen_metrics` call (threshold mean(gt), prune factor 1, 64 rays), behind the
-    vesselness columns, and the names of HULL_METRICS (OUTSIDE HULL 3D, DICE 3D HULL, HULL RATIO 3D), from one
-    `reconstruction_hull_metrics` call (threshold mean(gt), the hull of `hull_views` = engine.visual_hull_views(...) of the training views,
-    which they need besides `volume`), last.  The arguments are checked before any work on the GPU."""
+    binary_targets.
+
+    The whole-volume columns - DICE 3D, DOT 3D and the families of _VOLUME_FAMILIES, tabulated in that table's order behind the reference's
+    columns - need `volume` (a VoxelVolume), the hull columns `hull_views` = engine.visual_hull_views(...) of the training views as well.
+    Each family is one call of the table's function at its defaults (threshold mean(gt)) on volume_points points per axis over
+    [-volume_outside, volume_outside]^3 (default depth_samples_per_ray + 1 as upstream, :102), its scores repeated on every row (:490,
+    :495).  All families share one `GridAnalysis`: the two grids are evaluated once, and so is every mask, skeleton, centreline, mesh and
+    filter response more than one family reads.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume, hull_views)
     dev = model.flat_params.device
@@ -176,49 +139,17 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         scores["DICE 2D"] = (bp == bt).float().mean(-1).cpu().tolist()
     if "SSIM" in want:
         scores["SSIM"] = ssim(preds.view(n, int(img_height), int(img_width)), tgt.view(n, int(img_height), int(img_width))).cpu().tolist()
-    if any(m in want for m in ("DICE 3D", "DOT 3D") + _ALL_VOLUME_METRICS + HULL_METRICS):
-        # the two n^3 grids are evaluated once and shared by the three families of whole-volume scores
-        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
-        grids = _reconstruction_grids(model, volume, volume_outside, pts)
-    if "DICE 3D" in want or "DOT 3D" in want:
-        dice3d, dot3d, _, _ = reconstruction_metrics(model, volume, volume_outside, pts, grids=grids)
-        scores["DICE 3D"], scores["DOT 3D"] = [dice3d] * n, [dot3d] * n
-    if any(m in want for m in SURFACE_METRICS):
-        surf, _, _ = reconstruction_surface_metrics(model, volume, volume_outside, pts, grids=grids)
-        for name, key in zip(SURFACE_METRICS, ("dice_vessel", "assd", "hd", "hd_percentile")):
-            scores[name] = [surf[key]] * n
-    if any(m in want for m in TOPOLOGY_METRICS):
-        topo = reconstruction_topology_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(TOPOLOGY_METRICS, ("n_components", "lcc_fraction", "dice_lcc")):
-            scores[name] = [topo[key]] * n
-    if any(m in want for m in CENTRELINE_METRICS):
-        line = reconstruction_centreline_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(CENTRELINE_METRICS, ("cldice", "tprec", "tsens")):
-            scores[name] = [line[key]] * n
-    if any(m in want for m in MESH_METRICS):
-        mesh = reconstruction_mesh_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(MESH_METRICS, ("volume_ratio", "area_ratio", "euler")):
-            scores[name] = [mesh[key]] * n
-    if any(m in want for m in MESH_DISTANCE_METRICS):
-        apart = reconstruction_mesh_distance_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(MESH_DISTANCE_METRICS, ("assd", "hd", "hd_percentile")):
-            scores[name] = [apart[key]] * n
-    if any(m in want for m in GRAPH_METRICS):
-        tree = reconstruction_graph_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(GRAPH_METRICS, ("n_branches", "n_nodes", "length_ratio")):
-            scores[name] = [tree[key]] * n
-    if any(m in want for m in VESSELNESS_METRICS):
-        tube = reconstruction_vesselness_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(VESSELNESS_METRICS, ("tubular_fraction", "dice_tubular", "scale_ratio")):
-            scores[name] = [tube[key]] * n
-    if any(m in want for m in LUMEN_METRICS):
-        lumen = reconstruction_lumen_metrics(model, volume, volume_outside, pts, grids=grids)[0]
-        for name, key in zip(LUMEN_METRICS, ("lumen_area_err", "mla_ratio", "stenosis_err")):
-            scores[name] = [lumen[key]] * n
-    if any(m in want for m in HULL_METRICS):
-        carved = reconstruction_hull_metrics(model, volume, volume_outside, pts, hull_views, grids=grids)[0]
-        for name, key in zip(HULL_METRICS, ("outside_hull", "dice_hull", "hull_ratio")):
-            scores[name] = [carved[key]] * n
+    analysis = None
+    for names, score, keys in _VOLUME_FAMILIES:
+        if not any(m in want for m in names):
+            continue
+        if analysis is None:                                  # the two n^3 grids, evaluated once for every family
+            pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+            analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
+        views = (hull_views,) if names is HULL_METRICS else ()
+        got = score(model, volume, volume_outside, pts, *views, grids=analysis)[0]
+        for name, key in zip(names, keys):
+            scores[name] = [got[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -267,6 +198,103 @@ def _reconstruction_grids(model, volume, outside, n, grids=None):
     return density_grid(model, outside, int(n) - 1), ground_truth_grid(volume, outside, n)
 
 
+def centreline_skeleton(mask):
+    """The unpruned half of `centreline_tree` -> {"dist", "d2", "skeleton", "skeleton_record"}: the exact distance transform of a bool
+    device mask with its integer square (one `engine.distance_transform_edt_3d` call), its medial curves and their thinning record."""
+    from ..engine import distance_transform_edt_3d, skeletonize_3d
+    dist, d2 = distance_transform_edt_3d(mask, return_squared=True)
+    skeleton, record = skeletonize_3d(mask, return_record=True)
+    return {"dist": dist, "d2": d2, "skeleton": skeleton, "skeleton_record": record}
+
+
+def centreline_tree(mask, index_to_world, prune_factor=1.0, skeleton=None):
+    """The centreline of a bool device mask, from the mask to the graph -> `centreline_skeleton(mask)` (or `skeleton`, that result computed
+    earlier: the mask is not read then) plus "pruned" and "prune_record" (`engine.prune_spurs` at `prune_factor` with d2: a spur no longer
+    than prune_factor x the vessel radius at its junction is a thinning artefact) and "graph" (`engine.centreline_graph` of pruned)."""
+    from ..engine import centreline_graph, prune_spurs
+    tree = dict(centreline_skeleton(mask) if skeleton is None else skeleton)
+    tree["pruned"], tree["prune_record"] = prune_spurs(tree["skeleton"], tree["d2"], prune_factor, return_record=True)
+    tree["graph"] = centreline_graph(tree["pruned"], tree["d2"], index_to_world)
+    return tree
+
+
+class GridAnalysis:
+    """The predicted and the ground-truth grid of the whole-volume scores (n^3 points over [-outside, outside]^3; gt None where there is no
+    truth) and what more than one family of scores derives from them.  Each method computes its result once per set of the arguments it
+    depends on and keeps it in `cache`; everything kept is bit-reproducible, so sharing changes no number.  Every reconstruction_* function
+    takes one as `grids=`; whoever holds one leaves the tensors it hands out unchanged."""
+
+    def __init__(self, pred, gt, outside, n):
+        self.pred, self.gt, self.outside, self.n, self.cache = pred, gt, float(outside), int(n), {}
+        self.voxel, self.index_to_world = 2.0 * self.outside / (self.n - 1), grid_index_to_world(outside, n)      # voxel: the grid step
+
+    def _once(self, key, make):
+        if key not in self.cache:
+            self.cache[key] = make()
+        return self.cache[key]
+
+    def threshold(self, threshold=None):
+        """The level both grids are cut at, as a float: `threshold`, or mean(gt) in fp32 - the rule DICE 3D uses."""
+        return self._once("mean(gt)", lambda: float(torch.mean(self.gt))) if threshold is None else float(threshold)
+
+    def masks(self, thr):
+        """(A = pred >= thr, B = gt >= thr, |A|, |B|), thr rounded to fp32 as the grids are; without a ground truth B is None and |B| 0."""
+        def cut():
+            t32 = torch.tensor(thr, dtype=torch.float32, device=self.pred.device)
+            a, b = self.pred >= t32, None if self.gt is None else self.gt >= t32
+            return a, b, int(a.sum()), 0 if b is None else int(b.sum())
+        return self._once(("masks", thr), cut)
+
+    def body(self, thr, largest_component=False, connectivity=3):
+        """A, or with largest_component its largest connected piece alone (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours)."""
+        from ..engine import filter_components_3d
+        if not largest_component:
+            return self.masks(thr)[0]
+        return self._once(("body", thr, int(connectivity)), lambda: filter_components_3d(self.masks(thr)[0], connectivity, largest_only=True))
+
+    def skeleton(self, side, thr, largest_component=False):
+        """`centreline_skeleton` of `side`: "gt" is B, "pred" body(thr, largest_component) at 26 neighbours - the truth is never filtered."""
+        lc = side == "pred" and bool(largest_component)
+        return self._once(("skeleton", side, thr, lc), lambda: centreline_skeleton(self.body(thr, lc) if side == "pred" else self.masks(thr)[1]))
+
+    def tree(self, side, thr, largest_component=False, prune_factor=1.0):
+        """`centreline_tree` of the same mask at the grid's index_to_world, grown from the shared skeleton."""
+        lc = side == "pred" and bool(largest_component)
+        return self._once(("tree", side, thr, lc, float(prune_factor)),
+                          lambda: centreline_tree(None, self.index_to_world, prune_factor, self.skeleton(side, thr, lc)))
+
+    def mesh(self, side, thr, largest_component=False, connectivity=3):
+        """(vertices, triangles, info) of `_grid_mesh`: the capped surface of `side` at the level thr in world coordinates; the largest
+        component of the prediction is meshed at 0.5 - its surface runs half-way between the voxels."""
+        if side == "pred" and largest_component:
+            return self._once(("mesh", side, thr, int(connectivity)),
+                              lambda: _grid_mesh(self.body(thr, True, connectivity).float(), 0.5, self.outside, self.n))
+        return self._once(("mesh", side, thr), lambda: _grid_mesh(self.pred if side == "pred" else self.gt, thr, self.outside, self.n))
+
+    def frangi(self, side, sigmas):
+        """(vesselness float64, index of the selected scale uint8) of `engine.frangi_3d` over the grid of `side`."""
+        from ..engine import frangi_3d
+        return self._once(("frangi", side, tuple(float(s) for s in sigmas)),
+                          lambda: frangi_3d(self.pred if side == "pred" else self.gt, sigmas, return_scale=True))
+
+
+def _analysis(model, volume, outside, n, grids, threshold):
+    """(the GridAnalysis a reconstruction_* function works on, its threshold): `grids` itself when it is one, else a fresh one around the
+    (predicted, ground-truth) pair `grids`, or around the two grids evaluated here."""
+    if not isinstance(grids, GridAnalysis):
+        grids = GridAnalysis(*_reconstruction_grids(model, volume, outside, n, grids), outside, n)
+    if (grids.outside, grids.n) != (float(outside), int(n)):
+        raise ValueError(f"grids= holds {grids.n} points per axis over +-{grids.outside}, the call asks for {int(n)} over +-{float(outside)}")
+    return grids, grids.threshold(threshold)
+
+
+def _refuse_empty(who, n_pred, n_gt, what):
+    """The ValueError every family raises, under its own name, when its threshold leaves the prediction or the truth with nothing."""
+    empty = [name for cnt, name in ((n_pred, "pred"), (n_gt, "gt")) if cnt == 0]
+    if empty:
+        raise ValueError(f"{who}: no voxel of {' or '.join(empty)} reaches its threshold: an empty {what}")
+
+
 @torch.no_grad()
 def reconstruction_metrics(model, volume, outside, n, grids=None):
     """DICE 3D and DOT 3D of visualization.py:480-495 for 'ct' data -> (dice_3d, dot_3d, predicted grid, ground-truth grid).
@@ -275,7 +303,7 @@ def reconstruction_metrics(model, volume, outside, n, grids=None):
     :216-219), `density_grid(model, outside, n - 1)`; the ground truth `ground_truth_grid(volume, outside, n)`.  thr = mean(gt) in fp32 as
     torch.mean gives it; DICE 3D is the fraction of points where (pred >= thr) == (gt >= thr) (Dice(average='micro') over both classes of a
     0/1 volume, as DICE 2D); DOT 3D = mean(pred * gt), the products in fp32, their mean accumulated in fp64."""
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
+    pred, gt = (grids.pred, grids.gt) if isinstance(grids, GridAnalysis) else _reconstruction_grids(model, volume, outside, n, grids)
     thr = torch.mean(gt)
     agree = ((pred >= thr) == (gt >= thr)).sum()
     dice = agree.double() / gt.numel()
@@ -295,20 +323,18 @@ def reconstruction_surface_metrics(model, volume, outside, n, threshold=None, q=
     voxel_size, threshold, q and the counts.  ValueError when the threshold leaves either grid empty.  largest_component: the scores of
     the largest connected component of pred >= threshold alone (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) - the surface distances
     without the floaters, one stray voxel of which sets HD; the returned predicted grid is the unfiltered one.  grids: the (predicted,
-    ground-truth) pair another of the reconstruction_* functions returned for the same points, to save evaluating them again."""
-    from ..engine import filter_components_3d, surface_metrics_3d
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
+    ground-truth) pair another of the reconstruction_* functions returned for the same points, to save evaluating them again, or a
+    `GridAnalysis` of that pair, to share what the families derive from it as well."""
+    from ..engine import surface_metrics_3d
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
     if largest_component:
-        lcc = filter_components_3d(pred >= torch.tensor(thr, dtype=torch.float32, device=pred.device), connectivity, largest_only=True)
-        scores = surface_metrics_3d(lcc.float(), gt, 0.5, thr, q)
+        scores = surface_metrics_3d(an.body(thr, True, connectivity).float(), an.gt, 0.5, thr, q)
     else:
-        scores = surface_metrics_3d(pred, gt, thr, thr, q)
-    voxel = 2.0 * float(outside) / (int(n) - 1)
+        scores = surface_metrics_3d(an.pred, an.gt, thr, thr, q)
     for key in ("assd", "hd", "hd_percentile"):
-        scores[key] = scores[key] * voxel
-    scores["voxel_size"], scores["threshold"] = voxel, thr
-    return scores, pred, gt
+        scores[key] = scores[key] * an.voxel
+    scores["voxel_size"], scores["threshold"] = an.voxel, thr
+    return scores, an.pred, an.gt
 
 
 @torch.no_grad()
@@ -324,23 +350,17 @@ def reconstruction_topology_metrics(model, volume, outside, n, threshold=None, c
     threshold.  Both ratios are formed in fp64 from integer counts.  ValueError when the threshold leaves either grid empty.  grids: as
     in `reconstruction_surface_metrics`."""
     from ..engine import components_filter, components_record
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
-    a, b = (pred >= t32), (gt >= t32)
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    a, b, n_a, n_b = an.masks(thr)
+    _refuse_empty("reconstruction_topology_metrics", n_a, n_b, "volume has no components")
     labels, sizes, rec_a = components_record(a.to(torch.uint8).contiguous(), connectivity)
     lcc = components_filter(labels, sizes, rec_a, largest_only=True).bool()
     rec_b = components_record(b.to(torch.uint8).contiguous(), connectivity)[2]
-    n_a, k_a, n_l = (int(v) for v in rec_a[:3].cpu())
-    n_b, k_b = (int(v) for v in rec_b[:2].cpu())
-    if n_a == 0 or n_b == 0:
-        empty = [name for cnt, name in ((n_a, "pred"), (n_b, "gt")) if cnt == 0]
-        raise ValueError(f"reconstruction_topology_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has no "
-                         "components")
+    k_a, n_l = (int(v) for v in rec_a[1:3].cpu())
     n_lb = int((lcc & b).sum())
-    scores = {"n_components": k_a, "n_components_gt": k_b, "n_pred": n_a, "n_gt": n_b, "n_largest": n_l, "lcc_fraction": n_l / n_a,
+    scores = {"n_components": k_a, "n_components_gt": int(rec_b[1]), "n_pred": n_a, "n_gt": n_b, "n_largest": n_l, "lcc_fraction": n_l / n_a,
               "dice_lcc": 2.0 * n_lb / (n_l + n_b), "connectivity": int(connectivity), "threshold": thr}
-    return scores, pred, gt, lcc
+    return scores, an.pred, an.gt, lcc
 
 
 def cldice_scores(vp, vl, sp, sl):
@@ -372,22 +392,13 @@ def reconstruction_centreline_metrics(model, volume, outside, n, threshold=None,
     WORLD units - voxels times the grid step 2 outside / (n - 1), summed and multiplied in fp64; n_pred, n_gt, passes, passes_gt,
     voxel_size and threshold.  ValueError when the threshold leaves either mask, or either skeleton, empty.  grids: as in
     `reconstruction_surface_metrics`."""
-    from ..engine import distance_transform_edt_3d, filter_components_3d, skeletonize_3d
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
-    vp, vl = (pred >= t32), (gt >= t32)
-    n_p, n_l = int(vp.sum()), int(vl.sum())
-    if n_p == 0 or n_l == 0:
-        empty = [name for cnt, name in ((n_p, "pred"), (n_l, "gt")) if cnt == 0]
-        raise ValueError(f"reconstruction_centreline_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has "
-                         "no centreline")
-    body = filter_components_3d(vp, 3, largest_only=True) if largest_component else vp
-    sp, rec_p = skeletonize_3d(body, return_record=True)
-    sl, rec_l = skeletonize_3d(vl, return_record=True)
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    vp, vl, n_p, n_l = an.masks(thr)
+    _refuse_empty("reconstruction_centreline_metrics", n_p, n_l, "volume has no centreline")
+    line_p, line_l = an.skeleton("pred", thr, largest_component), an.skeleton("gt", thr)
+    sp, sl = line_p["skeleton"], line_l["skeleton"]
     scores = cldice_scores(vp, vl, sp, sl)                      # (thinning keeps every component: only an empty mask has an empty skeleton)
     n_sp, n_sl = scores["n_skeleton"], scores["n_skeleton_gt"]
-    voxel = 2.0 * float(outside) / (int(n) - 1)
 
     def ends(s):                                              # skeleton voxels with exactly one 26-neighbour: 2 voxels in their 3 x 3 x 3 box
         p = torch.nn.functional.pad(s.to(torch.int32), (1, 1, 1, 1, 1, 1))
@@ -395,10 +406,11 @@ def reconstruction_centreline_metrics(model, volume, outside, n, threshold=None,
         return int((s & (box == 2)).sum())
 
     scores.update({"n_end_points": ends(sp), "n_end_points_gt": ends(sl),
-                   "mean_radius": float(distance_transform_edt_3d(body)[sp].sum()) / n_sp * voxel,
-                   "mean_radius_gt": float(distance_transform_edt_3d(vl)[sl].sum()) / n_sl * voxel,
-                   "n_pred": n_p, "n_gt": n_l, "passes": rec_p["passes"], "passes_gt": rec_l["passes"], "voxel_size": voxel, "threshold": thr})
-    return scores, pred, gt, sp, sl
+                   "mean_radius": float(line_p["dist"][sp].sum()) / n_sp * an.voxel,
+                   "mean_radius_gt": float(line_l["dist"][sl].sum()) / n_sl * an.voxel,
+                   "n_pred": n_p, "n_gt": n_l, "passes": line_p["skeleton_record"]["passes"], "passes_gt": line_l["skeleton_record"]["passes"],
+                   "voxel_size": an.voxel, "threshold": thr})
+    return scores, an.pred, an.gt, sp, sl
 
 
 def graph_scores(graph_p, graph_l, rec_p, rec_l, voxel):
@@ -418,27 +430,19 @@ def reconstruction_graph_metrics(model, volume, outside, n, threshold=None, larg
     """The two centrelines read as graphs -> (scores, pruned predicted centreline, pruned true centreline, graph of the prediction, graph of
     the ground truth).
 
-    The masks and skeletons are those of `reconstruction_centreline_metrics` (same threshold, same largest_component).  Both skeletons are
-    pruned (`engine.prune_spurs` at `prune_factor`, with the squared distance transform of the mask that was thinned: a spur no longer than
-    prune_factor x the vessel radius at the junction it hangs on is a thinning artefact) and read with `engine.centreline_graph` at the
-    grid's index_to_world.  Scores, for the prediction and with the suffix _gt for the ground truth, AFTER pruning: n_branches, n_nodes
+    The masks and skeletons are those of `reconstruction_centreline_metrics` (same threshold, same largest_component); `centreline_tree`
+    prunes both skeletons at `prune_factor` and reads them as graphs at the grid's index_to_world.  Scores, for the prediction and with
+    the suffix _gt for the ground truth, AFTER pruning: n_branches, n_nodes
     (junction nodes), n_free_ends, n_spurs_removed, prune_rounds, length (the total centreline length in WORLD units) and min_radius
     (the smallest radius along any branch, world units: voxels times the grid step; NaN without a branch); length_ratio = length /
-    length_gt in fp64 (NaN when the true centreline has no step); voxel_size and threshold."""
-    from ..engine import centreline_graph, distance_transform_edt_3d, filter_components_3d, prune_spurs
-    line, pred, gt, sp, sl = reconstruction_centreline_metrics(model, volume, outside, n, threshold, largest_component, grids)
-    t32 = torch.tensor(line["threshold"], dtype=torch.float32, device=pred.device)
-    vp, vl = (pred >= t32), (gt >= t32)
-    body = filter_components_3d(vp, 3, largest_only=True) if largest_component else vp
-    a = grid_index_to_world(outside, n)
-    res = []
-    for mask, skel in ((body, sp), (vl, sl)):
-        d2 = distance_transform_edt_3d(mask, return_squared=True)[1]
-        pruned, rec = prune_spurs(skel, d2, prune_factor, return_record=True)
-        res.append((pruned, rec, centreline_graph(pruned, d2, a)))
-    scores = graph_scores(res[0][2], res[1][2], res[0][1], res[1][1], line["voxel_size"])
-    scores.update(voxel_size=line["voxel_size"], threshold=line["threshold"])
-    return scores, res[0][0], res[1][0], res[0][2], res[1][2]
+    length_gt in fp64 (NaN when the true centreline has no step); voxel_size and threshold.  ValueError when the threshold leaves either
+    mask empty."""
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    _refuse_empty("reconstruction_graph_metrics", *an.masks(thr)[2:], "volume has no centreline")
+    tree_p, tree_l = an.tree("pred", thr, largest_component, prune_factor), an.tree("gt", thr, prune_factor=prune_factor)
+    scores = graph_scores(tree_p["graph"], tree_l["graph"], tree_p["prune_record"], tree_l["prune_record"], an.voxel)
+    scores.update(voxel_size=an.voxel, threshold=thr)
+    return scores, tree_p["pruned"], tree_l["pruned"], tree_p["graph"], tree_l["graph"]
 
 
 def vesselness_scores(a, b, vp, vg, ip, ig, sigmas, v_min):
@@ -475,21 +479,13 @@ def reconstruction_vesselness_metrics(model, volume, outside, n, threshold=None,
     empty A' or B' gives NaN for the ratios that divide by it.  ValueError when the threshold leaves A or B empty.  v_min = 0.1 is a
     default, not a validated operating point.  The mask can be fed to the component, skeleton and surface functions.
     grids: as in `reconstruction_surface_metrics`."""
-    from ..engine import frangi_3d
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
-    a, b = (pred >= t32), (gt >= t32)
-    n_a, n_b = int(a.sum()), int(b.sum())
-    if n_a == 0 or n_b == 0:
-        empty = [name for cnt, name in ((n_a, "pred"), (n_b, "gt")) if cnt == 0]
-        raise ValueError(f"reconstruction_vesselness_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty volume has "
-                         "no tubular share")
-    vp, ip = frangi_3d(pred, sigmas, return_scale=True)
-    vg, ig = frangi_3d(gt, sigmas, return_scale=True)
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    a, b, n_a, n_b = an.masks(thr)
+    _refuse_empty("reconstruction_vesselness_metrics", n_a, n_b, "volume has no tubular share")
+    (vp, ip), (vg, ig) = an.frangi("pred", sigmas), an.frangi("gt", sigmas)
     scores, tubular = vesselness_scores(a, b, vp, vg, ip, ig, sigmas, v_min)
     scores["threshold"] = thr
-    return scores, pred, gt, tubular
+    return scores, an.pred, an.gt, tubular
 
 
 def lumen_scores(prof_p, prof_g, sum_p, sum_g):
@@ -525,17 +521,17 @@ def reconstruction_lumen_metrics(model, volume, outside, n, threshold=None, prun
     lumen_area_err = the mean over the both-valid points of |A_p - A_g| / A_g; mla, mla_gt, mla_ratio: the minimal lumen areas over those
     points and their ratio; max_stenosis, max_stenosis_gt: the largest area_stenosis of `engine.lumen_branch_summary` over the branches;
     stenosis_err = the largest |S_p,b - S_g,b| over the branches with a summary on both sides; threshold.  NaN where a divisor or a set
-    is empty; ValueError only when the true centreline has no point.  Near a bifurcation rays leak into the sibling branch: the median
+    is empty; ValueError when either mask is empty or the true centreline has no point.  Near a bifurcation rays leak into the sibling branch: the median
     and the minimum are robust to it.  grids: as in `reconstruction_surface_metrics`."""
     from ..engine import centreline_lumen_profile, lumen_branch_summary
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    tree, _, _, _, graph_l = reconstruction_graph_metrics(model, volume, outside, n, threshold, False, prune_factor, (pred, gt))
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    _refuse_empty("reconstruction_lumen_metrics", *an.masks(thr)[2:], "volume has no centreline")
+    graph_l = an.tree("gt", thr, prune_factor=prune_factor)["graph"]
     if int(graph_l["path_voxels"].numel()) == 0:
         raise ValueError("reconstruction_lumen_metrics: the true centreline has no point at this threshold")
-    a, thr = grid_index_to_world(outside, n), tree["threshold"]
     profiles = []
-    for x in (pred, gt):
-        prof = centreline_lumen_profile(graph_l, x, a, thr, **profile_kw)
+    for x in (an.pred, an.gt):
+        prof = centreline_lumen_profile(graph_l, x, an.index_to_world, thr, **profile_kw)
         profiles.append({k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in prof.items()})
     scores = lumen_scores(profiles[0], profiles[1], lumen_branch_summary(profiles[0]), lumen_branch_summary(profiles[1]))
     scores["threshold"] = thr
@@ -567,18 +563,15 @@ def reconstruction_hull_metrics(model, volume, outside, n, views, threshold=None
     if volume is None and grids is None:
         if threshold is None:
             raise ValueError("reconstruction_hull_metrics: without the ground-truth volume the threshold must be given")
-        pred, gt = density_grid(model, outside, int(n) - 1), None
-    else:
-        pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    t32 = torch.tensor(thr, dtype=torch.float32, device=pred.device)
-    hull = visual_hull(views, tuple(pred.shape), grid_index_to_world(outside, n))
-    a = pred >= t32
-    n_pred, n_out, n_hull = int(a.sum()), int((a & ~hull).sum()), int(hull.sum())
-    n_gt, n_both = (int((gt >= t32).sum()), int(((gt >= t32) & hull).sum())) if gt is not None else (0, 0)
-    scores = hull_scores(n_pred, n_out, n_hull if gt is not None else 0, n_gt, n_both)
+        grids = density_grid(model, outside, int(n) - 1), None
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    hull = visual_hull(views, tuple(an.pred.shape), an.index_to_world)
+    a, b, n_pred, n_gt = an.masks(thr)
+    n_out, n_hull = int((a & ~hull).sum()), int(hull.sum())
+    n_both = int((b & hull).sum()) if b is not None else 0
+    scores = hull_scores(n_pred, n_out, n_hull if b is not None else 0, n_gt, n_both)
     scores.update(n_pred=n_pred, n_pred_outside=n_out, n_hull=n_hull, n_gt=n_gt, n_hull_gt=n_both, threshold=thr)
-    return scores, hull, pred, gt
+    return scores, hull, an.pred, an.gt
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
@@ -624,16 +617,9 @@ def reconstruction_mesh(model, volume, outside, n, threshold=None, largest_compo
     half-way between the voxels).  info: V, T, E, B, n22, euler = V - E + T, area and volume (world units, fp64), threshold.  The surface
     is that of the piecewise-linear interpolant, which joins a voxel to 14 neighbours: euler is not the Euler number of the
     26-connected mask.  An empty mesh (nothing reaches the threshold) has V = T = 0.  grids: as in `reconstruction_surface_metrics`."""
-    from ..engine import filter_components_3d
-    pred, gt = _reconstruction_grids(model, volume, outside, n, grids)
-    thr = float(torch.mean(gt)) if threshold is None else float(threshold)
-    if largest_component:
-        lcc = filter_components_3d(pred >= torch.tensor(thr, dtype=torch.float32, device=pred.device), connectivity, largest_only=True)
-        vertices, triangles, info = _grid_mesh(lcc.float(), 0.5, outside, n)
-    else:
-        vertices, triangles, info = _grid_mesh(pred, thr, outside, n)
-    info["threshold"] = thr
-    return vertices, triangles, info, pred, gt
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    vertices, triangles, info = an.mesh("pred", thr, largest_component, connectivity)
+    return vertices, triangles, dict(info, threshold=thr), an.pred, an.gt
 
 
 @torch.no_grad()
@@ -644,19 +630,16 @@ def reconstruction_mesh_metrics(model, volume, outside, n, threshold=None, large
     volume (world units, fp64), euler, n_vertices, n_triangles, n_edges of the prediction, the same with the suffix _gt of the truth,
     volume_ratio = volume / volume_gt and area_ratio = area / area_gt (fp64), threshold and voxel_size.  ValueError when either mesh
     is empty."""
-    vertices, triangles, info, pred, gt = reconstruction_mesh(model, volume, outside, n, threshold, largest_component, connectivity, grids)
-    thr = info["threshold"]
-    info_gt = _grid_mesh(gt, thr, outside, n)[2]
-    if info["T"] == 0 or info_gt["T"] == 0:
-        empty = [name for i, name in ((info, "pred"), (info_gt, "gt")) if i["T"] == 0]
-        raise ValueError(f"reconstruction_mesh_metrics: no voxel of {' or '.join(empty)} reaches its threshold: an empty mesh has no measures")
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    info, info_gt = an.mesh("pred", thr, largest_component, connectivity)[2], an.mesh("gt", thr)[2]
+    _refuse_empty("reconstruction_mesh_metrics", info["T"], info_gt["T"], "mesh has no measures")
     scores = {}
     for suffix, i in (("", info), ("_gt", info_gt)):
         scores.update({"area" + suffix: i["area"], "volume" + suffix: i["volume"], "euler" + suffix: i["euler"], "n_vertices" + suffix: i["V"],
                        "n_triangles" + suffix: i["T"], "n_edges" + suffix: i["E"]})
     scores.update(volume_ratio=scores["volume"] / scores["volume_gt"], area_ratio=scores["area"] / scores["area_gt"], threshold=thr,
-                  voxel_size=2.0 * float(outside) / (int(n) - 1))
-    return scores, pred, gt
+                  voxel_size=an.voxel)
+    return scores, an.pred, an.gt
 
 
 @torch.no_grad()
@@ -672,9 +655,9 @@ def reconstruction_mesh_distance_metrics(model, volume, outside, n, threshold=No
     from ..engine import mesh_point_distance
     if not 0.0 <= float(q) <= 100.0:
         raise ValueError(f"reconstruction_mesh_distance_metrics: q = {q} must lie in [0, 100]")
-    vertices, triangles, info, pred, gt = reconstruction_mesh(model, volume, outside, n, threshold, largest_component, grids=grids)
-    thr = info["threshold"]
-    vertices_gt, triangles_gt, info_gt = _grid_mesh(gt, thr, outside, n)
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    vertices, triangles, info = an.mesh("pred", thr, largest_component)
+    vertices_gt, triangles_gt, info_gt = an.mesh("gt", thr)
     scores = {"assd": float("nan"), "hd": float("nan"), "hd_percentile": float("nan"), "n_vertices": info["V"], "n_vertices_gt": info_gt["V"],
               "threshold": thr, "q": float(q)}
     if info["T"] and info_gt["T"]:
@@ -683,7 +666,28 @@ def reconstruction_mesh_distance_metrics(model, volume, outside, n, threshold=No
         scores["assd"] = float((there.mean() + back.mean()) / 2.0)
         scores["hd"] = float(torch.maximum(there.max(), back.max()))
         scores["hd_percentile"] = float(torch.quantile(torch.cat([there, back]), float(q) / 100.0))
-    return scores, pred, gt
+    return scores, an.pred, an.gt
+
+
+def _reference_scores(*args, **kw):
+    dice, dot = reconstruction_metrics(*args, **kw)[:2]
+    return ({"dice_3d": dice, "dot_3d": dot},)
+
+
+# the whole-volume columns of evaluation_sweep in table order: (column names, the function whose first result holds the scores, the
+# score behind each column); the hull family takes the training views as a fifth argument
+_VOLUME_FAMILIES = (
+    (METRICS[-2:], _reference_scores, ("dice_3d", "dot_3d")),
+    (SURFACE_METRICS, reconstruction_surface_metrics, ("dice_vessel", "assd", "hd", "hd_percentile")),
+    (TOPOLOGY_METRICS, reconstruction_topology_metrics, ("n_components", "lcc_fraction", "dice_lcc")),
+    (CENTRELINE_METRICS, reconstruction_centreline_metrics, ("cldice", "tprec", "tsens")),
+    (MESH_METRICS, reconstruction_mesh_metrics, ("volume_ratio", "area_ratio", "euler")),
+    (MESH_DISTANCE_METRICS, reconstruction_mesh_distance_metrics, ("assd", "hd", "hd_percentile")),
+    (GRAPH_METRICS, reconstruction_graph_metrics, ("n_branches", "n_nodes", "length_ratio")),
+    (VESSELNESS_METRICS, reconstruction_vesselness_metrics, ("tubular_fraction", "dice_tubular", "scale_ratio")),
+    (LUMEN_METRICS, reconstruction_lumen_metrics, ("lumen_area_err", "mla_ratio", "stenosis_err")),
+    (HULL_METRICS, reconstruction_hull_metrics, ("outside_hull", "dice_hull", "hull_ratio")),
+)
 
 
 @torch.no_grad()
