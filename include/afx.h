@@ -1110,6 +1110,48 @@ int afx_visual_hull(int32_t n0, int32_t n1, int32_t n2, const double* index_to_w
  * binary or bits; a resolution outside 1..2048. */
 int afx_grid_apply_mask(const afx_grid_desc* grid, const uint8_t* mask, float* occs, uint8_t* binary, uint32_t* bits, void* stream);
 
+/* ---- Sparse-view algebraic reconstruction (SIRT): the line integrals of an fp64 attenuation volume along the rays of the training views
+ * and the voxel-driven backprojection of their images.  All arithmetic is fp64, every operation rounded on its own (no contraction), only
+ * + - * / sqrt floor and comparisons, in the order written: tests/sirt_reference.py restates both in NumPy and the device equals the
+ * restatement exactly.
+ *   Lattice.  Point p = (i n1 + j) n2 + k lies at x_a = ((A[a][0] i + A[a][1] j) + A[a][2] k) + A[a][3], A = index_to_world (12 doubles,
+ *      host, as afx_visual_hull takes it); B = world_to_index (12 doubles, host), its inverse taken in fp64 by the caller (W = inv(A),
+ *      offset -(W o), as for afx_lumen_profile) and handed to the library and the restatement alike.  n_a >= 2.
+ *   Views.  views: double [n_views][AFX_HULL_VIEW_DOUBLES] on the device, the records of afx_visual_hull: R[r][n] at [3 r + n], c at
+ *      [9..11], f at [12].  width W >= 2, height H >= 2, near, far and the sample count S are common to all views; pixel centres lie at
+ *      the integers.  Images are double [n_views][H][W].
+ *   afx_xray_project, per ray (v, iw, iu):
+ *      a = (iu - W / 2) / f;  b = -((iw - H / 2) / f);  d_r = (R[r][0] a + R[r][1] b) - R[r][2];  L = sqrt((d_0 d_0 + d_1 d_1) + d_2 d_2)
+ *      dt = (far - near) / S;  acc = +0;  for s = 0 .. S - 1 in order:
+ *         t = near + (s + 0.5) dt;  x_r = c_r + t d_r;  g_a = ((B[a][0] x_0 + B[a][1] x_1) + B[a][2] x_2) + B[a][3]
+ *         the sample is inside iff 0 <= g_a <= n_a - 1 for a = 0, 1, 2; outside it contributes +0 (so it may be skipped)
+ *         inside: i_a = min(floor(g_a), n_a - 2), phi_a = g_a - i_a; the trilinear value of the 8 voxels i_a, i_a + 1 by lerps
+ *         p + phi (q - p) along axis 2 (four), then axis 1 (two), then axis 0;  acc += value
+ *      y = (acc dt) L.  out[v][iw][iu] = y, or, with target and weight given (both or neither), weight (target - y).
+ *   afx_xray_backproject, per lattice point, over the views in order (acc = +0, cnt = 0):
+ *      e = x - c;  q_n = (R[0][n] e_0 + R[1][n] e_1) + R[2][n] e_2;  d = -q_2;  !(d > 0): next view
+ *      u = W / 2 + (f q_0) / d;  w = H / 2 - (f q_1) / d;  seen iff 0 <= u <= W - 1 && 0 <= w <= H - 1, else next view
+ *      iu = min(floor(u), W - 2), phi_u = u - iu; iw, phi_w likewise;  top = I[iw][iu] + phi_u (I[iw][iu + 1] - I[iw][iu]), bot the same
+ *      of row iw + 1;  acc += top + phi_w (bot - top);  cnt += 1
+ *      Outputs, each optional (NULL), at least one: acc double [n0 n1 n2]; seen uint16 [n0 n1 n2] = cnt; x_inout double [n0 n1 n2],
+ *      the fused SIRT update in place: upd = cnt > 0 ? acc / cnt : 0;  y = x + relax upd;  nonneg != 0: y = y > 0 ? y : 0;
+ *      mask (uint8 [n0 n1 n2], may be NULL, only with x_inout) and mask[p] == 0: y = 0;  x[p] = y.
+ * The backprojector is the voxel-driven gather, not the adjoint of the projector: every lane owns its voxel, so the sum over the views
+ * has one order, needs no fp64 atomics and the update can be fused and captured.  One launch each (projector: a lane per ray, a
+ * wavefront an 8 x 8 pixel tile; backprojector: a lane per point, k fastest); no LDS, atomics, workspace or synchronisation.
+ * AFX_E_INVALID before any launch, the message naming the argument: a null pointer; n_views outside 1..65535; an extent below 2 or
+ * n0 n1 n2 >= 2^31; width or height below 2; n_samples < 1; far <= near; a non-finite world_to_index, index_to_world, near, far or
+ * relax; target without weight or the reverse; no output at all; a mask without x_inout; a pointer that is not memory of the current
+ * device. */
+int afx_xray_project(const double* volume, int32_t n0, int32_t n1, int32_t n2, const double* world_to_index /* [12], host */,
+                     const double* views /* device */, int32_t n_views, int32_t width, int32_t height, double near, double far,
+                     int32_t n_samples, const double* target /* may be NULL */, const double* weight /* may be NULL */, double* out,
+                     void* stream);
+int afx_xray_backproject(const double* images, const double* views /* device */, int32_t n_views, int32_t width, int32_t height, int32_t n0,
+                         int32_t n1, int32_t n2, const double* index_to_world /* [12], host */, double* acc /* may be NULL */,
+                         uint16_t* seen /* may be NULL */, double* x_inout /* may be NULL */, double relax, int32_t nonneg,
+                         const uint8_t* mask /* may be NULL */, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -211,6 +211,10 @@ _SIGS = {
     "afx_visual_hull": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_grid_apply_mask": (C.c_int, [C.POINTER(GridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afx_xray_project": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afx_xray_backproject": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _libs = {}

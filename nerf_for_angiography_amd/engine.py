@@ -2164,6 +2164,161 @@ def grid_apply_mask(roi_aabb, resolution, mask_u8, occs, binary_u8, bits):
                "afx_grid_apply_mask")
 
 
+# ---- sparse-view algebraic reconstruction: the ray-driven projector (afx_xray_project), the voxel-driven backprojector
+# (afx_xray_backproject) and the SIRT iteration made of the two ----
+def line_integrals(images, eps: float = 1e-6) -> torch.Tensor:
+    """-log(clamp(I, eps, 1)) in fp64: the line integrals behind transmission images I = exp(-integral), the convention of
+    ray_tracing(type='ct')."""
+    if not 0.0 < float(eps) <= 1.0:
+        raise ValueError(f"line_integrals: eps must lie in (0, 1], got {eps!r}")
+    return -torch.log(torch.as_tensor(images).to(torch.float64).clamp(float(eps), 1.0))
+
+
+def xray_views(poses, focal, width: int, height: int, near: float, far: float, n_samples: int, device=None) -> dict:
+    """The views of the SIRT operators: poses [V, 4, 4] or [V, 3, 4] (cam2world), focal (a number, or one per view), the detector
+    width x height and the samples of a ray - n_samples of them at near + (s + 0.5) (far - near) / n_samples, common to all views.  The
+    records are those of the visual hull (`hull_view_records`), copied to `device` (default: the poses' device when they are a GPU tensor,
+    else the current GPU) -> dict(records float64 [V, 16] on the device, n_views, width, height, near, far, n_samples)."""
+    import math
+    rec = hull_view_records(poses, focal)
+    w, h, s = int(width), int(height), int(n_samples)
+    if w < 2 or h < 2:
+        raise ValueError(f"xray_views: width and height must be at least 2, got {w} x {h}")
+    if s < 1:
+        raise ValueError(f"xray_views: n_samples must be positive, got {s}")
+    if not (math.isfinite(near) and math.isfinite(far) and far > near):
+        raise ValueError(f"xray_views: near and far must be finite with far > near, got {near!r}, {far!r}")
+    if device is None:
+        device = poses.device if isinstance(poses, torch.Tensor) and poses.device.type == "cuda" else torch.device("cuda")
+    if torch.device(device).type != "cuda":
+        raise AfxError("xray_views: the views must live on a GPU; there is no CPU path")
+    return dict(records=torch.from_numpy(rec).to(device), n_views=rec.shape[0], width=w, height=h, near=float(near), far=float(far), n_samples=s)
+
+
+def _xray_views_checked(views: dict, who: str):
+    rec = views["records"]
+    dev = rec.device
+    if dev.type != "cuda":
+        raise AfxError(f"{who}: the views must live on a GPU; there is no CPU path")
+    v = int(views["n_views"])
+    if rec.dtype != torch.float64 or not rec.is_contiguous() or tuple(rec.shape) != (v, HULL_VIEW_DOUBLES):
+        raise ValueError(f"{who}: records must be contiguous float64 [{v}, {HULL_VIEW_DOUBLES}]")
+    return rec, dev, v, int(views["width"]), int(views["height"])
+
+
+def _xray_f64(t, name, count, dev, who):
+    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev
+                          or t.numel() != count):
+        raise ValueError(f"{who}: {name} must be a contiguous float64 tensor of {count} elements on {dev}")
+
+
+def xray_project(volume: torch.Tensor, views: dict, index_to_world=None, target=None, weight=None, out=None) -> torch.Tensor:
+    """afx_xray_project: the line integrals of the float64 [n0, n1, n2] device `volume`, trilinearly interpolated on the lattice
+    x = index_to_world (i, j, k, 1), along every ray of `views` (`xray_views`) -> float64 [V, H, W]; with target and weight (both
+    [V, H, W] float64) the fused weighted residual weight (target - y) instead.  The definition stands in include/afx.h.  One launch;
+    with `out` passed nothing is allocated and the call can be captured in a graph."""
+    import numpy as np
+    lib = _lib.load()
+    rec, dev, v, w, h = _xray_views_checked(views, "xray_project")
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
+        raise ValueError("xray_project: the volume must be a [n0, n1, n2] tensor")
+    _xray_f64(volume, "the volume", volume.numel(), dev, "xray_project")
+    if (target is None) != (weight is None):
+        raise ValueError("xray_project: target and weight are given together or not at all")
+    b = np.ascontiguousarray(lumen_world_to_index(_affine12(index_to_world, "xray_project")))
+    if out is None:
+        out = torch.empty((v, h, w), dtype=torch.float64, device=dev)
+    for t, name in ((target, "target"), (weight, "weight"), (out, "out")):
+        _xray_f64(t, name, v * h * w, dev, "xray_project")
+    n0, n1, n2 = volume.shape
+    _lib.check(lib.afx_xray_project(_ptr(volume), n0, n1, n2, b.ctypes.data_as(C.POINTER(C.c_double)), _ptr(rec), v, w, h, float(views["near"]),
+                                    float(views["far"]), int(views["n_samples"]), _ptr(target), _ptr(weight), _ptr(out), Engine._stream(dev)),
+               "afx_xray_project")
+    return out
+
+
+def xray_backproject(images: torch.Tensor, views: dict, shape, index_to_world=None, x_inout=None, relax: float = 1.0, nonneg: bool = False,
+                     mask=None, acc=None, seen=None):
+    """afx_xray_backproject: every point of the lattice x = index_to_world (i, j, k, 1) of `shape` gathers the bilinear value of the
+    float64 [V, H, W] device `images` at its projection into every view that sees it (include/afx.h).  Without x_inout -> (acc float64,
+    seen uint16) of `shape`: the sum over the views and their number.  With x_inout (float64, `shape`) the SIRT update is fused, in
+    place: x += relax acc / seen (0 where no view sees the point), clamped at 0 with nonneg, zeroed where the uint8 `mask` is 0 ->
+    x_inout; acc and seen are written only when passed.  One launch, nothing read back: capturable."""
+    import numpy as np
+    lib = _lib.load()
+    rec, dev, v, w, h = _xray_views_checked(views, "xray_backproject")
+    n0, n1, n2 = (int(s) for s in shape)
+    n = max(n0, 0) * max(n1, 0) * max(n2, 0)
+    if images is None:
+        raise ValueError("xray_backproject: images must be a float64 [V, H, W] tensor")
+    _xray_f64(images, "images", v * h * w, dev, "xray_backproject")
+    a = np.ascontiguousarray(_affine12(index_to_world, "xray_backproject"))
+    if x_inout is None:
+        if mask is not None:
+            raise ValueError("xray_backproject: mask belongs to the fused update (x_inout)")
+        acc = torch.empty((n0, n1, n2), dtype=torch.float64, device=dev) if acc is None else acc
+        seen = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev) if seen is None else seen
+    _xray_f64(acc, "acc", n, dev, "xray_backproject")
+    _xray_f64(x_inout, "x_inout", n, dev, "xray_backproject")
+    if seen is not None and (seen.dtype != torch.uint16 or not seen.is_contiguous() or seen.device != dev or seen.numel() != n):
+        raise ValueError(f"xray_backproject: seen must be a contiguous uint16 tensor of {n} elements on {dev}")
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev or mask.numel() != n):
+        raise ValueError(f"xray_backproject: mask must be a contiguous uint8 tensor of {n} elements on {dev}")
+    _lib.check(lib.afx_xray_backproject(_ptr(images), _ptr(rec), v, w, h, n0, n1, n2, a.ctypes.data_as(C.POINTER(C.c_double)), _ptr(acc),
+                                        _ptr(seen), _ptr(x_inout), float(relax), int(bool(nonneg)), _ptr(mask), Engine._stream(dev)),
+               "afx_xray_backproject")
+    return x_inout if x_inout is not None else (acc, seen)
+
+
+def sirt_residual_norm(residual: torch.Tensor) -> torch.Tensor:
+    """sqrt(sum r^2) of weighted residual images, a 0-d float64 tensor on their device: the entry of sirt_reconstruct's history."""
+    return torch.sqrt(torch.sum(residual * residual))
+
+
+def sirt_reconstruct(views: dict, line_integrals: torch.Tensor, shape, index_to_world=None, iterations: int = 50, relax: float = 1.0,
+                     mask=None, x0=None, nonneg: bool = True, return_history: bool = False):
+    """SIRT: the attenuation volume on the lattice x = index_to_world (i, j, k, 1) of `shape` whose line integrals along the rays of
+    `views` (`xray_views`) approach `line_integrals` (float64 [V, H, W] on the GPU; `line_integrals(I)` of transmission images) ->
+    float64 `shape`[, history float64 [iterations] on the host].
+
+    Once: l = xray_project(ones), weight = where(l > 0, 1 / l, 0) - the row weights; l is the chord of the ray through the lattice.  Each
+    iteration is two launches: r = weight (b - project(x)) (the fused residual) and x += relax backproject(r) / seen, clamped at 0 with
+    nonneg and zeroed outside `mask` (bool or uint8, `shape`: a support constraint such as the visual hull) - the fused update; every
+    voxel takes the mean of its residuals over the views that see it.  x0: the start volume (default zeros; it is not changed).  The
+    buffers are allocated once and nothing is read back inside the loop; return_history adds `sirt_residual_norm` of each iteration's
+    residual images (those of the volume BEFORE the iteration's update), read back once at the end."""
+    rec, dev, v, w, h = _xray_views_checked(views, "sirt_reconstruct")
+    shape = tuple(int(s) for s in shape)
+    if int(iterations) < 0:
+        raise ValueError(f"sirt_reconstruct: iterations must be >= 0, got {iterations}")
+    if not isinstance(line_integrals, torch.Tensor) or line_integrals.device != dev:
+        raise AfxError("sirt_reconstruct: the line integrals must live on the views' GPU; there is no CPU path")
+    b = line_integrals.to(torch.float64).contiguous()
+    if tuple(b.shape) != (v, h, w):
+        raise ValueError(f"sirt_reconstruct: line_integrals must be [{v}, {h}, {w}], got {tuple(b.shape)}")
+    m8 = None
+    if mask is not None:
+        if tuple(mask.shape) != shape:
+            raise ValueError(f"sirt_reconstruct: mask must have the shape {shape}, got {tuple(mask.shape)}")
+        m8 = (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    if x0 is None:
+        x = torch.zeros(shape, dtype=torch.float64, device=dev)
+    else:
+        if tuple(x0.shape) != shape:
+            raise ValueError(f"sirt_reconstruct: x0 must have the shape {shape}, got {tuple(x0.shape)}")
+        x = x0.to(device=dev, dtype=torch.float64).contiguous().clone()
+    ell = xray_project(torch.ones(shape, dtype=torch.float64, device=dev), views, index_to_world)
+    weight = torch.where(ell > 0, 1.0 / ell, torch.zeros_like(ell))
+    residual = ell                                        # (the buffer of the residual images; l is not needed any more)
+    history = torch.zeros(int(iterations), dtype=torch.float64, device=dev) if return_history else None
+    for it in range(int(iterations)):
+        xray_project(x, views, index_to_world, target=b, weight=weight, out=residual)
+        if history is not None:
+            history[it] = sirt_residual_norm(residual)
+        xray_backproject(residual, views, shape, index_to_world, x_inout=x, relax=relax, nonneg=nonneg, mask=m8)
+    return (x, history.cpu()) if return_history else x
+
+
 class RayBatchSampler:
     """sample_rays for a training loop: the batches of `prefetch` consecutive iterations are drawn by ONE launch sequence
     (afx_sample_batches; a single draw is launch latency, ~70 us of the reference's 1.3 ms iteration) and handed out one per call.

@@ -22,6 +22,8 @@ the march's candidates doubles as the alpha pass.
 `--entropy_weight LAMBDA` (with `grid_ops`) adds LAMBDA times the batch's mean ray entropy (`acc_ray_entropy`) to the loss.
 `--grid_init hull` (with `grid` or `grid_ops`, `--binary True`) carves both occupancy grids with the visual hull of the training views
 before training and keeps it as the ceiling of every grid update (`OccupancyGrid.carve_from_views`, `afx_visual_hull`).
+`--save_sirt PATH.npy` (`--binary True` or CT-type data) writes, at the end of the run, the classical baseline: the SIRT reconstruction
+of the attenuation volume from the training views on the 128^3 lattice of the occupancy grid's cell centres (`engine.sirt_reconstruct`).
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -144,6 +146,13 @@ def build_parser():
     p.add_argument('--save_hull', default=None, metavar='PATH',
                    help='--grid_init hull: write the vote volumes to PATH (.npy): uint16 [2, 128, 128, 128], the views that see each cell and '
                         'the views that reject it')
+    p.add_argument('--save_sirt', default=None, metavar='PATH',
+                   help='after training, write the algebraic reconstruction (SIRT) of the attenuation volume from the training views to PATH '
+                        '(.npy): float64 [128, 128, 128] on the cell centres of the occupancy grid\'s box (afx_xray_project, '
+                        'afx_xray_backproject); needs --binary True or CT-type data (pixel values exp(-line integral)); with --grid_init '
+                        'hull the hull is the support mask')
+    p.add_argument('--sirt_iterations', type=int, default=50, metavar='N', help='--save_sirt: SIRT iterations (default 50)')
+    p.add_argument('--sirt_relax', type=float, default=1.0, metavar='LAMBDA', help='--save_sirt: the relaxation factor (default 1.0)')
     p.add_argument('--phantom_mesh', default=None, metavar='PATH',
                    help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
                         'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
@@ -194,6 +203,16 @@ def check_args(args):
             raise ValueError("--save_hull: needs --grid_init hull")
         if os.path.splitext(args.save_hull)[1].lower() != '.npy':
             raise ValueError("--save_hull: PATH must end in .npy")
+    if getattr(args, 'save_sirt', None) is not None:
+        if args.binary != 'True' and (args.data_name or 'ct') != 'ct':
+            raise ValueError("--save_sirt: needs --binary True or CT-type data (--data_name ct): the pixel values must be transmissions "
+                             "exp(-line integral)")
+        if os.path.splitext(args.save_sirt)[1].lower() != '.npy':
+            raise ValueError("--save_sirt: PATH must end in .npy")
+        if args.sirt_iterations < 1:
+            raise ValueError("--sirt_iterations: needs N >= 1")
+        if not (np.isfinite(args.sirt_relax) and 0 < args.sirt_relax < 2):
+            raise ValueError("--sirt_relax: needs 0 < LAMBDA < 2")
     if args.phantom_mesh is not None:
         if not args.synthetic:
             raise ValueError("--phantom_mesh: needs --synthetic (the phantom replaces the capsule tree of the synthetic dataset)")
@@ -541,7 +560,50 @@ def main(argv=None):
         grid = density_grid(coarse_model, outside, depth_samples_per_ray_coarse)
     for key, save, path in exports:
         result[key] = save(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, path, grid=grid)
+    if args.save_sirt is not None:
+        mask = acc_grid._carve_u8 if acc_grid is not None and args.grid_init == 'hull' else None      # the hull the grids were carved with
+        result['sirt_info'] = save_sirt(proj_df, train_ray_df, test_proj_id, [-outside] * 3 + [outside] * 3, 128, near_thresh, far_thresh,
+                                        depth_samples_per_ray_coarse, args.sirt_iterations, args.sirt_relax, device, args.save_sirt, mask=mask)
     return result
+
+
+def training_view_images(proj_df, train_ray_df, test_proj_id, device):
+    """The training views' images from the training rays alone, as `training_view_masks` gathers their silhouettes: pixel (y_position,
+    x_position) of view image_id holds pixel_value; a pixel no ray covers holds 1 (no attenuation) -> (poses float64 [V, 4, 4], images
+    float64 [V, H, W] on `device`, focal float64 [V]), the views in the order of proj_df."""
+    ids = [i for i in proj_df.index if i != test_proj_id]
+    if not ids:
+        raise ValueError("--save_sirt: there is no training view")
+    w, h = int(proj_df['org_img_width'].iloc[0]), int(proj_df['org_img_height'].iloc[0])
+    slot = {image_id: v for v, image_id in enumerate(ids)}
+    image = train_ray_df['image_id'].map(slot)
+    if image.isna().any():
+        raise ValueError("--save_sirt: a training ray belongs to no training view of the projection frame")
+    images = torch.ones((len(ids), h, w), dtype=torch.float64)
+    images[torch.from_numpy(image.to_numpy().astype('int64')), torch.from_numpy(train_ray_df['y_position'].to_numpy().astype('int64')),
+           torch.from_numpy(train_ray_df['x_position'].to_numpy().astype('int64'))] = torch.from_numpy(
+               train_ray_df['pixel_value'].to_numpy().astype('float64'))
+    poses = np.asarray([proj_df.loc[i, 'tform_cam2world'] for i in ids], dtype=np.float64)
+    focal = np.asarray([proj_df.loc[i, 'focal_length'] for i in ids], dtype=np.float64)
+    return poses, images.to(device), focal
+
+
+def save_sirt(proj_df, train_ray_df, test_proj_id, roi_aabb, resolution, near, far, n_samples, iterations, relax, device, path, mask=None):
+    """--save_sirt: the SIRT reconstruction of the attenuation volume from the training views (`engine.sirt_reconstruct`, from zero,
+    clamped at zero) on the cell centres of the resolution^3 grid over `roi_aabb`, the line integrals -log(pixel_value) sampled as the
+    training rays are (n_samples between near and far); mask: a support constraint of that shape (the hull the grids were carved with)
+    -> its info (shape, iterations, relax, masked, n_views, the first and last residual norm, the volume's maximum and sum, path)."""
+    poses, images, focal = training_view_images(proj_df, train_ray_df, test_proj_id, device)
+    views = _engine.xray_views(poses, focal, images.shape[2], images.shape[1], near, far, n_samples, device=device)
+    shape = (int(resolution),) * 3
+    a12, _ = _engine.grid_cell_lattice(roi_aabb, shape)
+    x, history = _engine.sirt_reconstruct(views, _engine.line_integrals(images), shape, a12, iterations=iterations, relax=relax,
+                                          mask=None if mask is None else mask.reshape(shape), return_history=True)
+    np.save(path, x.cpu().numpy())
+    info = dict(shape=shape, iterations=int(iterations), relax=float(relax), masked=mask is not None, n_views=int(views['n_views']),
+                residual_first=float(history[0]), residual_last=float(history[-1]), max=float(x.max()), sum=float(x.sum()), path=str(path))
+    print('sirt', {k: info[k] for k in ('iterations', 'masked', 'n_views', 'residual_first', 'residual_last', 'max', 'path')}, flush=True)
+    return info
 
 
 def training_view_masks(proj_df, train_ray_df, test_proj_id, threshold, device):

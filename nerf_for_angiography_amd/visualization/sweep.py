@@ -11,14 +11,15 @@ no network - every view in one `afx_ssim` call, in fp64), normalised DOT 2D (:44
 DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against the ground-truth volume sampled at the same points
 (`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope.
 
-Beyond the reference: nine more families of whole-volume scores on the same two grids, each a reconstruction_* function with a tuple of
+Beyond the reference: ten more families of whole-volume scores on the same two grids, each a reconstruction_* function with a tuple of
 column names, listed in table order in _VOLUME_FAMILIES at the end of this file; what a family scores is in its function's docstring.
 The surface distances between the two thresholded grids (`afx_surface_metrics_3d`), the connected pieces of the reconstruction
 (`afx_label_components_3d`), clDice on the medial curves (`afx_skeletonize_3d`), the vessel as a capped triangle mesh
 (`reconstruction_mesh`, `afx_isosurface_3d`; visualization/mesh_io.py writes it) with its measures and the distance between the two
 meshes (`afx_mesh_point_distance`), the pruned centreline read as a graph (`afx_prune_spurs`, `afx_centreline_graph`), the tubular
-share by the 3-D Frangi filter (`afx_frangi_3d`), the lumen's cross-sections along the true centreline (`afx_lumen_profile`) and the
-visual hull of the training views (`afx_visual_hull`).  The families share what they derive from the grids through one `GridAnalysis`;
+share by the 3-D Frangi filter (`afx_frangi_3d`), the lumen's cross-sections along the true centreline (`afx_lumen_profile`), the
+visual hull of the training views (`afx_visual_hull`) and the classical baseline, the algebraic reconstruction (SIRT) of the attenuation
+volume from the same views (`afx_xray_project`, `afx_xray_backproject`).  The families share what they derive from the grids through one `GridAnalysis`;
 the chain mask -> distance transform -> skeleton -> pruned skeleton -> graph is `centreline_tree`."""
 from __future__ import annotations
 
@@ -49,6 +50,10 @@ LUMEN_METRICS = ("LUMEN AREA ERR 3D", "MLA RATIO 3D", "STENOSIS ERR 3D")        
 _ALL_VOLUME_METRICS = _VOLUME_METRICS + VESSELNESS_METRICS + LUMEN_METRICS
 # against the visual hull of the training views: needs the views (hull_views=engine.visual_hull_views(...)) besides the volume
 HULL_METRICS = ("OUTSIDE HULL 3D", "DICE 3D HULL", "HULL RATIO 3D")
+# and how it stands against the classical baseline, the algebraic reconstruction (SIRT) of the attenuation volume from the same training
+# views (reconstruction_sirt_metrics: afx_xray_project, afx_xray_backproject), a tuple of its own, tabulated behind the hull columns; it
+# needs the views with their line integrals (sirt_views=(engine.xray_views(...), line integrals)) and the ground-truth volume
+SIRT_METRICS = ("DICE 3D SIRT", "DICE GAIN 3D", "CORR 3D SIRT")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -70,7 +75,7 @@ def _poses(angles, src_pt, translation, device):
 def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length, src_pt, near_thresh, far_thresh,
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
                      views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3, metrics=None, volume=None,
-                     volume_outside=100.0, volume_points=None, hull_views=None):
+                     volume_outside=100.0, volume_points=None, hull_views=None, sirt_views=None, sirt_iterations=50, sirt_relax=1.0):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
 
     grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
@@ -91,9 +96,12 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     Each family is one call of the table's function at its defaults (threshold mean(gt)) on volume_points points per axis over
     [-volume_outside, volume_outside]^3 (default depth_samples_per_ray + 1 as upstream, :102), its scores repeated on every row (:490,
     :495).  All families share one `GridAnalysis`: the two grids are evaluated once, and so is every mask, skeleton, centreline, mesh and
-    filter response more than one family reads.  The arguments are checked before any work on the GPU."""
+    filter response more than one family reads.  The SIRT columns need `sirt_views` = (engine.xray_views(...) of the training views,
+    their line integrals [V, H, W]) besides `volume`: one `reconstruction_sirt_metrics` call at sirt_iterations and sirt_relax; when
+    `hull_views` is given as well, the hull - taken once, whoever asks first - is the support mask of the reconstruction.  The arguments
+    are checked before any work on the GPU."""
     from ..engine import ssim
-    want = _check_metrics(metrics, binary_targets, volume, hull_views)
+    want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views)
     dev = model.flat_params.device
     n = len(angles)
     poses = _poses(angles, src_pt, translation, dev)
@@ -146,8 +154,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         if analysis is None:                                  # the two n^3 grids, evaluated once for every family
             pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
             analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
-        views = (hull_views,) if names is HULL_METRICS else ()
-        got = score(model, volume, volume_outside, pts, *views, grids=analysis)[0]
+        views, kw = ((hull_views,), {}) if names is HULL_METRICS else ((), {})
+        if names is SIRT_METRICS:
+            views, kw = tuple(sirt_views), dict(iterations=sirt_iterations, relax=sirt_relax, hull_views=hull_views)
+        got = score(model, volume, volume_outside, pts, *views, grids=analysis, **kw)[0]
         for name, key in zip(names, keys):
             scores[name] = [got[key]] * n
     for name in want:
@@ -155,14 +165,15 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
 
 
-def _check_metrics(metrics, binary_targets, volume, hull_views=None):
+def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=None):
     """The metric columns evaluation_sweep fills, in order; raises on a request it cannot serve (before any GPU work)."""
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    unknown = [m for m in metrics if m not in METRICS + _ALL_VOLUME_METRICS + HULL_METRICS]
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS
+    unknown = [m for m in metrics if m not in known]
     if unknown:
-        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(METRICS + _ALL_VOLUME_METRICS + HULL_METRICS)}")
+        raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
     nets = [m for m in metrics if m in _NETWORK_METRICS]
     if nets:
         raise NotImplementedError(f"evaluation_sweep: {nets} need pretrained networks (LPIPS: AlexNet/VGG features, DISTS: VGG16 "
@@ -178,7 +189,13 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None):
         raise ValueError(f"evaluation_sweep: {hull} need the training views (hull_views=engine.visual_hull_views(poses, masks, focal))")
     if hull and volume is None:
         raise ValueError(f"evaluation_sweep: {hull} need the ground-truth volume (volume=VoxelVolume)")
-    return [m for m in METRICS + _ALL_VOLUME_METRICS + HULL_METRICS if m in metrics]
+    sirt = [m for m in metrics if m in SIRT_METRICS]
+    if sirt and sirt_views is None:
+        raise ValueError(f"evaluation_sweep: {sirt} need the training views and their line integrals "
+                         "(sirt_views=(engine.xray_views(...), engine.line_integrals(images)))")
+    if sirt and volume is None:
+        raise ValueError(f"evaluation_sweep: {sirt} need the ground-truth volume (volume=VoxelVolume)")
+    return [m for m in known if m in metrics]
 
 
 @torch.no_grad()
@@ -276,6 +293,12 @@ class GridAnalysis:
         from ..engine import frangi_3d
         return self._once(("frangi", side, tuple(float(s) for s in sigmas)),
                           lambda: frangi_3d(self.pred if side == "pred" else self.gt, sigmas, return_scale=True))
+
+    def hull(self, views):
+        """`engine.visual_hull` of `views` (engine.visual_hull_views) over the grid's points, each speaking for its voxel: bool [n^3].
+        Kept per views object (which the cache holds on to)."""
+        from ..engine import visual_hull
+        return self._once(("hull", id(views)), lambda: (visual_hull(views, tuple(self.pred.shape), self.index_to_world), views))[0]
 
 
 def _analysis(model, volume, outside, n, grids, threshold):
@@ -559,19 +582,65 @@ def reconstruction_hull_metrics(model, volume, outside, n, views, threshold=None
     share of the reconstructed vessel that contradicts a training image - it needs no ground truth (volume=None with `threshold` given
     leaves the other two NaN); dice_hull = the vessel Dice of H against B, what silhouettes alone achieve - the reconstruction should
     beat it; hull_ratio = |H| / |B|; and the counts n_pred, n_pred_outside, n_hull, n_gt, n_hull_gt, threshold."""
-    from ..engine import visual_hull
     if volume is None and grids is None:
         if threshold is None:
             raise ValueError("reconstruction_hull_metrics: without the ground-truth volume the threshold must be given")
         grids = density_grid(model, outside, int(n) - 1), None
     an, thr = _analysis(model, volume, outside, n, grids, threshold)
-    hull = visual_hull(views, tuple(an.pred.shape), an.index_to_world)
+    hull = an.hull(views)                                 # taken once per analysis, whoever asks first
     a, b, n_pred, n_gt = an.masks(thr)
     n_out, n_hull = int((a & ~hull).sum()), int(hull.sum())
     n_both = int((b & hull).sum()) if b is not None else 0
     scores = hull_scores(n_pred, n_out, n_hull if b is not None else 0, n_gt, n_both)
     scores.update(n_pred=n_pred, n_pred_outside=n_out, n_hull=n_hull, n_gt=n_gt, n_hull_gt=n_both, threshold=thr)
     return scores, hull, an.pred, an.gt
+
+
+def sirt_scores(n_sirt, n_pred, n_gt, n_sirt_gt, n_pred_gt, n, sx, sg, sxx, sgg, sxg):
+    """The scores of `reconstruction_sirt_metrics` from five voxel counts, the number of grid points and five fp64 sums over them (x the
+    SIRT volume, g the truth: sum x, sum g, sum x x, sum g g, sum x g), fp64 on the host, NaN where a divisor is 0: dice_sirt =
+    2 n_sirt_gt / (n_sirt + n_gt); dice_model = 2 n_pred_gt / (n_pred + n_gt); dice_gain = dice_model - dice_sirt; corr_sirt =
+    (n sxg - sx sg) / sqrt((n sxx - sx sx) (n sgg - sg sg)), Pearson's correlation."""
+    nan = float("nan")
+    dice_sirt = 2.0 * float(n_sirt_gt) / float(n_sirt + n_gt) if n_sirt + n_gt else nan
+    dice_model = 2.0 * float(n_pred_gt) / float(n_pred + n_gt) if n_pred + n_gt else nan
+    var = (float(n) * sxx - sx * sx) * (float(n) * sgg - sg * sg)
+    return dict(dice_sirt=dice_sirt, dice_model=dice_model, dice_gain=dice_model - dice_sirt,
+                corr_sirt=(float(n) * sxg - sx * sg) / float(np.sqrt(var)) if var > 0 else nan)
+
+
+@torch.no_grad()
+def reconstruction_sirt_metrics(model, volume, outside, n, views, images, iterations=50, relax=1.0, mask=None, threshold=None, grids=None,
+                                hull_views=None):
+    """How the reconstruction stands against the classical baseline, the algebraic reconstruction of the attenuation volume from the same
+    training views -> (scores, SIRT volume [float64, n^3], predicted grid, ground-truth grid).
+
+    `engine.sirt_reconstruct` (include/afx.h: afx_xray_project, afx_xray_backproject) runs `iterations` SIRT iterations at `relax`, from
+    zero and clamped at zero, on the n^3 points of the evaluation grids (`grid_index_to_world(outside, n)`) from `views` =
+    engine.xray_views(poses, focal, width, height, near, far, n_samples) of the TRAINING views and `images`, their line integrals
+    [V, H, W] (`engine.line_integrals(I)` of transmission images).  mask: a support constraint (bool, n^3); hull_views =
+    engine.visual_hull_views(...): the visual hull of these views is the mask (taken once per `GridAnalysis`; with `mask` as well,
+    their intersection).  S = sirt >= threshold, A = pred >= threshold, B = gt >= threshold (threshold: mean(gt) in fp32 unless given).
+    scores (`sirt_scores`, fp64 on the host from device counts and device sums): dice_sirt, the vessel Dice of S against B - what a
+    classical method achieves from these views; dice_model, that of A; dice_gain = dice_model - dice_sirt; corr_sirt, Pearson's
+    correlation of the SIRT volume with the truth over all grid points; and the counts n_sirt, n_pred, n_gt, n_sirt_gt, n_pred_gt,
+    residual (`engine.sirt_residual_norm` of the last iteration), iterations, relax, masked (whether a mask was used), threshold."""
+    from ..engine import sirt_reconstruct
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    support = mask
+    if hull_views is not None:
+        support = an.hull(hull_views) if mask is None else an.hull(hull_views) & (mask != 0)
+    x, history = sirt_reconstruct(views, images, tuple(an.pred.shape), an.index_to_world, iterations=iterations, relax=relax, mask=support,
+                                  return_history=True)
+    a, b, n_a, n_b = an.masks(thr)
+    s = x >= thr
+    g = an.gt.double()
+    sums = torch.stack([x.sum(), g.sum(), (x * x).sum(), (g * g).sum(), (x * g).sum()]).cpu().tolist()
+    n_s, n_sb, n_ab = int(s.sum()), int((s & b).sum()), int((a & b).sum())
+    scores = sirt_scores(n_s, n_a, n_b, n_sb, n_ab, x.numel(), *sums)
+    scores.update(n_sirt=n_s, n_pred=n_a, n_gt=n_b, n_sirt_gt=n_sb, n_pred_gt=n_ab, residual=float(history[-1]) if len(history) else float("nan"),
+                  iterations=int(iterations), relax=float(relax), masked=support is not None, threshold=thr)
+    return scores, x, an.pred, an.gt
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
@@ -687,6 +756,7 @@ _VOLUME_FAMILIES = (
     (VESSELNESS_METRICS, reconstruction_vesselness_metrics, ("tubular_fraction", "dice_tubular", "scale_ratio")),
     (LUMEN_METRICS, reconstruction_lumen_metrics, ("lumen_area_err", "mla_ratio", "stenosis_err")),
     (HULL_METRICS, reconstruction_hull_metrics, ("outside_hull", "dice_hull", "hull_ratio")),
+    (SIRT_METRICS, reconstruction_sirt_metrics, ("dice_sirt", "dice_gain", "corr_sirt")),
 )
 
 
