@@ -1152,6 +1152,36 @@ int afx_xray_backproject(const double* images, const double* views /* device */,
                          uint16_t* seen /* may be NULL */, double* x_inout /* may be NULL */, double relax, int32_t nonneg,
                          const uint8_t* mask /* may be NULL */, void* stream);
 
+/* ---- Total-variation denoising of an fp64 volume: the proximal operator of the isotropic 3-D total variation (the Rudin-Osher-Fatemi
+ * model: argmin_u 0.5 sum (u - x)^2 + weight TV(u)) by Chambolle's dual iteration.  All arithmetic is fp64, every operation rounded on
+ * its own (no contraction), only + - * / sqrt and comparisons, in the order written: tests/tv_reference.py restates it in NumPy and the
+ * device equals the restatement exactly.
+ *   x: double [n0][n1][n2], k fastest, unit lattice spacing; voxel i = (i_0, i_1, i_2), e_a the unit step along axis a; n_a >= 1.
+ *   c = tau / weight, taken once on the host.  Three dual fields p_0, p_1, p_2 of the volume's shape, all +0 at the start.
+ *   Per iteration, every voxel from the OLD p only:
+ *      div[i] = (b_0 + b_1) + b_2,  b_a = p_a[i] - (i_a > 0 ? p_a[i - e_a] : +0)
+ *      u[i] = x[i] - div[i]
+ *      g_a[i] = i_a < n_a - 1 ? u[i + e_a] - u[i] : +0
+ *      m = sqrt((g_0 g_0 + g_1 g_1) + g_2 g_2)
+ *      p_a[i] <- (p_a[i] - tau g_a) / (1 + c m)                 (so p_a stays +0 on the face i_a = n_a - 1)
+ *   After `iterations` of these: out[i] = x[i] - div[i] (iterations = 0: out[i] = x[i], no arithmetic); nonneg != 0: out = out > 0 ?
+ *   out : 0; then out = 0 where the byte mask (may be NULL) is 0.  out may be x.  A NaN or an infinity in x spreads to the neighbours,
+ *   two steps per iteration, and nothing else happens; every loop is bounded by an argument.
+ * One launch per iteration and one for out.  A workgroup owns a tile of AFX_TV_TILE_0 x AFX_TV_TILE_1 x AFX_TV_TILE_2 voxels, forms u on
+ * the tile and one layer on the high side of each axis in LDS - the layer by the operations the neighbouring workgroup uses, so no bit
+ * depends on the tile - and every lane writes the three new p of its voxel; p is ping-ponged between the two triples of the workspace
+ * (6 volumes: afx_tv_denoise_3d_workspace_bytes, 0 for a shape the call refuses; not needed, and not looked at, with iterations = 0).
+ * No atomics, reduction, synchronisation or read-back: the call can be captured in a graph.
+ * AFX_E_INVALID before any launch, the message naming the argument: a null x or out; an extent below 1 or n0 n1 n2 >= 2^31; weight or
+ * tau not finite or not positive; iterations < 0; with iterations > 0 a null or misaligned workspace or workspace_bytes too small; x,
+ * out, mask or workspace not memory of the current device. */
+#define AFX_TV_TILE_0 4
+#define AFX_TV_TILE_1 8
+#define AFX_TV_TILE_2 16
+size_t afx_tv_denoise_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int afx_tv_denoise_3d(const double* x, int32_t n0, int32_t n1, int32_t n2, double weight, double tau, int32_t iterations, int32_t nonneg,
+                      const uint8_t* mask /* may be NULL */, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

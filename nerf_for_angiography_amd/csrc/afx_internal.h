@@ -261,6 +261,18 @@ inline int check_device(const void* p, const char* what, const char* who) {
   return AFX_OK;
 }
 
+// check_device behind a refusal of plain host memory, which the runtime may know as an "unregistered" pointer and report with success
+inline int check_device_memory(const void* p, const char* what, const char* who) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeUnregistered) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s is not memory of a HIP device", what);
+    return set_error(AFX_E_INVALID, who, msg);
+  }
+  (void)hipGetLastError();                            // (a failed query is check_device's to report)
+  return check_device(p, what, who);
+}
+
 inline int launched(const char* who) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? AFX_OK : set_error(AFX_E_HIP, who, hipGetErrorString(e));

@@ -140,17 +140,7 @@ bool xr_finite(const double* p, int n) {
   return true;
 }
 
-// afx::check_device behind a refusal of plain host memory, which the runtime may know as an "unregistered" pointer and report with success
-int xr_check_device(const void* p, const char* what, const char* who) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeUnregistered) {
-    char msg[96];
-    snprintf(msg, sizeof msg, "%s is not memory of a HIP device", what);
-    return afx::set_error(AFX_E_INVALID, who, msg);
-  }
-  (void)hipGetLastError();                              // (a failed query is check_device's to report)
-  return afx::check_device(p, what, who);
-}
+int xr_check_device(const void* p, const char* what, const char* who) { return afx::check_device_memory(p, what, who); }
 
 // the checks the two entry points share; 0 when they pass
 int xr_check_shapes(const char* who, int32_t n0, int32_t n1, int32_t n2, int32_t n_views, int32_t width, int32_t height) {

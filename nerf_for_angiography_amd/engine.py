@@ -2275,8 +2275,64 @@ def sirt_residual_norm(residual: torch.Tensor) -> torch.Tensor:
     return torch.sqrt(torch.sum(residual * residual))
 
 
+def tv_denoise_3d_workspace(shape, device) -> torch.Tensor:
+    """The workspace of `tv_denoise_3d` for a volume of `shape`: afx_tv_denoise_3d_workspace_bytes (six volumes) as a uint8 tensor."""
+    n0, n1, n2 = (int(s) for s in shape)
+    return torch.empty(_lib.load().afx_tv_denoise_3d_workspace_bytes(n0, n1, n2), dtype=torch.uint8, device=device)
+
+
+def tv_denoise_3d(x: torch.Tensor, weight: float, iterations: int = 50, tau: float = 1.0 / 6.0, nonneg: bool = False, mask=None, out=None,
+                  workspace=None) -> torch.Tensor:
+    """afx_tv_denoise_3d: the float64 [n0, n1, n2] device volume `x` denoised by the proximal operator of the isotropic total variation,
+    argmin_u 0.5 sum (u - x)^2 + weight TV(u) (Rudin-Osher-Fatemi), `iterations` of Chambolle's dual iteration at the step tau from
+    p = 0 (include/afx.h holds the definition) -> float64 of x's shape; clamped at 0 with nonneg, zeroed where the uint8 or bool `mask`
+    of x's shape is 0.  out may be x.  One launch per iteration and one more; with `out` and `workspace` (`tv_denoise_3d_workspace`)
+    passed nothing is allocated and the call can be captured in a graph."""
+    lib = _lib.load()
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("tv_denoise_3d: x must be a [n0, n1, n2] tensor")
+    dev = x.device
+    if dev.type != "cuda":
+        raise AfxError("tv_denoise_3d: the volume must live on a GPU; there is no CPU path")
+    n = x.numel()
+    _xray_f64(x, "x", n, dev, "tv_denoise_3d")
+    if out is None:
+        out = torch.empty_like(x)
+    _xray_f64(out, "out", n, dev, "tv_denoise_3d")
+    if mask is not None:
+        if tuple(mask.shape) != tuple(x.shape):
+            raise ValueError(f"tv_denoise_3d: mask must have the shape {tuple(x.shape)}, got {tuple(mask.shape)}")
+        if mask.dtype == torch.bool and mask.is_contiguous() and mask.device == dev:
+            mask = mask.view(torch.uint8)                 # (the same bytes)
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev:
+            raise ValueError(f"tv_denoise_3d: mask must be a contiguous uint8 or bool tensor on {dev}")
+    n0, n1, n2 = x.shape
+    if workspace is None and int(iterations) > 0:
+        workspace = tv_denoise_3d_workspace(x.shape, dev)
+    if workspace is not None and (workspace.device != dev or not workspace.is_contiguous()):
+        raise ValueError(f"tv_denoise_3d: workspace must be a contiguous tensor on {dev}")
+    nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _lib.check(lib.afx_tv_denoise_3d(_ptr(x), n0, n1, n2, float(weight), float(tau), int(iterations), int(bool(nonneg)), _ptr(mask), _ptr(out),
+                                     _ptr(workspace), nbytes, Engine._stream(dev)), "afx_tv_denoise_3d")
+    return out
+
+
+def total_variation_3d(x: torch.Tensor) -> torch.Tensor:
+    """The isotropic total variation of a [n0, n1, n2] volume: the sum over the voxels of sqrt(g_0^2 + g_1^2 + g_2^2), g_a the forward
+    difference along axis a (0 on the last layer), in fp64 -> a 0-d tensor on x's device.  Plain torch: a figure to report, the sum in
+    torch's order."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("total_variation_3d: x must be a [n0, n1, n2] tensor")
+    u = x.to(torch.float64)
+    sq = torch.zeros_like(u)
+    sq[:-1] += (u[1:] - u[:-1]) ** 2
+    sq[:, :-1] += (u[:, 1:] - u[:, :-1]) ** 2
+    sq[:, :, :-1] += (u[:, :, 1:] - u[:, :, :-1]) ** 2
+    return torch.sqrt(sq).sum()
+
+
 def sirt_reconstruct(views: dict, line_integrals: torch.Tensor, shape, index_to_world=None, iterations: int = 50, relax: float = 1.0,
-                     mask=None, x0=None, nonneg: bool = True, return_history: bool = False):
+                     mask=None, x0=None, nonneg: bool = True, return_history: bool = False, tv_weight=None, tv_iterations: int = 10):
     """SIRT: the attenuation volume on the lattice x = index_to_world (i, j, k, 1) of `shape` whose line integrals along the rays of
     `views` (`xray_views`) approach `line_integrals` (float64 [V, H, W] on the GPU; `line_integrals(I)` of transmission images) ->
     float64 `shape`[, history float64 [iterations] on the host].
@@ -2286,11 +2342,18 @@ def sirt_reconstruct(views: dict, line_integrals: torch.Tensor, shape, index_to_
     nonneg and zeroed outside `mask` (bool or uint8, `shape`: a support constraint such as the visual hull) - the fused update; every
     voxel takes the mean of its residuals over the views that see it.  x0: the start volume (default zeros; it is not changed).  The
     buffers are allocated once and nothing is read back inside the loop; return_history adds `sirt_residual_norm` of each iteration's
-    residual images (those of the volume BEFORE the iteration's update), read back once at the end."""
+    residual images (those of the volume BEFORE the iteration's update), read back once at the end.
+
+    tv_weight (default None: plain SIRT, the launches above and nothing else): SIRT-TV - every update is followed by
+    `tv_denoise_3d(x, tv_weight, tv_iterations, nonneg=nonneg, mask=mask, out=x)`, in place, its dual fields from zero every time, its
+    workspace allocated once before the loop."""
+    import math
     rec, dev, v, w, h = _xray_views_checked(views, "sirt_reconstruct")
     shape = tuple(int(s) for s in shape)
     if int(iterations) < 0:
         raise ValueError(f"sirt_reconstruct: iterations must be >= 0, got {iterations}")
+    if tv_weight is not None and not (math.isfinite(tv_weight) and tv_weight > 0 and int(tv_iterations) >= 0):
+        raise ValueError(f"sirt_reconstruct: tv_weight must be finite and > 0 and tv_iterations >= 0, got {tv_weight!r}, {tv_iterations!r}")
     if not isinstance(line_integrals, torch.Tensor) or line_integrals.device != dev:
         raise AfxError("sirt_reconstruct: the line integrals must live on the views' GPU; there is no CPU path")
     b = line_integrals.to(torch.float64).contiguous()
@@ -2311,11 +2374,14 @@ def sirt_reconstruct(views: dict, line_integrals: torch.Tensor, shape, index_to_
     weight = torch.where(ell > 0, 1.0 / ell, torch.zeros_like(ell))
     residual = ell                                        # (the buffer of the residual images; l is not needed any more)
     history = torch.zeros(int(iterations), dtype=torch.float64, device=dev) if return_history else None
+    tv_workspace = tv_denoise_3d_workspace(shape, dev) if tv_weight is not None and int(tv_iterations) > 0 else None
     for it in range(int(iterations)):
         xray_project(x, views, index_to_world, target=b, weight=weight, out=residual)
         if history is not None:
             history[it] = sirt_residual_norm(residual)
         xray_backproject(residual, views, shape, index_to_world, x_inout=x, relax=relax, nonneg=nonneg, mask=m8)
+        if tv_weight is not None:
+            tv_denoise_3d(x, tv_weight, tv_iterations, nonneg=nonneg, mask=m8, out=x, workspace=tv_workspace)
     return (x, history.cpu()) if return_history else x
 
 

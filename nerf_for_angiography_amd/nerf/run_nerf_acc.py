@@ -23,7 +23,8 @@ the march's candidates doubles as the alpha pass.
 `--grid_init hull` (with `grid` or `grid_ops`, `--binary True`) carves both occupancy grids with the visual hull of the training views
 before training and keeps it as the ceiling of every grid update (`OccupancyGrid.carve_from_views`, `afx_visual_hull`).
 `--save_sirt PATH.npy` (`--binary True` or CT-type data) writes, at the end of the run, the classical baseline: the SIRT reconstruction
-of the attenuation volume from the training views on the 128^3 lattice of the occupancy grid's cell centres (`engine.sirt_reconstruct`).
+of the attenuation volume from the training views on the 128^3 lattice of the occupancy grid's cell centres (`engine.sirt_reconstruct`);
+`--sirt_tv_weight W` makes it SIRT-TV, a total-variation denoising step after every update (`engine.tv_denoise_3d`, `afx_tv_denoise_3d`).
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -153,6 +154,11 @@ def build_parser():
                         'hull the hull is the support mask')
     p.add_argument('--sirt_iterations', type=int, default=50, metavar='N', help='--save_sirt: SIRT iterations (default 50)')
     p.add_argument('--sirt_relax', type=float, default=1.0, metavar='LAMBDA', help='--save_sirt: the relaxation factor (default 1.0)')
+    p.add_argument('--sirt_tv_weight', type=float, default=0.0, metavar='W',
+                   help='--save_sirt: SIRT-TV - after every SIRT update the volume is denoised by the proximal operator of the total variation '
+                        'at the weight W (afx_tv_denoise_3d); 0 (the default): plain SIRT')
+    p.add_argument('--sirt_tv_iterations', type=int, default=10, metavar='N',
+                   help='--sirt_tv_weight: iterations of the denoising step after every SIRT update (default 10)')
     p.add_argument('--phantom_mesh', default=None, metavar='PATH',
                    help='--synthetic: the phantom is the vessel surface in PATH (.stl or .vtk) instead of the capsule tree: its signed distance '
                         'field on the GPU (afx_mesh_sdf_3d), passed through rev_sigmoid(., 2) and projected with type=\'sdf\' as the '
@@ -213,6 +219,13 @@ def check_args(args):
             raise ValueError("--sirt_iterations: needs N >= 1")
         if not (np.isfinite(args.sirt_relax) and 0 < args.sirt_relax < 2):
             raise ValueError("--sirt_relax: needs 0 < LAMBDA < 2")
+    tv_weight = getattr(args, 'sirt_tv_weight', 0.0)
+    if not (np.isfinite(tv_weight) and tv_weight >= 0):
+        raise ValueError("--sirt_tv_weight: needs a finite W >= 0")
+    if tv_weight > 0 and getattr(args, 'save_sirt', None) is None:
+        raise ValueError("--sirt_tv_weight: needs --save_sirt")
+    if getattr(args, 'sirt_tv_iterations', 10) < 0:
+        raise ValueError("--sirt_tv_iterations: needs N >= 0")
     if args.phantom_mesh is not None:
         if not args.synthetic:
             raise ValueError("--phantom_mesh: needs --synthetic (the phantom replaces the capsule tree of the synthetic dataset)")
@@ -563,7 +576,8 @@ def main(argv=None):
     if args.save_sirt is not None:
         mask = acc_grid._carve_u8 if acc_grid is not None and args.grid_init == 'hull' else None      # the hull the grids were carved with
         result['sirt_info'] = save_sirt(proj_df, train_ray_df, test_proj_id, [-outside] * 3 + [outside] * 3, 128, near_thresh, far_thresh,
-                                        depth_samples_per_ray_coarse, args.sirt_iterations, args.sirt_relax, device, args.save_sirt, mask=mask)
+                                        depth_samples_per_ray_coarse, args.sirt_iterations, args.sirt_relax, device, args.save_sirt, mask=mask,
+                                        tv_weight=args.sirt_tv_weight if args.sirt_tv_weight > 0 else None, tv_iterations=args.sirt_tv_iterations)
     return result
 
 
@@ -588,21 +602,27 @@ def training_view_images(proj_df, train_ray_df, test_proj_id, device):
     return poses, images.to(device), focal
 
 
-def save_sirt(proj_df, train_ray_df, test_proj_id, roi_aabb, resolution, near, far, n_samples, iterations, relax, device, path, mask=None):
+def save_sirt(proj_df, train_ray_df, test_proj_id, roi_aabb, resolution, near, far, n_samples, iterations, relax, device, path, mask=None,
+              tv_weight=None, tv_iterations=10):
     """--save_sirt: the SIRT reconstruction of the attenuation volume from the training views (`engine.sirt_reconstruct`, from zero,
     clamped at zero) on the cell centres of the resolution^3 grid over `roi_aabb`, the line integrals -log(pixel_value) sampled as the
     training rays are (n_samples between near and far); mask: a support constraint of that shape (the hull the grids were carved with)
-    -> its info (shape, iterations, relax, masked, n_views, the first and last residual norm, the volume's maximum and sum, path)."""
+    -> its info (shape, iterations, relax, masked, n_views, the first and last residual norm, the volume's maximum and sum, path).
+    tv_weight (--sirt_tv_weight; None: plain SIRT): SIRT-TV, `engine.tv_denoise_3d` at tv_weight and tv_iterations after every update;
+    the info gains tv_weight, tv_iterations and total_variation (`engine.total_variation_3d` of the volume)."""
     poses, images, focal = training_view_images(proj_df, train_ray_df, test_proj_id, device)
     views = _engine.xray_views(poses, focal, images.shape[2], images.shape[1], near, far, n_samples, device=device)
     shape = (int(resolution),) * 3
     a12, _ = _engine.grid_cell_lattice(roi_aabb, shape)
+    tv = {} if tv_weight is None else dict(tv_weight=float(tv_weight), tv_iterations=int(tv_iterations))
     x, history = _engine.sirt_reconstruct(views, _engine.line_integrals(images), shape, a12, iterations=iterations, relax=relax,
-                                          mask=None if mask is None else mask.reshape(shape), return_history=True)
+                                          mask=None if mask is None else mask.reshape(shape), return_history=True, **tv)
     np.save(path, x.cpu().numpy())
     info = dict(shape=shape, iterations=int(iterations), relax=float(relax), masked=mask is not None, n_views=int(views['n_views']),
                 residual_first=float(history[0]), residual_last=float(history[-1]), max=float(x.max()), sum=float(x.sum()), path=str(path))
-    print('sirt', {k: info[k] for k in ('iterations', 'masked', 'n_views', 'residual_first', 'residual_last', 'max', 'path')}, flush=True)
+    if tv:
+        info.update(tv, total_variation=float(_engine.total_variation_3d(x)))
+    print('sirt', {k: info[k] for k in ('iterations', 'masked', 'n_views', 'residual_first', 'residual_last', 'max', 'path') + tuple(tv)}, flush=True)
     return info
 
 

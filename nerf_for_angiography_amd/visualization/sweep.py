@@ -11,7 +11,7 @@ no network - every view in one `afx_ssim` call, in fp64), normalised DOT 2D (:44
 DOT 3D (:480-495) of `reconstruction_metrics`: the model's density grid against the ground-truth volume sampled at the same points
 (`afx_volume_grid`).  LPIPS and DISTS upstream are pretrained networks whose weights this project does not ship: out of scope.
 
-Beyond the reference: ten more families of whole-volume scores on the same two grids, each a reconstruction_* function with a tuple of
+Beyond the reference: eleven more families of whole-volume scores on the same two grids, each a reconstruction_* function with a tuple of
 column names, listed in table order in _VOLUME_FAMILIES at the end of this file; what a family scores is in its function's docstring.
 The surface distances between the two thresholded grids (`afx_surface_metrics_3d`), the connected pieces of the reconstruction
 (`afx_label_components_3d`), clDice on the medial curves (`afx_skeletonize_3d`), the vessel as a capped triangle mesh
@@ -19,7 +19,7 @@ The surface distances between the two thresholded grids (`afx_surface_metrics_3d
 meshes (`afx_mesh_point_distance`), the pruned centreline read as a graph (`afx_prune_spurs`, `afx_centreline_graph`), the tubular
 share by the 3-D Frangi filter (`afx_frangi_3d`), the lumen's cross-sections along the true centreline (`afx_lumen_profile`), the
 visual hull of the training views (`afx_visual_hull`) and the classical baseline, the algebraic reconstruction (SIRT) of the attenuation
-volume from the same views (`afx_xray_project`, `afx_xray_backproject`).  The families share what they derive from the grids through one `GridAnalysis`;
+volume from the same views (`afx_xray_project`, `afx_xray_backproject`), plain and with a total-variation step (`afx_tv_denoise_3d`).  The families share what they derive from the grids through one `GridAnalysis`;
 the chain mask -> distance transform -> skeleton -> pruned skeleton -> graph is `centreline_tree`."""
 from __future__ import annotations
 
@@ -54,6 +54,9 @@ HULL_METRICS = ("OUTSIDE HULL 3D", "DICE 3D HULL", "HULL RATIO 3D")
 # views (reconstruction_sirt_metrics: afx_xray_project, afx_xray_backproject), a tuple of its own, tabulated behind the hull columns; it
 # needs the views with their line integrals (sirt_views=(engine.xray_views(...), line integrals)) and the ground-truth volume
 SIRT_METRICS = ("DICE 3D SIRT", "DICE GAIN 3D", "CORR 3D SIRT")
+# and SIRT-TV, the same reconstruction with a total-variation denoising step (afx_tv_denoise_3d) after every update, against plain SIRT;
+# it needs sirt_views, the ground-truth volume and a weight (sirt_tv_weight)
+SIRT_TV_METRICS = ("DICE 3D SIRT-TV", "TV GAIN 3D", "CORR 3D SIRT-TV")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -75,7 +78,8 @@ def _poses(angles, src_pt, translation, device):
 def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length, src_pt, near_thresh, far_thresh,
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
                      views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3, metrics=None, volume=None,
-                     volume_outside=100.0, volume_points=None, hull_views=None, sirt_views=None, sirt_iterations=50, sirt_relax=1.0):
+                     volume_outside=100.0, volume_points=None, hull_views=None, sirt_views=None, sirt_iterations=50, sirt_relax=1.0,
+                     sirt_tv_weight=None, sirt_tv_iterations=10):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
 
     grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
@@ -98,10 +102,11 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     :495).  All families share one `GridAnalysis`: the two grids are evaluated once, and so is every mask, skeleton, centreline, mesh and
     filter response more than one family reads.  The SIRT columns need `sirt_views` = (engine.xray_views(...) of the training views,
     their line integrals [V, H, W]) besides `volume`: one `reconstruction_sirt_metrics` call at sirt_iterations and sirt_relax; when
-    `hull_views` is given as well, the hull - taken once, whoever asks first - is the support mask of the reconstruction.  The arguments
-    are checked before any work on the GPU."""
+    `hull_views` is given as well, the hull - taken once, whoever asks first - is the support mask of the reconstruction.  The SIRT-TV
+    columns need sirt_tv_weight as well: the same call with tv_weight = sirt_tv_weight and tv_iterations = sirt_tv_iterations; plain
+    SIRT, which both families read, runs once.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
-    want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views)
+    want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views, sirt_tv_weight)
     dev = model.flat_params.device
     n = len(angles)
     poses = _poses(angles, src_pt, translation, dev)
@@ -155,8 +160,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
             pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
             analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
         views, kw = ((hull_views,), {}) if names is HULL_METRICS else ((), {})
-        if names is SIRT_METRICS:
+        if names is SIRT_METRICS or names is SIRT_TV_METRICS:
             views, kw = tuple(sirt_views), dict(iterations=sirt_iterations, relax=sirt_relax, hull_views=hull_views)
+        if names is SIRT_TV_METRICS:
+            kw.update(tv_weight=sirt_tv_weight, tv_iterations=sirt_tv_iterations)
         got = score(model, volume, volume_outside, pts, *views, grids=analysis, **kw)[0]
         for name, key in zip(names, keys):
             scores[name] = [got[key]] * n
@@ -165,12 +172,12 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
 
 
-def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=None):
+def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=None, sirt_tv_weight=None):
     """The metric columns evaluation_sweep fills, in order; raises on a request it cannot serve (before any GPU work)."""
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
@@ -189,12 +196,15 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
         raise ValueError(f"evaluation_sweep: {hull} need the training views (hull_views=engine.visual_hull_views(poses, masks, focal))")
     if hull and volume is None:
         raise ValueError(f"evaluation_sweep: {hull} need the ground-truth volume (volume=VoxelVolume)")
-    sirt = [m for m in metrics if m in SIRT_METRICS]
+    sirt = [m for m in metrics if m in SIRT_METRICS + SIRT_TV_METRICS]
     if sirt and sirt_views is None:
         raise ValueError(f"evaluation_sweep: {sirt} need the training views and their line integrals "
                          "(sirt_views=(engine.xray_views(...), engine.line_integrals(images)))")
     if sirt and volume is None:
         raise ValueError(f"evaluation_sweep: {sirt} need the ground-truth volume (volume=VoxelVolume)")
+    tv = [m for m in metrics if m in SIRT_TV_METRICS]
+    if tv and sirt_tv_weight is None:
+        raise ValueError(f"evaluation_sweep: {tv} need the weight of the total variation (sirt_tv_weight=W)")
     return [m for m in known if m in metrics]
 
 
@@ -299,6 +309,19 @@ class GridAnalysis:
         Kept per views object (which the cache holds on to)."""
         from ..engine import visual_hull
         return self._once(("hull", id(views)), lambda: (visual_hull(views, tuple(self.pred.shape), self.index_to_world), views))[0]
+
+    def sirt(self, views, images, iterations, relax, support=None, tv_weight=None, tv_iterations=10):
+        """(volume, residual history) of `engine.sirt_reconstruct` on the grid's points with `support` (None, or a mask this analysis or
+        the caller made) as its mask.  Kept per views, images and support object (which the cache holds on to) and per setting, so plain
+        SIRT runs once for every family that reads it."""
+        from ..engine import sirt_reconstruct
+        tv = None if tv_weight is None else (float(tv_weight), int(tv_iterations))
+        key = ("sirt", id(views), id(images), id(support), int(iterations), float(relax), tv)
+        def run():
+            kw = {} if tv is None else dict(tv_weight=tv[0], tv_iterations=tv[1])
+            return sirt_reconstruct(views, images, tuple(self.pred.shape), self.index_to_world, iterations=iterations, relax=relax, mask=support,
+                                    return_history=True, **kw), (views, images, support)
+        return self._once(key, run)[0]
 
 
 def _analysis(model, volume, outside, n, grids, threshold):
@@ -611,7 +634,7 @@ def sirt_scores(n_sirt, n_pred, n_gt, n_sirt_gt, n_pred_gt, n, sx, sg, sxx, sgg,
 
 @torch.no_grad()
 def reconstruction_sirt_metrics(model, volume, outside, n, views, images, iterations=50, relax=1.0, mask=None, threshold=None, grids=None,
-                                hull_views=None):
+                                hull_views=None, tv_weight=None, tv_iterations=10):
     """How the reconstruction stands against the classical baseline, the algebraic reconstruction of the attenuation volume from the same
     training views -> (scores, SIRT volume [float64, n^3], predicted grid, ground-truth grid).
 
@@ -624,14 +647,17 @@ def reconstruction_sirt_metrics(model, volume, outside, n, views, images, iterat
     scores (`sirt_scores`, fp64 on the host from device counts and device sums): dice_sirt, the vessel Dice of S against B - what a
     classical method achieves from these views; dice_model, that of A; dice_gain = dice_model - dice_sirt; corr_sirt, Pearson's
     correlation of the SIRT volume with the truth over all grid points; and the counts n_sirt, n_pred, n_gt, n_sirt_gt, n_pred_gt,
-    residual (`engine.sirt_residual_norm` of the last iteration), iterations, relax, masked (whether a mask was used), threshold."""
-    from ..engine import sirt_reconstruct
+    residual (`engine.sirt_residual_norm` of the last iteration), iterations, relax, masked (whether a mask was used), threshold.
+
+    tv_weight (default None: plain SIRT): the reconstruction is SIRT-TV, `engine.tv_denoise_3d` (afx_tv_denoise_3d) at tv_weight and
+    tv_iterations after every update, and the scores gain dice_sirt_tv and corr_sirt_tv, the two scores above of the SIRT-TV volume -
+    which is the volume returned -, tv_gain = dice_sirt_tv - dice_sirt, and tv_weight, tv_iterations; dice_sirt, corr_sirt and the
+    rest stay those of plain SIRT from the same views with the same mask (kept on the `GridAnalysis`: it runs once)."""
     an, thr = _analysis(model, volume, outside, n, grids, threshold)
     support = mask
     if hull_views is not None:
         support = an.hull(hull_views) if mask is None else an.hull(hull_views) & (mask != 0)
-    x, history = sirt_reconstruct(views, images, tuple(an.pred.shape), an.index_to_world, iterations=iterations, relax=relax, mask=support,
-                                  return_history=True)
+    x, history = an.sirt(views, images, iterations, relax, support)
     a, b, n_a, n_b = an.masks(thr)
     s = x >= thr
     g = an.gt.double()
@@ -640,6 +666,14 @@ def reconstruction_sirt_metrics(model, volume, outside, n, views, images, iterat
     scores = sirt_scores(n_s, n_a, n_b, n_sb, n_ab, x.numel(), *sums)
     scores.update(n_sirt=n_s, n_pred=n_a, n_gt=n_b, n_sirt_gt=n_sb, n_pred_gt=n_ab, residual=float(history[-1]) if len(history) else float("nan"),
                   iterations=int(iterations), relax=float(relax), masked=support is not None, threshold=thr)
+    if tv_weight is not None:
+        x = an.sirt(views, images, iterations, relax, support, tv_weight, tv_iterations)[0]
+        s = x >= thr
+        sums[0], sums[2], sums[4] = torch.stack([x.sum(), (x * x).sum(), (x * g).sum()]).cpu().tolist()
+        n_s, n_sb = int(s.sum()), int((s & b).sum())
+        tv = sirt_scores(n_s, n_a, n_b, n_sb, n_ab, x.numel(), *sums)
+        scores.update(dice_sirt_tv=tv["dice_sirt"], corr_sirt_tv=tv["corr_sirt"], tv_gain=tv["dice_sirt"] - scores["dice_sirt"],
+                      n_sirt_tv=n_s, n_sirt_tv_gt=n_sb, tv_weight=float(tv_weight), tv_iterations=int(tv_iterations))
     return scores, x, an.pred, an.gt
 
 
@@ -757,6 +791,7 @@ _VOLUME_FAMILIES = (
     (LUMEN_METRICS, reconstruction_lumen_metrics, ("lumen_area_err", "mla_ratio", "stenosis_err")),
     (HULL_METRICS, reconstruction_hull_metrics, ("outside_hull", "dice_hull", "hull_ratio")),
     (SIRT_METRICS, reconstruction_sirt_metrics, ("dice_sirt", "dice_gain", "corr_sirt")),
+    (SIRT_TV_METRICS, reconstruction_sirt_metrics, ("dice_sirt_tv", "tv_gain", "corr_sirt_tv")),
 )
 
 
