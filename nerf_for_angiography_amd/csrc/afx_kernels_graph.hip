@@ -5,6 +5,7 @@
 // NOTHING CAN HANG: no thread waits for a value that another thread writes, and every loop runs a number of times the thread holds
 // before it enters - the 26 neighbours, CG_ITERS, the chunk counts, and in the walk the branch's own size.
 #include "afx_internal.h"
+#include "afx_scan.h"
 #include <algorithm>
 #include <cmath>
 
@@ -139,52 +140,32 @@ __global__ void __launch_bounds__(CG_BLOCK) k_cg_terminals(const uint8_t* __rest
 template <int PASS>
 __global__ void __launch_bounds__(CG_BLOCK) k_cg_scan(const uint32_t* __restrict__ sizes, uint32_t total, uint32_t* __restrict__ chunk,
                                                       uint32_t* __restrict__ offs) {
-  __shared__ uint32_t ts[CG_BLOCK];
-  const int t = threadIdx.x;
-  const uint32_t e0 = blockIdx.x * CG_CHUNK + (uint32_t)t * CG_ITERS;
-  uint32_t x[CG_ITERS], s = 0;
+  const uint32_t e0 = blockIdx.x * CG_CHUNK + threadIdx.x * CG_ITERS;
+  uint32_t x[CG_ITERS], p[1] = {0}, tot[1];
 #pragma unroll
   for (int q = 0; q < CG_ITERS; ++q) {
     x[q] = e0 + q < total ? sizes[e0 + q] : 0;
-    s += x[q];
+    p[0] += x[q];
   }
-  ts[t] = s;
-  __syncthreads();
-#pragma unroll
-  for (int d = 1; d < CG_BLOCK; d <<= 1) {            // Hillis-Steele over the 256 thread sums
-    const uint32_t a = t >= d ? ts[t - d] : 0;
-    __syncthreads();
-    ts[t] += a;
-    __syncthreads();
-  }
+  afx::block_exclusive_scan<CG_BLOCK>(p, tot);
   if (PASS == 0) {
-    if (t == CG_BLOCK - 1) chunk[blockIdx.x] = ts[t];
+    if (threadIdx.x == CG_BLOCK - 1) chunk[blockIdx.x] = tot[0];
     return;
   }
-  uint32_t p = chunk[blockIdx.x] + ts[t] - s;
+  p[0] += chunk[blockIdx.x];
 #pragma unroll
   for (int q = 0; q < CG_ITERS; ++q) {
-    if (e0 + q < total) offs[e0 + q] = p;
-    p += x[q];
+    if (e0 + q < total) offs[e0 + q] = p[0];
+    p[0] += x[q];
   }
 }
 
 __global__ void __launch_bounds__(1024) k_cg_scan_chunks(uint32_t* chunk, uint32_t nb) {
-  __shared__ uint32_t ts[1024];
-  const int t = threadIdx.x;
-  const uint32_t per = (nb + 1023) / 1024, b0 = min((uint32_t)t * per, nb), b1 = min(b0 + per, nb);
-  uint32_t s = 0;
-  for (uint32_t b = b0; b < b1; ++b) s += chunk[b];
-  ts[t] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const uint32_t a = t >= d ? ts[t - d] : 0;
-    __syncthreads();
-    ts[t] += a;
-    __syncthreads();
-  }
-  uint32_t p = ts[t] - s;
-  for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = chunk[b]; chunk[b] = p; p += c; }
+  uint32_t b0, b1, p[1] = {0}, tot[1];
+  afx::scan_run<1024>(nb, b0, b1);
+  for (uint32_t b = b0; b < b1; ++b) p[0] += chunk[b];
+  afx::block_exclusive_scan<1024>(p, tot);
+  for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = chunk[b]; chunk[b] = p[0]; p[0] += c; }
 }
 
 // (((n_0 L_0) + n_1 L_1) + ...) + n_12 L_12, every product and sum rounded on its own

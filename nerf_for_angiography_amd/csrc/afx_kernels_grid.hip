@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "afx_scan.h"
 
 namespace afx {
 
@@ -170,55 +171,23 @@ __device__ __forceinline__ uint32_t grid_word(const uint32_t* bits, int64_t w, i
 }
 // word_pre[w]: set bits in the words of w's workgroup before w; block_tot[b]: set bits in workgroup b's SEL_WORDS words
 __global__ void __launch_bounds__(256) k_grid_occ_count(const uint32_t* bits, int64_t n_cells, int64_t n_words, int32_t* word_pre, int32_t* block_tot) {
-  __shared__ int32_t wsum[4];
   const int64_t w = (int64_t)blockIdx.x * SEL_WORDS + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = w < n_words ? __popc(grid_word(bits, w, n_cells)) : 0;
-  int inc = c;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int v = __shfl_up(inc, d);
-    if (lane >= d) inc += v;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int k = 0; k < wave; ++k) base += wsum[k];
-  if (w < n_words) word_pre[w] = base + inc - c;
-  if (threadIdx.x == 255) block_tot[blockIdx.x] = base + inc;
+  int32_t c[1] = {w < n_words ? (int32_t)__popc(grid_word(bits, w, n_cells)) : 0}, tot[1];
+  block_exclusive_scan<256>(c, tot);
+  if (w < n_words) word_pre[w] = c[0];
+  if (threadIdx.x == 255) block_tot[blockIdx.x] = tot[0];
 }
 // one workgroup: block_pre = exclusive scan of block_tot[nb]; n_occ[0] = the total, count[0] = n_draw + min(n_draw, total)
 __global__ void __launch_bounds__(1024) k_grid_occ_scan(const int32_t* block_tot, int64_t nb, int32_t* block_pre, int64_t n_draw, int64_t* n_occ,
                                                          int64_t* count) {
-  __shared__ int64_t ws_[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
-  int64_t s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += block_tot[b];
-  int64_t is = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t v = __shfl_up(is, d);
-    if (lane >= d) is += v;
-  }
-  if (lane == 63) ws_[wave] = is;
-  __syncthreads();
-  if (wave == 0) {
-    int64_t a = lane < 16 ? ws_[lane] : 0;
-    const int64_t a0 = a;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const int64_t v = __shfl_up(a, d);
-      if (lane >= d) a += v;
-    }
-    if (lane < 16) ws_[lane] = a - a0;      // exclusive
-  }
-  __syncthreads();
-  int64_t p = ws_[wave] + is - s;           // exclusive prefix of this thread's blocks
-  for (int64_t b = b0; b < b1; ++b) { block_pre[b] = (int32_t)p; p += block_tot[b]; }
-  if (t == 1023) {
-    *n_occ = p;
-    *count = n_draw + (n_draw < p ? n_draw : p);
+  int64_t b0, b1, p[1] = {0}, tot[1];
+  scan_run<1024>(nb, b0, b1);
+  for (int64_t b = b0; b < b1; ++b) p[0] += block_tot[b];
+  block_exclusive_scan<1024>(p, tot);
+  for (int64_t b = b0; b < b1; ++b) { block_pre[b] = (int32_t)p[0]; p[0] += block_tot[b]; }
+  if (threadIdx.x == 1023) {
+    *n_occ = tot[0];
+    *count = n_draw + (n_draw < tot[0] ? n_draw : tot[0]);
   }
 }
 // cells[i], i < n_draw: the uniform draw ((u24 * num_cells) >> 24); i = n_draw + j: the occupied cell of rank (u24 * n_occ) >> 24 when n_draw < n_occ,
@@ -574,45 +543,22 @@ __global__ void __launch_bounds__(256) k_single_eval_composite(const float* row_
 // polls the tag instead of queueing a copy and a stream synchronisation behind the kernel.
 __global__ void __launch_bounds__(1024) k_ray_offsets(const int32_t* counts, int64_t n_rays, int64_t* offsets, int64_t* group_offsets, int64_t* totals,
                                                        volatile int64_t* mailbox = nullptr, int64_t tag = 0) {
-  __shared__ int64_t ws_[16], wg_[16];      // the 16 waves' totals, then their exclusive prefix
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t per = (n_rays + 1023) / 1024, r0 = t * per, r1 = r0 + per < n_rays ? r0 + per : n_rays;
-  int64_t s = 0, g = 0;
-  for (int64_t r = r0; r < r1; ++r) { const int64_t c = counts[r]; s += c; g += (c + 31) >> 5; }
-  // inclusive scan inside the wave (6 shuffle steps), the 16 wave totals by one wave, two barriers in all
-  int64_t is = s, ig = g;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t as = __shfl_up(is, d), ag = __shfl_up(ig, d);
-    if (lane >= d) { is += as; ig += ag; }
-  }
-  if (lane == 63) { ws_[wave] = is; wg_[wave] = ig; }
-  __syncthreads();
-  if (wave == 0) {
-    int64_t a = lane < 16 ? ws_[lane] : 0, b = lane < 16 ? wg_[lane] : 0;
-    const int64_t a0 = a, b0 = b;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const int64_t as = __shfl_up(a, d), ag = __shfl_up(b, d);
-      if (lane >= d) { a += as; b += ag; }
-    }
-    if (lane < 16) { ws_[lane] = a - a0; wg_[lane] = b - b0; }      // exclusive
-  }
-  __syncthreads();
-  const int64_t tot_s = ws_[15] + __shfl(is, 63), tot_g = wg_[15] + __shfl(ig, 63);      // (valid in wave 15)
-  s = ws_[wave] + is - s; g = wg_[wave] + ig - g;             // exclusive prefix of this thread's rays
+  int64_t r0, r1, p[2] = {0, 0}, tot[2];             // samples, 32-sample groups
+  scan_run<1024>(n_rays, r0, r1);
+  for (int64_t r = r0; r < r1; ++r) { const int64_t c = counts[r]; p[0] += c; p[1] += (c + 31) >> 5; }
+  block_exclusive_scan<1024>(p, tot);
   for (int64_t r = r0; r < r1; ++r) {
     const int64_t c = counts[r];
-    offsets[r] = s;
-    if (group_offsets) group_offsets[r] = g;
-    s += c; g += (c + 31) >> 5;
+    offsets[r] = p[0];
+    if (group_offsets) group_offsets[r] = p[1];
+    p[0] += c; p[1] += (c + 31) >> 5;
   }
-  if (t == 1023) {
-    offsets[n_rays] = tot_s;
-    if (group_offsets) group_offsets[n_rays] = tot_g;
-    if (totals) { totals[0] = tot_s; totals[1] = tot_g; }
+  if (threadIdx.x == 1023) {
+    offsets[n_rays] = tot[0];
+    if (group_offsets) group_offsets[n_rays] = tot[1];
+    if (totals) { totals[0] = tot[0]; totals[1] = tot[1]; }
     if (mailbox) {
-      mailbox[0] = tot_s; mailbox[1] = tot_g;
+      mailbox[0] = tot[0]; mailbox[1] = tot[1];
       __threadfence_system();
       mailbox[2] = tag;
     }
@@ -794,45 +740,30 @@ __global__ void __launch_bounds__(256) k_sel_count(const float* keys, int64_t n,
 }
 // one block: exclusive prefix sums of the per-block counts, in place
 __global__ void __launch_bounds__(1024) k_sel_offsets(uint32_t* cnt_gt, uint32_t* cnt_eq, int64_t nb) {
-  __shared__ uint32_t pg[1024], pe[1024];
   cnt_gt += (size_t)blockIdx.y * nb; cnt_eq += (size_t)blockIdx.y * nb;
-  const int t = threadIdx.x;
-  const int64_t per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
-  uint32_t g = 0, e = 0;
-  for (int64_t b = b0; b < b1; ++b) { g += cnt_gt[b]; e += cnt_eq[b]; }
-  pg[t] = g; pe[t] = e;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t rg = 0, re = 0;
-    for (int i = 0; i < 1024; ++i) { const uint32_t a = pg[i], c = pe[i]; pg[i] = rg; pe[i] = re; rg += a; re += c; }
-  }
-  __syncthreads();
-  g = pg[t]; e = pe[t];
-  for (int64_t b = b0; b < b1; ++b) { const uint32_t a = cnt_gt[b], c = cnt_eq[b]; cnt_gt[b] = g; cnt_eq[b] = e; g += a; e += c; }
+  int64_t b0, b1;
+  scan_run<1024>(nb, b0, b1);
+  uint32_t p[2] = {0, 0}, tot[2];                     // above, equal
+  for (int64_t b = b0; b < b1; ++b) { p[0] += cnt_gt[b]; p[1] += cnt_eq[b]; }
+  block_exclusive_scan<1024>(p, tot);
+  for (int64_t b = b0; b < b1; ++b) { const uint32_t a = cnt_gt[b], c = cnt_eq[b]; cnt_gt[b] = p[0]; cnt_eq[b] = p[1]; p[0] += a; p[1] += c; }
 }
 // output position of a selected key = (# keys above T before it) + min(# keys equal to T before it, need_eq)
 __global__ void __launch_bounds__(256) k_sel_write(const float* keys, int64_t n, const SelState* st, const uint32_t* off_gt,
                                                    const uint32_t* off_eq, int64_t k, int64_t* out_idx) {
-  __shared__ uint32_t sg[256], se[256];
   keys += (int64_t)blockIdx.y * n; st += blockIdx.y; off_gt += (size_t)blockIdx.y * gridDim.x; off_eq += (size_t)blockIdx.y * gridDim.x;
   out_idx += (int64_t)blockIdx.y * k;
   const uint32_t T = st->prefix, need_eq = st->remaining;
   const int t = threadIdx.x;
   const int64_t base = (int64_t)blockIdx.x * SEL_PER_BLOCK + 4 * t;
-  uint32_t u[4], g = 0, e = 0;
+  uint32_t u[4], p[2] = {0, 0}, tot[2];               // keys above T, equal to T
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     u[j] = base + j < n ? key_bits(keys[base + j]) : 0u;
-    if (base + j < n) { g += u[j] > T; e += u[j] == T; }
+    if (base + j < n) { p[0] += u[j] > T; p[1] += u[j] == T; }
   }
-  sg[t] = g; se[t] = e;
-  __syncthreads();
-  if (t == 0) {      // 256-entry exclusive scan (tiny next to the key reads)
-    uint32_t rg = off_gt[blockIdx.x], re = off_eq[blockIdx.x];
-    for (int i = 0; i < 256; ++i) { const uint32_t a = sg[i], c = se[i]; sg[i] = rg; se[i] = re; rg += a; re += c; }
-  }
-  __syncthreads();
-  g = sg[t]; e = se[t];
+  block_exclusive_scan<256>(p, tot);
+  uint32_t g = off_gt[blockIdx.x] + p[0], e = off_eq[blockIdx.x] + p[1];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (base + j >= n) break;

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include "../../include/afx.h"
 #include "afx_internal.h"
+#include "afx_scan.h"
 
 // every product and sum below is rounded on its own (the vertex positions and the measures are defined operation by operation)
 #pragma clang fp contract(off)
@@ -118,11 +119,10 @@ __device__ __forceinline__ int iso_tet_bits(uint32_t in, int codes) {
 // threads overlap: they are served by the L2 (the volume is read about once from HBM).
 __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(const float* __restrict__ f, int n0, int n1, int n2, float iso, int none,
                                                             IsoBufs b) {
-  __shared__ uint32_t wsum[ISO_ITERS][ISO_BLOCK / 64];
   __shared__ uint32_t wfb[ISO_BLOCK / 64][3];
   const uint32_t total = (uint32_t)n0 * (uint32_t)n1 * (uint32_t)n2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t cnt[ISO_ITERS], inc[ISO_ITERS];
+  uint32_t cnt[ISO_ITERS], sum[ISO_ITERS];            // per pass: the point's packed counts, then those before it in the pass; the pass's sum
   uint32_t faces = 0, bfaces = 0, n22 = 0;
 #pragma unroll
   for (int i = 0; i < ISO_ITERS; ++i) {
@@ -159,14 +159,6 @@ __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(const float* __restr
       }
       cnt[i] = (uint32_t)__popc(mask) | (nt << 16);
     }
-    uint32_t s = cnt[i];                              // the wave's inclusive prefix
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t u = __shfl_up(s, d);
-      if (lane >= d) s += u;
-    }
-    inc[i] = s;
-    if (lane == 63) wsum[i][wave] = s;
   }
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
@@ -175,19 +167,17 @@ __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(const float* __restr
     n22 += __shfl_down(n22, d);
   }
   if (lane == 0) { wfb[wave][0] = faces; wfb[wave][1] = bfaces; wfb[wave][2] = n22; }
-  __syncthreads();
+  afx::block_exclusive_scan<ISO_BLOCK>(cnt, sum);     // (its barriers also publish wfb)
   uint32_t run = 0;
 #pragma unroll
   for (int i = 0; i < ISO_ITERS; ++i) {
-    uint32_t before = run;
-    for (int w = 0; w < wave; ++w) before += wsum[i][w];
     const uint32_t v = blockIdx.x * ISO_CHUNK + i * ISO_BLOCK + threadIdx.x;
     if (v < total) {
-      const uint32_t ex = before + inc[i] - cnt[i];
+      const uint32_t ex = run + cnt[i];
       b.vpre[v] = (uint16_t)(ex & 0xffffu);
       b.tpre[v] = (uint16_t)(ex >> 16);
     }
-    run += wsum[i][0] + wsum[i][1] + wsum[i][2] + wsum[i][3];
+    run += sum[i];
   }
   if (threadIdx.x == 0) {
     b.cv[blockIdx.x] = run & 0xffffu;
@@ -198,39 +188,20 @@ __global__ void __launch_bounds__(ISO_BLOCK) k_iso_classify(const float* __restr
   }
 }
 
-// the workgroup's exclusive prefix of x (Hillis-Steele in LDS); *sum = the total
-__device__ __forceinline__ unsigned long long iso_block_scan(unsigned long long x, unsigned long long* sh, unsigned long long* sum) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  sh[t] = x;
-  __syncthreads();
-  for (int d = 1; d < ISO_SCAN; d <<= 1) {
-    const unsigned long long u = t >= d ? sh[t - d] : 0ull;
-    __syncthreads();
-    sh[t] += u;
-    __syncthreads();
-  }
-  *sum = sh[ISO_SCAN - 1];
-  return sh[t] - x;
-}
-
 // one workgroup: voff[] / toff[] = the exclusive scans of cv[] / ct[] (64-bit: 7 * 2^30 vertices do not fit 32), and the record
 __global__ void __launch_bounds__(ISO_SCAN) k_iso_scan(IsoBufs b, uint32_t nb, unsigned long long max_vertices, unsigned long long max_triangles,
                                                        unsigned long long* __restrict__ rec) {
-  __shared__ unsigned long long sh[ISO_SCAN];
-  const uint32_t t = threadIdx.x, per = (nb + ISO_SCAN - 1) / ISO_SCAN, b0 = min(t * per, nb), b1 = min(b0 + per, nb);
-  unsigned long long sv = 0, st = 0, sf = 0, sb = 0, s22 = 0;
-  for (uint32_t k = b0; k < b1; ++k) { sv += b.cv[k]; st += b.ct[k]; sf += b.cf[k]; sb += b.cb[k]; s22 += b.c22[k]; }
-  unsigned long long V, T, F, B, N22;
-  unsigned long long pv = iso_block_scan(sv, sh, &V), pt = iso_block_scan(st, sh, &T);
-  iso_block_scan(sf, sh, &F);
-  iso_block_scan(sb, sh, &B);
-  iso_block_scan(s22, sh, &N22);
+  uint32_t b0, b1;
+  afx::scan_run<ISO_SCAN>(nb, b0, b1);
+  unsigned long long p[5] = {0, 0, 0, 0, 0}, tot[5];  // vertices, triangles, crossed faces, boundary faces, 2-2 tetrahedra
+  for (uint32_t k = b0; k < b1; ++k) { p[0] += b.cv[k]; p[1] += b.ct[k]; p[2] += b.cf[k]; p[3] += b.cb[k]; p[4] += b.c22[k]; }
+  afx::block_exclusive_scan<ISO_SCAN>(p, tot);
   for (uint32_t k = b0; k < b1; ++k) {
-    b.voff[k] = pv; pv += b.cv[k];
-    b.toff[k] = pt; pt += b.ct[k];
+    b.voff[k] = p[0]; p[0] += b.cv[k];
+    b.toff[k] = p[1]; p[1] += b.ct[k];
   }
-  if (t == 0) {
+  if (threadIdx.x == 0) {
+    const unsigned long long V = tot[0], T = tot[1], F = tot[2], B = tot[3], N22 = tot[4];
     rec[ISO_V] = V; rec[ISO_T] = T; rec[ISO_E] = F + N22; rec[ISO_B] = B; rec[ISO_22] = N22;
     rec[ISO_STATUS] = (V > max_vertices ? 1ull : 0ull) | (T > max_triangles ? 2ull : 0ull);
     rec[6] = 0; rec[7] = 0;

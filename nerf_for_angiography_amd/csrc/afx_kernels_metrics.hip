@@ -11,6 +11,7 @@
 #include <algorithm>
 #include "../../include/afx.h"
 #include "afx_internal.h"
+#include "afx_scan.h"
 
 // After the includes: vol_sample (afx_internal.h) keeps the contraction rules k_project_volume is compiled with.
 #pragma clang fp contract(off)
@@ -565,33 +566,12 @@ __global__ void __launch_bounds__(CC_BLOCK) k_cc_flatten(const uint32_t* __restr
 
 // one workgroup: count[nb] becomes its own exclusive scan (the roots before each chunk); st->k = the total, K
 __global__ void __launch_bounds__(1024) k_cc_scan(uint32_t* count, uint32_t nb, CcState* st) {
-  __shared__ uint32_t ws_[16];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const uint32_t per = (nb + 1023) / 1024, b0 = min((uint32_t)t * per, nb), b1 = min(b0 + per, nb);
-  uint32_t s = 0;
-  for (uint32_t b = b0; b < b1; ++b) s += count[b];
-  uint32_t is = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(is, d);
-    if (lane >= d) is += v;
-  }
-  if (lane == 63) ws_[wave] = is;
-  __syncthreads();
-  if (wave == 0) {
-    uint32_t a = lane < 16 ? ws_[lane] : 0;
-    const uint32_t a0 = a;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
-      const uint32_t v = __shfl_up(a, d);
-      if (lane >= d) a += v;
-    }
-    if (lane < 16) ws_[lane] = a - a0;      // exclusive
-  }
-  __syncthreads();
-  uint32_t p = ws_[wave] + is - s;          // the roots before this thread's chunks
-  for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = count[b]; count[b] = p; p += c; }
-  if (t == 1023) st->k = p;
+  uint32_t b0, b1, p[1] = {0}, tot[1];
+  afx::scan_run<1024>(nb, b0, b1);
+  for (uint32_t b = b0; b < b1; ++b) p[0] += count[b];
+  afx::block_exclusive_scan<1024>(p, tot);            // p: the roots before this thread's chunks
+  for (uint32_t b = b0; b < b1; ++b) { const uint32_t c = count[b]; count[b] = p[0]; p[0] += c; }
+  if (threadIdx.x == 1023) st->k = tot[0];
 }
 
 // Rank: the label of a root is 1 + the number of roots before it in raster order = 1 + pre[chunk] + the roots before it in its chunk

@@ -1,7 +1,8 @@
 """The inputs of the many-chunk tests (tests/test_many_chunks_cpu.py, tests/test_gpu_many_chunks.py): the smallest problems at which the
 two-level scans of the compaction, labelling and selection kernels hold MORE THAN 1024 PARTIALS, so that each of the 1024 threads of the
 scanning workgroup walks a run of per = ceil(nb / 1024) > 1 of them (k_cc_scan, k_cg_scan_chunks, k_iso_scan, k_sel_offsets,
-k_grid_occ_scan; the chunked init and mark launches of the thinning).  Not a test module.
+k_grid_occ_scan; the chunked init and mark launches of the thinning), and, kept apart, the cases at exactly 1024 and 1025 partials of
+tests/test_gpu_scan_boundary.py and tests/test_scan_boundary_cpu.py.  Not a test module.
 
 Every volume is sparse - three thin capsules from corner to corner, single-voxel specks at density 0.001, the first and the last voxel -
 so that the host references stay at a second per call, yet nearly every chunk holds components, end points and one-voxel branches of its
@@ -30,6 +31,12 @@ GRID_DENSITY = 0.02
 GRID_FEW = 1500                                  # occupied cells of the second mask: fewer than either n_draw
 GRID_DRAWS = (4096, GRID_RES[0] * GRID_RES[1] * GRID_RES[2] // 4)
 SAMPLER_SIZES = (1_050_001, 2_100_001)           # 1 026 chunks (per = 2); 2 051 chunks (per = 3, the last run short)
+
+# The cases of tests/test_gpu_scan_boundary.py, AT the boundary: exactly 1024 partials (per = 1, no scanning thread idle) and 1025 (per = 2,
+# the threads from 513 on have empty runs).  Kept apart from VOLUMES and SAMPLER_SIZES, whose entries all exceed 1024 partials.
+BOUNDARY_SHAPES = ((128, 128, 128), (4, 513, 1023))       # 1 024 chunks of 2048; 1 025, the last one ragged (no side may exceed 1024)
+BOUNDARY_SAMPLER_SIZES = (1024 * 1024, 1024 * 1024 + 1)   # 1 024 and 1 025 blocks of SEL_PER_BLOCK keys
+BOUNDARY_RAY_COUNTS = (1023, 1024, 1025, 2049)            # the offsets kernel scans one partial per ray: per = 1, 1, 2 and 3
 
 
 def _ceil_div(a, b):
@@ -84,10 +91,14 @@ def capsule(shape, a, b, r):
     return sum((g[q] - a[q] - t * d[q]) ** 2 for q in range(3)) <= r * r
 
 
-@functools.lru_cache(maxsize=None)
 def volume(name):
     """The sparse boolean volume `name` of VOLUMES (read-only; built once per process)."""
-    shape = VOLUMES[name]
+    return sparse_volume(VOLUMES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def sparse_volume(shape):
+    """Capsules along three diagonals, specks, the first and the last voxel, in a volume of `shape` (read-only; built once per process)."""
     hi = [s - 1 for s in shape]
     m = np.random.default_rng(sum(shape)).random(shape) < SPECK_DENSITY
     for a, b in (((0, 0, 0), hi), ((0, hi[1], 0), (hi[0], 0, hi[2])), ((hi[0], 0, 0), (0, hi[1], hi[2]))):      # three of the four diagonals
