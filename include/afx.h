@@ -1182,6 +1182,56 @@ size_t afx_tv_denoise_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
 int afx_tv_denoise_3d(const double* x, int32_t n0, int32_t n1, int32_t n2, double weight, double tau, int32_t iterations, int32_t nonneg,
                       const uint8_t* mask /* may be NULL */, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Optimal C-arm views: how much of each branch of a vessel tree a view foreshortens, and how much of it lies under another branch.
+ * The tree is a list of capsules (the segments of the centreline polylines with the lumen radius); a view is a record of
+ * afx_visual_hull.  All arithmetic is fp64, every operation rounded on its own (no contraction), only + - * / sqrt and comparisons, in
+ * the order written; every comparison with a NaN is false.  tests/viewmap_reference.py restates it in NumPy and the device equals the
+ * restatement exactly: the integer outputs are counts, and the two floating-point sums have one order.
+ *   Inputs.  segments: double [N][AFX_VIEWMAP_SEGMENT_DOUBLES] on the device: p0 at [0..2], p1 at [3..5], the radius r >= 0 at [6], [7]
+ *      unused.  seg_branch: int32 [N] on the device, the 1-based branch ids, non-decreasing (the segments of a branch are contiguous),
+ *      seg_branch[N - 1] = B = n_branches, 1 <= B <= 65535 (an id that no segment carries is a branch with no segment: area 0, proj +0).
+ *      views: double [V][AFX_HULL_VIEW_DOUBLES] on the device, 1 <= V <= 65535.  width W and height H in 1..16384, common to the views.
+ *   Projection of a point p in view v (the hull's operations in the hull's order; pixel centres at the integers):
+ *      e = p - c;  q_n = (R[0][n] e_0 + R[1][n] e_1) + R[2][n] e_2;  d = -q_2;  u = W / 2 + (f q_0) / d;  w = H / 2 - (f q_1) / d
+ *   Visibility.  A segment is visible in v iff d0 > 0 && d1 > 0 (its two ends).  Its 2-D capsule: a = (u0, w0), b = (u1, w1),
+ *      rho = (f r) / (0.5 (d0 + d1)).
+ *   Coverage of pixel (iu, iw) by a visible segment:
+ *      g = b - a;  g2 = g_x g_x + g_y g_y;  h = (iu, iw) - a;  t = g2 > 0 ? (h_x g_x + h_y g_y) / g2 : 0;  t < 0: t = 0;  t > 1: t = 1
+ *      e = h - t g;  covered iff e_x e_x + e_y e_y <= rho rho
+ *   Outputs per view, integers (given together or not at all):
+ *      count  uint16 [V][H][W]   the number of distinct branches with at least one covering visible segment
+ *      area   int32 [V][B]       the pixels branch b covers
+ *      shared int32 [V][B]       those of them with count >= 2
+ *      tree   int32 [V][AFX_VIEWMAP_TREE_SLOTS]   [UNION] the pixels with count >= 1, [MULTI] those with count >= 2, [INVISIBLE] the
+ *             segments that are not visible; tree[0][BAD] != 0: seg_branch is not what is stated above (an id outside 1..B, a
+ *             decreasing one, or a last one other than B - such segments cover nothing and the other numbers mean nothing); checked on
+ *             the device by a launch of its own, the caller reads the flag with the results.
+ *   Foreshortening (optional outputs; either, both or neither).  For segment s in view v:
+ *      l = p1 - p0;  e = (p0 - c) + (p1 - c);  n2 = (e_0 e_0 + e_1 e_1) + e_2 e_2;  le = (l_0 e_0 + l_1 e_1) + l_2 e_2;
+ *      l2 = (l_0 l_0 + l_1 l_1) + l_2 l_2;  perp2 = l2 - (le le) / n2;  perp = sqrt(perp2 > 0 ? perp2 : 0)
+ *      proj double [V][B] = the sum of perp over the branch's segments in segment order, from +0;  length double [B] = the same sum of
+ *      sqrt(l2).  perp is the segment's length seen at right angles to the ray through its midpoint: a segment that points at the
+ *      source projects to 0.  Foreshortening of b in v = 1 - proj / length, overlap = shared / area: taken on the host.
+ *   Known bias.  Branches that meet at a junction always share a few pixels around it; the amount is nearly the same in every view,
+ *      so the ranking of views survives it.  Branch ends are not trimmed.
+ * Launches: one that zeroes area, shared and tree (the caller zeroes nothing), the check of seg_branch, the raster (a workgroup a
+ * 16 x 16 pixel tile of one view; segments culled per tile by their box padded by rho + 1 pixel; flag AFX_VIEWMAP_BRUTE
+ * switches the cull off and the bytes stay the same) and the foreshortening (a lane per view and branch).  Integer atomicAdd only: the
+ * result does not depend on any order.  Nothing is allocated or read back: the call can be captured in a graph.
+ * AFX_E_INVALID before any launch, the message naming the argument: null segments, seg_branch or views; some but not all of count,
+ * area, shared and tree; no output at all; n_views or n_branches outside 1..65535; n_segments outside 1..2^30; width or height outside
+ * 1..16384; unknown flags; a pointer that is not memory of the current device. */
+#define AFX_VIEWMAP_SEGMENT_DOUBLES 8
+#define AFX_VIEWMAP_BRUTE 1u
+#define AFX_VIEWMAP_TREE_SLOTS 4
+#define AFX_VIEWMAP_TREE_UNION 0
+#define AFX_VIEWMAP_TREE_MULTI 1
+#define AFX_VIEWMAP_TREE_INVISIBLE 2
+#define AFX_VIEWMAP_TREE_BAD 3
+int afx_view_map(const double* segments, const int32_t* seg_branch, int32_t n_segments, int32_t n_branches, const double* views,
+                 int32_t n_views, int32_t width, int32_t height, uint32_t flags, uint16_t* count, int32_t* area, int32_t* shared,
+                 int32_t* tree, double* proj /* may be NULL */, double* length /* may be NULL */, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

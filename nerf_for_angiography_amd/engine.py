@@ -2164,6 +2164,208 @@ def grid_apply_mask(roi_aabb, resolution, mask_u8, occs, binary_u8, bits):
                "afx_grid_apply_mask")
 
 
+# ---- optimal C-arm views: the foreshortening and overlap map of a vessel tree (afx_view_map) ----
+VIEWMAP_SEGMENT_DOUBLES = 8
+VIEWMAP_BRUTE = 1
+VIEWMAP_TREE_SLOTS = 4
+VIEWMAP_COUNT_BYTES = 256 << 20      # view_map keeps the count buffer of a chunk of views below this
+
+
+def view_map_segments(points, offsets, radius):
+    """The capsules of polylines -> (segments float64 [N, 8], seg_branch int32 [N]) in NumPy on the host, the inputs of afx_view_map:
+    points [P, 3] and offsets [B + 1] as `centreline_world_points` gives them, radius [P] (or one number).  A branch's consecutive points
+    i, i + 1 make the segment p0, p1 with r = 0.5 (r_i + r_i+1); a one-point branch becomes one degenerate segment (p0 = p1, r = r_i: a
+    disc); a branch without points has no segment.  Branch ids are 1-based and non-decreasing."""
+    import numpy as np
+    pts = np.asarray(points, np.float64).reshape(-1, 3)
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    r = np.asarray(radius, np.float64).reshape(-1)
+    if r.size == 1:
+        r = np.broadcast_to(r, (pts.shape[0],))
+    if off.size < 2 or off[0] != 0 or off[-1] != pts.shape[0] or (off[1:] < off[:-1]).any():
+        raise ValueError(f"view_map_segments: offsets must rise from 0 to the number of points ({pts.shape[0]}), got {off.tolist()[:8]}...")
+    if r.shape[0] != pts.shape[0]:
+        raise ValueError(f"view_map_segments: one radius per point ({pts.shape[0]}) or one number, got {r.shape[0]}")
+    first, last, ids = [], [], []
+    for b in range(off.size - 1):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if hi - lo == 1:
+            first.append(lo), last.append(lo), ids.append(b + 1)
+        for i in range(lo, hi - 1):
+            first.append(i), last.append(i + 1), ids.append(b + 1)
+    i0, i1 = np.asarray(first, np.int64), np.asarray(last, np.int64)
+    seg = np.zeros((i0.size, VIEWMAP_SEGMENT_DOUBLES), np.float64)
+    seg[:, 0:3], seg[:, 3:6], seg[:, 6] = pts[i0], pts[i1], 0.5 * (r[i0] + r[i1])
+    return seg, np.asarray(ids, np.int32)
+
+
+def view_angles_records(angles, src_pt, focal, translation=(0.0, 0.0, 0.0)):
+    """The view records (`hull_view_records`, float64 [V, 16] on the host) of (theta, phi) pairs in degrees: the poses
+    source_matrix(src_pt, theta mod 360, phi mod 360, 0, translation) of the evaluation sweep."""
+    import numpy as np
+    from .phantomdata.proj_helpers import source_matrix
+    mats = []
+    for theta, phi in np.asarray(angles, np.float64).reshape(-1, 2):
+        th = theta if theta >= 0 else 360 + theta
+        ph = phi if phi >= 0 else 360 + phi
+        mats.append(source_matrix(np.asarray(src_pt, dtype=np.float64), th, ph, 0.0, np.asarray(translation, dtype=np.float64)))
+    return hull_view_records(np.stack(mats), focal)
+
+
+def _view_map_inputs(segments, seg_branch, views, who: str):
+    """The three inputs on one GPU, checked: NumPy arrays are uploaded to the device of whichever input is a device tensor (else the
+    current GPU); a seg_branch given on the host is checked here, one on the device by the library's own launch."""
+    import numpy as np
+    given = [t for t in (segments, seg_branch, views) if isinstance(t, torch.Tensor)]
+    if any(t.device.type != "cuda" for t in given) or (not given and not torch.cuda.is_available()):
+        raise AfxError(f"{who}: the view map is taken on a GPU; there is no CPU path")
+    dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(seg_branch, torch.Tensor):
+        br = np.asarray(seg_branch)
+        if br.ndim != 1 or br.size < 1 or int(br.min()) < 1 or (br[1:] < br[:-1]).any():
+            raise ValueError(f"{who}: seg_branch must be a non-empty, non-decreasing list of branch ids >= 1")
+        seg_branch = torch.from_numpy(np.ascontiguousarray(br, np.int32)).to(dev)
+    up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
+    segments, views = up(segments), up(views)
+    n = seg_branch.numel()
+    if segments.dtype != torch.float64 or not segments.is_contiguous() or tuple(segments.shape) != (n, VIEWMAP_SEGMENT_DOUBLES) or segments.device != dev:
+        raise ValueError(f"{who}: segments must be contiguous float64 [{n}, {VIEWMAP_SEGMENT_DOUBLES}] on {dev}")
+    if seg_branch.dtype != torch.int32 or not seg_branch.is_contiguous() or seg_branch.dim() != 1 or seg_branch.device != dev:
+        raise ValueError(f"{who}: seg_branch must be contiguous int32 [N] on {dev}")
+    if views.dtype != torch.float64 or not views.is_contiguous() or views.dim() != 2 or views.shape[1] != HULL_VIEW_DOUBLES or views.device != dev:
+        raise ValueError(f"{who}: views must be contiguous float64 [V, {HULL_VIEW_DOUBLES}] on {dev}")
+    return segments, seg_branch, views
+
+
+def view_map_record(segments, seg_branch, views, width: int, height: int, brute: bool = False, counts: bool = True, foreshortening: bool = True,
+                    n_branches=None, out=None) -> dict:
+    """afx_view_map, the launches alone -> the raw device tensors dict(count uint16 [V, H, W], area int32 [V, B], shared int32 [V, B],
+    tree int32 [V, 4] (union, multi, n_invisible; tree[0][3] != 0: a bad seg_branch) with counts; proj float64 [V, B], length float64 [B]
+    with foreshortening) of segments [N, 8], seg_branch [N] (`view_map_segments`) and view records [V, 16] (`hull_view_records`,
+    `view_angles_records`), each a NumPy array or a device tensor.  n_branches: B, by default the last branch id (read on the host; pass
+    it with device inputs to read nothing back).  brute: no culling, the same bytes.  out: a dict of buffers to fill instead of
+    allocating; with device inputs, n_branches and out the call reads nothing back, allocates nothing and can be captured in a graph."""
+    lib = _lib.load()
+    if n_branches is None and not isinstance(seg_branch, torch.Tensor):
+        import numpy as np
+        n_branches = int(np.asarray(seg_branch).reshape(-1)[-1]) if np.size(seg_branch) else 0
+    segments, seg_branch, views = _view_map_inputs(segments, seg_branch, views, "view_map_record")
+    if n_branches is None:
+        n_branches = int(seg_branch[-1])
+    dev = segments.device
+    n, v, b, w, h = seg_branch.numel(), views.shape[0], int(n_branches), int(width), int(height)
+    if not (counts or foreshortening):
+        raise ValueError("view_map_record: counts and foreshortening are both off: nothing to compute")
+    ok = 1 <= b <= 65535 and 1 <= v <= 65535 and 1 <= w <= 16384 and 1 <= h <= 16384      # else one-element buffers: the library names the offender
+    want = {}
+    if counts:
+        want.update(count=((v, h, w), torch.uint16), area=((v, b), torch.int32), shared=((v, b), torch.int32),
+                    tree=((v, VIEWMAP_TREE_SLOTS), torch.int32))
+    if foreshortening:
+        want.update(proj=((v, b), torch.float64), length=((b,), torch.float64))
+    res = {}
+    for name, (shape, dtype) in want.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape if ok else (1,), dtype=dtype, device=dev)
+        elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"view_map_record: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
+        res[name] = t
+    _lib.check(lib.afx_view_map(_ptr(segments), _ptr(seg_branch), n, b, _ptr(views), v, w, h, VIEWMAP_BRUTE if brute else 0, _ptr(res.get("count")),
+                                _ptr(res.get("area")), _ptr(res.get("shared")), _ptr(res.get("tree")), _ptr(res.get("proj")), _ptr(res.get("length")),
+                                Engine._stream(dev)), "afx_view_map")
+    return res
+
+
+def view_map(graph_or_segments, views, width: int, height: int, radius=None, chunk_views=None, index_to_world=None, d2=None, voxel_size=1.0,
+             return_count: bool = False) -> dict:
+    """The foreshortening and overlap of every branch of a vessel tree in every view (include/afx.h: afx_view_map) -> dict of NumPy
+    arrays on the host: foreshortening [V, B] = 1 - proj / length (0: seen at right angles, 1: seen end on), overlap [V, B] = shared /
+    area (the share of the branch's pixels that another branch covers too; NaN where area == 0), tree_foreshortening [V] = 1 - sum proj
+    / sum length, tree_overlap [V] = multi / union (NaN for an empty union), area, shared (int32 [V, B]), union, multi, n_invisible
+    (int32 [V]), proj [V, B], length [B], n_segments, and with return_count count (uint16 [V, H, W]).
+
+    graph_or_segments: (segments, seg_branch) of `view_map_segments`, or a `centreline_graph` result - then the points are
+    `centreline_world_points(graph, index_to_world)` and the radii `radius` (one per path voxel or one number, e.g. a lumen profile's
+    r_mean) or, by default, voxel_size x sqrt(d2) at the path voxels (d2: the squared EDT the graph was made with).  views: records
+    [V, 16].  The views are taken in chunks of chunk_views (default: as many as keep the count buffer below 256 MiB).  Branches that
+    meet at a junction always share a few pixels around it, in every view alike.  There is no CPU path (AfxError)."""
+    import numpy as np
+    if isinstance(graph_or_segments, dict):
+        graph = graph_or_segments
+        points, offsets = centreline_world_points(graph, _affine12(index_to_world, "view_map"))
+        if radius is None:
+            if d2 is None:
+                raise ValueError("view_map: a centreline graph needs radius= or d2= (the squared EDT the graph was made with)")
+            vox = graph["path_voxels"].cpu().numpy().astype(np.int64)
+            dd = (d2.reshape(-1).cpu().numpy().astype(np.int64) & 0xffffffff)[vox]
+            radius = np.sqrt(dd.astype(np.float64)) * float(voxel_size)
+        segments, seg_branch = view_map_segments(points, offsets, radius)
+        n_branches = offsets.size - 1
+    else:
+        segments, seg_branch = graph_or_segments
+        n_branches = int(seg_branch[-1]) if len(seg_branch) else 0
+    if len(seg_branch) == 0:
+        raise ValueError("view_map: the tree has no segment")
+    segments, seg_branch, views = _view_map_inputs(segments, seg_branch, views, "view_map")
+    v, w, h = views.shape[0], int(width), int(height)
+    if chunk_views is None:
+        chunk_views = max(1, VIEWMAP_COUNT_BYTES // max(2 * w * h, 1))
+    chunk_views = max(1, min(int(chunk_views), v))
+    parts = []
+    for v0 in range(0, v, chunk_views):
+        res = view_map_record(segments, seg_branch, views[v0:v0 + chunk_views], w, h, n_branches=n_branches)
+        keep = ("area", "shared", "tree", "proj", "length") + (("count",) if return_count else ())
+        parts.append({k: res[k].cpu().numpy() if k != "count" else res[k].view(torch.int16).cpu().numpy().view(np.uint16) for k in keep})
+    raw = {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0] if k != "length"}
+    raw["length"] = parts[0]["length"]
+    if raw["tree"][:, 3].any():
+        raise ValueError("view_map: seg_branch is not a non-decreasing list of branch ids 1..B ending in B")
+    out = view_map_derive(raw)
+    out["n_segments"] = int(seg_branch.numel())
+    return out
+
+
+def view_map_derive(raw: dict) -> dict:
+    """The host's figures from the read-back outputs of afx_view_map (area, shared, tree, proj, length[, count] as NumPy arrays): what
+    `view_map` returns.  fp64 on the host."""
+    import numpy as np
+    area, shared, tree, proj, length = raw["area"], raw["shared"], raw["tree"], raw["proj"], raw["length"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = dict(foreshortening=1.0 - proj / length[None],
+                   overlap=np.where(area > 0, shared.astype(np.float64) / area.astype(np.float64), np.nan),
+                   tree_foreshortening=1.0 - proj.sum(axis=1) / length.sum(),
+                   tree_overlap=np.where(tree[:, 0] > 0, tree[:, 1].astype(np.float64) / tree[:, 0].astype(np.float64), np.nan))
+    out.update(area=area, shared=shared, union=tree[:, 0].copy(), multi=tree[:, 1].copy(), n_invisible=tree[:, 2].copy(), proj=proj, length=length)
+    if "count" in raw:
+        out["count"] = raw["count"]
+    return out
+
+
+def optimal_views(vmap: dict, branch=None, overlap_weight: float = 1.0, k: int = 5):
+    """The k best views of a `view_map` result -> (indices int64 [k'], scores float64 [k']), k' = min(k, V), best first.  The score of a
+    view is foreshortening + overlap_weight x overlap - of branch `branch` (1-based), or of the whole tree (branch None) - lower is
+    better.  Views whose score is not a number (the branch covers no pixel there: area == 0, overlap NaN) or in which a segment of the
+    tree is invisible come last, among themselves by index, with the score NaN; ties go to the lower index.  Host arithmetic."""
+    import numpy as np
+    if branch is None:
+        fs, ov = np.asarray(vmap["tree_foreshortening"], np.float64), np.asarray(vmap["tree_overlap"], np.float64)
+    else:
+        nb = np.asarray(vmap["foreshortening"]).shape[1]
+        if not 1 <= int(branch) <= nb:
+            raise ValueError(f"optimal_views: branch {branch} outside 1..{nb}")
+        fs, ov = np.asarray(vmap["foreshortening"], np.float64)[:, int(branch) - 1], np.asarray(vmap["overlap"], np.float64)[:, int(branch) - 1]
+    with np.errstate(invalid="ignore"):
+        score = fs + float(overlap_weight) * ov
+    bad = ~np.isfinite(score)
+    if "n_invisible" in vmap:
+        bad = bad | (np.asarray(vmap["n_invisible"]) > 0)
+    score = np.where(bad, np.nan, score)
+    order = np.lexsort((np.arange(score.size), np.where(bad, 0.0, score), bad))      # the last key is the first criterion
+    order = order[:max(0, min(int(k), score.size))].astype(np.int64)
+    return order, score[order]
+
+
 # ---- sparse-view algebraic reconstruction: the ray-driven projector (afx_xray_project), the voxel-driven backprojector
 # (afx_xray_backproject) and the SIRT iteration made of the two ----
 def line_integrals(images, eps: float = 1e-6) -> torch.Tensor:

@@ -132,6 +132,13 @@ def build_parser():
                         'centreline of --save_centreline at --mesh_threshold, and at each of its points the area and the diameters of the '
                         'cross-section of the density grid at that level (afx_lumen_profile: 64 rays in the plane normal to the centreline, '
                         'crossings interpolated below the voxel), one row per point; without the flag nothing changes')
+    p.add_argument('--save_view_map', default=None, metavar='PATH',
+                   help='after training, write the foreshortening and overlap map of the final model\'s vessel centreline to PATH (.csv): the '
+                        'pruned centreline of --save_centreline at --mesh_threshold with its radii, scored over the evaluation sweep\'s angles '
+                        '(--limited_size, --view_map_step) on the test view\'s detector (afx_view_map), one row per angle: theta, phi, '
+                        'tree_foreshortening, tree_overlap, then foreshortening and overlap of every branch; the five best whole-tree views are '
+                        'printed; without the flag nothing changes')
+    p.add_argument('--view_map_step', type=float, default=5.0, metavar='DEGREES', help='--save_view_map: the step of the angle grid')
     p.add_argument('--grid_init', default=None, choices=['hull'],
                    help='hull (--march grid or grid_ops, --binary True): before training, carve both occupancy grids with the visual hull of '
                         'the training views - a cell stays only where no training view\'s vessel silhouette (pixel_value < --hull_threshold) '
@@ -248,6 +255,13 @@ def check_args(args):
             raise ValueError("--save_lumen: PATH must end in .csv")
         if not args.mesh_threshold > 0:
             raise ValueError("--mesh_threshold: needs SIGMA > 0")
+    if args.save_view_map is not None:
+        if os.path.splitext(args.save_view_map)[1].lower() != '.csv':
+            raise ValueError("--save_view_map: PATH must end in .csv")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
+        if not (args.view_map_step > 0 and np.isfinite(args.view_map_step)):
+            raise ValueError("--view_map_step: needs DEGREES > 0")
 
 
 def checkpoint_interval(checkpoint_every: int, graph_rounds: bool, round_len: int = 16) -> int:
@@ -568,11 +582,16 @@ def main(argv=None):
     exports = (('mesh_info', save_mesh, args.save_mesh), ('centreline_info', save_centreline, args.save_centreline),
                ('lumen_info', save_lumen, args.save_lumen))
     exports = [e for e in exports if e[2] is not None]
-    if exports:      # the density grid the exports read, evaluated once
+    if exports or args.save_view_map is not None:      # the density grid the exports read, evaluated once
         from ..render import density_grid
         grid = density_grid(coarse_model, outside, depth_samples_per_ray_coarse)
     for key, save, path in exports:
         result[key] = save(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, path, grid=grid)
+    if args.save_view_map is not None:
+        from ..visualization.sweep import sweep_angles
+        result['view_map_info'] = save_view_map(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_view_map,
+                                                sweep_angles(limited_size, args.view_map_step), img_width, img_height,
+                                                float(proj_df['focal_length'].iloc[0]), (0.0, 0.0, src_pt_z), grid=grid)
     if args.save_sirt is not None:
         mask = acc_grid._carve_u8 if acc_grid is not None and args.grid_init == 'hull' else None      # the hull the grids were carved with
         result['sirt_info'] = save_sirt(proj_df, train_ray_df, test_proj_id, [-outside] * 3 + [outside] * 3, 128, near_thresh, far_thresh,
@@ -764,6 +783,43 @@ def save_lumen(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
     info = dict(path=str(path), n_points=n_points, n_valid=int((host['flags'] == 0).sum()), max_area_stenosis=worst[0], branch=worst[1],
                 threshold=float(threshold))
     print('lumen', info, flush=True)
+    return info
+
+
+def save_view_map(model, outside, n, threshold, path, angles, width, height, focal, src_pt, prune_factor=1.0, grid=None, k=5):
+    """--save_view_map: the foreshortening and overlap (`engine.view_map`: afx_view_map) of the pruned centreline of {sigma >= threshold} on
+    the model's density grid (that of --save_centreline, radii voxel x sqrt(d2)) over `angles` [V, 2] posed as the evaluation sweep poses
+    them, on a width x height detector; one CSV row per angle (theta, phi, tree_foreshortening, tree_overlap, then
+    foreshortening_b and overlap_b of every branch b; numbers written with repr) -> its info (path, n_views, n_branches, n_segments,
+    threshold, best: the k best whole-tree views as (theta, phi, score) by `engine.optimal_views`).  A centreline without a point writes
+    NaN in the two whole-tree columns.  grid: as in `save_mesh`."""
+    from ..engine import optimal_views, view_angles_records, view_map
+    tree, a = _export_tree(_export_grid(model, outside, n, grid), outside, n, threshold, prune_factor)
+    angles = np.asarray(angles, np.float64).reshape(-1, 2)
+    nb = int(tree['graph']['n_branches']) if int(tree['graph']['path_voxels'].numel()) else 0
+    vm = None
+    if nb:
+        vm = view_map(tree['graph'], view_angles_records(angles, src_pt, focal), int(width), int(height), index_to_world=a, d2=tree['d2'],
+                      voxel_size=2.0 * float(outside) / (int(n) - 1))
+    header = ['theta', 'phi', 'tree_foreshortening', 'tree_overlap']
+    header += [f'{name}_{b + 1}' for b in range(nb) for name in ('foreshortening', 'overlap')]
+    tmp = f'{path}.tmp.{os.getpid()}'
+    with open(tmp, 'w') as f:
+        f.write(','.join(header) + '\n')
+        for v in range(angles.shape[0]):
+            row = [repr(float(angles[v, 0])), repr(float(angles[v, 1])), repr(float(vm['tree_foreshortening'][v]) if nb else float('nan')),
+                   repr(float(vm['tree_overlap'][v]) if nb else float('nan'))]
+            for b in range(nb):
+                row += [repr(float(vm['foreshortening'][v, b])), repr(float(vm['overlap'][v, b]))]
+            f.write(','.join(str(x) for x in row) + '\n')
+    os.replace(tmp, path)
+    best = []
+    if nb:
+        idx, score = optimal_views(vm, k=k)
+        best = [(float(angles[i, 0]), float(angles[i, 1]), float(s)) for i, s in zip(idx, score)]
+    info = dict(path=str(path), n_views=int(angles.shape[0]), n_branches=nb, n_segments=vm['n_segments'] if nb else 0, threshold=float(threshold),
+                best=best)
+    print('view map', info, flush=True)
     return info
 
 

@@ -57,6 +57,10 @@ SIRT_METRICS = ("DICE 3D SIRT", "DICE GAIN 3D", "CORR 3D SIRT")
 # and SIRT-TV, the same reconstruction with a total-variation denoising step (afx_tv_denoise_3d) after every update, against plain SIRT;
 # it needs sirt_views, the ground-truth volume and a weight (sirt_tv_weight)
 SIRT_TV_METRICS = ("DICE 3D SIRT-TV", "TV GAIN 3D", "CORR 3D SIRT-TV")
+# and whether the reconstruction would send the C-arm where the truth would: the foreshortening and overlap map (engine.view_map:
+# afx_view_map) of the two pruned centrelines over the sweep's own angles, a tuple of its own behind all the families above; it needs
+# the ground-truth volume
+VIEW_METRICS = ("FORESHORTENING ERR 3D", "OVERLAP ERR 3D", "VIEW REGRET 3D")
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -104,7 +108,9 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     their line integrals [V, H, W]) besides `volume`: one `reconstruction_sirt_metrics` call at sirt_iterations and sirt_relax; when
     `hull_views` is given as well, the hull - taken once, whoever asks first - is the support mask of the reconstruction.  The SIRT-TV
     columns need sirt_tv_weight as well: the same call with tv_weight = sirt_tv_weight and tv_iterations = sirt_tv_iterations; plain
-    SIRT, which both families read, runs once.  The arguments are checked before any work on the GPU."""
+    SIRT, which both families read, runs once.  The VIEW_METRICS columns stand behind all of these and need `volume` alone: one
+    `reconstruction_view_metrics` call over the sweep's own angles, detector, focal length and source, on the pruned centrelines the
+    shared analysis holds.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views, sirt_tv_weight)
     dev = model.flat_params.device
@@ -167,6 +173,14 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         got = score(model, volume, volume_outside, pts, *views, grids=analysis, **kw)[0]
         for name, key in zip(names, keys):
             scores[name] = [got[key]] * n
+    if any(m in want for m in VIEW_METRICS):                  # behind the families: its views are the sweep's own angles
+        if analysis is None:
+            pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+            analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
+        got = reconstruction_view_metrics(model, volume, volume_outside, pts, angles, img_width, img_height, focal_length, src_pt, translation,
+                                          grids=analysis)[0]
+        for name, key in zip(VIEW_METRICS, ("foreshortening_err", "overlap_err", "view_regret")):
+            scores[name] = [got[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -177,7 +191,7 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
@@ -205,6 +219,9 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     tv = [m for m in metrics if m in SIRT_TV_METRICS]
     if tv and sirt_tv_weight is None:
         raise ValueError(f"evaluation_sweep: {tv} need the weight of the total variation (sirt_tv_weight=W)")
+    view = [m for m in metrics if m in VIEW_METRICS]
+    if view and volume is None:
+        raise ValueError(f"evaluation_sweep: {view} need the ground-truth volume (volume=VoxelVolume)")
     return [m for m in known if m in metrics]
 
 
@@ -675,6 +692,61 @@ def reconstruction_sirt_metrics(model, volume, outside, n, views, images, iterat
         scores.update(dice_sirt_tv=tv["dice_sirt"], corr_sirt_tv=tv["corr_sirt"], tv_gain=tv["dice_sirt"] - scores["dice_sirt"],
                       n_sirt_tv=n_s, n_sirt_tv_gt=n_sb, tv_weight=float(tv_weight), tv_iterations=int(tv_iterations))
     return scores, x, an.pred, an.gt
+
+
+def view_scores(vm_p, vm_g, overlap_weight=1.0):
+    """The scores of `reconstruction_view_metrics` from two `engine.view_map` results over the same views, fp64 on the host:
+    foreshortening_err = the mean over the views of |tree_foreshortening_p - tree_foreshortening_g|; overlap_err = the same of
+    tree_overlap over the views where both are numbers (NaN without one); view_regret = the truth's whole-tree score (foreshortening +
+    overlap_weight x overlap) at the prediction's best view (`engine.optimal_views`, k = 1) minus the truth's best score: >= 0, and 0
+    when the reconstruction recommends the view the truth would; best_view, best_view_gt: the two indices (-1 without a view)."""
+    from ..engine import optimal_views
+    fp, fg = np.asarray(vm_p["tree_foreshortening"], np.float64), np.asarray(vm_g["tree_foreshortening"], np.float64)
+    op, og = np.asarray(vm_p["tree_overlap"], np.float64), np.asarray(vm_g["tree_overlap"], np.float64)
+    both = np.isfinite(op) & np.isfinite(og)
+    best_p, _ = optimal_views(vm_p, overlap_weight=overlap_weight, k=1)
+    best_g, score_g = optimal_views(vm_g, overlap_weight=overlap_weight, k=1)
+    with np.errstate(invalid="ignore"):
+        truth_at = fg + float(overlap_weight) * og
+    nan = float("nan")
+    regret = float(truth_at[best_p[0]] - score_g[0]) if best_p.size and best_g.size else nan
+    return dict(foreshortening_err=float(np.abs(fp - fg).mean()) if fp.size else nan,
+                overlap_err=float(np.abs(op[both] - og[both]).mean()) if both.any() else nan, view_regret=regret,
+                best_view=int(best_p[0]) if best_p.size else -1, best_view_gt=int(best_g[0]) if best_g.size else -1)
+
+
+@torch.no_grad()
+def reconstruction_view_metrics(model, volume, outside, n, angles, img_width=100, img_height=100, focal_length=1300.0, src_pt=(0.0, 0.0, 1500.0),
+                                translation=(0.0, 0.0, 0.0), threshold=None, largest_component=False, prune_factor=1.0, overlap_weight=1.0,
+                                grids=None):
+    """Would the reconstruction send the C-arm where the truth would -> (scores, view map of the prediction, view map of the truth).
+
+    The two trees are the pruned centrelines of `reconstruction_graph_metrics` (same threshold, largest_component, prune_factor: with
+    `grids=` a GridAnalysis nothing is thinned twice) with the radii voxel x sqrt(d2) of their own masks; the views are `angles` [V, 2]
+    (theta, phi in degrees) as the evaluation sweep poses them (`engine.view_angles_records` with src_pt, focal_length, translation) on a
+    detector of img_width x img_height; `engine.view_map` (afx_view_map: include/afx.h) takes both maps.  Scores: `view_scores` plus
+    threshold.  A predicted centreline without a point scores NaN (its map is None); ValueError when either mask is empty or the true
+    centreline has no point."""
+    from ..engine import view_angles_records, view_map
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    _refuse_empty("reconstruction_view_metrics", *an.masks(thr)[2:], "volume has no centreline")
+    rec = view_angles_records(angles, src_pt, float(focal_length), translation)
+    maps = []
+    for side, lc in (("gt", False), ("pred", largest_component)):
+        tree = an.tree(side, thr, lc, prune_factor)
+        if int(tree["graph"]["path_voxels"].numel()) == 0:
+            if side == "gt":
+                raise ValueError("reconstruction_view_metrics: the true centreline has no point at this threshold")
+            maps.append(None)
+            continue
+        maps.append(view_map(tree["graph"], rec, int(img_width), int(img_height), index_to_world=an.index_to_world, d2=tree["d2"],
+                             voxel_size=an.voxel))
+    maps.reverse()
+    nan = float("nan")
+    scores = dict(foreshortening_err=nan, overlap_err=nan, view_regret=nan, best_view=-1, best_view_gt=-1) if maps[0] is None else \
+        view_scores(maps[0], maps[1], overlap_weight)
+    scores["threshold"] = thr
+    return scores, maps[0], maps[1]
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
