@@ -17,6 +17,14 @@
  *     is afx_march_train_step_mse_capturable (or afx_march_train_step_mse_single_eval).
  *   - all other calls are asynchronous on the stream passed in.
  *   - results are deterministic: no floating-point atomics anywhere.
+ *   - workspaces (every `void* workspace, size_t workspace_bytes` pair, as a parameter or in an args struct; the sizes come from the
+ *     *_workspace_bytes functions and the AFX_Q_*_WORKSPACE queries): device memory whose BASE IS A MULTIPLE OF 16 BYTES (hipMalloc and the
+ *     PyTorch allocator give 256 and more).  A null base, fewer bytes than the call needs, or a misaligned base is refused on the host with
+ *     the entry point's workspace error (AFX_E_WORKSPACE unless its comment says otherwise), before anything is launched or written.  The
+ *     library lays its regions out at multiples of 256 bytes from the base and reads or writes them with accesses of up to 16 bytes.
+ *     Nothing is assumed about the contents: every byte a kernel reads was written by the same call, so the buffer may hold whatever an
+ *     earlier call - of this or another entry point, on a larger problem - left in it.  Nothing beyond workspace_bytes is touched.
+ *     afx_tv_denoise_3d keeps its own rule (8 bytes, AFX_E_INVALID).
  */
 #ifndef AFX_H
 #define AFX_H
@@ -938,7 +946,8 @@ int afx_mesh_point_distance(const float* points, int64_t n_points, const float* 
  *
  * afx_centreline_graph: node_labels, branch_labels (int32 [n0][n1][n2]: 0, or the node / branch of the voxel) and path_voxels (int32
  * [n0 n1 n2]: the first record[2] entries are written) are required.  branches: max_branches rows of AFX_GRAPH_BRANCH_SLOTS 8-byte
- * slots (row b - 1 for branch b; may be NULL with max_branches 0); lo / hi = the low / high 32 bits of a slot:
+ * slots (row b - 1 for branch b; may be NULL with max_branches 0).  What path_voxels holds from entry record[2] on, and the rows from
+ * min(B, max_branches) on, is unspecified.  lo / hi = the low / high 32 bits of a slot:
  *   [0] lo voxels, hi offset into path_voxels   [1] lo flags: bit 0 cycle, bit 1 spur, bits 8..9 free ends, bits 16..17 attachments;
  *   hi the path position of the first d2 minimum   [2] lo the node of the start side, hi of the end side (0 = free)
  *   [3] lo min d2, hi max d2 along the path (0 without d2)   [4] lo d2 at the start side's J voxel, hi at the end side's (0 = free)

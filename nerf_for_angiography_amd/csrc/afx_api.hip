@@ -535,7 +535,7 @@ extern "C" int afx_render_forward(afx_ctx* c, int prec, const void* prepared, co
   if (!prepared) return fail(AFX_E_INVALID, "afx_render_forward: null prepared");
   if (r->n_rays == 0) return AFX_OK;
   const size_t need = (size_t)afx_query(c, AFX_Q_FWD_WORKSPACE, r->n_rays, r->n_samples, 0);
-  if (!r->workspace || r->workspace_bytes < need) return fail(AFX_E_WORKSPACE, "afx_render_forward: workspace %zu < %zu bytes", r->workspace_bytes, need);
+  if (int rc2 = afx::check_workspace(r->workspace, r->workspace_bytes, need, "afx_render_forward")) return rc2;
   hipStream_t st = (hipStream_t)stream;
   ChainArgs a = {};
   fill_model(c, prec, false, prepared, a);
@@ -781,13 +781,13 @@ extern "C" int afx_render_backward(afx_ctx* c, int prec, const void* prepared, c
   if (!prepared || !dL_dpixel || !grad_flat) return fail(AFX_E_INVALID, "afx_render_backward: null argument");
   if (r->n_rays == 0) return AFX_OK;
   if (!r->workspace) return fail(AFX_E_WORKSPACE, "afx_render_backward: workspace required");
+  const size_t head = rup64((size_t)r->n_rays * 4, 256);
+  if ((rc = afx::check_workspace(r->workspace, r->workspace_bytes, head, "afx_render_backward"))) return rc;
   hipStream_t st = (hipStream_t)stream;
   ChainArgs a = {};
   fill_model(c, prec, true, prepared, a);
   fill_render(r, a);
   a.sigma = nullptr; a.tau = nullptr;
-  const size_t head = rup64((size_t)r->n_rays * 4, 256);
-  if (r->workspace_bytes < head) return fail(AFX_E_WORKSPACE, "afx_render_backward: workspace too small");
   float* dod = (float*)r->workspace;
   hipLaunchKernelGGL(k_finish_bwd, dim3((unsigned)((r->n_rays + 255) / 256)), dim3(256), 0, st, r->pixel, dL_dpixel, r->n_rays, dod);
   a.dod = dod;
@@ -801,6 +801,7 @@ extern "C" int afx_train_step_mse(afx_ctx* c, int prec, const void* prepared, co
   if (rc) return rc;
   if (!is_bf16(prec)) return fail(AFX_E_INVALID, "afx_train_step_mse: needs a bf16 precision (use afx_render_forward/backward for f32)");
   if (!prepared || !target || !grad_flat || !r->workspace) return fail(AFX_E_INVALID, "afx_train_step_mse: null argument");
+  if ((rc = afx::check_workspace(r->workspace, r->workspace_bytes, 0, "afx_train_step_mse"))) return rc;
   const int64_t s_pad = s_pad_of(r->n_samples);
   // rays inside one workgroup tile: ONE kernel per chunk.  Otherwise (the reference's own 300 samples per ray, the 128 + 64 of the
   // hierarchical pass) the same work as two launches per chunk - forward half, per-ray reduction, backward half - for the
@@ -860,7 +861,7 @@ static int packed_step(afx_ctx* c, int prec, const void* prepared, const float* 
     return fail(AFX_E_INVALID, "afx_train_step_packed_mse: AFX_PREC_F16S8 only");
   hipStream_t st = (hipStream_t)stream;
   const size_t dod_bytes = rup64((size_t)n_rays * 4, 256), od_bytes = rup64((size_t)std::max<int64_t>(n_groups, 1) * 4, 256);
-  if (workspace_bytes < dod_bytes + od_bytes) return fail(AFX_E_WORKSPACE, "afx_train_step_packed_mse: workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, dod_bytes + od_bytes, "afx_train_step_packed_mse")) return rc;
   float* dod = (float*)workspace;
   float* od_part = (float*)((char*)workspace + dod_bytes);
   if (n_groups == 0) {      // nothing survived the march: every pixel is the empty product, no gradient (the reference skips the step, :293)
@@ -975,7 +976,7 @@ extern "C" int afx_hier_train_step_mse(afx_ctx* c, int prec, const void* prepare
   if (NF < 2) return fail(AFX_E_INVALID, "afx_hier_train_step_mse: n_fine must be >= 2");
   hipStream_t st = (hipStream_t)stream;
   const int64_t R = r->n_rays, spA = s_pad_of(S), spB = s_pad_of(NF);
-  if (r->workspace_bytes < hier_bytes(c, R, S, NF, 0)) return fail(AFX_E_WORKSPACE, "afx_hier_train_step_mse: workspace %zu too small", r->workspace_bytes);
+  if (int rc2 = afx::check_workspace(r->workspace, r->workspace_bytes, hier_bytes(c, R, S, NF, 0), "afx_hier_train_step_mse")) return rc2;
   int64_t nr = hier_max_rays(c, R, S);
   while (nr >= 8 && hier_bytes(c, R, S, NF, nr) > r->workspace_bytes) {
     if (nr == 8) { nr = 0; break; }
@@ -1036,6 +1037,7 @@ extern "C" int afx_mlp_backward(afx_ctx* c, int prec, const void* prepared, cons
   if (check_prec(prec, "afx_mlp_backward")) return AFX_E_INVALID;
   if (n_pts < 0 || n_pts > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "afx_mlp_backward: n_pts must be < 2^31 per call");
   if (n_pts == 0) return AFX_OK;
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, 0, "afx_mlp_backward")) return rc;
   ChainArgs a = {};
   fill_model(c, prec, true, prepared, a);
   a.n_total = n_pts; a.mode = 0; a.pts = pts; a.dod = d_out;
@@ -1093,8 +1095,7 @@ extern "C" int afx_mlp_backward_inputs(afx_ctx* c, int prec, const void* prepare
   if (n_pts < 0 || n_pts > ((int64_t)1 << 31) - 256) return fail(AFX_E_INVALID, "afx_mlp_backward_inputs: n_pts must be < 2^31 per call");
   if (n_pts == 0) return AFX_OK;
   const size_t need = (size_t)ingrad_workspace(c, prec, 0, n_pts, 1);
-  if (workspace_bytes < need)
-    return fail(AFX_E_WORKSPACE, "afx_mlp_backward_inputs: workspace %zu < %zu bytes (AFX_Q_BWD_INPUTS_WORKSPACE_MIN)", workspace_bytes, need);
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, "afx_mlp_backward_inputs", "AFX_Q_BWD_INPUTS_WORKSPACE_MIN")) return rc;
   if (int rc = check_dev(c, "afx_mlp_backward_inputs")) return rc;
   ChainArgs a = {};
   fill_model(c, prec, true, prepared, a);
@@ -1116,10 +1117,8 @@ extern "C" int afx_render_backward_inputs(afx_ctx* c, int prec, const void* prep
   if (r->ray_mode != AFX_RAYS_ARRAYS && (d_origins || d_dirs))
     return fail(AFX_E_INVALID, "%s: ray gradients need rays given as origin / direction arrays (AFX_RAYS_ARRAYS); rays generated from poses in the "
                 "kernel (AFX_RAYS_POSE) have none", who);
-  if (!r->workspace) return fail(AFX_E_WORKSPACE, "%s: workspace required", who);
   const size_t need = (size_t)ingrad_workspace(c, prec, r->n_rays, r->n_samples, 1);
-  if (r->workspace_bytes < need)
-    return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (AFX_Q_BWD_INPUTS_WORKSPACE_MIN)", who, r->workspace_bytes, need);
+  if ((rc = afx::check_workspace(r->workspace, r->workspace_bytes, need, who, "AFX_Q_BWD_INPUTS_WORKSPACE_MIN"))) return rc;
   if ((rc = check_dev(c, who))) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)r->workspace;
@@ -1423,7 +1422,7 @@ extern "C" int afx_grid_select_cells(const afx_grid_desc* grid, const uint32_t* 
   if (int rc = check_step(step, step_dev, who)) return rc;
   Carve w{(uintptr_t)workspace};
   const SelBufs b = carve_select(nc, w);
-  if (workspace_bytes < w.end) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.end);
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, w.end, who)) return rc;
   const uint64_t sid = AFX_GRID_SELECT_TAG | (step_dev ? 0 : (uint64_t)step);
   return launch_select(nc, bits, n_draw, seed, sid, step_dev, cells_out, count_dev, b, (hipStream_t)stream);
 }
@@ -1469,8 +1468,7 @@ extern "C" int afx_grid_refresh(afx_ctx* c, int prec, const void* prepared, cons
   if (int rc = carve_refresh(&a->grid, a->n_draw, a->all_cells, w, L, &nc, who)) return rc;
   if (!a->occs || !a->binary || !a->bits || !a->workspace) return fail(AFX_E_INVALID, "%s: null argument", who);
   if (int rc = check_step(a->step, a->step_dev, who)) return rc;
-  if (a->workspace_bytes < w.end) return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (afx_grid_refresh_workspace_bytes)", who,
-                                              a->workspace_bytes, w.end);
+  if (int rc = afx::check_workspace(a->workspace, a->workspace_bytes, w.end, who, "afx_grid_refresh_workspace_bytes")) return rc;
   if (int rc = check_dev(c, who)) return rc;
   hipStream_t st = (hipStream_t)stream;
   int32_t* cells = L.cells;
@@ -1591,7 +1589,7 @@ extern "C" int afx_topk_indices(const float* keys, int64_t n, int64_t k, int64_t
   if (k == 0) return AFX_OK;
   if (n <= 0 || k < 0 || k > n || n >= ((int64_t)1 << 32)) return fail(AFX_E_INVALID, "afx_topk_indices: need 0 <= k <= n < 2^32");
   if (!keys || !out_idx || !workspace) return fail(AFX_E_INVALID, "afx_topk_indices: null argument");
-  if (workspace_bytes < afx_topk_workspace_bytes(n)) return fail(AFX_E_WORKSPACE, "afx_topk_indices: workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, afx_topk_workspace_bytes(n), "afx_topk_indices")) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t nb = (n + SEL_PER_BLOCK - 1) / SEL_PER_BLOCK;
   uint32_t* hist = (uint32_t*)workspace;
@@ -1658,7 +1656,7 @@ extern "C" int afx_sample_batches(const float* weights, int64_t n, uint64_t seed
   if (n <= 0 || k < 0 || k > n || n >= ((int64_t)1 << 32) || n_batches < 0 || n_batches > 65535)
     return fail(AFX_E_INVALID, "afx_sample_batches: need 0 <= k <= n < 2^32 and 0 <= n_batches <= 65535");
   if (!out_idx || !workspace) return fail(AFX_E_INVALID, "afx_sample_batches: null argument");
-  if (workspace_bytes < afx_sample_batches_workspace_bytes(n, n_batches)) return fail(AFX_E_WORKSPACE, "afx_sample_batches: workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, afx_sample_batches_workspace_bytes(n, n_batches), "afx_sample_batches")) return rc;
   return launch_sample_batches(weights, n, seed, stream_id0, nullptr, n_batches, k, out_idx, workspace, (hipStream_t)stream);
 }
 
@@ -1671,7 +1669,7 @@ extern "C" int afx_sample_batches_dev(const float* weights, int64_t n, uint64_t 
   if (n_batches < 1 || n_batches > 65535) return fail(AFX_E_INVALID, "%s: n_batches must be in 1..65535 (got %d)", who, (int)n_batches);
   if (n <= 0 || n >= ((int64_t)1 << 32)) return fail(AFX_E_INVALID, "%s: need 0 < n < 2^32 (got %lld)", who, (long long)n);
   if (k < 0 || k > n) return fail(AFX_E_INVALID, "%s: need 0 <= k <= n (k = %lld, n = %lld)", who, (long long)k, (long long)n);
-  if (workspace_bytes < afx_sample_batches_workspace_bytes(n, n_batches)) return fail(AFX_E_WORKSPACE, "%s: workspace too small", who);
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, afx_sample_batches_workspace_bytes(n, n_batches), who)) return rc;
   if (k == 0) return AFX_OK;
   return launch_sample_batches(weights, n, seed, 0, stream_id0_dev, n_batches, k, out_idx, workspace, (hipStream_t)stream);
 }
@@ -1757,6 +1755,7 @@ extern "C" int afx_march_train_step_mse(afx_ctx* c, int prec, const void* prepar
   if (!m.origins || !m.dirs || !t->target || !t->pixel || !t->grad_flat || !t->workspace)
     return fail(AFX_E_INVALID, "afx_march_train_step_mse: null argument");
   if (prec != AFX_PREC_F16S8 || !c->small_in_kernel) return fail(AFX_E_INVALID, "afx_march_train_step_mse: AFX_PREC_F16S8 only");
+  if (int rc = afx::check_workspace(t->workspace, t->workspace_bytes, 0, "afx_march_train_step_mse")) return rc;
   if (int rc = check_dev(c, "afx_march_train_step_mse")) return rc;
   // carved in stages as the sizes become known; a stage that does not fit reports what the call needs so far
   Carve w{(uintptr_t)t->workspace};
@@ -1870,10 +1869,14 @@ static int check_grid_step(const afx_ctx* c, int prec, const void* prepared, afx
 }
 
 // A worst-case workspace (carved up to `end`) against the caller's (the shortfall reported in *needed), then the device.
-static int check_carve(const afx_ctx* c, size_t end, size_t bytes, size_t* needed, const char* who, const char* query) {
+static int check_carve(const afx_ctx* c, const void* ws, size_t end, size_t bytes, size_t* needed, const char* who, const char* query) {
   if (end > bytes) {
     *needed = end;
     return fail(AFX_E_WORKSPACE, "%s: workspace %zu < %zu bytes (%s)", who, bytes, end, query);
+  }
+  if (int rc = afx::check_workspace(ws, bytes, end, who)) {      // (large enough but misaligned: the size is reported all the same)
+    *needed = end;
+    return rc;
   }
   return check_dev(c, who);
 }
@@ -1922,7 +1925,7 @@ extern "C" int afx_march_train_step_mse_capturable(afx_ctx* c, int prec, const v
   Carve w{(uintptr_t)t->workspace};
   CapBufs L;
   if (int rc = carve_capturable(c, prec, R, S, w, L, who)) return rc;
-  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_train_workspace_bytes")) return rc;
+  if (int rc = check_carve(c, t->workspace, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_train_workspace_bytes")) return rc;
   hipStream_t st = (hipStream_t)stream;
   int32_t *counts = L.counts, *counts2 = L.counts2, *ri = L.ri, *ri2 = L.ri2, *gray = L.gray;
   int64_t *offsets = L.offsets, *totals = L.totals, *off2 = L.off2, *goff = L.goff, *dsz = L.dsz;
@@ -2005,7 +2008,7 @@ extern "C" int afx_march_train_step_mse_single_eval(afx_ctx* c, int prec, const 
   Carve w{(uintptr_t)t->workspace};
   SeBufs L;
   if (int rc = carve_single_eval(c, R, S, w, L, who)) return rc;
-  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_single_eval_workspace_bytes")) return rc;
+  if (int rc = check_carve(c, t->workspace, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_single_eval_workspace_bytes")) return rc;
   const int N = c->d.n_hidden;
   hipStream_t st = (hipStream_t)stream;
   int32_t *counts = L.counts, *counts2 = L.counts2, *ri = L.ri, *gray = L.gray;
@@ -2112,7 +2115,7 @@ extern "C" int afx_march_render(afx_ctx* c, int prec, const void* prepared, afx_
   Carve w{(uintptr_t)t->workspace};
   RenderBufs L;
   if (int rc = carve_render(t->ray_mode, R, S, w, L, who)) return rc;
-  if (int rc = check_carve(c, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_render_workspace_bytes")) return rc;
+  if (int rc = check_carve(c, t->workspace, w.end, t->workspace_bytes, &t->workspace_needed, who, "afx_march_render_workspace_bytes")) return rc;
   hipStream_t st = (hipStream_t)stream;
   int32_t* counts = L.counts;
   int64_t *offsets = L.offsets, *totals = L.totals;

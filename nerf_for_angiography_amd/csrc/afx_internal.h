@@ -201,6 +201,30 @@ struct Carve {
   }
 };
 
+// Sets afx_last_error()'s message to "<who>: <msg>" and returns `code` (defined in afx_api.hip, for the other translation units).
+int set_error(int code, const char* who, const char* msg);
+
+// The caller's workspace, checked on the host before check_device and before any launch: not null, at least `need` bytes, and its base
+// a multiple of WORKSPACE_ALIGN bytes - each refused with `code` (the entry point's workspace error) and a message that says which.
+// Why 16: every carved offset is a multiple of Carve's 256-byte granule, so the base decides the alignment of every region, and the widest
+// access any kernel makes to carved memory is one 16-byte vector (the u32x4 / f32x4 casts of the stash, mask and group-record planes in
+// afx_kernels_bf16.hip and afx_kernels_f32.hip; the wider vector types there are MFMA register operands, never a memory access).  The
+// doubles and the 64-bit atomic targets carved by the analysis units need 8.
+constexpr size_t WORKSPACE_ALIGN = 16;
+inline int check_workspace(const void* ptr, size_t bytes, size_t need, const char* who, const char* query = nullptr, int code = AFX_E_WORKSPACE) {
+  char msg[192];
+  if (!ptr) return set_error(code, who, "workspace is null");
+  if (bytes < need) {      // `query`: the size query to name in the message, when the entry point has one of its own
+    snprintf(msg, sizeof msg, "workspace too small: %zu < %zu bytes%s%s%s", bytes, need, query ? " (" : "", query ? query : "", query ? ")" : "");
+    return set_error(code, who, msg);
+  }
+  if ((uintptr_t)ptr % WORKSPACE_ALIGN) {
+    snprintf(msg, sizeof msg, "workspace must be aligned to %zu bytes", WORKSPACE_ALIGN);
+    return set_error(code, who, msg);
+  }
+  return AFX_OK;
+}
+
 // A voxel volume vol[nx][ny][nz] (fp32) on a regular grid: axis a has its first sample at a0 and spacing da.  vol_sample is scipy's
 // RegularGridInterpolator(method='linear', bounds_error=False, fill_value=fill) at (px, py, pz) in fp64: the 8-voxel trilinear blend,
 // `fill` outside the box (the box's faces belong to it).  k_project_volume (ground-truth projections) and k_volume_grid (the
@@ -237,9 +261,6 @@ __device__ __forceinline__ double vol_sample(const VolArgs& v, double px, double
   }
   return mu;
 }
-
-// Sets afx_last_error()'s message to "<who>: <msg>" and returns `code` (defined in afx_api.hip, for the other translation units).
-int set_error(int code, const char* who, const char* msg);
 
 // The C entry points of the image and metric units: `p` (named `what` in the message) is memory of the current device (launches go to a
 // stream of the current device); and the launches just made were accepted.

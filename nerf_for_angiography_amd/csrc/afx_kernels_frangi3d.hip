@@ -255,7 +255,7 @@ extern "C" int afx_frangi_3d(const void* x, int32_t x_is_f64, int32_t n0, int32_
   if (gamma != gamma || gamma == INFINITY) return afx::set_error(AFX_E_INVALID, who, "gamma must be finite (<= 0: per-scale sqrt(max S) / 2)");
   const size_t need = afx_frangi_3d_workspace_bytes(n0, n1, n2, n_sigmas);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(x, "the volume", who)) return rc;
   afx::Carve c;
   c.base = (uintptr_t)workspace;

@@ -497,7 +497,7 @@ extern "C" int afx_centreline_graph(const uint8_t* skel, const uint32_t* d2, int
       if (!(step_lengths[c] >= 0.0) || std::isinf(step_lengths[c])) return afx::set_error(AFX_E_INVALID, who, "step_lengths must be finite and >= 0");
   const size_t need = afx_centreline_graph_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(skel, "the mask", who)) return rc;
   if (int rc = afx::check_device(path_voxels, "path_voxels", who)) return rc;
   afx::Carve c;
@@ -525,7 +525,7 @@ extern "C" int afx_prune_spurs(const uint8_t* skel, const uint32_t* d2, int32_t 
   if (sync_every < 0) return afx::set_error(AFX_E_INVALID, who, "sync_every must be 0 (no read-back) or the rounds between two read-backs");
   const size_t need = afx_prune_spurs_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(skel, "the mask", who)) return rc;
   if (int rc = afx::check_device(out, "the output mask", who)) return rc;
   hipStream_t st = (hipStream_t)stream;

@@ -362,7 +362,7 @@ extern "C" int afx_frangi(const double* img, int32_t n, int32_t h, int32_t w, co
   if (!(beta > 0.0) || !(gamma > 0.0) || !isfinite(beta) || !isfinite(gamma)) return afx::set_error(AFX_E_INVALID, who, "beta and gamma must be finite and > 0");
   const size_t need = afx_frangi_workspace_bytes(n, h, w, n_sigmas);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(img, "the image", who)) return rc;
   afx::Carve c;
   c.base = (uintptr_t)workspace;
@@ -385,7 +385,7 @@ extern "C" int afx_distance_transform_edt(const double* x, int32_t n, int32_t h,
   if (!shape_ok(n, h, w, 1)) return afx::set_error(AFX_E_INVALID, who, "need 1 <= n <= 65535 images of 1..16384 x 1..16384 pixels");
   const size_t need = afx_distance_transform_edt_workspace_bytes(n, h, w);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(x, "the image", who)) return rc;
   launch_edt(x, n, h, w, FG_NONZERO, nullptr, (uint32_t*)workspace, out, (hipStream_t)stream);
   return afx::launched(who);
@@ -421,7 +421,7 @@ extern "C" int afx_sampling_weights(const double* img, int32_t n, int32_t h, int
   }
   const size_t need = afx_sampling_weights_workspace_bytes(strategy, n, h, w, frangi ? n_sigmas : 0);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(img, "the image", who)) return rc;
   hipStream_t st = (hipStream_t)stream;
   afx::Carve c;

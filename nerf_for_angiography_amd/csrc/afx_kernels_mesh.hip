@@ -383,7 +383,7 @@ extern "C" int afx_isosurface_3d(const float* f, int32_t n0, int32_t n1, int32_t
   if (!(det != 0.0) || !isfinite(det)) return afx::set_error(AFX_E_INVALID, who, "index_to_world is singular (det(m) is 0 or not finite)");
   const size_t need = afx_isosurface_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(f, "the volume", who)) return rc;
   if (int rc = afx::check_device(record, "the record", who)) return rc;
   if (vertices) if (int rc = afx::check_device(vertices, "vertices", who)) return rc;
@@ -427,7 +427,7 @@ extern "C" int afx_mesh_measures(const float* vertices, int64_t max_vertices, co
     }
   const size_t need = afx_mesh_measures_workspace_bytes();
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(record, "the record", who)) return rc;
   if (int rc = afx::check_device(out, "the output", who)) return rc;
   if (vertices) if (int rc = afx::check_device(vertices, "vertices", who)) return rc;

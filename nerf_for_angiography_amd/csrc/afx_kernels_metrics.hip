@@ -925,7 +925,7 @@ extern "C" int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int
   if (max_passes < 1) return afx::set_error(AFX_E_INVALID, who, "max_passes must be at least 1");
   if (sync_every < 0) return afx::set_error(AFX_E_INVALID, who, "sync_every must be 0 (no read-back) or the passes between two read-backs");
   const size_t need = afx_skeletonize_3d_workspace_bytes(n0, n1, n2);
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(fg, "the volume", who)) return rc;
   if (int rc = afx::check_device(skel, "the skeleton", who)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -974,7 +974,7 @@ extern "C" int afx_label_components_3d(const uint8_t* fg, int32_t n0, int32_t n1
   if (connectivity < 1 || connectivity > 3) return afx::set_error(AFX_E_INVALID, who, "connectivity must be 1, 2 or 3 (6, 18 or 26 neighbours)");
   const size_t need = afx_label_components_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(fg, "the volume", who)) return rc;
   if (int rc = afx::check_device(labels, "labels", who)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -1025,7 +1025,7 @@ extern "C" int afx_distance_transform_edt_3d(const uint8_t* fg, int32_t n0, int3
   if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   const size_t need = afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(fg, "the volume", who)) return rc;
   launch_edt3(fg, n0, n1, n2, (uint16_t*)workspace, d2, dist, (hipStream_t)stream);
   return afx::launched(who);
@@ -1048,7 +1048,7 @@ extern "C" int afx_surface_metrics_3d(const float* pred, const float* gt, int32_
   if (!(q >= 0.0 && q <= 100.0)) return afx::set_error(AFX_E_INVALID, who, "the percentile q must lie in [0, 100]");
   const size_t need = afx_surface_metrics_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(pred, "pred", who)) return rc;
   if (int rc = afx::check_device(gt, "gt", who)) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -1086,7 +1086,7 @@ extern "C" int afx_ssim(const float* preds, const float* targets, int32_t n, int
     return afx::set_error(AFX_E_INVALID, who, "need n >= 1 pairs of h x w >= 11 x 11 pixels, h w < 2^31 and n x tiles < 2^24");
   const size_t need = afx_ssim_workspace_bytes(n, h, w);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(preds, "preds", who)) return rc;
   if (int rc = afx::check_device(targets, "targets", who)) return rc;
   hipStream_t st = (hipStream_t)stream;

@@ -472,7 +472,7 @@ extern "C" int afx_mesh_sdf_3d(const float* vertices, int64_t n_vertices, const 
   if (!(det != 0.0) || !isfinite(det)) return afx::set_error(AFX_E_INVALID, who, "index_to_world is singular (det(m) is 0 or not finite)");
   const size_t need = afx_mesh_sdf_3d_workspace_bytes(n_triangles);
   if (workspace_needed) *workspace_needed = need;
-  if (!workspace || workspace_bytes < need) return afx::set_error(AFX_E_WORKSPACE, who, "workspace too small");
+  if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
   if (int rc = afx::check_device(sdf_out, "sdf_out", who)) return rc;
   if (int rc = afx::check_device(record, "the record", who)) return rc;
   if (int rc = afx::check_device(workspace, "the workspace", who)) return rc;

@@ -1233,9 +1233,14 @@ def surface_metrics_3d(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float, th
     come from the device, NumPy's linear interpolation between them is finished here - and the counts n_pred, n_gt, n_overlap,
     n_surface_pred, n_surface_gt.  One launch sequence and one read-back of 128 bytes.  ValueError: a threshold that leaves a volume
     empty (no surface to measure from)."""
+    return _surface_scores_from_record(surface_metrics_record(pred, gt, thr_pred, thr_gt, q), q)
+
+
+def _surface_scores_from_record(record: torch.Tensor, q: float = 95.0) -> dict:
+    """The scores of `surface_metrics_3d` from the 16-slot record of `surface_metrics_record` (one read-back of 128 bytes)."""
     import math
     import numpy as np
-    rec = surface_metrics_record(pred, gt, thr_pred, thr_gt, q).cpu().numpy()
+    rec = record.cpu().numpy()
     f = rec.view(np.float64)
     status = int(rec[12])
     if status:

@@ -10,6 +10,7 @@ from test_gpu_parity import DEV, TOL
 from test_gpu_grid_graph import AABB, NEAR, FAR, SPR, EPS, THRE, _capturable, _grid, _mask, _model, _rays
 
 pytestmark = pytest.mark.gpu
+SINGLE_EVAL_GRAD_TOL = 2e-2          # relative L2 of the gradient against the two-evaluation step (the sums run in another order)
 
 
 def _single(m, grid, o, d, tgt, grad, **kw):
@@ -94,7 +95,7 @@ def test_single_eval_equals_the_two_evaluation_step(layers, width, kind):
     assert torch.equal(skip1, skip2) and float(skip2) == 0.0
     assert torch.equal(pix1, pix2)
     assert torch.equal(torch.nn.functional.mse_loss(pix1, tgt), torch.nn.functional.mse_loss(pix2, tgt))
-    assert rel_l2(g2.cpu().numpy(), g1.cpu().numpy()) < 2e-2
+    assert rel_l2(g2.cpu().numpy(), g1.cpu().numpy()) < SINGLE_EVAL_GRAD_TOL
 
 
 def test_gradient_with_many_dropped_samples_vs_fp32_operator_sequence():
