@@ -1241,6 +1241,41 @@ int afx_view_map(const double* segments, const int32_t* seg_branch, int32_t n_se
                  int32_t n_views, int32_t width, int32_t height, uint32_t flags, uint16_t* count, int32_t* area, int32_t* shared,
                  int32_t* tree, double* proj /* may be NULL */, double* length /* may be NULL */, void* stream);
 
+/* ---- Curved-planar reformation: planes carried along a centreline, sampled out of a volume.  A plane is a centre and two in-plane unit
+ * vectors (the rotation-minimising frame of the centreline point, made on the host); the in-plane positions of the samples are one table
+ * shared by all planes, so the same call gives the stack of cross-sections (the straightened vessel: a K x K table) and the longitudinal
+ * images (a table of lines through the centre at a few angles).  Defined here so that every implementation gives the same result;
+ * tests/reformat_reference.py restates it in NumPy and the device equals the restatement exactly.  fp64 throughout, only + - * /, floor
+ * and comparisons, every product and sum rounded on its own (no contraction).
+ *
+ * afx_reformat_planes: vol, vol_is_f64, n0, n1, n2 and world_to_index W as afx_lumen_profile takes them (every side >= 2, N < 2^31, W 12
+ * doubles on the host).  planes: double [P][AFX_REFORMAT_PLANE_DOUBLES] on the device, the row = the centre c at [0..2], the in-plane
+ * unit vector u at [3..5], the in-plane unit vector v at [6..8], world coordinates.  table: double [Q][AFX_REFORMAT_TABLE_DOUBLES] on
+ * the device, the row = (a, b, sa, sb): the sample's in-plane offset along u and v, and the slab step in the same in-plane coordinates.
+ * H = half_slab in 0..127, mode AFX_REFORMAT_MEAN or AFX_REFORMAT_MAX, fill a finite double.  Per (p, q), for m = -H .. H in that order:
+ *   1. alpha = a + m sa;  beta = b + m sb                         (m as a double; the product, then the sum)
+ *   2. x_r = (c_r + alpha u_r) + beta v_r,  r = 0, 1, 2
+ *   3. f_m = the lookup of afx_lumen_profile step 4 at x: the same q_a, the same inside test (a NaN or a huge q is outside; nothing is
+ *      converted to an integer and nothing is loaded before the test passes), the same i_a = min(floor(q_a), n_a - 2) and the same lerps
+ *      along axis 2, 1, 0 - but outside the box it gives `fill`, not 0.  A NaN or infinite plane row is therefore outside: its row is fill.
+ *   MEAN: acc = +0.0; acc = acc + f_m in order; out = acc / (2 H + 1)     (the divisor as a double; H = 0: (+0.0 + f_0) / 1.0)
+ *   MAX:  out = f_{-H}; then out = f_m > out ? f_m : out                   (H = 0: f_0)
+ * out: double [P][Q].  The result of a sample does not depend on where its row stands in the table: the caller may order the table so
+ * that a wavefront (64 consecutive rows) covers a compact patch of the plane, and undo the order afterwards.
+ * One launch: a lane per (p, q) under a 64-bit flat index p Q + q, q fastest, 4 wavefronts per workgroup; the slab loop is bounded by the
+ * argument H and no lane waits for another: the kernel ends on any input.  No LDS, no atomics, no workspace, nothing allocated,
+ * synchronised or read back: the call can be captured in a graph.  NaN voxels are out of scope.
+ * AFX_E_INVALID, the message naming the argument, before any HIP call: a null vol or world_to_index; a side < 2 or N >= 2^31; n_planes
+ * < 0 or > 2^31 - 1; n_table < 0 or > 2^20 (and n_planes n_table beyond the 2^22 x 65535 workgroups of a launch); half_slab outside 0..127; mode outside {0, 1}; a non-finite fill or world_to_index; and,
+ * with n_planes > 0 and n_table > 0, a null planes, table or out.  n_planes == 0 or n_table == 0 returns AFX_OK without a launch. */
+#define AFX_REFORMAT_PLANE_DOUBLES 9
+#define AFX_REFORMAT_TABLE_DOUBLES 4
+#define AFX_REFORMAT_MEAN 0
+#define AFX_REFORMAT_MAX 1
+int afx_reformat_planes(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t n1, int32_t n2, const double* world_to_index /* [12], host */,
+                        const double* planes, int64_t n_planes, const double* table, int64_t n_table, int32_t half_slab, int32_t mode,
+                        double fill, double* out, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -1991,6 +1991,354 @@ def lumen_branch_summary(profile: dict, min_points: int = 5) -> dict:
     return out
 
 
+REFORMAT_PLANE_DOUBLES, REFORMAT_TABLE_DOUBLES = 9, 4
+REFORMAT_MODES = {"mean": 0, "max": 1}
+REFORMAT_TILE = 8                     # the side of the tiles of a tiled cross-section table
+REFORMAT_TILED = True                 # the order straighten_volume hands its table over in: the faster of the two in profiles/r27_cpr.md
+FRAME_KEPT = 1                        # rotation_minimising_frames: the point kept the previous frame
+
+
+def _host(x):
+    import numpy as np
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def centreline_main_path(graph: dict, index_to_world, start=None, end=None, d2=None) -> dict:
+    """The main path of a `centreline_graph` result, from the ostium side to the farthest distal end, across branches and junctions.
+    The path graph: its vertices are the junction nodes and the free ends (a free side of a branch), its edges the non-cycle branches
+    weighted by their `length` (a branch from a node back to the same node is no edge).  Shortest paths by Dijkstra in fp64; where two
+    ways to a vertex are equally long the one whose last branch has the smaller label stays.  start, end: the linear voxel index of a
+    free end.  Default start: the free end with the largest d2 (d2: the squared EDT volume the graph was made with, read at the end
+    voxel; without it every free end ties), a tie to the smaller voxel index - the ostium side.  Default end: the free end farthest from
+    start, a tie to the smaller voxel index.  -> dict: points (float64 [P, 3], world: the branches' path voxels in travel order, a branch
+    reversed when it is entered from its end side; a junction cluster is bridged by the straight step between the two extremes next to
+    it), voxels (int64 [P], the linear indices), branches (1-based, in travel order), reversed (per branch), start, end (voxels) and
+    length (the sum of the branch lengths).  ValueError: no free end, start or end no free end, start and end not connected.  NumPy on
+    the host, as `centreline_world_points`."""
+    import heapq
+    import numpy as np
+    a = _affine12(index_to_world, "centreline_main_path").reshape(3, 4)
+    size = _host(graph["branch_size"]).astype(np.int64).reshape(-1)
+    nb = size.size
+    offset = _host(graph["path_offset"]).astype(np.int64).reshape(-1) if "path_offset" in graph else np.concatenate([[0], np.cumsum(size)[:-1]])
+    cyc = _host(graph["is_cycle"]).astype(bool).reshape(-1)
+    node = np.stack([_host(graph["node_start"]).astype(np.int64).reshape(-1), _host(graph["node_end"]).astype(np.int64).reshape(-1)], axis=1)
+    length = _host(graph["length"]).astype(np.float64).reshape(-1)
+    vox = _host(graph["path_voxels"]).astype(np.int64).reshape(-1)
+    side_voxel = lambda b, s: int(vox[offset[b] + (size[b] - 1 if s else 0)])
+    vertex = lambda b, s: ("n", int(node[b, s])) if node[b, s] else ("f", b, s)
+    edges, ends = {}, []                                  # vertex -> [(branch, other vertex)]; the free ends (voxel, vertex)
+    for b in range(nb):
+        if cyc[b] or size[b] < 1:
+            continue
+        va, vb = vertex(b, 0), vertex(b, 1)
+        ends += [(side_voxel(b, s), v) for s, v in ((0, va), (1, vb)) if v[0] == "f"]
+        if va != vb:
+            edges.setdefault(va, []).append((b, vb))
+            edges.setdefault(vb, []).append((b, va))
+    if not ends:
+        raise ValueError("centreline_main_path: the graph has no free end")
+
+    def pick(voxel, what):
+        found = [v for x, v in ends if x == int(voxel)]
+        if not found:
+            raise ValueError(f"centreline_main_path: {what} = {voxel} is not the voxel of a free end")
+        return found[0]
+
+    if start is None:
+        dd = None if d2 is None else _host(d2).reshape(-1)
+        key = lambda e: (-(int(dd[e[0]]) & 0xffffffff) if dd is not None else 0, e[0])
+        v_start = min(ends, key=key)[1]
+    else:
+        v_start = pick(start, "start")
+    dist, via = {v_start: 0.0}, {}
+    heap, done = [(0.0, 0, v_start)], set()
+    tick = 1
+    while heap:
+        d, _, v = heapq.heappop(heap)
+        if v in done:
+            continue
+        done.add(v)
+        for b, w in edges.get(v, ()):
+            nd = d + float(length[b])
+            if w not in done and (w not in dist or nd < dist[w] or (nd == dist[w] and b < via[w][0])):
+                dist[w], via[w] = nd, (b, v)
+                heapq.heappush(heap, (nd, tick, w))
+                tick += 1
+    if end is None:
+        far = [(-dist[v], x, v) for x, v in ends if v in dist and v != v_start]
+        if not far:
+            raise ValueError("centreline_main_path: no other free end is connected to start")
+        v_end = min(far, key=lambda e: e[:2])[2]
+    else:
+        v_end = pick(end, "end")
+        if v_end == v_start and len([1 for x, v in ends if x == int(end)]) > 1:
+            v_end = [v for x, v in ends if x == int(end)][1]          # a lone voxel: its two free sides
+    if v_end not in dist:
+        raise ValueError("centreline_main_path: start and end are not connected")
+    hops, v = [], v_end
+    while v != v_start:
+        b, prev = via[v]
+        hops.append((b, vertex(b, 0) != prev))            # entered from its end side: reversed
+        v = prev
+    hops.reverse()
+    if not hops:
+        raise ValueError("centreline_main_path: start and end are the same free end")
+    voxels = np.concatenate([vox[offset[b]:offset[b] + size[b]][::-1 if rev else 1] for b, rev in hops])
+    n0, n1, n2 = graph["shape"]
+    ijk = np.stack([voxels // (n1 * n2), voxels // n2 % n1, voxels % n2], axis=1).astype(np.float64)
+    return {"points": ijk @ a[:, :3].T + a[:, 3], "voxels": voxels, "branches": [b + 1 for b, _ in hops], "reversed": [bool(r) for _, r in hops],
+            "start": int(voxels[0]), "end": int(voxels[-1]), "length": float(dist[v_end])}
+
+
+def polyline_smooth(points, passes: int = 8, lam: float = 0.5):
+    """Laplacian smoothing of a polyline [P, 3]: `passes` Jacobi passes of x_k <- x_k + lam ((x_{k-1} + x_{k+1}) / 2 - x_k), every point
+    from the previous pass, the two ends fixed.  NumPy fp64 on the host."""
+    import numpy as np
+    x = np.array(points, np.float64).reshape(-1, 3)
+    for _ in range(int(passes)):
+        if len(x) < 3:
+            break
+        new = x.copy()
+        new[1:-1] = x[1:-1] + float(lam) * ((x[:-2] + x[2:]) / 2.0 - x[1:-1])
+        x = new
+    return x
+
+
+def _arc_length(pts):
+    """0 at the first point, the Euclidean steps sqrt((dx dx + dy dy) + dz dz) added one after another (as `centreline_segments`)."""
+    import numpy as np
+    d = pts[1:] - pts[:-1]
+    steps = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    arc = np.zeros(len(pts), np.float64)
+    for q in range(steps.size):
+        arc[q + 1] = arc[q] + steps[q]
+    return arc
+
+
+def polyline_resample(points, spacing: float):
+    """A polyline [P, 3] at the arc lengths 0, spacing, 2 spacing, .. (linear interpolation between its points; the last partial step is
+    dropped, the first point is kept).  NumPy fp64 on the host."""
+    import numpy as np
+    x = np.array(points, np.float64).reshape(-1, 3)
+    spacing = float(spacing)
+    if not (spacing > 0.0 and np.isfinite(spacing)):
+        raise ValueError(f"polyline_resample: spacing must be finite and > 0, got {spacing!r}")
+    if len(x) < 2:
+        return x
+    arc = _arc_length(x)
+    n = int(np.floor(arc[-1] / spacing)) + 1
+    while n > 1 and (n - 1) * spacing > arc[-1]:
+        n -= 1
+    s = np.arange(n, dtype=np.float64) * spacing
+    k = np.clip(np.searchsorted(arc, s, side="right") - 1, 0, len(x) - 2)
+    seg = arc[k + 1] - arc[k]
+    w = np.where(seg > 0.0, (s - arc[k]) / np.where(seg > 0.0, seg, 1.0), 0.0)
+    return x[k] + w[:, None] * (x[k + 1] - x[k])
+
+
+def rotation_minimising_frames(points, half_window: int = 3):
+    """Frames (t, u, v) along one polyline [P, 3] that do not twist about it: the rotation-minimising frame by double reflection (Wang,
+    Juettler, Zheng, Liu 2008) -> (t, u, v float64 [P, 3], flags int32 [P]).  dot(a, b) = (a0 b0 + a1 b1) + a2 b2 and cross(a, b) =
+    (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0) throughout, every operation in fp64 rounded on its own, in this order:
+      tangent (afx_lumen_profile step 1):  a = max(k - h, 0), b = min(k + h, P - 1), d = x_b - x_a, n2 = dot(d, d); b <= a or n2 == 0:
+          no tangent; else t_k = d / sqrt(n2)
+      first frame (step 2), at the first point k0 that has a tangent:  e = the unit axis of the first smallest |t_a|, w = cross(t, e),
+          u = w / sqrt(dot(w, w)), v = cross(t, u)
+      from point i to i + 1:  v1 = x_{i+1} - x_i, c1 = dot(v1, v1);  k1 = 2 / c1;  rL = u_i - (k1 dot(v1, u_i)) v1;
+          tL = t_i - (k1 dot(v1, t_i)) v1;  v2 = t_{i+1} - tL, c2 = dot(v2, v2);  w = rL when c2 == 0, else
+          w = rL - ((2 / c2) dot(v2, rL)) v2;  w <- w - dot(w, t_{i+1}) t_{i+1};  n = sqrt(dot(w, w));  u_{i+1} = w / n;
+          v_{i+1} = cross(t_{i+1}, u_{i+1})
+    A point without a tangent, with c1 == 0 or with n == 0 keeps the frame (t, u and v) of the point before it and gets flag FRAME_KEPT;
+    the points before k0 get the frame of k0 and the flag; a polyline without any tangent gets zeros.  NumPy on the host, point by point:
+    centrelines have hundreds to a few thousand points."""
+    import numpy as np
+    x = np.array(points, np.float64).reshape(-1, 3)
+    p, h = len(x), int(half_window)
+    if h < 1:
+        raise ValueError(f"rotation_minimising_frames: half_window must be at least 1, got {half_window!r}")
+    t, u, v, flags = np.zeros((p, 3)), np.zeros((p, 3)), np.zeros((p, 3)), np.zeros(p, np.int32)
+    if p == 0:
+        return t, u, v, flags
+    dot = lambda a, b: (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+    cross = lambda a, b: np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+    k = np.arange(p)
+    ia, ib = np.maximum(k - h, 0), np.minimum(k + h, p - 1)
+    d = x[ib] - x[ia]
+    n2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    has = (ib > ia) & (n2 > 0.0) & np.isfinite(n2)
+    t[has] = d[has] / np.sqrt(n2[has])[:, None]
+    if not has.any():
+        flags[:] = FRAME_KEPT
+        return t, u, v, flags
+    k0 = int(np.flatnonzero(has)[0])
+    e = np.eye(3)[int(np.argmin(np.abs(t[k0])))]
+    w = cross(t[k0], e)
+    u[k0] = w / np.sqrt(dot(w, w))
+    v[k0] = cross(t[k0], u[k0])
+    t[:k0], u[:k0], v[:k0], flags[:k0] = t[k0], u[k0], v[k0], FRAME_KEPT
+    for i in range(k0, p - 1):
+        v1 = x[i + 1] - x[i]
+        c1 = dot(v1, v1)
+        n = 0.0
+        if has[i + 1] and c1 > 0.0:
+            k1 = 2.0 / c1
+            r_l = u[i] - (k1 * dot(v1, u[i])) * v1
+            t_l = t[i] - (k1 * dot(v1, t[i])) * v1
+            v2 = t[i + 1] - t_l
+            c2 = dot(v2, v2)
+            w = r_l if c2 == 0.0 else r_l - ((2.0 / c2) * dot(v2, r_l)) * v2
+            w = w - dot(w, t[i + 1]) * t[i + 1]
+            n = np.sqrt(dot(w, w))
+        if n > 0.0:
+            u[i + 1] = w / n
+            v[i + 1] = cross(t[i + 1], u[i + 1])
+        else:
+            t[i + 1], u[i + 1], v[i + 1], flags[i + 1] = t[i], u[i], v[i], FRAME_KEPT
+    return t, u, v, flags
+
+
+def reformat_table_grid(k: int, step: float, tiled: bool = False):
+    """The sample table of a K x K cross-section, K = 2 k + 1, centred -> (table float64 [K K, 4], perm int64 [K K]).  Sample (i, j) lies
+    at (a, b) = ((i - k) step, (j - k) step) in the plane, no slab (sa = sb = 0); its row-order position is i K + j.  table[n] is the
+    sample perm[n]: tiled = False is the row order (perm = 0, 1, ..); tiled = True walks REFORMAT_TILE x REFORMAT_TILE tiles one after
+    another (tiles in row order, the samples of a tile in row order, the tiles at the high edges partial), so that 64 consecutive rows
+    cover a compact patch.  A result out [P, K K] of the table is put back into row order by `rows[:, perm] = out`."""
+    import numpy as np
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"reformat_table_grid: k must be >= 0, got {k}")
+    side = 2 * k + 1
+    i, j = np.divmod(np.arange(side * side, dtype=np.int64), side)
+    if tiled:
+        perm = np.lexsort((j, i, j // REFORMAT_TILE, i // REFORMAT_TILE)).astype(np.int64)      # the last key is the primary one
+    else:
+        perm = np.arange(side * side, dtype=np.int64)
+    table = np.zeros((side * side, REFORMAT_TABLE_DOUBLES), np.float64)
+    table[:, 0] = (i[perm] - k).astype(np.float64) * float(step)
+    table[:, 1] = (j[perm] - k).astype(np.float64) * float(step)
+    return table, perm
+
+
+def reformat_table_cpr(k: int, step: float, angles, slab_step=None):
+    """The sample table of longitudinal images at the in-plane angles `angles` (degrees) -> float64 [A K, 4], K = 2 k + 1: row (n, j) =
+    n K + j is the sample at r (cos theta_n, sin theta_n), r = (j - k) step, with the slab direction slab_step (-sin theta_n,
+    cos theta_n) at right angles to the line (slab_step: `step` unless given).  cos and sin by NumPy on the host, of np.deg2rad(theta)."""
+    import numpy as np
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"reformat_table_cpr: k must be >= 0, got {k}")
+    theta = np.deg2rad(np.asarray(angles, np.float64).reshape(-1))
+    cs, sn = np.cos(theta)[:, None], np.sin(theta)[:, None]
+    r = ((np.arange(2 * k + 1) - k).astype(np.float64) * float(step))[None, :]
+    sl = float(step if slab_step is None else slab_step)
+    one = np.ones_like(r)
+    return np.stack([r * cs, r * sn, (sl * -sn) * one, (sl * cs) * one], axis=2).reshape(-1, REFORMAT_TABLE_DOUBLES)
+
+
+def reformat_planes_record(volume: torch.Tensor, planes: torch.Tensor, table: torch.Tensor, world_to_index, fill: float = 0.0, half_slab: int = 0,
+                           mode: str = "mean", out=None):
+    """afx_reformat_planes on a contiguous float32 or float64 [n0, n1, n2] device volume, planes float64 [P, 9] (centre, u, v: world) and
+    table float64 [Q, 4] (a, b, sa, sb) on its device -> out float64 [P, Q]; the definition stands in include/afx.h.  world_to_index: 12
+    host numbers (`lumen_world_to_index`); mode "mean" or "max" over the slab of 2 half_slab + 1 samples.  Launches only: nothing is read
+    back, and with `out` passed nothing is allocated - the call can be captured in a graph."""
+    import numpy as np
+    lib = _lib.load()
+    _volume_on_gpu(volume, "the volume", "reformat_planes")
+    if volume.dtype not in (torch.float32, torch.float64) or not volume.is_contiguous():
+        raise ValueError(f"reformat_planes_record: the volume must be a contiguous float32 or float64 tensor, got {volume.dtype}, "
+                         f"contiguous = {volume.is_contiguous()}")
+    dev = volume.device
+    for t, name, cols in ((planes, "planes", REFORMAT_PLANE_DOUBLES), (table, "table", REFORMAT_TABLE_DOUBLES)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise AfxError(f"reformat_planes_record: {name} must be a tensor on a GPU; there is no CPU path")
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols or t.device != dev:
+            raise ValueError(f"reformat_planes_record: {name} must be contiguous float64 [n, {cols}] on {dev}")
+    if mode not in REFORMAT_MODES:
+        raise ValueError(f"reformat_planes_record: mode must be one of {sorted(REFORMAT_MODES)}, got {mode!r}")
+    w = np.ascontiguousarray(world_to_index, np.float64).reshape(-1)
+    if w.size != 12:
+        raise ValueError(f"reformat_planes_record: world_to_index must hold 12 numbers, got {w.size}")
+    p, q = planes.shape[0], table.shape[0]
+    if out is None:
+        out = torch.empty((p, q), dtype=torch.float64, device=dev)
+    if out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev or out.numel() != p * q:
+        raise ValueError(f"reformat_planes_record: out must be a contiguous float64 tensor of {p * q} elements on {dev}")
+    n0, n1, n2 = volume.shape
+    _lib.check(lib.afx_reformat_planes(_ptr(volume), int(volume.dtype == torch.float64), n0, n1, n2, w.ctypes.data_as(C.POINTER(C.c_double)),
+                                       _ptr(planes) if p else None, p, _ptr(table) if q else None, q, int(half_slab), REFORMAT_MODES[mode],
+                                       float(fill), _ptr(out) if p * q else None, Engine._stream(dev)), "afx_reformat_planes")
+    return out
+
+
+def _reformat_frames(volume, points, index_to_world, step, half_window, who):
+    """The shared front of straighten_volume and cpr_images: the frames of the polyline and the planes on the volume's device."""
+    import numpy as np
+    _volume_on_gpu(volume, "the volume", who)
+    if volume.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{who}: the volume must be float32 or float64, got {volume.dtype}")
+    pts = np.ascontiguousarray(_host(points), np.float64).reshape(-1, 3)
+    t, u, v, flags = rotation_minimising_frames(pts, half_window)
+    step = float(lumen_default_step(index_to_world) if step is None else step)
+    if not (step > 0.0 and np.isfinite(step)):
+        raise ValueError(f"{who}: step must be finite and > 0, got {step!r}")
+    planes = torch.from_numpy(np.ascontiguousarray(np.concatenate([pts, u, v], axis=1))).to(volume.device)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(volume.device)
+    fields = {"points": dev(pts), "t": dev(t), "u": dev(u), "v": dev(v), "arc_length": dev(_arc_length(pts)), "flags": dev(flags), "step": step}
+    return planes, fields
+
+
+def straighten_volume(volume: torch.Tensor, points, index_to_world=None, half_width: int = 16, step=None, half_window: int = 3, fill: float = 0.0,
+                      tiled=None) -> dict:
+    """The vessel straightened along a polyline (world points [P, 3], e.g. `polyline_resample` of a smoothed `centreline_main_path`): at
+    every point the K x K cross-section, K = 2 half_width + 1, of the trilinearly interpolated float32 / float64 [n0, n1, n2] device
+    volume in the plane of the point's rotation-minimising frame, sample (i, j) at c + (i - half_width) step u + (j - half_width) step v
+    (`fill` outside the volume).  step: world units, `lumen_default_step` unless given.  tiled: the order the sample table is handed over
+    in (None: REFORMAT_TILED); the result does not depend on it.  -> dict: volume (float64 [P, K, K]), points, t, u, v ([P, 3]),
+    arc_length, flags (int32 [P]: FRAME_KEPT) - device tensors - and step."""
+    import numpy as np
+    planes, out = _reformat_frames(volume, points, index_to_world, step, half_window, "straighten_volume")
+    table, perm = reformat_table_grid(half_width, out["step"], REFORMAT_TILED if tiled is None else bool(tiled))
+    side = 2 * int(half_width) + 1
+    got = reformat_planes_record(volume.contiguous(), planes, torch.from_numpy(table).to(volume.device), lumen_world_to_index(index_to_world), fill)
+    rows = torch.empty_like(got)
+    rows[:, torch.from_numpy(perm).to(volume.device)] = got
+    out["volume"] = rows.reshape(planes.shape[0], side, side)
+    return out
+
+
+def cpr_images(volume: torch.Tensor, points, index_to_world=None, angles=(0.0, 90.0), half_width: int = 16, step=None, slab: int = 0,
+               mode: str = "mean", half_window: int = 3, fill: float = 0.0) -> dict:
+    """Longitudinal (straightened curved-planar) images of a vessel along a polyline: image n, row p is the line through point p at the
+    in-plane angle angles[n] (degrees from u towards v of the point's rotation-minimising frame), K = 2 half_width + 1 samples `step`
+    apart, each the mean or the maximum (`mode`) over a slab of 2 slab + 1 samples `step` apart at right angles to the line.  -> the dict
+    of `straighten_volume` with images (float64 [A, P, K]) and angles in place of volume."""
+    import numpy as np
+    planes, out = _reformat_frames(volume, points, index_to_world, step, half_window, "cpr_images")
+    ang = np.asarray(angles, np.float64).reshape(-1)
+    table = reformat_table_cpr(half_width, out["step"], ang)
+    got = reformat_planes_record(volume.contiguous(), planes, torch.from_numpy(table).to(volume.device), lumen_world_to_index(index_to_world), fill,
+                                 int(slab), mode)
+    out["images"] = got.reshape(planes.shape[0], ang.size, 2 * int(half_width) + 1).permute(1, 0, 2).contiguous()
+    out["angles"] = ang
+    return out
+
+
+def centreline_cpr(graph: dict, volume: torch.Tensor, index_to_world, d2=None, smooth_passes: int = 8, spacing=None, start=None, end=None,
+                   **kw) -> dict:
+    """`cpr_images` along the main path of a `centreline_graph` result: `centreline_main_path` (d2: the squared EDT, for the ostium side),
+    `polyline_smooth(smooth_passes)`, `polyline_resample(spacing)` (spacing: the smallest voxel step unless given), then the images.
+    -> the dict of `cpr_images` plus path (the dict of `centreline_main_path`) and spacing."""
+    _volume_on_gpu(volume, "the volume", "centreline_cpr")
+    a = _affine12(index_to_world, "centreline_cpr")
+    path = centreline_main_path(graph, a, start=start, end=end, d2=d2)
+    spacing = float(2.0 * lumen_default_step(a) if spacing is None else spacing)
+    pts = polyline_resample(polyline_smooth(path["points"], smooth_passes), spacing)
+    out = cpr_images(volume, pts, a, **kw)
+    out.update(path=path, spacing=spacing)
+    return out
+
+
 def frangi_3d_record(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta: float = 0.5, gamma=None, black_ridges: bool = False, out=None,
                      scale_index=None, workspace=None, want_scale: bool = True):
     """afx_frangi_3d on a contiguous float32 or float64 [n0, n1, n2] device volume -> (out float64 [n0, n1, n2], scale_index uint8

@@ -132,6 +132,15 @@ def build_parser():
                         'centreline of --save_centreline at --mesh_threshold, and at each of its points the area and the diameters of the '
                         'cross-section of the density grid at that level (afx_lumen_profile: 64 rays in the plane normal to the centreline, '
                         'crossings interpolated below the voxel), one row per point; without the flag nothing changes')
+    p.add_argument('--save_cpr', default=None, metavar='PATH',
+                   help='after training, write the curved-planar reformation of the final model\'s vessel to PATH (.npy, float64 [A, P, K]): the '
+                        'main path of the pruned centreline of --save_centreline at --mesh_threshold (from the widest free end to the farthest '
+                        'one), smoothed and resampled at the grid step, and along it the longitudinal images of the density grid at the '
+                        'in-plane angles --cpr_angles, K = 2 --cpr_half_width + 1 samples half a grid step apart (afx_reformat_planes on '
+                        'rotation-minimising frames); without the flag nothing changes')
+    p.add_argument('--cpr_angles', type=float, nargs='+', default=[0.0, 45.0, 90.0, 135.0], metavar='DEGREES',
+                   help='--save_cpr: the in-plane angles of the longitudinal images')
+    p.add_argument('--cpr_half_width', type=int, default=16, metavar='K', help='--save_cpr: samples on either side of the centreline')
     p.add_argument('--save_view_map', default=None, metavar='PATH',
                    help='after training, write the foreshortening and overlap map of the final model\'s vessel centreline to PATH (.csv): the '
                         'pruned centreline of --save_centreline at --mesh_threshold with its radii, scored over the evaluation sweep\'s angles '
@@ -255,6 +264,15 @@ def check_args(args):
             raise ValueError("--save_lumen: PATH must end in .csv")
         if not args.mesh_threshold > 0:
             raise ValueError("--mesh_threshold: needs SIGMA > 0")
+    if args.save_cpr is not None:
+        if os.path.splitext(args.save_cpr)[1].lower() != '.npy':
+            raise ValueError("--save_cpr: PATH must end in .npy")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
+        if not args.cpr_angles or not all(np.isfinite(a) for a in args.cpr_angles):
+            raise ValueError("--cpr_angles: needs at least one finite angle")
+        if not 0 <= args.cpr_half_width <= 511:
+            raise ValueError("--cpr_half_width: needs K in 0..511")
     if args.save_view_map is not None:
         if os.path.splitext(args.save_view_map)[1].lower() != '.csv':
             raise ValueError("--save_view_map: PATH must end in .csv")
@@ -582,7 +600,7 @@ def main(argv=None):
     exports = (('mesh_info', save_mesh, args.save_mesh), ('centreline_info', save_centreline, args.save_centreline),
                ('lumen_info', save_lumen, args.save_lumen))
     exports = [e for e in exports if e[2] is not None]
-    if exports or args.save_view_map is not None:      # the density grid the exports read, evaluated once
+    if exports or args.save_view_map is not None or args.save_cpr is not None:      # the density grid the exports read, evaluated once
         from ..render import density_grid
         grid = density_grid(coarse_model, outside, depth_samples_per_ray_coarse)
     for key, save, path in exports:
@@ -592,6 +610,9 @@ def main(argv=None):
         result['view_map_info'] = save_view_map(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_view_map,
                                                 sweep_angles(limited_size, args.view_map_step), img_width, img_height,
                                                 float(proj_df['focal_length'].iloc[0]), (0.0, 0.0, src_pt_z), grid=grid)
+    if args.save_cpr is not None:
+        result['cpr_info'] = save_cpr(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_cpr, args.cpr_angles,
+                                      args.cpr_half_width, grid=grid)
     if args.save_sirt is not None:
         mask = acc_grid._carve_u8 if acc_grid is not None and args.grid_init == 'hull' else None      # the hull the grids were carved with
         result['sirt_info'] = save_sirt(proj_df, train_ray_df, test_proj_id, [-outside] * 3 + [outside] * 3, 128, near_thresh, far_thresh,
@@ -783,6 +804,37 @@ def save_lumen(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
     info = dict(path=str(path), n_points=n_points, n_valid=int((host['flags'] == 0).sum()), max_area_stenosis=worst[0], branch=worst[1],
                 threshold=float(threshold))
     print('lumen', info, flush=True)
+    return info
+
+
+def save_cpr(model, outside, n, threshold, path, angles, half_width=16, prune_factor=1.0, smooth_passes=8, grid=None):
+    """--save_cpr: the longitudinal images (`engine.centreline_cpr`: afx_reformat_planes) of the model's density grid (n points per axis
+    over [-outside, outside]^3) along the main path of the pruned centreline of {sigma >= threshold} (that of --save_centreline), smoothed
+    and resampled at the grid step, written as a float64 [A, P, K] array -> its info (path, shape, angles, step, n_rows, rows_flagged,
+    branches, path_length, threshold).  A centreline without a free end (an empty mask among them) writes an array of no rows.  grid: as
+    in `save_mesh`."""
+    from ..engine import centreline_cpr
+    grid = _export_grid(model, outside, n, grid)
+    tree, a = _export_tree(grid, outside, n, threshold, prune_factor)
+    angles = [float(x) for x in angles]
+    step = float(outside) / (int(n) - 1)                  # half the grid step
+    info = dict(branches=[], path_length=0.0, rows_flagged=0)
+    images = np.zeros((len(angles), 0, 2 * int(half_width) + 1), np.float64)
+    try:
+        cpr = centreline_cpr(tree['graph'], grid, a, d2=tree['d2'], smooth_passes=smooth_passes, angles=angles, half_width=half_width, step=step)
+    except ValueError as e:
+        if 'centreline_main_path' not in str(e):
+            raise
+        info['reason'] = str(e)
+    else:
+        images = cpr['images'].cpu().numpy()
+        info.update(branches=cpr['path']['branches'], path_length=cpr['path']['length'], rows_flagged=int((cpr['flags'] != 0).sum()))
+    tmp = f'{path}.tmp.{os.getpid()}'
+    with open(tmp, 'wb') as f:
+        np.save(f, images)
+    os.replace(tmp, path)
+    info.update(path=str(path), shape=tuple(images.shape), angles=angles, step=step, n_rows=int(images.shape[1]), threshold=float(threshold))
+    print('cpr', info, flush=True)
     return info
 
 

@@ -61,6 +61,11 @@ SIRT_TV_METRICS = ("DICE 3D SIRT-TV", "TV GAIN 3D", "CORR 3D SIRT-TV")
 # afx_view_map) of the two pruned centrelines over the sweep's own angles, a tuple of its own behind all the families above; it needs
 # the ground-truth volume
 VIEW_METRICS = ("FORESHORTENING ERR 3D", "OVERLAP ERR 3D", "VIEW REGRET 3D")
+# and the picture behind the lumen numbers: the longitudinal (curved-planar reformation) images of the two grids along the main path of
+# the TRUE centreline (engine.cpr_images: afx_reformat_planes), compared as images; a tuple of its own behind the view columns; it needs
+# the ground-truth volume
+CPR_METRICS = ("CPR PSNR 3D", "CPR SSIM 3D", "CPR CORR 3D")
+CPR_MIN_ROWS = 11                     # afx_ssim takes images of at least 11 x 11
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -181,6 +186,13 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
                                           grids=analysis)[0]
         for name, key in zip(VIEW_METRICS, ("foreshortening_err", "overlap_err", "view_regret")):
             scores[name] = [got[key]] * n
+    if any(m in want for m in CPR_METRICS):                   # behind the view columns
+        if analysis is None:
+            pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+            analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
+        got = reconstruction_cpr_metrics(model, volume, volume_outside, pts, grids=analysis)[0]
+        for name, key in zip(CPR_METRICS, ("cpr_psnr", "cpr_ssim", "cpr_corr")):
+            scores[name] = [got[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -191,7 +203,7 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS + CPR_METRICS
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
@@ -219,7 +231,7 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     tv = [m for m in metrics if m in SIRT_TV_METRICS]
     if tv and sirt_tv_weight is None:
         raise ValueError(f"evaluation_sweep: {tv} need the weight of the total variation (sirt_tv_weight=W)")
-    view = [m for m in metrics if m in VIEW_METRICS]
+    view = [m for m in metrics if m in VIEW_METRICS + CPR_METRICS]
     if view and volume is None:
         raise ValueError(f"evaluation_sweep: {view} need the ground-truth volume (volume=VoxelVolume)")
     return [m for m in known if m in metrics]
@@ -747,6 +759,60 @@ def reconstruction_view_metrics(model, volume, outside, n, angles, img_width=100
         view_scores(maps[0], maps[1], overlap_weight)
     scores["threshold"] = thr
     return scores, maps[0], maps[1]
+
+
+def cpr_scores(images_p, images_g):
+    """The scores of `reconstruction_cpr_metrics` from the two image stacks [A, P, K] (read back: NumPy fp64) but for the SSIM, NumPy fp64
+    on the host -> (scores, the two stacks as they are compared).  Both stacks are divided by the largest value of the truth's and
+    clamped to [0, 1]; cpr_psnr = -10 log10(mean((p - g)^2)) over all angles (data range 1; inf when the stacks agree); cpr_corr =
+    Pearson's correlation over all pixels (NaN when either stack is constant).  A truth without a positive value scores NaN."""
+    nan = float("nan")
+    # C-contiguous copies: NumPy's sums run pairwise over the memory order, so a transposed view of the same numbers may round differently
+    p, g = np.ascontiguousarray(images_p, np.float64), np.ascontiguousarray(images_g, np.float64)
+    top = float(g.max()) if g.size else 0.0
+    if not top > 0.0:
+        return {"cpr_psnr": nan, "cpr_corr": nan}, p, g
+    p, g = np.clip(p / top, 0.0, 1.0), np.clip(g / top, 0.0, 1.0)
+    mse = float(np.mean((p - g) ** 2))
+    dp, dg = p - p.mean(), g - g.mean()
+    den = float(np.sqrt((dp * dp).sum() * (dg * dg).sum()))
+    with np.errstate(divide="ignore"):
+        return {"cpr_psnr": float(-10.0 * np.log10(mse)), "cpr_corr": float((dp * dg).sum() / den) if den > 0 else nan}, p, g
+
+
+@torch.no_grad()
+def reconstruction_cpr_metrics(model, volume, outside, n, threshold=None, angles=(0.0, 45.0, 90.0, 135.0), half_width=16, prune_factor=1.0,
+                               smooth_passes=8, grids=None):
+    """Does the straightened vessel look like the true one -> (scores, image stack of the prediction, of the truth, the path).
+
+    The path is the main path (`engine.centreline_main_path`: from the ostium side to the farthest end) of the pruned TRUE centreline of
+    `reconstruction_graph_metrics` (same threshold, prune_factor), so no branch of one graph has to be matched with a branch of the
+    other; it is smoothed (`engine.polyline_smooth`, smooth_passes) and resampled at the grid step (`engine.polyline_resample`).
+    `engine.cpr_images` (afx_reformat_planes: include/afx.h) takes the longitudinal images of the predicted and of the true grid along it
+    at `angles` (degrees), K = 2 half_width + 1 samples half a grid step apart.  Both stacks [A, P, K] are read back and scored on the
+    host (`cpr_scores`): cpr_psnr, cpr_corr, and cpr_ssim = the mean over the angles of `engine.ssim` of the normalised images; n_rows =
+    P, path_length (the graph length of the path, world units), path_share = path_length / the total centreline length, threshold.
+    NaN where a divisor is empty.  ValueError when either mask is empty, the true centreline has no free end, or the path has fewer
+    than CPR_MIN_ROWS rows (or K is below it).  grids: as in `reconstruction_surface_metrics`."""
+    from ..engine import cpr_images, centreline_main_path, polyline_resample, polyline_smooth, ssim
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    _refuse_empty("reconstruction_cpr_metrics", *an.masks(thr)[2:], "volume has no centreline")
+    if 2 * int(half_width) + 1 < CPR_MIN_ROWS:
+        raise ValueError(f"reconstruction_cpr_metrics: half_width = {half_width} gives images narrower than {CPR_MIN_ROWS} samples")
+    tree = an.tree("gt", thr, prune_factor=prune_factor)
+    path = centreline_main_path(tree["graph"], an.index_to_world, d2=tree["d2"])
+    points = polyline_resample(polyline_smooth(path["points"], smooth_passes), an.voxel)
+    if len(points) < CPR_MIN_ROWS:
+        raise ValueError(f"reconstruction_cpr_metrics: the main path has {len(points)} rows, the SSIM needs {CPR_MIN_ROWS}")
+    stacks = [cpr_images(x, points, an.index_to_world, angles, half_width)["images"].cpu().numpy() for x in (an.pred, an.gt)]
+    scores, p, g = cpr_scores(*stacks)
+    scores["cpr_ssim"] = float("nan")
+    if scores["cpr_psnr"] == scores["cpr_psnr"]:
+        dev = an.pred.device
+        scores["cpr_ssim"] = float(ssim(torch.from_numpy(p).to(dev), torch.from_numpy(g).to(dev)).mean())
+    total = float(tree["graph"]["total_length"])
+    scores.update(n_rows=len(points), path_length=path["length"], path_share=path["length"] / total if total > 0 else float("nan"), threshold=thr)
+    return scores, stacks[0], stacks[1], dict(path, resampled=points)
 
 
 def centreline_polylines(graph, d2, index_to_world, voxel_size=1.0):
