@@ -346,7 +346,10 @@ typedef struct afx_grid_desc {
 int afx_grid_points(const afx_grid_desc* grid, const int32_t* cell_idx, int64_t n, const float* jitter, uint64_t seed,
                     uint64_t stream_id, float* pts, void* stream);
 /* step 2: occs[c] = max(occs[c] * ema_decay, occ_new) for the selected cells; deterministic when a cell is selected more
- * than once (max over its draws).  occs_scratch: n_cells floats (snapshot of occs). */
+ * than once (max over its draws).  occs_scratch: n_cells floats (snapshot of occs).  cell_idx (here and in afx_grid_points): every index
+ * in [0, num_cells), unchecked - a check would need a device read; NULL: cells 0..n-1, n <= num_cells.  A selected cell first drops to
+ * its decayed value, taken once from the snapshot however often it is drawn (not above 0: +0), then rises to the largest of its draws
+ * that are > 0; draws that are 0, negative or NaN change nothing, and cells that are not selected keep their bits. */
 int afx_grid_update(const afx_grid_desc* grid, float* occs, float* occs_scratch, const int32_t* cell_idx, int64_t n,
                     const float* occ_new, float ema_decay, void* stream);
 /* step 3: binary[c] = occs[c] > min(mean(occs), occ_thre) as bytes (the module's `binary` tensor) and as the packed

@@ -60,6 +60,22 @@ __device__ __forceinline__ bool grid_cell(const GridDesc& g, float px, float py,
   return inside;
 }
 
+// One fp32 operation, rounded on its own.  HIP's __fadd_rn / __fmul_rn are plain operators inside header functions that allow contraction, and
+// hipcc fuses __fadd_rn(__fmul_rn(a, b), c) into one fma; these carry the contraction-off pragma in their own bodies, so a product formed by
+// mul_rn reaches the following add_rn already rounded.
+__device__ __forceinline__ float add_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+__device__ __forceinline__ float sub_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x - y;
+}
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+
 // --- OccupancyGrid._update, step 1: one jittered world point per selected cell -----------------------------------
 // cell_idx == nullptr: all cells (cell i).  jitter [n,3] in [0,1) (parity mode) or nullptr: Philox(seed, stream 3*?).
 // afx_grid_refresh: count_dev bounds the work of a launch sized for the capacity n, and the stream id is stream | *step_dev, the training
@@ -77,9 +93,9 @@ __global__ void k_grid_points(const int32_t* cell_idx, int64_t n, const float* j
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float u = jitter ? jitter[3 * i + a] : philox_uniform(seed, stream, 3 * (uint64_t)i + a);
-    // x = (coords + u) / resolution; x * (hi - lo) + lo
-    const float x = __fdiv_rn(__fadd_rn((float)ijk[a], u), (float)g.res[a]);
-    pts[3 * i + a] = __fadd_rn(__fmul_rn(x, __fsub_rn(g.hi[a], g.lo[a])), g.lo[a]);
+    // x = (coords + u) / resolution; x * (hi - lo) + lo, the product and the sum rounded separately as in the torch expression
+    const float x = __fdiv_rn(add_rn((float)ijk[a], u), (float)g.res[a]);
+    pts[3 * i + a] = add_rn(mul_rn(x, sub_rn(g.hi[a], g.lo[a])), g.lo[a]);
   }
 }
 
@@ -224,21 +240,9 @@ __global__ void k_grid_select(const uint32_t* bits, int64_t n_cells, int64_t n_w
 
 // --- ray marching (nerfacc.ray_marching, fixed-step lattice, AABB contraction) ----------------------------------------
 // Every operation of the lattice t_min + k dt, of the mid-points and of the position a step is decided at is rounded on its own (add_rn, sub_rn,
-// mul_rn below).  HIP's __fadd_rn / __fmul_rn are plain operators inside header functions that allow contraction, and hipcc fused
-// t_min + k dt and o + d m into one fma each: the lattice then differed by an ulp from the oracle's and from the one the host's
-// afx_march_max_steps walks, and a ray starting at max(0, near) could keep one step more than that bound.
-__device__ __forceinline__ float add_rn(float x, float y) {
-#pragma clang fp contract(off)
-  return x + y;
-}
-__device__ __forceinline__ float sub_rn(float x, float y) {
-#pragma clang fp contract(off)
-  return x - y;
-}
-__device__ __forceinline__ float mul_rn(float x, float y) {
-#pragma clang fp contract(off)
-  return x * y;
-}
+// mul_rn above k_grid_points).  hipcc fused t_min + k dt and o + d m into one fma each when they were written with __fadd_rn / __fmul_rn: the
+// lattice then differed by an ulp from the oracle's and from the one the host's afx_march_max_steps walks, and a ray starting at max(0, near)
+// could keep one step more than that bound.
 struct MarchArgs {
   const float* org; const float* dir;      // [R,3]
   int64_t n_rays;

@@ -850,42 +850,106 @@ def philox_uniform(seed: int, stream_id: int, n: int, device) -> torch.Tensor:
     return out
 
 
+def _grid_args(fn, resolution, named):
+    """What the occupancy-grid wrappers hand to the library by pointer, in the style of grid_apply_mask and _packed_args: `named`
+    [(name, tensor or None, dtype, entries, at_least)] - every tensor that is given must have exactly that dtype, be contiguous and hold
+    `entries` elements (at_least: that many or more), all of them on the one GPU of the first.  Nothing is converted: a violation is a
+    ValueError naming the argument, raised before the library is called (an int64 cell_idx or a short bits tensor would otherwise go
+    straight to a kernel).  Types and sizes are checked before the devices.  The VALUES of cell_idx are not checked - that would need a
+    device read -: every index must lie in [0, num_cells) (include/afx.h).  -> the device."""
+    given = [e for e in named if e[1] is not None]
+    for name, t, dtype, count, at_least in given:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{fn}: {name}: expected a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{fn}: {name}: dtype {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{fn}: {name}: expected a contiguous tensor")
+        if t.numel() < count if at_least else t.numel() != count:
+            raise ValueError(f"{fn}: {name}: {t.numel()} entries, expected {'at least ' if at_least else ''}{count} "
+                             f"(resolution {list(resolution)})")
+    dev = given[0][1].device
+    for name, t, _, _, _ in given:
+        if t.device.type != "cuda":
+            raise ValueError(f"{fn}: {name} must live on the GPU; there is no CPU fallback")
+        if t.device != dev:
+            raise ValueError(f"{fn}: {name}: on {t.device}, expected {dev}")
+    return dev
+
+
+def _num_cells(resolution) -> int:
+    r = [int(x) for x in resolution]
+    return r[0] * r[1] * r[2]
+
+
 def grid_points(roi_aabb, resolution, cell_idx, n, jitter=None, seed=0, stream_id=0, device=None):
+    """afx_grid_points: one jittered world point per selected cell -> [n, 3].  cell_idx: None (cells 0 .. n-1) or int32 [n], every index in
+    [0, num_cells), unchecked; jitter: None (the Philox stream (seed, stream_id)) or float32 [n, 3]."""
     lib = _lib.load()
-    dev = device if device is not None else (cell_idx.device if cell_idx is not None else jitter.device)
-    if torch.device(dev).type != "cuda":
-        raise AfxError("grid_points: the occupancy grid lives on a GPU; there is no CPU fallback")
+    n = int(n)
+    if cell_idx is not None and (not isinstance(cell_idx, torch.Tensor) or cell_idx.dim() != 1):
+        raise ValueError("grid_points: cell_idx: expected a 1-D tensor")
+    if jitter is not None and (not isinstance(jitter, torch.Tensor) or tuple(jitter.shape) != (n, 3)):
+        raise ValueError(f"grid_points: jitter: expected a tensor of shape [{n}, 3]")
+    named = [("cell_idx", cell_idx, torch.int32, n, False), ("jitter", jitter, torch.float32, 3 * n, False)]
+    if cell_idx is None and jitter is None:
+        dev = torch.device(device) if device is not None else None
+        if dev is None or dev.type != "cuda":
+            raise AfxError("grid_points: the occupancy grid lives on a GPU; there is no CPU fallback")
+    else:
+        dev = _grid_args("grid_points", resolution, named)
+        if device is not None and torch.device(device).index not in (None, dev.index):
+            raise ValueError(f"grid_points: device {device}, but the tensors are on {dev}")
     g = _grid_desc(roi_aabb, resolution)
-    pts = torch.empty(int(n), 3, dtype=torch.float32, device=dev)
-    if jitter is not None:
-        jitter = _f32(jitter, "jitter", pts.device)
-    _lib.check(lib.afx_grid_points(C.byref(g), _ptr(cell_idx), int(n), _ptr(jitter), int(seed), int(stream_id), _ptr(pts),
+    pts = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    _lib.check(lib.afx_grid_points(C.byref(g), _ptr(cell_idx), n, _ptr(jitter), int(seed), int(stream_id), _ptr(pts),
                                    Engine._stream(pts.device)), "afx_grid_points")
     return pts
 
 
 def grid_update(roi_aabb, resolution, occs, cell_idx, occ_new, ema_decay, scratch):
+    """afx_grid_update, in place: occs[c] = max(occs[c] * ema_decay, occ_new) over the selected cells.  occs, scratch: float32 [num_cells];
+    cell_idx: None (cells 0 .. n-1) or int32 [n], every index in [0, num_cells), unchecked; occ_new: float32, n entries."""
     lib = _lib.load()
+    if not isinstance(occ_new, torch.Tensor):
+        raise ValueError("grid_update: occ_new: expected a tensor")
+    if cell_idx is not None and (not isinstance(cell_idx, torch.Tensor) or cell_idx.dim() != 1):
+        raise ValueError("grid_update: cell_idx: expected a 1-D tensor")
+    nc, n = _num_cells(resolution), occ_new.numel()
+    if cell_idx is None and n > nc:
+        raise ValueError(f"grid_update: occ_new: {n} entries for the first cells of a grid of {nc}")
+    occ_new = occ_new.reshape(-1)
+    occ_new = occ_new if occ_new.is_contiguous() else occ_new.contiguous()
+    dev = _grid_args("grid_update", resolution, [("occs", occs, torch.float32, nc, False), ("scratch", scratch, torch.float32, nc, False),
+                                                 ("cell_idx", cell_idx, torch.int32, n, False), ("occ_new", occ_new, torch.float32, n, False)])
     g = _grid_desc(roi_aabb, resolution)
-    occ_new = _f32(occ_new.reshape(-1), "occ_new", occs.device)
-    _lib.check(lib.afx_grid_update(C.byref(g), _ptr(occs), _ptr(scratch), _ptr(cell_idx), occ_new.numel(), _ptr(occ_new),
-                                   float(ema_decay), Engine._stream(occs.device)), "afx_grid_update")
+    _lib.check(lib.afx_grid_update(C.byref(g), _ptr(occs), _ptr(scratch), _ptr(cell_idx), n, _ptr(occ_new),
+                                   float(ema_decay), Engine._stream(dev)), "afx_grid_update")
 
 
 def grid_binarize(roi_aabb, resolution, occs, occ_thre, binary_u8, bits, partial_ws):
+    """afx_grid_binarize: binary_u8[c] = occs[c] > min(mean(occs), occ_thre) and the march's bitfield.  occs float32 and binary_u8 uint8
+    [num_cells], bits int32 [(num_cells + 31) // 32], partial_ws float64, at least 256 entries."""
     lib = _lib.load()
+    nc = _num_cells(resolution)
+    dev = _grid_args("grid_binarize", resolution, [("occs", occs, torch.float32, nc, False), ("binary_u8", binary_u8, torch.uint8, nc, False),
+                                                   ("bits", bits, torch.int32, (nc + 31) // 32, False),
+                                                   ("partial_ws", partial_ws, torch.float64, 256, True)])
     g = _grid_desc(roi_aabb, resolution)
     _lib.check(lib.afx_grid_binarize(C.byref(g), _ptr(occs), float(occ_thre), _ptr(binary_u8), _ptr(bits), _ptr(partial_ws),
-                                     Engine._stream(occs.device)), "afx_grid_binarize")
+                                     Engine._stream(dev)), "afx_grid_binarize")
 
 
 def grid_pack(roi_aabb, resolution, binary_u8, bits):
-    """afx_grid_pack: the march's bitfield from a byte mask (a restored grid)."""
+    """afx_grid_pack: the march's bitfield from a byte mask (a restored grid).  binary_u8 uint8 [num_cells], bits int32
+    [(num_cells + 31) // 32]."""
     lib = _lib.load()
-    if binary_u8.device.type != "cuda":
+    if isinstance(binary_u8, torch.Tensor) and binary_u8.device.type != "cuda":
         raise AfxError("grid_pack: the occupancy grid lives on a GPU; there is no CPU fallback")
+    nc = _num_cells(resolution)
+    dev = _grid_args("grid_pack", resolution, [("binary_u8", binary_u8, torch.uint8, nc, False), ("bits", bits, torch.int32, (nc + 31) // 32, False)])
     g = _grid_desc(roi_aabb, resolution)
-    _lib.check(lib.afx_grid_pack(C.byref(g), _ptr(binary_u8), _ptr(bits), Engine._stream(binary_u8.device)), "afx_grid_pack")
+    _lib.check(lib.afx_grid_pack(C.byref(g), _ptr(binary_u8), _ptr(bits), Engine._stream(dev)), "afx_grid_pack")
 
 
 def _step_args(step, dev, who):

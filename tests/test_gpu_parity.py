@@ -1240,14 +1240,15 @@ def test_grid_kernels_vs_oracle():
     aabb = torch.tensor([-100.0, -80, -100, 100, 120, 90])
     res = (16, 12, 20)
     nc = res[0] * res[1] * res[2]
-    # --- points of jittered cells, all cells and an index list with duplicates
+    # --- points of jittered cells, all cells and an index list with duplicates: the kernel rounds x (hi - lo) and the sum separately, as the
+    # torch expression does, so the points are equal (tests/test_gpu_grid_update.py compares the bits on ragged grids and the Philox path)
     jit = torch.rand(nc, 3, generator=g)
     pts = eng.grid_points(aabb.tolist(), res, None, nc, jitter=jit.to(DEV), device=torch.device(DEV))
-    same(pts, orc.grid_jittered_points(torch.arange(nc), jit, aabb, res), "points", 220.0)
+    assert torch.equal(pts.cpu(), orc.grid_jittered_points(torch.arange(nc), jit, aabb, res)), "points"
     cells = torch.randint(nc, (1500,), generator=g)
     cells[100:200] = cells[0:100]                                          # duplicates
     pts2 = eng.grid_points(aabb.tolist(), res, cells.to(DEV, torch.int32), cells.numel(), jitter=jit[:1500].to(DEV))
-    same(pts2, orc.grid_jittered_points(cells, jit[:1500], aabb, res), "points (index list)", 220.0)
+    assert torch.equal(pts2.cpu(), orc.grid_jittered_points(cells, jit[:1500], aabb, res)), "points (index list)"
     # --- update rule + binarisation
     occs0 = torch.rand(nc, generator=g) * (torch.rand(nc, generator=g) < 0.3)
     occ_new = torch.rand(1500, generator=g) * 0.8

@@ -1,0 +1,247 @@
+"""The problems of tests/test_gpu_grid_update.py and what that file assumes of them (no GPU needed): the restatement of
+tests/grid_reference.py on hand-made cases and against oracle.grid_update, the share of points a contracted kernel would get wrong on each
+box, the planted cells and draws of the update problems, the ties of the exact binarize problems, the rounding margins of the random ones,
+and the wrappers' refusals that need no device.  The figures printed here are the ones DESIGN 1.19 quotes."""
+import numpy as np
+import pytest
+import torch
+
+import grid_reference as gr
+from test_grid_refresh_cpu import JITTER_TAG, philox_u24
+
+F32 = np.float32
+UPDATE_GRIDS = [r for r in gr.GRIDS if gr.num_cells(r) > 1]
+BINARIZE_GRIDS = [r for r in gr.GRIDS if gr.num_cells(r) > 32]
+
+
+def test_grids_are_the_ragged_ones():
+    cells = [gr.num_cells(r) for r in gr.GRIDS]
+    assert cells == [1, 105, 257, 2079, 4096, 24679]
+    assert [c % 32 for c in cells] == [1, 9, 1, 31, 0, 7] and [(c + 31) // 32 for c in cells] == [1, 4, 9, 65, 128, 772]
+    assert (24679 + 31) // 32 > 3 * 256                                     # four 256-word blocks of k_grid_binarize / k_grid_pack
+    per = [(c + 255) // 256 for c in cells]                                 # k_grid_sum's slice per workgroup, 256 workgroups
+    assert per == [1, 1, 2, 9, 16, 97]
+    assert 256 * 2 - 257 > 2 * 127 and 24679 - 254 * 97 == 41               # 257: 127 empty slices; 24679: one short slice, one empty
+    for box in gr.BOXES:
+        ext = np.array(box[3:], F32) - np.array(box[:3], F32)
+        assert all(float(np.log2(e)) % 1 != 0 for e in ext), ext
+
+
+def test_points_on_hand_made_cells():
+    """The flat index decodes as ((i r1) + j) r2 + k, and the four roundings are what they claim on numbers small enough to follow by hand."""
+    res, box = (5, 3, 7), [0.0, 0.0, 0.0, 5.0, 3.0, 7.0]
+    cells = np.array([0, 1, 7, 21, 104, 52])
+    ijk = np.array([[0, 0, 0], [0, 0, 1], [0, 1, 0], [1, 0, 0], [4, 2, 6], [2, 1, 3]])
+    assert np.array_equal((ijk[:, 0] * 3 + ijk[:, 1]) * 7 + ijk[:, 2], cells)
+    half = np.full((6, 3), 0.5, F32)
+    p = gr.points(cells, half, box, res)
+    want = ((ijk.astype(F32) + F32(0.5)) / np.array(res, F32)) * np.array(res, F32)
+    assert p.dtype == np.float32 and np.array_equal(gr.bits_of(p), gr.bits_of(want.astype(F32)))
+    assert np.abs(p - (ijk + 0.5)).max() < 1e-6
+    # a point drawn at 1 - 2^-24 need not stay in its cell: from ijk >= 2 on the sum ijk + u rounds up to ijk + 1, at ijk = 1
+    # it is a tie that goes to the even 2 (the reference formula does the same)
+    top = gr.points(np.array([104]), np.full((1, 3), gr.TOP, F32), box, res)
+    assert (F32(4) + gr.TOP == F32(5)) and (F32(1) + gr.TOP == F32(2)) and (F32(0) + gr.TOP < F32(1)) and top[0, 0] == F32(5.0)
+
+
+@pytest.mark.parametrize("box", gr.BOXES, ids=["box0", "box1"])
+def test_a_contracted_kernel_cannot_pass_by_luck(box):
+    """points differs from the fused form (fp64 product and sum, rounded once) on more than 30 % of the points of the problems on this box
+    (a point differs when one of its coordinates does; the share of coordinates is printed beside it), on some point of every problem of
+    more than one cell, and nowhere on a box with power-of-two extents - which is why no test uses one.  The two forms are never further apart than the roundings allow: half an ulp of the product (at most the extent) for the extra
+    rounding, and one ulp of the result (at most the box's largest coordinate) between two roundings of numbers that close."""
+    ext = np.array(box[3:], F32) - np.array(box[:3], F32)
+    bar = 0.5 * float(np.spacing(ext.max())) + float(np.spacing(np.abs(np.array(box, F32)).max()))
+    differ, total, shares, worst, coords = 0, 0, {}, 0.0, np.zeros(3, np.int64)
+    for res in gr.GRIDS:
+        n = gr.num_cells(res)
+        for kind, cells in (("all", np.arange(n)), ("list", gr.index_list(res))):
+            jit = gr.jitter_problem(cells.size, 1 if kind == "all" else 2)
+            a, b = gr.points(cells, jit, box, res), gr.points_fused(cells, jit, box, res)
+            dc = gr.bits_of(a) != gr.bits_of(b)
+            d = dc.any(1)
+            coords += dc.sum(0)
+            differ, total, shares[(res, kind)] = differ + int(d.sum()), total + d.size, float(d.mean())
+            worst = max(worst, float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max()))
+            assert n == 1 or d.any(), (res, kind)
+    big = gr.GRIDS[-1]
+    print(f"box {box}: the fused form differs on {100 * differ / total:.1f} % of {total} points ({100 * shares[(big, 'all')]:.1f} % on {big}, "
+          f"per problem {min(shares.values()):.3f} .. {max(shares.values()):.3f}; of the coordinates, per axis "
+          f"{[round(100 * float(c) / total, 1) for c in coords]} %), by at most {worst:.3g} (bar {bar:.3g})")
+    assert differ / total > 0.30 and shares[(big, "all")] > 0.30 and shares[(big, "list")] > 0.30
+    assert worst <= bar
+    dyadic, n = [-64.0, -128.0, 1024.0, 64.0, 128.0, 1536.0], gr.num_cells(big)
+    a, b = gr.points(np.arange(n), gr.jitter_problem(n, 1), dyadic, big), gr.points_fused(np.arange(n), gr.jitter_problem(n, 1), dyadic, big)
+    assert np.array_equal(gr.bits_of(a), gr.bits_of(b))
+
+
+def test_jitter_problems_and_the_philox_jitter():
+    for n in (1, 7, 105, 24679):
+        u = gr.jitter_problem(n, 3)
+        assert u.dtype == np.float32 and u.shape == (n, 3) and u.min() >= 0 and u.max() < 1
+        if n >= 3:
+            assert (u[1] == 0).all() and (u[2] == gr.TOP).all() and F32(1) - gr.TOP == F32(2.0 ** -24)
+    j = gr.philox_jitter(5, JITTER_TAG | 272, 1000)
+    assert j.dtype == np.float32 and j.shape == (1000, 3) and j.min() >= 0 and j.max() < 1
+    assert np.array_equal(j.reshape(-1).astype(np.float64) * (1 << 24), philox_u24(5, JITTER_TAG | 272, 3000))
+    assert np.array_equal(gr.philox_jitter(5, JITTER_TAG | 272, 100), j[:100])              # a prefix is a prefix
+    assert not np.array_equal(gr.philox_jitter(5, JITTER_TAG | 288, 100), j[:100])
+
+
+def test_index_lists():
+    for res in gr.GRIDS:
+        c, n = gr.index_list(res), gr.num_cells(res)
+        assert c.size % 256 and c.min() >= 0 and c.max() < n and np.unique(c).size < c.size
+        if n > 1:
+            assert (np.diff(c) < 0).any() and abs(c.size - n / 2) <= 1
+
+
+def test_update_on_hand_made_cases():
+    f = lambda *v: np.array(v, F32)
+    out = gr.update(f(1.0, 0.2, 0.5, -0.0), np.array([0, 0, 1, 3]), f(0.3, 0.99, 0.1, 0.25), 0.5)
+    assert np.array_equal(gr.bits_of(out), gr.bits_of(f(0.99, 0.1, 0.5, 0.25)))              # decays once; max over the draws; untouched cell
+    out = gr.update(f(0.8, -0.0, -1.0, 0.4), np.array([0, 1, 2, 3, 3]), f(0.0, -0.0, np.nan, -2.0, 0.0), 0.5)
+    assert np.array_equal(gr.bits_of(out), gr.bits_of(f(0.4, 0.0, 0.0, 0.2)))                # -0.0 and a negative cell become +0
+    out = gr.update(f(0.8, 0.6, 0.4), None, f(0.5, np.inf), 0.5)                             # the first n cells
+    assert np.array_equal(gr.bits_of(out), gr.bits_of(f(0.5, np.inf, 0.4)))
+    tiny = gr.update(f(gr.TINY, 0.0), None, f(0.0, gr.TINY), 0.95)
+    assert tiny[0] == F32(gr.TINY * F32(0.95)) and 0 < tiny[0] < gr.TINY and tiny[1] == gr.TINY   # denormals are kept, not flushed
+
+
+@pytest.mark.parametrize("res", UPDATE_GRIDS, ids=str)
+def test_update_problems_hold_what_they_claim(res):
+    from oracle import angio_oracle as orc
+    p = gr.update_problem(res)
+    n, s, c, v = gr.num_cells(res), p.special, p.cells, p.occ_new
+    assert abs(c.size - n / 2) <= 1 and c.size % 256 and (np.diff(c) < 0).any() and c.min() >= 0 and c.max() < n
+    draws = lambda k: [float(x) for x in v[c == s[k]]]
+    assert draws("twice_down") == [F32(0.7), F32(0.3)] and draws("twice_up") == [F32(0.2), F32(0.6)]
+    assert draws("thrice_a") == [F32(0.1), F32(0.9), F32(0.5)] and draws("thrice_b") == [F32(0.9), F32(0.1), F32(0.5)]
+    assert draws("zero") == [0.0] and draws("negative") == [F32(-0.3)] and np.isnan(draws("nan")).all() and draws("inf") == [np.inf]
+    assert draws("tiny_draw") == [float(gr.TINY)] and p.occs[s["tiny_cell"]] == gr.TINY and 0 < gr.TINY < np.finfo(F32).tiny
+    assert np.signbit(v[c == s["neg_zero_draw"]]).all() and draws("neg_zero_draw") == [0.0]
+    assert np.signbit(p.occs[s["neg_zero_cell"]]) and p.occs[s["neg_zero_cell"]] == 0 and draws("neg_zero_cell") == [0.25]
+    selected = np.zeros(n, bool)
+    selected[c] = True
+    assert (~selected & (p.occs != 0)).sum() >= 1
+    counts = np.bincount(c, minlength=n)
+    print(f"{res}: {c.size} draws of {int(selected.sum())} cells, {int((counts == 2).sum())} drawn twice, {int((counts >= 3).sum())} three times "
+          f"or more, {int((~selected & (p.occs != 0)).sum())} unselected non-zero cells")
+    for decay in gr.DECAYS:
+        out = gr.update(p.occs, c, v, decay)
+        assert np.array_equal(gr.bits_of(out[~selected]), gr.bits_of(p.occs[~selected]))
+        d = F32(p.occs[s["decayed_wins"]] * F32(decay))
+        assert out[s["decayed_wins"]] == d and d > max(draws("decayed_wins"))
+        assert out[s["twice_down"]] == max(F32(p.occs[s["twice_down"]] * F32(decay)), F32(0.7))
+        assert out[s["thrice_a"]] == max(F32(p.occs[s["thrice_a"]] * F32(decay)), F32(0.9))
+        assert out[s["zero"]] == F32(F32(0.4) * F32(decay)) and out[s["negative"]] == F32(F32(0.3) * F32(decay))
+        assert out[s["nan"]] == F32(F32(0.2) * F32(decay)) and out[s["inf"]] == np.inf and out[s["tiny_draw"]] == gr.TINY
+        assert out[s["tiny_cell"]] == F32(gr.TINY * F32(decay)) and 0 < out[s["tiny_cell"]] < gr.TINY
+        assert out[s["neg_zero_cell"]] == F32(0.25) and out[s["neg_zero_draw"]] == F32(F32(0.35) * F32(decay))
+        assert not np.isnan(out).any()
+        # the oracle on the sub-problem it defines
+        o, cc, vv = gr.oracle_subproblem(p)
+        want, _ = orc.grid_update(torch.from_numpy(o), torch.from_numpy(cc), torch.from_numpy(vv), decay, 1e-2)
+        assert np.array_equal(gr.bits_of(gr.update(o, cc, vv, decay)), gr.bits_of(want.numpy()))
+        assert cc.size > c.size - 12 and np.unique(cc).size < cc.size
+
+
+@pytest.mark.parametrize("res", BINARIZE_GRIDS, ids=str)
+def test_exact_binarize_problems(res):
+    occs, n = gr.exact_binarize_problem(res), gr.num_cells(res)
+    o64 = occs.astype(np.float64)
+    assert np.array_equal(o64 * 64, np.round(o64 * 64)) and occs.min() >= 0.125 and occs.max() <= 0.375
+    total = gr.mean64(occs) * n
+    assert total == n / 4 == float(np.cumsum(o64)[-1]) == float(np.cumsum(o64[::-1])[-1])      # forward, reversed and fsum agree: exact
+    assert gr.mean64(occs) == 0.25
+    ties, above, below = int((occs == 0.25).sum()), int((occs > 0.25).sum()), int((occs < 0.25).sum())
+    on_thre = int((occs == 0.125).sum())
+    print(f"{res}: {n} cells, {ties} on the mean 0.25, {above} above, {below} below; {on_thre} on 0.125")
+    assert ties > 0 and above > 0 and below > 0 and on_thre > 0
+    for thre, want_thr, want_on in ((0.5, 0.25, above), (0.125, 0.125, n - on_thre), (0.25, 0.25, above)):
+        thr, mean = gr.threshold(occs, thre)
+        b, words = gr.binarize(occs, thre)
+        assert thr == F32(want_thr) and mean == F32(0.25) and int(b.sum()) == want_on
+        assert gr.decision_counts(occs, thre) == (want_on, n - want_on, ties if want_thr == 0.25 else on_thre)
+        assert words.size == (n + 31) // 32 and (n % 32 == 0 or int(words[-1]) >> (n % 32) == 0)
+        unpacked = ((words[:, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(-1)[:n]
+        assert np.array_equal(unpacked, b)
+    for flat in (np.zeros(n, F32), np.full(n, 0.3, F32)):      # an all-zero and a constant grid: the mean is the value, nothing is above it
+        assert gr.mean64(flat) == float(flat[0]) and gr.binarize(flat, 0.5)[0].sum() == 0 and not gr.binarize(flat, 0.5)[1].any()
+
+
+@pytest.mark.parametrize("res", BINARIZE_GRIDS, ids=str)
+def test_random_binarize_problems(res):
+    occs = gr.random_binarize_problem(res)
+    assert occs.dtype == np.float32 and occs.min() >= 0 and occs.max() < 0.03
+    margin, bound = gr.mean_margin(occs)
+    thr, mean = gr.threshold(occs, gr.RANDOM_THRE)
+    nearest = float(np.abs(occs.astype(np.float64) - float(thr)).min())
+    print(f"{res}: mean {gr.mean64(occs):.9f}, rounding margin {margin:.2e} against a bound of {bound:.2e}; the cell nearest the threshold "
+          f"{float(thr):.9g} is {nearest:.2e} away, one ulp is {float(np.spacing(thr)):.2e}; on / off / ties {gr.decision_counts(occs, gr.RANDOM_THRE)}")
+    assert margin > bound                                  # any order of the fp64 sum rounds to the same fp32 mean
+    assert thr == F32(gr.RANDOM_THRE) < mean               # the threshold decides
+    assert nearest > float(np.spacing(thr))
+    on, off, ties = gr.decision_counts(occs, gr.RANDOM_THRE)
+    assert ties == 0 and on > 0 and off > 0
+
+
+def test_pack_on_hand_made_bytes():
+    b = np.zeros(41, np.uint8)
+    b[[0, 5, 31, 32, 40]] = [1, 2, 255, 1, 2]
+    w = gr.pack(b)
+    assert w.dtype == np.uint32 and w.tolist() == [(1 << 0) | (1 << 5) | (1 << 31), (1 << 0) | (1 << 8)]
+    for res in gr.GRIDS:
+        p = gr.pack_problem(res)
+        assert set(np.unique(p).tolist()) <= {0, 1, 2, 255} and (gr.num_cells(res) < 8 or len(np.unique(p)) == 4)
+        assert sum(bin(int(x)).count("1") for x in gr.pack(p)) == int((p != 0).sum())
+
+
+def test_wrappers_refuse_by_type_and_size_before_the_device():
+    """The checks that need no GPU: a wrong dtype, size or layout is a ValueError naming the argument, raised before the device is looked at
+    and before the library is called (host tensors of the right type and size are refused for living on the host)."""
+    from nerf_for_angiography_amd import engine
+    box, res, n = gr.BOXES[0], (5, 3, 7), 105
+    occs, scratch, b8 = torch.zeros(n), torch.zeros(n), torch.zeros(n, dtype=torch.uint8)
+    bits, part = torch.zeros(4, dtype=torch.int32), torch.zeros(256, dtype=torch.float64)
+    cells, new = torch.zeros(9, dtype=torch.int32), torch.zeros(9)
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_update(box, res, occs, cells.long(), new, 0.95, scratch)
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_update(box, res, occs, cells[:8], new, 0.95, scratch)
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_update(box, res, occs, torch.zeros(18, dtype=torch.int32)[::2], new, 0.95, scratch)
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_update(box, res, occs, cells.view(3, 3), new, 0.95, scratch)
+    with pytest.raises(ValueError, match="occs"):
+        engine.grid_update(box, res, occs.double(), cells, new, 0.95, scratch)
+    with pytest.raises(ValueError, match="scratch"):
+        engine.grid_update(box, res, occs, cells, new, 0.95, scratch[:-1])
+    with pytest.raises(ValueError, match="occ_new"):
+        engine.grid_update(box, res, occs, None, torch.zeros(n + 1), 0.95, scratch)
+    with pytest.raises(ValueError, match="occ_new"):
+        engine.grid_update(box, res, occs, cells, new.double(), 0.95, scratch)
+    with pytest.raises(ValueError, match="bits"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8, bits[:3], part)
+    with pytest.raises(ValueError, match="bits"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8, bits.long(), part)
+    with pytest.raises(ValueError, match="binary_u8"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8.bool(), bits, part)
+    with pytest.raises(ValueError, match="partial_ws"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8, bits, part[:255])
+    with pytest.raises(ValueError, match="partial_ws"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8, bits, part.float())
+    with pytest.raises(ValueError, match="jitter"):
+        engine.grid_points(box, res, cells, 9, jitter=torch.zeros(27))
+    with pytest.raises(ValueError, match="jitter"):
+        engine.grid_points(box, res, cells, 9, jitter=torch.zeros(8, 3))
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_points(box, res, cells.long(), 9)
+    with pytest.raises(ValueError, match="cell_idx"):
+        engine.grid_points(box, res, cells, 10)
+    with pytest.raises(ValueError, match="GPU"):
+        engine.grid_update(box, res, occs, cells, new, 0.95, scratch)
+    with pytest.raises(ValueError, match="GPU"):
+        engine.grid_binarize(box, res, occs, 1e-2, b8, bits, part)
+    with pytest.raises(ValueError, match="GPU"):
+        engine.grid_points(box, res, cells, 9, jitter=torch.zeros(9, 3))
