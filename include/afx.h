@@ -1279,6 +1279,101 @@ int afx_reformat_planes(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t
                         const double* planes, int64_t n_planes, const double* table, int64_t n_table, int32_t half_slab, int32_t mode,
                         double fill, double* out, void* stream);
 
+/* ---- Registering C-arm poses to the vessel silhouettes: the 2D-3D chamfer cost of a point set (the centreline of the reconstructed
+ * vessel, with radii) against one distance image per view, its Gauss-Newton normal equations in a rigid pose increment, a
+ * Levenberg-Marquardt step and the selection of a coarse search.  All arithmetic is fp64, every operation rounded on its own (no
+ * contraction), only + - * / sqrt floor and comparisons, in the order written; every comparison with a NaN is false; no floating-point
+ * atomics: every sum has one order.  tests/pose_reference.py restates it in NumPy and the device equals the restatement exactly.
+ *   View record.  The record of afx_visual_hull, AFX_HULL_VIEW_DOUBLES doubles: R[r][n] at [3 r + n], c at [9..11], f at [12].
+ *   Field.  field: double [V][H][W] on the device, W, H >= 2, one distance image per VIEW (the Python layer builds the signed distance
+ *      EDT(~mask) - EDT(mask): negative inside the silhouette; the kernel does not care what it holds).
+ *   Points.  points: double [N][3], world coordinates; radius: double [N], world units (NULL: 0); weight: double [N] (NULL: 1).
+ *   Pose increment.  xi = (a0, a1, a2, t0, t1, t2) acts in the camera frame, q' = C(a) q + t, with the Cayley rotation
+ *      C(a) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a) (a rotation by theta about a / |a|, |a| = tan(theta / 2)).
+ *      afx_pose_compose, record (R, c, f) and xi -> (R', c', f):  all six of xi == 0: the record is returned as it is.  Otherwise
+ *        n = (a0 a0 + a1 a1) + a2 a2;  s = 1 - n;  den = 1 + n
+ *        C[i][i] = (s + 2 (a_i a_i)) / den;  C[0][1] = (2 (a0 a1) - 2 a2) / den;  C[0][2] = (2 (a0 a2) + 2 a1) / den;
+ *        C[1][0] = (2 (a0 a1) + 2 a2) / den;  C[1][2] = (2 (a1 a2) - 2 a0) / den;  C[2][0] = (2 (a0 a2) - 2 a1) / den;
+ *        C[2][1] = (2 (a1 a2) + 2 a0) / den
+ *        R'[i][j] = (R[i][0] C[j][0] + R[i][1] C[j][1]) + R[i][2] C[j][2]                  (R' = R C^T)
+ *        c'_i = c_i - ((R'[i][0] t0 + R'[i][1] t1) + R'[i][2] t2)                        (c' = c - R' t);  [12..15] are copied
+ *      records: double [n_records][16]; n_xi == 0: xi double [n_records][6], out[r] = compose(records[r], xi[r]); n_xi >= 1: xi double
+ *      [n_xi][6], out[r n_xi + j] = compose(records[r], xi[j]) (every candidate of a search about every view).
+ *   afx_pose_chamfer.  records: double [K][16]; rec_view: int32 [K], the view v whose image record k is scored against.  Residual of
+ *   point i under record k:
+ *        e = x - c;  q_n = (R[0][n] e_0 + R[1][n] e_1) + R[2][n] e_2;  d = -q_2                      (the hull's operations, its order)
+ *        su = (f q_0) / d;  sw = (f q_1) / d;  u = W / 2 + su;  w = H / 2 - sw
+ *        lost unless d > 0 && u >= 0 && u <= W - 1 && w >= 0 && w <= H - 1:  r = tau
+ *        iu = min(floor(u), W - 2), pu = u - iu;  iw, pw likewise;  f00 = F[iw][iu], f01 = F[iw][iu + 1], f10 = F[iw + 1][iu], f11
+ *        ga = f01 - f00;  gb = f11 - f10;  top = f00 + pu ga;  bot = f10 + pu gb;  g_w = bot - top;  val = top + pw g_w
+ *        g_u = ga + pw (gb - ga);  err = val + (f r_i) / d
+ *        err <= 0: satisfied, r = 0;  else err >= tau: saturated, r = tau;  else active, r = err  (tau = trunc, finite and > 0)
+ *      Only an active point has a Jacobian row (the radius term's dependence on d is ignored):
+ *        fd = f / d;  J_3 = g_u fd;  J_4 = -(g_w fd);  J_5 = (g_u su - g_w sw) / d             (d r / d q)
+ *        J_0 = 2 (q_1 J_5 - q_2 J_4);  J_1 = 2 (q_2 J_3 - q_0 J_5);  J_2 = 2 (q_0 J_4 - q_1 J_3)      (d q' / d a = -2 [q]x at a = 0)
+ *      Sums per record and slice, AFX_POSE_SUM_DOUBLES = 32 doubles, with wr = w_i r, wJ_k = w_i J_k:
+ *        [0] sum (wr) r;  [1] sum wr;  [2] sum w_i (every point);  [3 + k] sum (wJ_k) r;  [9..29] sum (wJ_k) J_l, k <= l, the upper
+ *        triangle row-major (active points only: the others are skipped, not multiplied by 0);  [30], [31] = 0.
+ *        counts: int32 [4] = active, satisfied, saturated, lost.  AFX_POSE_COST_ONLY leaves [3..29] at 0.
+ *      Order of the sums.  n_slices = S >= 1; slice s owns the points [s L, min(N, (s + 1) L)), L = ceil(N / S) rounded up to a multiple
+ *        of 256.  Thread t of 256 adds its points s L + t, s L + t + 256, ... in ascending order into accumulators that start at +0.0;
+ *        the 256 values meet in the adjacent-pair tree (level l + 1: s_j = s_2j + s_2j+1).  Output sums: double [K][S][32], counts:
+ *        int32 [K][S][4]; the slices are NOT combined here (afx_pose_select and afx_pose_lm_step add them in slice order from +0.0).
+ *      A record whose rec_view lies outside 0..V - 1 is dropped on the device: its counts are -1, sums[0] = +inf and the rest 0 in every
+ *        slice (it is never selected and never accepted); the caller reads that flag with the results.
+ *   afx_pose_select.  sums: double [V M][S][32], record v M + m = candidate m of view v.  cost_m = the slices' [0] added in order;
+ *      selected[v] = the m of lowest cost, a later one only if strictly lower (ties, and NaN, to the lowest index).  records_out (may be
+ *      NULL): double [V][16] = cand_records[v M + selected[v]].
+ *   afx_pose_lm_step, a lane per view, on the caller-owned state: double [V][AFX_POSE_STATE_DOUBLES = 64]:
+ *        [0..15] the current record; [16] its cost; [17..22] g; [23..43] H (upper triangle); [44] lambda; [45] accepted, [46] rejected,
+ *        [47] singular (counts, as doubles); [48..63] the trial record.
+ *      tot = the S slice sums of record v added in slice order from +0.0 (sums: double [V][S][32], record v = view v).
+ *      AFX_POSE_LM_INIT: the row is zeroed; current = records_in[v]; cost, g, H = tot; lambda = lambda0.
+ *      AFX_POSE_LM_UPDATE, AFX_POSE_LM_FINAL: tot is the trial's.  tot[0] < cost (strict): current = trial; cost, g, H = tot;
+ *        lambda = max(lambda / 3, 1e-12); accepted += 1.  Otherwise lambda = min(4 lambda, 1e12); rejected += 1.
+ *      INIT and UPDATE then solve (H + lambda diag H) delta = -g:  A = H made symmetric, b = -g; a k whose bit of dof_mask is 0 has its
+ *        row and column zeroed, A_kk = 1, b_k = +0 (so delta_k = 0 exactly); otherwise A_kk = A_kk + lambda A_kk.  Cholesky, for j = 0..5:
+ *        s = A_jj;  s = s - L_jp L_jp for p = 0..j-1 in order;  L_jj = sqrt(s);  for i > j: t = A_ij;  t = t - L_ip L_jp for p < j in
+ *        order;  L_ij = t / L_jj.  Forward: t = b_i;  t = t - L_ip y_p, p < i in order;  y_i = t / L_ii.  Backward, i = 5..0: t = y_i;
+ *        t = t - L_pi delta_p, p = i + 1..5 in order;  delta_i = t / L_ii.  If any pivot s is not > 0: delta = 0 and singular += 1.
+ *        trial = compose(current, delta) (the operations of afx_pose_compose: with delta = 0 the trial is the current record).
+ *      AFX_POSE_LM_FINAL solves nothing: trial = current (the last step of a run, whose trial nobody would score).
+ *      trial_records: double [V][16] = the trial, the records of the next afx_pose_chamfer.
+ *   Known ambiguities.  The residual is one-sided (a point inside the silhouette costs nothing), so a centreline thinner than the vessel
+ *      leaves the pose free by the lumen's width; a translation along the view axis moves the projection only by its perspective and is
+ *      barely observable at a C-arm's source distance.
+ * k_pose_chamfer runs on a grid of (S, K) workgroups of 256 threads: the record through a wave-uniform address, 30 accumulators in
+ * registers, the tree by wave shuffles and 4 x 30 doubles of LDS.  No atomics, nothing allocated, synchronised or read back, every loop
+ * bounded by an argument: each call is one launch and can be captured in a graph.
+ * AFX_E_INVALID before any launch, the message naming the argument: a null pointer (radius, weight, records_out and, outside INIT,
+ * records_in may be NULL); n_views, n_records, n_candidates outside 1..65535; n_points outside 1..2^30; n_slices outside 1..4096; width
+ * or height outside 2..16384; trunc or lambda0 not finite or not > 0; unknown flags; a phase other than the three; dof_mask above 63;
+ * n_xi outside 0..65535; a pointer that is not memory of the current device. */
+#define AFX_POSE_SUM_DOUBLES 32
+#define AFX_POSE_STATE_DOUBLES 64
+#define AFX_POSE_COST_ONLY 1u
+#define AFX_POSE_LM_INIT 0
+#define AFX_POSE_LM_UPDATE 1
+#define AFX_POSE_LM_FINAL 2
+#define AFX_POSE_ST_RECORD 0
+#define AFX_POSE_ST_COST 16
+#define AFX_POSE_ST_G 17
+#define AFX_POSE_ST_H 23
+#define AFX_POSE_ST_LAMBDA 44
+#define AFX_POSE_ST_ACCEPTED 45
+#define AFX_POSE_ST_REJECTED 46
+#define AFX_POSE_ST_SINGULAR 47
+#define AFX_POSE_ST_TRIAL 48
+int afx_pose_chamfer(const double* field, int32_t n_views, int32_t width, int32_t height, const double* points,
+                     const double* radius /* may be NULL */, const double* weight /* may be NULL */, int32_t n_points, const double* records,
+                     const int32_t* rec_view, int32_t n_records, double trunc, int32_t n_slices, uint32_t flags, double* sums, int32_t* counts,
+                     void* stream);
+int afx_pose_compose(const double* records, int32_t n_records, const double* xi, int32_t n_xi, double* out, void* stream);
+int afx_pose_select(const double* sums, int32_t n_views, int32_t n_candidates, int32_t n_slices, const double* cand_records,
+                    int32_t* selected, double* records_out /* may be NULL */, void* stream);
+int afx_pose_lm_step(double* state, int32_t n_views, const double* sums, int32_t n_slices, int32_t phase, uint32_t dof_mask, double lambda0,
+                     const double* records_in /* AFX_POSE_LM_INIT only */, double* trial_records, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -2785,6 +2785,300 @@ def optimal_views(vmap: dict, branch=None, overlap_weight: float = 1.0, k: int =
 
 # ---- sparse-view algebraic reconstruction: the ray-driven projector (afx_xray_project), the voxel-driven backprojector
 # (afx_xray_backproject) and the SIRT iteration made of the two ----
+# ---- registering C-arm poses to the vessel silhouettes (afx_pose_chamfer, afx_pose_compose, afx_pose_select, afx_pose_lm_step) ----
+POSE_SUM_DOUBLES = 32
+POSE_STATE_DOUBLES = 64
+POSE_COST_ONLY = 1
+POSE_LM_INIT, POSE_LM_UPDATE, POSE_LM_FINAL = 0, 1, 2
+POSE_LAMBDA0 = 1e-3
+POSE_ST_COST, POSE_ST_LAMBDA, POSE_ST_ACCEPTED, POSE_ST_REJECTED, POSE_ST_SINGULAR, POSE_ST_TRIAL = 16, 44, 45, 46, 47, 48
+POSE_DOF = {"all": 63, "rotation": 7, "translation": 56, "inplane": 4 | 8 | 16}      # bits a0 a1 a2 t0 t1 t2 of afx_pose_lm_step's dof_mask
+
+
+def pose_views(poses, masks: torch.Tensor, focal, signed: bool = True) -> dict:
+    """The views a pose is registered against: poses [V, 4, 4] or [V, 3, 4] (cam2world), masks [V, H, W] on the GPU (the vessel
+    silhouettes), focal (a number or one per view).  field = EDT(~mask) - EDT(mask), the signed distance in pixels (negative inside the
+    silhouette), or with signed=False the hull's unsigned EDT(~mask).  A view with an empty mask is refused, as `visual_hull_views` does.
+    -> dict(records float64 [V, 16] and field float64 [V, H, W] on the device, n_views, width, height, poses float64 [V, 4, 4] (host))."""
+    import numpy as np
+    hull = visual_hull_views(poses, masks, focal, margin_px=0.0)
+    field = hull["dist"]
+    if signed:
+        field = field - distance_transform_edt((masks != 0).to(torch.float64))
+    p = np.asarray(poses.detach().cpu().numpy() if isinstance(poses, torch.Tensor) else poses, dtype=np.float64)
+    full = np.tile(np.eye(4), (p.shape[0], 1, 1))
+    full[:, :3, :] = p[:, :3, :]
+    return dict(records=hull["records"], field=field.contiguous(), n_views=hull["n_views"], width=hull["width"], height=hull["height"], poses=full)
+
+
+def pose_search_offsets(rot_deg: float, shift: float, steps: int = 3):
+    """The in-plane grid of a coarse search -> float64 [steps^3, 6] of increments xi: a2 = tan(theta / 2) for theta in
+    linspace(-rot_deg, rot_deg, steps) degrees about the view axis, t0 and t1 in linspace(-shift, shift, steps) world units; a0, a1 and
+    t2 are 0.  steps is odd; candidate 0 is the identity (the grid's centre is moved to the front), so a search never raises the cost."""
+    import numpy as np
+    steps = int(steps)
+    if steps < 1 or steps % 2 == 0:
+        raise ValueError(f"pose_search_offsets: steps must be odd and >= 1, got {steps}")
+    if not (rot_deg >= 0 and shift >= 0 and np.isfinite(rot_deg) and np.isfinite(shift) and rot_deg < 180):
+        raise ValueError(f"pose_search_offsets: rot_deg must lie in [0, 180) and shift be finite and >= 0, got {rot_deg!r}, {shift!r}")
+    rot = np.tan(np.deg2rad(np.linspace(-rot_deg, rot_deg, steps)) / 2.0)
+    sh = np.linspace(-shift, shift, steps)
+    rot[steps // 2], sh[steps // 2] = 0.0, 0.0
+    grid = np.zeros((steps, steps, steps, 6))
+    grid[..., 2], grid[..., 3], grid[..., 4] = rot[:, None, None], sh[None, :, None], sh[None, None, :]
+    grid = grid.reshape(-1, 6)
+    centre = (steps ** 3) // 2
+    return np.ascontiguousarray(np.concatenate([grid[centre:centre + 1], grid[:centre], grid[centre + 1:]]))
+
+
+def _pose_f64(x, shape, name, dev, who):
+    import numpy as np
+    if x is None:
+        return None
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64)))
+    if t.device != dev:
+        t = t.to(dev)
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be contiguous float64 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _pose_out(t, shape, dtype, name, dev, who):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
+    return t
+
+
+def _pose_device(views: dict, who: str):
+    dev = views["field"].device
+    if dev.type != "cuda":
+        raise AfxError(f"{who}: the views must live on a GPU; there is no CPU path")
+    return dev
+
+
+def pose_compose(records, xi, outer: bool = False, out=None) -> torch.Tensor:
+    """afx_pose_compose: records [R, 16] composed with the increments xi = (a0, a1, a2, t0, t1, t2) in the camera frame (Cayley
+    rotation, q' = C(a) q + t) -> [R, 16] with xi [R, 6], or with outer=True and xi [M, 6] every pair, [R, M, 16].  Device tensors in,
+    a device tensor out; nothing is read back."""
+    lib = _lib.load()
+    if not isinstance(records, torch.Tensor) or records.device.type != "cuda":
+        raise AfxError("pose_compose: the records must be a tensor on a GPU; there is no CPU path")
+    dev = records.device
+    r = records.shape[0]
+    records = _pose_f64(records, (r, HULL_VIEW_DOUBLES), "records", dev, "pose_compose")
+    m = int(xi.shape[0]) if outer else r
+    xi = _pose_f64(xi, (m, 6), "xi", dev, "pose_compose")
+    out = _pose_out(out, (r, m, HULL_VIEW_DOUBLES) if outer else (r, HULL_VIEW_DOUBLES), torch.float64, "out", dev, "pose_compose")
+    _lib.check(lib.afx_pose_compose(_ptr(records), r, _ptr(xi), m if outer else 0, _ptr(out), Engine._stream(dev)), "afx_pose_compose")
+    return out
+
+
+def pose_default_slices(n_points: int, n_records: int) -> int:
+    """The slice count `pose_chamfer` and `register_poses` use by default: enough workgroups to fill the device (256 compute units)
+    when the records are few, never a slice without a point, at most 64."""
+    per = max(1, -(-int(n_points) // 256))
+    return int(max(1, min(per, 64, -(-512 // max(1, int(n_records))))))
+
+
+def pose_chamfer_record(views: dict, points, radius, weight, records, rec_view, trunc: float, n_slices: int = 1, cost_only: bool = False,
+                        sums=None, counts=None):
+    """afx_pose_chamfer, the launch alone -> (sums float64 [K, S, 32], counts int32 [K, S, 4]) on the device, the slices apart.  points
+    float64 [N, 3], radius and weight float64 [N] or None, records float64 [K, 16] and rec_view int32 [K] device tensors.  With sums and
+    counts passed nothing is allocated and nothing is read back: the call can be captured in a graph."""
+    lib = _lib.load()
+    dev = _pose_device(views, "pose_chamfer_record")
+    v, w, h = int(views["n_views"]), int(views["width"]), int(views["height"])
+    field = _pose_f64(views["field"], (v, h, w), "field", dev, "pose_chamfer_record")
+    n, k, s = int(points.shape[0]), int(records.shape[0]), int(n_slices)
+    points = _pose_f64(points, (n, 3), "points", dev, "pose_chamfer_record")
+    radius = _pose_f64(radius, (n,), "radius", dev, "pose_chamfer_record")
+    weight = _pose_f64(weight, (n,), "weight", dev, "pose_chamfer_record")
+    records = _pose_f64(records, (k, HULL_VIEW_DOUBLES), "records", dev, "pose_chamfer_record")
+    if not isinstance(rec_view, torch.Tensor) or rec_view.dtype != torch.int32 or not rec_view.is_contiguous() or rec_view.device != dev or \
+            tuple(rec_view.shape) != (k,):
+        raise ValueError(f"pose_chamfer_record: rec_view must be contiguous int32 [{k}] on {dev}")
+    ok = k >= 1 and s >= 1
+    sums = _pose_out(sums, (k, s, POSE_SUM_DOUBLES) if ok else (1,), torch.float64, "sums", dev, "pose_chamfer_record")
+    counts = _pose_out(counts, (k, s, 4) if ok else (1,), torch.int32, "counts", dev, "pose_chamfer_record")
+    _lib.check(lib.afx_pose_chamfer(_ptr(field), v, w, h, _ptr(points), _ptr(radius), _ptr(weight), n, _ptr(records), _ptr(rec_view), k,
+                                    float(trunc), s, POSE_COST_ONLY if cost_only else 0, _ptr(sums), _ptr(counts), Engine._stream(dev)),
+               "afx_pose_chamfer")
+    return sums, counts
+
+
+def _pose_points(points, radius, weight, dev, who):
+    import numpy as np
+    n = int(points.shape[0])
+    if n < 1:
+        raise ValueError(f"{who}: no points")
+    if radius is not None and not isinstance(radius, torch.Tensor) and np.ndim(radius) == 0:
+        radius = np.full(n, float(radius))
+    return _pose_f64(points, (n, 3), "points", dev, who), _pose_f64(radius, (n,), "radius", dev, who), _pose_f64(weight, (n,), "weight", dev, who)
+
+
+def _pose_figures(sums, counts):
+    """Host figures of read-back sums [K, S, 32] and counts [K, S, 4]: the slices added in order."""
+    import numpy as np
+    tot = np.zeros((sums.shape[0], POSE_SUM_DOUBLES))
+    for s in range(sums.shape[1]):
+        tot = tot + sums[:, s]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(cost=tot[:, 0], mean_residual=tot[:, 1] / tot[:, 2], rms_residual=np.sqrt(tot[:, 0] / tot[:, 2]),
+                    counts=counts.sum(axis=1).astype(np.int64))
+
+
+def pose_chamfer(points, radius, views: dict, records=None, trunc: float = 8.0, weight=None, n_slices=None) -> dict:
+    """The truth-free score of every view's pose: how far the points (the reconstructed centreline; radius in world units or None)
+    miss that view's silhouette.  records: [V, 16] to score instead of the views' own.  -> dict of NumPy arrays per view: cost (sum w
+    r^2), mean_residual (sum w r / sum w, pixels; a lost or saturated point counts trunc), rms_residual (sqrt(cost / sum w), pixels: the
+    figure the registration never raises), counts int64 [V, 4] (active, satisfied, saturated, lost)."""
+    dev = _pose_device(views, "pose_chamfer")
+    points, radius, weight = _pose_points(points, radius, weight, dev, "pose_chamfer")
+    v = int(views["n_views"])
+    records = views["records"] if records is None else _pose_f64(records, (v, HULL_VIEW_DOUBLES), "records", dev, "pose_chamfer")
+    s = pose_default_slices(points.shape[0], v) if n_slices is None else int(n_slices)
+    rec_view = torch.arange(v, dtype=torch.int32, device=dev)
+    sums, counts = pose_chamfer_record(views, points, radius, weight, records, rec_view, trunc, s, cost_only=True)
+    return _pose_figures(sums.cpu().numpy(), counts.cpu().numpy())
+
+
+def register_poses_buffers(n_views: int, n_candidates: int, n_slices: int, device) -> dict:
+    """Every buffer `register_poses_record` writes, allocated once: with them passed the registration allocates nothing."""
+    v, m, s = int(n_views), max(1, int(n_candidates)), int(n_slices)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=device)
+    return dict(state=f64(v, POSE_STATE_DOUBLES), trial_records=f64(v, HULL_VIEW_DOUBLES), start=f64(v, HULL_VIEW_DOUBLES),
+                sums=f64(v, s, POSE_SUM_DOUBLES), counts=torch.empty((v, s, 4), dtype=torch.int32, device=device),
+                cand=f64(v, m, HULL_VIEW_DOUBLES), cand_sums=f64(v * m, s, POSE_SUM_DOUBLES),
+                cand_counts=torch.empty((v * m, s, 4), dtype=torch.int32, device=device),
+                selected=torch.zeros(v, dtype=torch.int32, device=device), rec_view=torch.arange(v, dtype=torch.int32, device=device),
+                cand_view=torch.arange(v, dtype=torch.int32, device=device).repeat_interleave(m).contiguous())
+
+
+def register_poses_record(views: dict, points, radius, weight, records, iterations: int = 20, trunc: float = 8.0, dof_mask: int = 63,
+                          offsets=None, n_slices: int = 1, lambda0: float = POSE_LAMBDA0, buffers=None) -> dict:
+    """The whole registration as launches alone: [compose the candidates `offsets` [M, 6] about every record, score them cost-only,
+    select] -> score the start -> afx_pose_lm_step INIT -> iterations x [score the trial, step] (the last step FINAL: it solves
+    nothing).  All inputs are device tensors; nothing is read back and, with `buffers` (`register_poses_buffers`) passed, nothing is
+    allocated: the call can be captured in a graph.  -> the buffers: state [V, 64] (the refined record at [0..15], its cost, lambda and
+    the accepted / rejected / singular counts), start [V, 16], selected int32 [V]."""
+    lib = _lib.load()
+    dev = _pose_device(views, "register_poses_record")
+    v, s, it = int(views["n_views"]), int(n_slices), int(iterations)
+    if it < 1:
+        raise ValueError(f"register_poses_record: iterations must be >= 1, got {iterations}")
+    records = _pose_f64(records, (v, HULL_VIEW_DOUBLES), "records", dev, "register_poses_record")
+    m = 0 if offsets is None else int(offsets.shape[0])
+    b = buffers if buffers is not None else register_poses_buffers(v, m, s, dev)
+    stream = Engine._stream(dev)
+    if m:
+        offsets = _pose_f64(offsets, (m, 6), "offsets", dev, "register_poses_record")
+        pose_compose(records, offsets, outer=True, out=b["cand"])
+        pose_chamfer_record(views, points, radius, weight, b["cand"].view(v * m, HULL_VIEW_DOUBLES), b["cand_view"], trunc, s, True,
+                            b["cand_sums"], b["cand_counts"])
+        _lib.check(lib.afx_pose_select(_ptr(b["cand_sums"]), v, m, s, _ptr(b["cand"]), _ptr(b["selected"]), _ptr(b["start"]), stream),
+                   "afx_pose_select")
+    else:
+        b["start"].copy_(records)
+        b["selected"].zero_()
+    step = lambda phase, rec_in: _lib.check(lib.afx_pose_lm_step(_ptr(b["state"]), v, _ptr(b["sums"]), s, phase, int(dof_mask), float(lambda0),
+                                                                  _ptr(rec_in), _ptr(b["trial_records"]), stream), "afx_pose_lm_step")
+    pose_chamfer_record(views, points, radius, weight, b["start"], b["rec_view"], trunc, s, False, b["sums"], b["counts"])
+    step(POSE_LM_INIT, b["start"])
+    for i in range(it):
+        pose_chamfer_record(views, points, radius, weight, b["trial_records"], b["rec_view"], trunc, s, False, b["sums"], b["counts"])
+        step(POSE_LM_UPDATE if i + 1 < it else POSE_LM_FINAL, None)
+    return b
+
+
+def pose_records_to_matrices(records):
+    """View records [V, 16] (NumPy) -> cam2world float64 [V, 4, 4]."""
+    import numpy as np
+    rec = np.asarray(records, np.float64).reshape(-1, HULL_VIEW_DOUBLES)
+    out = np.tile(np.eye(4), (rec.shape[0], 1, 1))
+    out[:, :3, :3], out[:, :3, 3] = rec[:, :9].reshape(-1, 3, 3), rec[:, 9:12]
+    return out
+
+
+def pose_projection_shift(points, records_a, records_b, width: int, height: int):
+    """The mean pixel displacement of the points between two sets of view records -> float64 [V] (NumPy on the host; points behind a
+    source are left out, NaN where none is left)."""
+    import numpy as np
+    p = np.asarray(points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points, np.float64).reshape(-1, 3)
+    out = []
+    for ra, rb in zip(np.asarray(records_a, np.float64), np.asarray(records_b, np.float64)):
+        uv = []
+        for rec in (ra, rb):
+            q = (p - rec[9:12]) @ rec[:9].reshape(3, 3)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                uv.append((width / 2 + rec[12] * q[:, 0] / -q[:, 2], height / 2 - rec[12] * q[:, 1] / -q[:, 2], -q[:, 2] > 0))
+        keep = uv[0][2] & uv[1][2]
+        d = np.sqrt((uv[0][0] - uv[1][0]) ** 2 + (uv[0][1] - uv[1][1]) ** 2)[keep]
+        out.append(float(d.mean()) if d.size else float("nan"))
+    return np.asarray(out)
+
+
+def register_poses(points, radius, views: dict, iterations: int = 20, trunc: float = 8.0, dof="all", search=None, n_slices=None,
+                   weight=None) -> dict:
+    """Rigid 2D-3D registration of every view's pose to its silhouette (include/afx.h: afx_pose_chamfer ...): Levenberg-Marquardt on
+    the one-sided, truncated chamfer residual of the points (the reconstructed centreline; radius in world units, a number or None)
+    against the views' signed distance images (`pose_views`).  dof: "all", "translation", "rotation", "inplane" (a2, t0, t1) or a 6-bit
+    mask.  search: None, or (rot_deg, shift, steps) / an [M, 6] array of increments scored first (`pose_search_offsets`; candidate 0
+    should be the identity).  -> dict of NumPy arrays: poses [V, 4, 4] and records [V, 16] (refined), cost_before / cost_after,
+    mean_residual_before / mean_residual_after and rms_residual_before / rms_residual_after (pixels), counts_before / counts_after, accepted, rejected, singular, selected, shift_px
+    (the mean displacement of the points' projections), n_slices."""
+    import numpy as np
+    dev = _pose_device(views, "register_poses")
+    mask = POSE_DOF[dof] if isinstance(dof, str) else int(dof)
+    if not 0 <= mask <= 63:
+        raise ValueError(f"register_poses: dof must be one of {sorted(POSE_DOF)} or a mask in 0..63")
+    points, radius, weight = _pose_points(points, radius, weight, dev, "register_poses")
+    v = int(views["n_views"])
+    offsets = None
+    if search is not None:
+        offsets = pose_search_offsets(*search) if isinstance(search, (tuple, list)) and len(search) == 3 and np.ndim(search[0]) == 0 else search
+        offsets = _pose_f64(np.asarray(offsets, np.float64).reshape(-1, 6) if not isinstance(offsets, torch.Tensor) else offsets,
+                            (len(offsets), 6), "search", dev, "register_poses")
+    s = pose_default_slices(points.shape[0], v) if n_slices is None else int(n_slices)
+    before = pose_chamfer(points, radius, views, trunc=trunc, weight=weight, n_slices=s)
+    b = register_poses_record(views, points, radius, weight, views["records"], iterations, trunc, mask, offsets, s)
+    state = b["state"].cpu().numpy()
+    rec = np.ascontiguousarray(state[:, :HULL_VIEW_DOUBLES])
+    after = pose_chamfer(points, radius, views, records=rec, trunc=trunc, weight=weight, n_slices=s)
+    if (before["counts"] < 0).any() or (after["counts"] < 0).any():
+        raise AfxError("register_poses: a record was dropped on the device (a view index out of range)")
+    given = views["records"].cpu().numpy()
+    return dict(poses=pose_records_to_matrices(rec), records=rec, cost_before=before["cost"], cost_after=after["cost"],
+                mean_residual_before=before["mean_residual"], mean_residual_after=after["mean_residual"],
+                rms_residual_before=before["rms_residual"], rms_residual_after=after["rms_residual"], counts_before=before["counts"],
+                counts_after=after["counts"], accepted=state[:, POSE_ST_ACCEPTED].astype(np.int64),
+                rejected=state[:, POSE_ST_REJECTED].astype(np.int64), singular=state[:, POSE_ST_SINGULAR].astype(np.int64),
+                selected=b["selected"].cpu().numpy(), shift_px=pose_projection_shift(points, given, rec, views["width"], views["height"]),
+                n_slices=s)
+
+
+def centreline_pose_points(graph: dict, index_to_world, radius=None, d2=None, voxel_size=1.0):
+    """(points float64 [P, 3], radius float64 [P]) of a `centreline_graph` result, as `view_map` takes them: the path voxels in world
+    coordinates and `radius` (one per path voxel or one number) or, by default, voxel_size x sqrt(d2) at the path voxels; without either
+    the radius is 0 (the centreline alone)."""
+    import numpy as np
+    points, _ = centreline_world_points(graph, _affine12(index_to_world, "centreline_pose_points"))
+    if radius is None and d2 is not None:
+        vox = graph["path_voxels"].cpu().numpy().astype(np.int64)
+        radius = np.sqrt(((d2.reshape(-1).cpu().numpy().astype(np.int64) & 0xffffffff)[vox]).astype(np.float64)) * float(voxel_size)
+    rad = np.zeros(points.shape[0]) if radius is None else np.broadcast_to(np.asarray(radius, np.float64), (points.shape[0],)).copy()
+    return points, rad
+
+
+def centreline_register_poses(graph: dict, views: dict, index_to_world=None, radius=None, d2=None, voxel_size=1.0, **kw) -> dict:
+    """`register_poses` of the centreline of a `centreline_graph` result (`centreline_pose_points`)."""
+    points, rad = centreline_pose_points(graph, index_to_world, radius, d2, voxel_size)
+    if points.shape[0] == 0:
+        raise ValueError("centreline_register_poses: the centreline has no point")
+    return register_poses(points, rad, views, **kw)
+
+
 def line_integrals(images, eps: float = 1e-6) -> torch.Tensor:
     """-log(clamp(I, eps, 1)) in fp64: the line integrals behind transmission images I = exp(-integral), the convention of
     ray_tracing(type='ct')."""

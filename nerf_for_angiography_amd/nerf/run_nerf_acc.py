@@ -25,6 +25,9 @@ before training and keeps it as the ceiling of every grid update (`OccupancyGrid
 `--save_sirt PATH.npy` (`--binary True` or CT-type data) writes, at the end of the run, the classical baseline: the SIRT reconstruction
 of the attenuation volume from the training views on the 128^3 lattice of the occupancy grid's cell centres (`engine.sirt_reconstruct`);
 `--sirt_tv_weight W` makes it SIRT-TV, a total-variation denoising step after every update (`engine.tv_denoise_3d`, `afx_tv_denoise_3d`).
+`--save_poses PATH.csv` (`--binary True`) registers, at the end of the run, the pose of every training view to its vessel silhouette by
+2D-3D chamfer registration of the final model's centreline (`engine.register_poses`, `afx_pose_chamfer`, `afx_pose_lm_step`) and writes
+the given and the refined poses; `--pose_noise DEG UNITS` (`--synthetic`) hands training perturbed poses of images rendered at the true ones.
 The training rays live on the GPU: one table (origins, directions, pixel, weight) built once, and every iteration's
 batch is drawn there (weighted sampling without replacement, `engine.sample_rays`); --host_sampler restores the
 reference's per-iteration pandas draw (`sample_pixel_rays`).
@@ -148,6 +151,24 @@ def build_parser():
                         'tree_foreshortening, tree_overlap, then foreshortening and overlap of every branch; the five best whole-tree views are '
                         'printed; without the flag nothing changes')
     p.add_argument('--view_map_step', type=float, default=5.0, metavar='DEGREES', help='--save_view_map: the step of the angle grid')
+    p.add_argument('--save_poses', default=None, metavar='PATH',
+                   help='after training, register the pose of every training view to its vessel silhouette and write the result to PATH '
+                        '(.csv): the pruned centreline of --save_centreline at --mesh_threshold with its radii against the signed distance '
+                        'images of the silhouettes (pixel_value < --hull_threshold), by Levenberg-Marquardt on the 2D-3D chamfer residual '
+                        '(afx_pose_chamfer, afx_pose_lm_step); one row per view: the id, the given and the refined cam2world, the chamfer '
+                        'before and after, the shift in pixels and the accepted steps.  Needs --binary True.  The refined poses are written, '
+                        'not trained with; without the flag nothing changes')
+    p.add_argument('--pose_dof', default='all', choices=['all', 'translation', 'rotation', 'inplane'],
+                   help='--save_poses: the degrees of freedom that move (inplane: the rotation about the view axis and the two detector shifts)')
+    p.add_argument('--pose_trunc', type=float, default=8.0, metavar='PIXELS',
+                   help='--save_poses: the residual is truncated at PIXELS (a point further from the silhouette pulls no more)')
+    p.add_argument('--pose_search', type=float, nargs=3, default=None, metavar=('DEGREES', 'UNITS', 'STEPS'),
+                   help='--save_poses: before the refinement, score an in-plane grid of STEPS^3 poses (STEPS odd) within +-DEGREES about the '
+                        'view axis and +-UNITS along the two detector axes, and start from the best')
+    p.add_argument('--pose_noise', type=float, nargs=2, default=None, metavar=('DEG', 'UNITS'),
+                   help='--synthetic: the images are rendered at the true poses, but the poses and rays handed to training are perturbed by a '
+                        'seeded rigid increment of up to +-DEG about each camera axis and +-UNITS along each (make_synthetic_dataset '
+                        'pose_noise); unshifted_tform_cam2world keeps the true poses')
     p.add_argument('--grid_init', default=None, choices=['hull'],
                    help='hull (--march grid or grid_ops, --binary True): before training, carve both occupancy grids with the visual hull of '
                         'the training views - a cell stays only where no training view\'s vessel silhouette (pixel_value < --hull_threshold) '
@@ -280,6 +301,27 @@ def check_args(args):
             raise ValueError("--mesh_threshold: needs SIGMA > 0")
         if not (args.view_map_step > 0 and np.isfinite(args.view_map_step)):
             raise ValueError("--view_map_step: needs DEGREES > 0")
+    if getattr(args, 'save_poses', None) is not None:
+        if args.binary != 'True':
+            raise ValueError("--save_poses: needs --binary True (vessel-only data: on data with background every pixel attenuates, and "
+                             "there is no vessel silhouette to register a pose to)")
+        if os.path.splitext(args.save_poses)[1].lower() != '.csv':
+            raise ValueError("--save_poses: PATH must end in .csv")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
+        if not (args.pose_trunc > 0 and np.isfinite(args.pose_trunc)):
+            raise ValueError("--pose_trunc: needs a finite PIXELS > 0")
+        if args.pose_search is not None:
+            deg, units, steps = args.pose_search
+            if not (0 <= deg < 180 and units >= 0 and np.isfinite(units) and steps == int(steps) and steps >= 1 and int(steps) % 2 == 1):
+                raise ValueError("--pose_search: needs 0 <= DEGREES < 180, UNITS >= 0 and an odd STEPS >= 1")
+    elif getattr(args, 'pose_search', None) is not None:
+        raise ValueError("--pose_search: needs --save_poses")
+    if getattr(args, 'pose_noise', None) is not None:
+        if not args.synthetic:
+            raise ValueError("--pose_noise: needs --synthetic (the poses of the synthetic dataset are perturbed)")
+        if not all(np.isfinite(x) and x >= 0 for x in args.pose_noise):
+            raise ValueError("--pose_noise: needs DEG >= 0 and UNITS >= 0")
 
 
 def checkpoint_interval(checkpoint_every: int, graph_rounds: bool, round_len: int = 16) -> int:
@@ -313,11 +355,11 @@ def main(argv=None):
                                                     img_size=args.img_size, sampling_strategy=sampling_strategy,
                                                     device=device, seed=args.seed, binary=binary,
                                                     phantom=mesh_phantom(args.phantom_mesh, args.phantom_points, outside, device),
-                                                    projection_type='sdf')
+                                                    projection_type='sdf', pose_noise=args.pose_noise)
     elif args.synthetic:
         proj_df, ray_df = ds.make_synthetic_dataset(ds.angle_grid(limited_size, int(number_angles), center_point),
                                                     img_size=args.img_size, sampling_strategy=sampling_strategy,
-                                                    device=device, seed=args.seed, binary=binary)
+                                                    device=device, seed=args.seed, binary=binary, pose_noise=args.pose_noise)
     else:
         step_size = limited_size / number_angles if number_angles > 0 else limited_size
         proj_df, ray_df, _, _ = ds.load_data(data_name, file_name, False, binary, args.img_size, step_size, args.data_root)
@@ -600,7 +642,7 @@ def main(argv=None):
     exports = (('mesh_info', save_mesh, args.save_mesh), ('centreline_info', save_centreline, args.save_centreline),
                ('lumen_info', save_lumen, args.save_lumen))
     exports = [e for e in exports if e[2] is not None]
-    if exports or args.save_view_map is not None or args.save_cpr is not None:      # the density grid the exports read, evaluated once
+    if exports or args.save_view_map is not None or args.save_cpr is not None or args.save_poses is not None:      # the density grid the exports read, evaluated once
         from ..render import density_grid
         grid = density_grid(coarse_model, outside, depth_samples_per_ray_coarse)
     for key, save, path in exports:
@@ -610,6 +652,10 @@ def main(argv=None):
         result['view_map_info'] = save_view_map(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_view_map,
                                                 sweep_angles(limited_size, args.view_map_step), img_width, img_height,
                                                 float(proj_df['focal_length'].iloc[0]), (0.0, 0.0, src_pt_z), grid=grid)
+    if args.save_poses is not None:
+        result['pose_info'] = save_poses(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_poses, proj_df,
+                                         train_ray_df, test_proj_id, args.hull_threshold, device, dof=args.pose_dof, trunc=args.pose_trunc,
+                                         search=args.pose_search, grid=grid)
     if args.save_cpr is not None:
         result['cpr_info'] = save_cpr(coarse_model, outside, depth_samples_per_ray_coarse + 1, args.mesh_threshold, args.save_cpr, args.cpr_angles,
                                       args.cpr_half_width, grid=grid)
@@ -872,6 +918,47 @@ def save_view_map(model, outside, n, threshold, path, angles, width, height, foc
     info = dict(path=str(path), n_views=int(angles.shape[0]), n_branches=nb, n_segments=vm['n_segments'] if nb else 0, threshold=float(threshold),
                 best=best)
     print('view map', info, flush=True)
+    return info
+
+
+POSE_CSV_COLUMNS = ('image_id',) + tuple(f'given_{r}{c}' for r in range(3) for c in range(4)) + \
+    tuple(f'refined_{r}{c}' for r in range(3) for c in range(4)) + ('chamfer_before', 'chamfer_after', 'rms_before', 'rms_after', 'shift_px', 'accepted', 'selected')
+
+
+def save_poses(model, outside, n, threshold, path, proj_df, train_ray_df, test_proj_id, mask_threshold, device, dof='all', trunc=8.0,
+               search=None, iterations=20, prune_factor=1.0, grid=None):
+    """--save_poses: every training view's pose registered (`engine.centreline_register_poses`: afx_pose_chamfer, afx_pose_lm_step) to its
+    silhouette (`training_view_masks` at mask_threshold): the points are the pruned centreline of {sigma >= threshold} on the model's
+    density grid (that of --save_centreline, radii voxel x sqrt(d2)).  One CSV row per view (POSE_CSV_COLUMNS: the first three rows of the
+    given and the refined cam2world, the mean chamfer residual in pixels before and after, its root mean square before and after (the
+    figure the registration minimises, so it never rises), the mean shift of the points' projections,
+    the accepted steps and the search's candidate; numbers written with repr) -> its info (path, n_views, n_points, dof, trunc,
+    chamfer_before, chamfer_after, shift_px: the means over the views).  A centreline without a point writes the header alone."""
+    tree, a = _export_tree(_export_grid(model, outside, n, grid), outside, n, threshold, prune_factor)
+    poses, masks, focal = training_view_masks(proj_df, train_ray_df, test_proj_id, mask_threshold, device)
+    ids = [i for i in proj_df.index if i != test_proj_id]
+    n_points = int(tree['graph']['path_voxels'].numel())
+    reg = None
+    if n_points:
+        views = _engine.pose_views(poses, masks, focal)
+        reg = _engine.centreline_register_poses(tree['graph'], views, index_to_world=a, d2=tree['d2'],
+                                                voxel_size=2.0 * float(outside) / (int(n) - 1), iterations=iterations, trunc=float(trunc),
+                                                dof=dof, search=None if search is None else (float(search[0]), float(search[1]), int(search[2])))
+    tmp = f'{path}.tmp.{os.getpid()}'
+    with open(tmp, 'w') as f:
+        f.write(','.join(POSE_CSV_COLUMNS) + '\n')
+        for v in range(len(ids) if reg is not None else 0):
+            row = [ids[v]] + [repr(float(x)) for x in np.asarray(poses[v], np.float64)[:3].reshape(-1)] + \
+                  [repr(float(x)) for x in reg['poses'][v, :3].reshape(-1)] + \
+                  [repr(float(reg[k][v])) for k in ('mean_residual_before', 'mean_residual_after', 'rms_residual_before', 'rms_residual_after')] + \
+                  [repr(float(reg['shift_px'][v])),
+                   int(reg['accepted'][v]), int(reg['selected'][v])]
+            f.write(','.join(str(x) for x in row) + '\n')
+    os.replace(tmp, path)
+    mean = lambda key: float(np.mean(reg[key])) if reg is not None else float('nan')
+    info = dict(path=str(path), n_views=len(ids), n_points=n_points, dof=str(dof), trunc=float(trunc), chamfer_before=mean('mean_residual_before'),
+                chamfer_after=mean('mean_residual_after'), shift_px=mean('shift_px'))
+    print('poses', info, flush=True)
     return info
 
 

@@ -93,13 +93,31 @@ def angle_grid(limited_size: float, number_angles: int, center_point=(90, 0)):
     return grid
 
 
+def perturb_pose(cam2world, rot_deg, shift):
+    """cam2world [4, 4] moved by a rigid increment in the camera frame, q' = C(a) q + t: the Cayley rotation C(a) with a_k =
+    tan(rot_deg_k / 2) and t = shift, composed as afx_pose_compose does (R' = R C^T, c' = c - R' t).  float64 on the host."""
+    m = np.array(cam2world, dtype=np.float64)
+    a = np.tan(np.deg2rad(np.asarray(rot_deg, np.float64)) / 2.0)
+    t = np.asarray(shift, np.float64)
+    n = float(a @ a)
+    ax = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    c = ((1.0 - n) * np.eye(3) + 2.0 * np.outer(a, a) + 2.0 * ax) / (1.0 + n)
+    out = m.copy()
+    out[:3, :3] = m[:3, :3] @ c.T
+    out[:3, 3] = m[:3, 3] - out[:3, :3] @ t
+    return out
+
+
 def make_synthetic_dataset(angles, img_size: int = 64, depth_samples_per_ray: int = 160, outside: float = 100.0,
                            src_z: float = 1500.0, sampling_strategy: str = "segmentation", device="cpu", seed: int = 0,
-                           binary: bool = True, phantom=None, projection_type: str = "ct"):
+                           binary: bool = True, phantom=None, projection_type: str = "ct", pose_noise=None):
     """(proj_df, ray_df) for a capsule-tree phantom seen from `angles` = [(theta, phi), ...]; larm = 0, no shifts.
     phantom: a `VoxelVolume` (e.g. `voxel_volume_from_mesh` of an STL vessel) that replaces the capsule tree; it is projected by
     `helpers.ray_tracing` with type=projection_type ('ct', or 'sdf' as the reference's sdftoray.py projects a distance field).  None:
     the capsule tree, as before.
+    pose_noise: None, or (degrees, units): the images are rendered at the true poses, but `tform_cam2world` and the ray table come from
+    poses perturbed by a seeded increment in the camera frame (`perturb_pose`: up to +-degrees about each camera axis and +-units along
+    each); `unshifted_tform_cam2world` keeps the true ones.  None is byte for byte the dataset without the argument.
     sampling_strategy 'frangi' computes the weights of all views with one sampling_weights_device call (`binary` False: with
     cttoray's percentile pre-step) and needs a GPU `device`; 'segmentation' and 'random' run the host sampling_weights per view."""
     w = h = int(img_size)
@@ -112,6 +130,12 @@ def make_synthetic_dataset(angles, img_size: int = 64, depth_samples_per_ray: in
         raise ValueError(f"make_synthetic_dataset: projection_type must be 'ct' or 'sdf', got {projection_type!r}")
     caps = capsule_tree(levels=5, seed=seed) if phantom is None else None
     views = []
+    noise_rng = None
+    if pose_noise is not None:
+        noise_deg, noise_units = (float(x) for x in pose_noise)
+        if not (noise_deg >= 0 and noise_units >= 0 and np.isfinite(noise_deg) and np.isfinite(noise_units)):
+            raise ValueError(f"make_synthetic_dataset: pose_noise must be two finite numbers >= 0, got {pose_noise!r}")
+        noise_rng = np.random.RandomState(int(seed) + 7919)
     for theta, phi in angles:
         o, d, mat, ii, jj = get_ray_values(theta, phi, 0.0, src_pt, w, h, focal, device)
         z = get_depth_values(near, far, depth_samples_per_ray, device, stratified=False)
@@ -121,19 +145,24 @@ def make_synthetic_dataset(angles, img_size: int = 64, depth_samples_per_ray: in
             else:
                 img = ray_tracing(lambda p: capsule_mu(p, caps), o.reshape(-1, 3).float(), d.reshape(-1, 3).float(),
                                   z.float(), batch_rays=8192).reshape(h, w).cpu()
-        views.append((theta, phi, o, d, mat, ii, jj, z, img.numpy().astype(np.float64)))
+        true_mat = mat
+        if noise_rng is not None:                  # the image above is the true view; the pose and the rays handed on are the perturbed ones
+            from .._geometry import camera_rays
+            mat = perturb_pose(mat, noise_rng.uniform(-noise_deg, noise_deg, 3), noise_rng.uniform(-noise_units, noise_units, 3))
+            o, d = camera_rays(torch.from_numpy(mat).to(device), ii, jj, w, h, focal)
+        views.append((theta, phi, o, d, mat, ii, jj, z, img.numpy().astype(np.float64), true_mat))
     if sampling_strategy == "frangi":
         if torch.device(device).type != "cuda":
             raise NotImplementedError("sampling_strategy='frangi' runs on the GPU only (sampling_weights_device): pass a cuda device")
-        stack = torch.from_numpy(np.stack([v[-1] for v in views])).to(device)
+        stack = torch.from_numpy(np.stack([v[8] for v in views])).to(device)
         all_wts = list(sampling_weights_device(stack, "frangi", binary=binary).cpu().numpy())
     else:
-        all_wts = [sampling_weights(v[-1], sampling_strategy) for v in views]
+        all_wts = [sampling_weights(v[8], sampling_strategy) for v in views]
     proj_rows, ray_frames = [], []
-    for image_id, ((theta, phi, o, d, mat, ii, jj, z, img_np), wts) in enumerate(zip(views, all_wts)):
+    for image_id, ((theta, phi, o, d, mat, ii, jj, z, img_np, true_mat), wts) in enumerate(zip(views, all_wts)):
         proj_rows.append(dict(image_id=image_id, theta=theta, phi=phi, larm=0.0, theta_shift=0.0, phi_shift=0.0,
                               larm_shift=0.0, translation_x=0.0, translation_y=0.0, translation_z=0.0,
-                              tform_cam2world=mat.tolist(), unshifted_tform_cam2world=mat.tolist(),
+                              tform_cam2world=mat.tolist(), unshifted_tform_cam2world=true_mat.tolist(),
                               image_data=img_np.tolist(), image_distance_data=wts.tolist(), org_img_width=w,
                               org_img_height=h, focal_length=focal, near_thresh=near, far_thresh=far,
                               depth_sample=depth_samples_per_ray, grid_scaling_factor=1,

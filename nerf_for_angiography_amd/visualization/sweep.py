@@ -65,6 +65,11 @@ VIEW_METRICS = ("FORESHORTENING ERR 3D", "OVERLAP ERR 3D", "VIEW REGRET 3D")
 # the TRUE centreline (engine.cpr_images: afx_reformat_planes), compared as images; a tuple of its own behind the view columns; it needs
 # the ground-truth volume
 CPR_METRICS = ("CPR PSNR 3D", "CPR SSIM 3D", "CPR CORR 3D")
+# and whether the poses the model was trained with fit the silhouettes of its training views: the 2D-3D chamfer of the pruned predicted
+# centreline against the views' signed distance images before and after a rigid registration of every pose (engine.register_poses:
+# afx_pose_chamfer, afx_pose_lm_step); a tuple of its own behind the CPR columns.  It needs the training views
+# (pose_views=engine.pose_views(poses, masks, focal)) and NO ground truth: volume=None works, with a threshold
+POSE_METRICS = ("CHAMFER 2D", "CHAMFER 2D REFINED", "POSE SHIFT 2D")
 CPR_MIN_ROWS = 11                     # afx_ssim takes images of at least 11 x 11
 
 
@@ -88,7 +93,7 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
                      depth_samples_per_ray, translation=(0.0, 0.0, 0.0), binary_thresh=0.05, binary_targets=None,
                      views_per_launch=512, grid=None, scene_aabb=None, early_stop_eps=1e-2, alpha_thre=1e-3, metrics=None, volume=None,
                      volume_outside=100.0, volume_points=None, hull_views=None, sirt_views=None, sirt_iterations=50, sirt_relax=1.0,
-                     sirt_tv_weight=None, sirt_tv_iterations=10):
+                     sirt_tv_weight=None, sirt_tv_iterations=10, pose_views=None, pose_threshold=None):
     """Per-view metrics of `model` over `angles` [n,2] (theta, phi in degrees).
 
     grid: an occupancy grid (nerf.occupancy.OccupancyGrid, e.g. restored with `grid._binary = mask` as visualization.py:162 does) - the views
@@ -115,9 +120,11 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     columns need sirt_tv_weight as well: the same call with tv_weight = sirt_tv_weight and tv_iterations = sirt_tv_iterations; plain
     SIRT, which both families read, runs once.  The VIEW_METRICS columns stand behind all of these and need `volume` alone: one
     `reconstruction_view_metrics` call over the sweep's own angles, detector, focal length and source, on the pruned centrelines the
-    shared analysis holds.  The arguments are checked before any work on the GPU."""
+    shared analysis holds.  The POSE_METRICS columns stand last and need `pose_views` = engine.pose_views(...) of the training views
+    and no ground truth: one `reconstruction_pose_metrics` call at pose_threshold (None: mean(gt), which needs `volume`).  The arguments
+    are checked before any work on the GPU."""
     from ..engine import ssim
-    want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views, sirt_tv_weight)
+    want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views, sirt_tv_weight, pose_views, pose_threshold)
     dev = model.flat_params.device
     n = len(angles)
     poses = _poses(angles, src_pt, translation, dev)
@@ -193,17 +200,22 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         got = reconstruction_cpr_metrics(model, volume, volume_outside, pts, grids=analysis)[0]
         for name, key in zip(CPR_METRICS, ("cpr_psnr", "cpr_ssim", "cpr_corr")):
             scores[name] = [got[key]] * n
+    if any(m in want for m in POSE_METRICS):                  # behind the CPR columns; the one family that needs no truth
+        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+        got = reconstruction_pose_metrics(model, volume, volume_outside, pts, pose_views, threshold=pose_threshold, grids=analysis)[0]
+        for name, key in zip(POSE_METRICS, ("chamfer", "chamfer_refined", "pose_shift")):
+            scores[name] = [got[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
 
 
-def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=None, sirt_tv_weight=None):
+def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=None, sirt_tv_weight=None, pose_views=None, pose_threshold=None):
     """The metric columns evaluation_sweep fills, in order; raises on a request it cannot serve (before any GPU work)."""
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS + CPR_METRICS
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS + CPR_METRICS + POSE_METRICS
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
@@ -234,6 +246,11 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     view = [m for m in metrics if m in VIEW_METRICS + CPR_METRICS]
     if view and volume is None:
         raise ValueError(f"evaluation_sweep: {view} need the ground-truth volume (volume=VoxelVolume)")
+    pose = [m for m in metrics if m in POSE_METRICS]
+    if pose and pose_views is None:
+        raise ValueError(f"evaluation_sweep: {pose} need the training views (pose_views=engine.pose_views(poses, masks, focal))")
+    if pose and volume is None and pose_threshold is None:
+        raise ValueError(f"evaluation_sweep: {pose} without a ground-truth volume need the level the prediction is cut at (pose_threshold=T)")
     return [m for m in known if m in metrics]
 
 
@@ -759,6 +776,39 @@ def reconstruction_view_metrics(model, volume, outside, n, angles, img_width=100
         view_scores(maps[0], maps[1], overlap_weight)
     scores["threshold"] = thr
     return scores, maps[0], maps[1]
+
+
+@torch.no_grad()
+def reconstruction_pose_metrics(model, volume, outside, n, views, threshold=None, largest_component=False, prune_factor=1.0, iterations=20,
+                                trunc=8.0, dof="all", search=None, grids=None):
+    """Do the training poses fit the silhouettes of their views, judged by the reconstruction alone -> (scores, `engine.register_poses`'
+    result or None).
+
+    The points are the pruned predicted centreline of `reconstruction_graph_metrics` (same threshold, largest_component, prune_factor:
+    with `grids=` a GridAnalysis nothing is thinned twice) with the radii voxel x sqrt(d2) of its mask; `views` = engine.pose_views(poses,
+    masks, focal) of the training views.  Scores: chamfer = the mean over the views of sum w r / sum w in pixels (the one-sided residual
+    truncated at `trunc`: a point inside its silhouette costs nothing), chamfer_refined the same after `engine.register_poses`
+    (iterations, trunc, dof, search), pose_shift the mean pixel displacement of the points between the given and the refined poses,
+    plus threshold and n_points.  No ground truth is read: volume=None works, and then needs `threshold` (None is mean(gt)).  A
+    predicted centreline without a point scores NaN."""
+    from ..engine import centreline_register_poses
+    if volume is None and not isinstance(grids, GridAnalysis):
+        if threshold is None:
+            raise ValueError("reconstruction_pose_metrics: without a ground-truth volume the threshold must be given")
+        grids = GridAnalysis(density_grid(model, outside, int(n) - 1) if grids is None else grids[0], None, outside, n)
+    if isinstance(grids, GridAnalysis) and grids.gt is None and threshold is None:
+        raise ValueError("reconstruction_pose_metrics: without a ground-truth volume the threshold must be given")
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    tree = an.tree("pred", thr, largest_component, prune_factor)
+    n_points = int(tree["graph"]["path_voxels"].numel())
+    nan = float("nan")
+    if n_points == 0:
+        return dict(chamfer=nan, chamfer_refined=nan, pose_shift=nan, threshold=thr, n_points=0), None
+    reg = centreline_register_poses(tree["graph"], views, index_to_world=an.index_to_world, d2=tree["d2"], voxel_size=an.voxel,
+                                    iterations=iterations, trunc=trunc, dof=dof, search=search)
+    scores = dict(chamfer=float(np.mean(reg["mean_residual_before"])), chamfer_refined=float(np.mean(reg["mean_residual_after"])),
+                  pose_shift=float(np.mean(reg["shift_px"])), threshold=thr, n_points=n_points)
+    return scores, reg
 
 
 def cpr_scores(images_p, images_g):
