@@ -1374,6 +1374,55 @@ int afx_pose_select(const double* sums, int32_t n_views, int32_t n_candidates, i
 int afx_pose_lm_step(double* state, int32_t n_views, const double* sums, int32_t n_slices, int32_t phase, uint32_t dof_mask, double lambda0,
                      const double* records_in /* AFX_POSE_LM_INIT only */, double* trial_records, void* stream);
 
+/* ---- Territories: the exact 3-D feature transform (the nearest labelled voxel of any mask) and per-label overlap counts.  With the
+ * voxels of a centreline graph as sites, every vessel voxel gets the branch it lies nearest to, and one counting call gives the
+ * per-branch Dice, sensitivity, precision and coverage.  Integer arithmetic only; device pointers; nothing allocated, synchronised or
+ * read back; every call is a fixed launch sequence and can be captured in a graph; the same bits on every run.
+ * tests/territory_reference.py restates both in NumPy and the device equals the restatement exactly.
+ *
+ * afx_feature_transform_3d.  sites: uint8 [n0][n1][n2], row-major; a non-zero voxel is a site.  The linear index of voxel (i0, i1, i2)
+ * is (i0 n1 + i1) n2 + i2.  For every voxel v = (v0, v1, v2) and every site s = (s0, s1, s2):
+ *        dist2(v, s) = (v0 - s0)^2 + (v1 - s1)^2 + (v2 - s2)^2                                  (integers, below 2^22)
+ *        d2[v]      = min over the sites s of dist2(v, s)
+ *        nearest[v] = the LOWEST linear index among the sites s with dist2(v, s) == d2[v]
+ *   i.e. the lexicographic minimum of the pair (dist2(v, s), index of s).  On a site, d2 = 0 and nearest[v] = v.  Without any site
+ *   d2 = AFX_EDT3D_NONE and nearest = -1 everywhere.  d2 equals the d2 of afx_distance_transform_edt_3d of the inverted mask
+ *   (fg = sites == 0) bit for bit.
+ *   Three separable passes, each the lexicographic minimum of (value, carried site index), which reaches the rule above (the pair's
+ *   minimum over a plane is the minimum over its lines of the lines' minima, a constant added to the first entry keeping the order):
+ *     axis 2:  g2[v] = min over the sites s of v's own line (s0 = v0, s1 = v1) of ((v2 - s2)^2, index of s): a wave per line, ballots
+ *              for the nearest site below and above; at an equal distance the lower side stays.
+ *     axis 1:  g1[v] = min over c in 0..n1-1 of (g2[(v0, c, v2)].value + (v1 - c)^2, g2[(v0, c, v2)].site), lines without a site left out.
+ *     axis 0:  (d2[v], nearest[v]) = min over c in 0..n0-1 of (g1[(c, v1, v2)].value + (v0 - c)^2, g1[(c, v1, v2)].site).
+ *   The line passes pack the pair as value << 32 | site (value < 2^22, site < 2^30; all ones = no site) and compare 64-bit unsigned.  A
+ *   workgroup takes a tile of 16 adjacent lines (lines of up to 512 voxels; 8 beyond) into 64 KiB of LDS and searches the lower
+ *   envelope outwards from each voxel; the search stops once (v - c)^2 alone is GREATER than the best value (at equality a site
+ *   straight along the axis still ties and may carry a lower index).  d2 and nearest are the passes' own storage: the axis-2 pass
+ *   writes them, the line passes work in place (a workgroup reads its whole tile before it writes and no other workgroup touches that
+ *   tile), so the call takes no scratch buffer.  No atomics.
+ *   AFX_E_INVALID before any HIP call: a null sites, d2 or nearest; an axis outside 1..AFX_EDT3D_MAX_SIDE.
+ *
+ * afx_label_overlap_3d.  labels: int32 [n]; index: int32 [n] or NULL; d2: uint32 [n] or NULL; a: uint8 [n]; b: uint8 [n] or NULL;
+ * counts: uint64 [n_labels + 1][4]; territory: int32 [n] or NULL.  For every v in 0..n-1:
+ *        s = index ? index[v] : v
+ *        l = 0                         if s < 0 or s >= n, or if d2 && d2[v] > max_d2      (a voxel exactly at max_d2 is inside)
+ *        l = labels[s]                 otherwise; an l outside 1..n_labels becomes 0
+ *        territory[v] = l              (when territory is given)
+ *        counts[l][0] += 1;  counts[l][1] += (a[v] != 0);  counts[l][2] += (b && b[v] != 0);  counts[l][3] += (a[v] != 0 && b && b[v] != 0)
+ *   Row 0 collects what belongs to no label.  counts is zeroed by the call's first launch, so the output is fully defined; n == 0
+ *   leaves it all zero.  Integer atomics only, so the result does not depend on the order of execution: the lanes of a wave that hold
+ *   the same label meet in ballots and add once to a per-workgroup table in LDS, which goes to global memory once per workgroup.
+ *   With index = nearest and d2 of afx_feature_transform_3d and labels = the labels of the sites, l is the territory of v, cut off at
+ *   the squared distance max_d2.
+ *   AFX_E_INVALID before any HIP call: a null labels, a or counts; n < 0 or n > AFX_LABEL_OVERLAP_MAX_N; n_labels < 0 or
+ *   n_labels > AFX_LABEL_OVERLAP_MAX_LABELS (the table of a workgroup fits in 64 KiB of LDS). */
+#define AFX_LABEL_OVERLAP_MAX_LABELS 4095
+#define AFX_LABEL_OVERLAP_MAX_N (1ll << 40)
+int afx_feature_transform_3d(const uint8_t* sites, int32_t n0, int32_t n1, int32_t n2, uint32_t* d2, int32_t* nearest, void* stream);
+int afx_label_overlap_3d(const int32_t* labels, const int32_t* index /* may be NULL */, const uint32_t* d2 /* may be NULL */,
+                         uint32_t max_d2, const uint8_t* a, const uint8_t* b /* may be NULL */, int64_t n, int32_t n_labels,
+                         uint64_t* counts /* [n_labels + 1][4] */, int32_t* territory /* [n], may be NULL */, void* stream);
+
 /* Trainable fourier coefficients (model/CPPN.py:92 makes them an nn.Parameter; fourier_pos_enc, CPPN.py:320-327, is
  * differentiable in them).  After this call every backward entry point (afx_mlp_backward, afx_render_backward,
  * afx_train_step_mse) at a 16-bit precision also does d_enc_aux[3*n_freq] += d loss / d coefficients; `params` is the

@@ -228,6 +228,9 @@ _SIGS = {
     "afx_pose_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "afx_pose_lm_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "afx_feature_transform_3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "afx_label_overlap_3d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 _libs = {}

@@ -3079,6 +3079,147 @@ def centreline_register_poses(graph: dict, views: dict, index_to_world=None, rad
     return register_poses(points, rad, views, **kw)
 
 
+LABEL_OVERLAP_MAX_LABELS = 4095       # AFX_LABEL_OVERLAP_MAX_LABELS
+EDT3D_NONE = 0xffffffff               # AFX_EDT3D_NONE
+EDT3D_MAX_SIDE = 1024                 # AFX_EDT3D_MAX_SIDE
+
+
+def _territory_tensor(t, shape, dtype, name, dev, who):
+    """A caller's buffer of the territory entry points: contiguous, of that dtype and shape, on that GPU."""
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def feature_transform_record(sites: torch.Tensor, d2=None, nearest=None):
+    """afx_feature_transform_3d, the launches alone, on a contiguous uint8 [n0, n1, n2] device mask (non-zero = a site) -> (d2, nearest):
+    int32 tensors of the mask's shape, d2 holding the library's uint32 squared distance (0xffffffff as -1: no site), nearest the linear
+    index of the nearest site (ties to the lowest index; -1: no site).  With both buffers passed nothing is allocated and nothing is read
+    back: the call can be captured in a graph.  There is no workspace: the two outputs are the passes' own storage."""
+    lib = _lib.load()
+    _volume_on_gpu(sites, "the sites", "feature_transform_3d")
+    if sites.dtype != torch.uint8 or not sites.is_contiguous():
+        raise ValueError(f"feature_transform_record: the sites must be a contiguous uint8 tensor, got {sites.dtype}, contiguous = {sites.is_contiguous()}")
+    dev = sites.device
+    n0, n1, n2 = sites.shape
+    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
+    ok = all(1 <= s <= EDT3D_MAX_SIDE for s in sites.shape)
+    shape = tuple(sites.shape) if ok else (1,)
+    d2 = torch.empty(shape, dtype=torch.int32, device=dev) if d2 is None else _territory_tensor(d2, shape, torch.int32, "d2", dev, "feature_transform_record")
+    nearest = torch.empty(shape, dtype=torch.int32, device=dev) if nearest is None else \
+        _territory_tensor(nearest, shape, torch.int32, "nearest", dev, "feature_transform_record")
+    _lib.check(lib.afx_feature_transform_3d(_ptr(sites), n0, n1, n2, _ptr(d2), _ptr(nearest), Engine._stream(dev)), "afx_feature_transform_3d")
+    return d2, nearest
+
+
+def feature_transform_3d(sites: torch.Tensor):
+    """The exact feature transform of a [n0, n1, n2] device tensor (any dtype, non-zero = a site) -> (d2, nearest), both int64
+    [n0, n1, n2]: the integer squared distance, in voxels, from every voxel to the nearest site (the library's 0xffffffff without any
+    site) and the linear index of that site, the LOWEST index among the sites at that distance (-1 without any site).  d2 equals
+    distance_transform_edt_3d(sites == 0, return_squared=True)[1] exactly (include/afx.h: afx_feature_transform_3d)."""
+    _volume_on_gpu(sites, "the sites", "feature_transform_3d")
+    d2, nearest = feature_transform_record((sites != 0).to(torch.uint8).contiguous())
+    return d2.to(torch.int64) & 0xffffffff, nearest.to(torch.int64)
+
+
+def label_overlap_record(labels: torch.Tensor, a: torch.Tensor, n_labels: int, b=None, index=None, d2=None, max_d2: int = EDT3D_NONE, counts=None,
+                         territory=None):
+    """afx_label_overlap_3d, the launches alone, on contiguous device tensors of n elements each (any shape): labels int32, a uint8, b
+    uint8 or None, index int32 or None, d2 int32 (holding the library's uint32) or None -> (counts int64 [n_labels + 1, 4], territory):
+    counts[l] = (voxels, voxels of a, voxels of b, voxels of both) whose label l = labels[index[v]] (labels[v] without index; 0 for a
+    negative index, a d2 above max_d2 or a label outside 1..n_labels); territory (int32, written only when passed) = l per voxel.  The
+    call zeroes counts itself.  With counts passed nothing is allocated or read back: the call can be captured in a graph."""
+    lib = _lib.load()
+    who = "label_overlap_record"
+    if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
+        raise AfxError("label_overlap_3d: the labels must be a tensor on a GPU; there is no CPU path")
+    dev, shape, n = labels.device, tuple(labels.shape), labels.numel()
+    labels = _territory_tensor(labels, shape, torch.int32, "labels", dev, who)
+    a = _territory_tensor(a, shape, torch.uint8, "a", dev, who)
+    b = None if b is None else _territory_tensor(b, shape, torch.uint8, "b", dev, who)
+    index = None if index is None else _territory_tensor(index, shape, torch.int32, "index", dev, who)
+    d2 = None if d2 is None else _territory_tensor(d2, shape, torch.int32, "d2", dev, who)
+    territory = None if territory is None else _territory_tensor(territory, shape, torch.int32, "territory", dev, who)
+    if not 0 <= int(max_d2) <= EDT3D_NONE:
+        raise ValueError(f"{who}: max_d2 = {max_d2} must lie in 0..0xffffffff")
+    rows = int(n_labels) + 1 if 0 <= int(n_labels) <= LABEL_OVERLAP_MAX_LABELS else 1      # a refused n_labels: the call reports the limits
+    counts = torch.empty((rows, 4), dtype=torch.int64, device=dev) if counts is None else _territory_tensor(counts, (rows, 4), torch.int64, "counts", dev, who)
+    _lib.check(lib.afx_label_overlap_3d(_ptr(labels), _ptr(index), _ptr(d2), int(max_d2), _ptr(a), _ptr(b), n, int(n_labels), _ptr(counts),
+                                        _ptr(territory), Engine._stream(dev)), "afx_label_overlap_3d")
+    return counts, territory
+
+
+def _u32_in_i32(x: torch.Tensor) -> torch.Tensor:
+    """Values 0..2^32 - 1 of any integer dtype as the library's uint32, held in a contiguous int32 tensor."""
+    if x.dtype == torch.int32:
+        return x.contiguous()
+    x = x.to(torch.int64)
+    return torch.where(x >= 2 ** 31, x - 2 ** 32, x).to(torch.int32).contiguous()
+
+
+def label_overlap_3d(labels: torch.Tensor, a: torch.Tensor, b=None, index=None, d2=None, max_d2=None, n_labels=None, return_territory: bool = False):
+    """Per-label overlap counts (include/afx.h: afx_label_overlap_3d) -> counts int64 [n_labels + 1, 4] on the device, with
+    return_territory (counts, territory int32 of labels' shape).  labels: integer device tensor; a, b: masks of the same shape (non-zero
+    = in; b may be None); index: integer tensor of the same shape (e.g. `feature_transform_3d`'s nearest; None: every voxel speaks for
+    itself); d2 with max_d2: voxels whose d2 lies above max_d2 go to row 0 (both or neither).  n_labels=None: max(labels), read back.
+    counts[l] = (voxels, voxels of a, of b, of both) with label l; row 0 collects what belongs to no label."""
+    if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
+        raise AfxError("label_overlap_3d: the labels must be a tensor on a GPU; there is no CPU path")
+    if (d2 is None) != (max_d2 is None):
+        raise ValueError("label_overlap_3d: d2 and max_d2 go together")
+    shape, dev = tuple(labels.shape), labels.device
+    for name, t in (("a", a), ("b", b), ("index", index), ("d2", d2)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != dev):
+            raise ValueError(f"label_overlap_3d: {name} must be a tensor of the labels' shape {shape} on {dev}")
+    lab = labels.to(torch.int32).contiguous()
+    if n_labels is None:
+        n_labels = max(int(lab.max()), 0) if lab.numel() else 0
+    mask = lambda m: None if m is None else (m != 0).to(torch.uint8).contiguous()
+    territory = torch.empty(shape, dtype=torch.int32, device=dev) if return_territory else None
+    counts, _ = label_overlap_record(lab, mask(a), int(n_labels), mask(b), None if index is None else index.to(torch.int32).contiguous(),
+                                     None if d2 is None else _u32_in_i32(d2), EDT3D_NONE if max_d2 is None else int(max_d2), territory=territory)
+    return (counts, territory) if return_territory else counts
+
+
+def branch_site_labels(graph: dict):
+    """The site labels of `branch_territories` -> (labels int32 [n0, n1, n2], B, K): branch b of a `centreline_graph` result carries
+    label b on its path voxels, junction node k label B + k on its voxels, everything else 0."""
+    bl, nl = graph["branch_labels"], graph["node_labels"]
+    nb, nk = int(graph["n_branches"]), int(graph["n_nodes"])
+    return torch.where(bl > 0, bl, torch.where(nl > 0, nl + nb, torch.zeros_like(nl))).to(torch.int32).contiguous(), nb, nk
+
+
+def branch_territories(graph: dict, max_distance=None) -> dict:
+    """The territories of the branches of a `centreline_graph` result: the feature transform (`feature_transform_record`) of the
+    centreline's voxels with `branch_site_labels` as their labels -> {"labels" (int32 volume: the sites' labels), "d2", "nearest" (int32
+    volumes as the library writes them), "n_branches" B, "n_nodes" K, "n_labels" = B + K, "max_d2" (None, or floor(max_distance^2): a
+    voxel farther than max_distance voxels from the centreline belongs to nobody), "names" (B + K strings, "branch b" / "junction k")}.
+    A voxel's territory is labels[nearest[v]]: branch b's row is b, junction k's row B + k, so the junction clusters are rows of their
+    own and no branch gets their voxels.  `territory_overlap` counts masks over it."""
+    labels, nb, nk = branch_site_labels(graph)
+    if nb + nk > LABEL_OVERLAP_MAX_LABELS:
+        raise ValueError(f"branch_territories: {nb} branches and {nk} junctions are more than {LABEL_OVERLAP_MAX_LABELS} labels")
+    if max_distance is not None and not float(max_distance) >= 0.0:
+        raise ValueError(f"branch_territories: max_distance = {max_distance} must be >= 0")
+    d2, nearest = feature_transform_record((labels > 0).to(torch.uint8))
+    max_d2 = None if max_distance is None else min(int(float(max_distance) * float(max_distance)), EDT3D_NONE)
+    return {"labels": labels, "d2": d2, "nearest": nearest, "n_branches": nb, "n_nodes": nk, "n_labels": nb + nk, "max_d2": max_d2,
+            "names": [f"branch {b}" for b in range(1, nb + 1)] + [f"junction {k}" for k in range(1, nk + 1)], "shape": tuple(labels.shape)}
+
+
+def territory_overlap(terr: dict, a: torch.Tensor, b=None, return_territory: bool = False, sites_only: bool = False):
+    """`label_overlap_3d` of the masks a, b (b may be None) over the territories of a `branch_territories` result -> counts int64
+    [B + K + 1, 4] on the device (with return_territory: and the int32 territory volume).  sites_only: every voxel speaks for itself
+    (index = None), so only the centreline's own voxels carry a label - a branch's coverage by a mask."""
+    if sites_only:
+        return label_overlap_3d(terr["labels"], a, b, n_labels=terr["n_labels"], return_territory=return_territory)
+    cut = terr["max_d2"] is not None
+    return label_overlap_3d(terr["labels"], a, b, index=terr["nearest"], d2=terr["d2"] if cut else None, max_d2=terr["max_d2"] if cut else None,
+                            n_labels=terr["n_labels"], return_territory=return_territory)
+
+
 def line_integrals(images, eps: float = 1e-6) -> torch.Tensor:
     """-log(clamp(I, eps, 1)) in fp64: the line integrals behind transmission images I = exp(-integral), the convention of
     ray_tracing(type='ct')."""

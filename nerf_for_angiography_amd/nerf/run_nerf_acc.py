@@ -135,6 +135,11 @@ def build_parser():
                         'centreline of --save_centreline at --mesh_threshold, and at each of its points the area and the diameters of the '
                         'cross-section of the density grid at that level (afx_lumen_profile: 64 rays in the plane normal to the centreline, '
                         'crossings interpolated below the voxel), one row per point; without the flag nothing changes')
+    p.add_argument('--save_branches', default=None, metavar='PATH',
+                   help='after training, write one row per branch and junction of the final model\'s vessel centreline to PATH (.csv): the '
+                        'pruned centreline of --save_centreline at --mesh_threshold, every vessel voxel given to the branch or junction it '
+                        'lies nearest to (afx_feature_transform_3d, afx_label_overlap_3d): territory voxels and volume in world units, '
+                        'length, mean, minimum and maximum radius, attached nodes; needs no ground truth; without the flag nothing changes')
     p.add_argument('--save_cpr', default=None, metavar='PATH',
                    help='after training, write the curved-planar reformation of the final model\'s vessel to PATH (.npy, float64 [A, P, K]): the '
                         'main path of the pruned centreline of --save_centreline at --mesh_threshold (from the widest free end to the farthest '
@@ -283,6 +288,11 @@ def check_args(args):
     if args.save_lumen is not None:
         if os.path.splitext(args.save_lumen)[1].lower() != '.csv':
             raise ValueError("--save_lumen: PATH must end in .csv")
+        if not args.mesh_threshold > 0:
+            raise ValueError("--mesh_threshold: needs SIGMA > 0")
+    if getattr(args, 'save_branches', None) is not None:
+        if os.path.splitext(args.save_branches)[1].lower() != '.csv':
+            raise ValueError("--save_branches: PATH must end in .csv")
         if not args.mesh_threshold > 0:
             raise ValueError("--mesh_threshold: needs SIGMA > 0")
     if args.save_cpr is not None:
@@ -640,7 +650,7 @@ def main(argv=None):
     if hull_info is not None:
         result['hull_info'] = hull_info
     exports = (('mesh_info', save_mesh, args.save_mesh), ('centreline_info', save_centreline, args.save_centreline),
-               ('lumen_info', save_lumen, args.save_lumen))
+               ('lumen_info', save_lumen, args.save_lumen), ('branches_info', save_branches, args.save_branches))
     exports = [e for e in exports if e[2] is not None]
     if exports or args.save_view_map is not None or args.save_cpr is not None or args.save_poses is not None:      # the density grid the exports read, evaluated once
         from ..render import density_grid
@@ -850,6 +860,52 @@ def save_lumen(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
     info = dict(path=str(path), n_points=n_points, n_valid=int((host['flags'] == 0).sum()), max_area_stenosis=worst[0], branch=worst[1],
                 threshold=float(threshold))
     print('lumen', info, flush=True)
+    return info
+
+
+BRANCH_CSV_COLUMNS = ('label', 'kind', 'territory_voxels', 'territory_volume', 'centreline_voxels', 'length', 'r_mean', 'r_min', 'r_max',
+                      'node_start', 'node_end')
+
+
+def save_branches(model, outside, n, threshold, path, prune_factor=1.0, grid=None):
+    """--save_branches: one CSV row (BRANCH_CSV_COLUMNS, numbers written with repr) per branch, then per junction, of the pruned
+    centreline of {sigma >= threshold} on the model's density grid (that of --save_centreline): territory_voxels = the voxels of the
+    mask that lie nearest to that branch or junction (`engine.branch_territories`), territory_volume the same in world units, length
+    (world units; 0 for a junction), the mean, minimum and maximum of the radius voxel x sqrt(d2) over its own centreline voxels, and the
+    junction nodes its two ends are attached to (0: a free end; a junction row repeats its own number) -> its info (path, n_branches,
+    n_nodes, n_rows, n_voxels, n_assigned, threshold).  No ground truth is read.  An empty mask writes the header alone.  grid: as in
+    `save_mesh`."""
+    from ..engine import branch_territories, territory_overlap
+    if os.path.splitext(str(path))[1].lower() != '.csv':
+        raise ValueError("--save_branches: PATH must end in .csv")
+    grid = _export_grid(model, outside, n, grid)
+    tree, _ = _export_tree(grid, outside, n, threshold, prune_factor)
+    mask = grid >= torch.tensor(float(threshold), dtype=torch.float32, device=grid.device)
+    graph = tree['graph']
+    terr = branch_territories(graph)
+    counts = territory_overlap(terr, mask).cpu().numpy()
+    voxel = 2.0 * float(outside) / (int(n) - 1)
+    labels = terr['labels'].reshape(-1)
+    vox = torch.nonzero(labels, as_tuple=False).reshape(-1)
+    lab = labels[vox].cpu().numpy()
+    radius = np.sqrt((tree['d2'].reshape(-1)[vox].to(torch.int64) & 0xffffffff).cpu().numpy().astype(np.float64)) * voxel
+    nb, nk = terr['n_branches'], terr['n_nodes']
+    length = graph['length'].cpu().numpy()
+    ends = np.stack([graph['node_start'].cpu().numpy(), graph['node_end'].cpu().numpy()], axis=1).reshape(nb, 2)
+    tmp = f'{path}.tmp.{os.getpid()}'
+    with open(tmp, 'w') as f:
+        f.write(','.join(BRANCH_CSV_COLUMNS) + '\n')
+        for l in range(1, nb + nk + 1):
+            r = radius[lab == l]
+            branch = l <= nb
+            row = [l, 'branch' if branch else 'junction', int(counts[l, 1]), repr(float(counts[l, 1]) * voxel ** 3), int(r.size),
+                   repr(float(length[l - 1]) if branch else 0.0), repr(float(r.mean())), repr(float(r.min())), repr(float(r.max())),
+                   int(ends[l - 1, 0]) if branch else l - nb, int(ends[l - 1, 1]) if branch else l - nb]
+            f.write(','.join(str(v) for v in row) + '\n')
+    os.replace(tmp, path)
+    info = dict(path=str(path), n_branches=nb, n_nodes=nk, n_rows=nb + nk, n_voxels=int(counts[:, 1].sum()), n_assigned=int(counts[1:, 1].sum()),
+                threshold=float(threshold))
+    print('branches', info, flush=True)
     return info
 
 

@@ -70,7 +70,11 @@ CPR_METRICS = ("CPR PSNR 3D", "CPR SSIM 3D", "CPR CORR 3D")
 # afx_pose_chamfer, afx_pose_lm_step); a tuple of its own behind the CPR columns.  It needs the training views
 # (pose_views=engine.pose_views(poses, masks, focal)) and NO ground truth: volume=None works, with a threshold
 POSE_METRICS = ("CHAMFER 2D", "CHAMFER 2D REFINED", "POSE SHIFT 2D")
-CPR_MIN_ROWS = 11                     # afx_ssim takes images of at least 11 x 11
+# and WHICH branch was lost, thinned or doubled: every vessel voxel of either mask goes to the branch of the TRUE pruned centreline it
+# lies nearest to (engine.branch_territories: afx_feature_transform_3d, afx_label_overlap_3d), scored branch by branch
+# (reconstruction_branch_metrics); a tuple of its own behind the pose columns; it needs the ground-truth volume
+BRANCH_METRICS = ("BRANCH RECALL 3D", "WORST BRANCH DICE 3D", "BRANCH RADIUS ERR 3D")
+CPR_MIN_ROWS = 11                    # afx_ssim takes images of at least 11 x 11
 
 
 def sweep_angles(limited_size_vis: float = 180.0, angle_step_vis: float = 5.0):
@@ -120,9 +124,10 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
     columns need sirt_tv_weight as well: the same call with tv_weight = sirt_tv_weight and tv_iterations = sirt_tv_iterations; plain
     SIRT, which both families read, runs once.  The VIEW_METRICS columns stand behind all of these and need `volume` alone: one
     `reconstruction_view_metrics` call over the sweep's own angles, detector, focal length and source, on the pruned centrelines the
-    shared analysis holds.  The POSE_METRICS columns stand last and need `pose_views` = engine.pose_views(...) of the training views
-    and no ground truth: one `reconstruction_pose_metrics` call at pose_threshold (None: mean(gt), which needs `volume`).  The arguments
-    are checked before any work on the GPU."""
+    shared analysis holds.  The POSE_METRICS columns stand behind the CPR columns and need `pose_views` = engine.pose_views(...) of the training views
+    and no ground truth: one `reconstruction_pose_metrics` call at pose_threshold (None: mean(gt), which needs `volume`).  The BRANCH_METRICS
+    columns stand behind those and need `volume` alone: one `reconstruction_branch_metrics` call at its defaults on the pruned
+    centrelines the shared analysis holds.  The arguments are checked before any work on the GPU."""
     from ..engine import ssim
     want = _check_metrics(metrics, binary_targets, volume, hull_views, sirt_views, sirt_tv_weight, pose_views, pose_threshold)
     dev = model.flat_params.device
@@ -205,6 +210,13 @@ def evaluation_sweep(model, targets, angles, img_width, img_height, focal_length
         got = reconstruction_pose_metrics(model, volume, volume_outside, pts, pose_views, threshold=pose_threshold, grids=analysis)[0]
         for name, key in zip(POSE_METRICS, ("chamfer", "chamfer_refined", "pose_shift")):
             scores[name] = [got[key]] * n
+    if any(m in want for m in BRANCH_METRICS):                # behind the pose columns
+        pts = int(volume_points) if volume_points is not None else int(depth_samples_per_ray) + 1
+        if analysis is None:
+            analysis = GridAnalysis(*_reconstruction_grids(model, volume, volume_outside, pts), volume_outside, pts)
+        got = reconstruction_branch_metrics(model, volume, volume_outside, pts, grids=analysis)[0]
+        for name, key in zip(BRANCH_METRICS, ("branch_recall", "worst_branch_dice", "branch_radius_err")):
+            scores[name] = [got[key]] * n
     for name in want:
         cols[name] = scores[name]
     return pd.DataFrame(cols), preds.view(n, int(img_height), int(img_width))
@@ -215,7 +227,8 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     if metrics is None:
         return ["PSNR", "DOT 2D"] + (["DICE 2D"] if binary_targets is not None else [])
     metrics = [metrics] if isinstance(metrics, str) else list(metrics)
-    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS + CPR_METRICS + POSE_METRICS
+    known = METRICS + _ALL_VOLUME_METRICS + HULL_METRICS + SIRT_METRICS + SIRT_TV_METRICS + VIEW_METRICS + CPR_METRICS + POSE_METRICS + \
+        BRANCH_METRICS
     unknown = [m for m in metrics if m not in known]
     if unknown:
         raise ValueError(f"evaluation_sweep: unknown metrics {unknown}; choose from {list(known)}")
@@ -243,7 +256,7 @@ def _check_metrics(metrics, binary_targets, volume, hull_views=None, sirt_views=
     tv = [m for m in metrics if m in SIRT_TV_METRICS]
     if tv and sirt_tv_weight is None:
         raise ValueError(f"evaluation_sweep: {tv} need the weight of the total variation (sirt_tv_weight=W)")
-    view = [m for m in metrics if m in VIEW_METRICS + CPR_METRICS]
+    view = [m for m in metrics if m in VIEW_METRICS + CPR_METRICS + BRANCH_METRICS]
     if view and volume is None:
         raise ValueError(f"evaluation_sweep: {view} need the ground-truth volume (volume=VoxelVolume)")
     pose = [m for m in metrics if m in POSE_METRICS]
@@ -809,6 +822,97 @@ def reconstruction_pose_metrics(model, volume, outside, n, views, threshold=None
     scores = dict(chamfer=float(np.mean(reg["mean_residual_before"])), chamfer_refined=float(np.mean(reg["mean_residual_after"])),
                   pose_shift=float(np.mean(reg["shift_px"])), threshold=thr, n_points=n_points)
     return scores, reg
+
+
+def branch_scores(counts, cover, n_branches, lengths, site_label, d2_offset, d2_true, d2_pred, found_at=0.5):
+    """The table and the scores of `reconstruction_branch_metrics` from what the device counted, fp64 NumPy on the host -> (scores,
+    table).  counts, cover: integer [B + K + 1, 4] rows of afx_label_overlap_3d (cover: the call without an index, so its column 0 is
+    the label's own centreline voxels and column 1 those of them in A); lengths [B]; site_label, d2_offset, d2_true, d2_pred: one entry
+    per voxel of the true centreline in raster order - its label, the squared distance to the predicted centreline, the true mask's
+    squared EDT there, and the predicted mask's squared EDT at the nearest predicted centreline voxel (d2_offset 0xffffffff: there is
+    no predicted centreline, the three means are NaN).  A ratio whose divisor is 0 is NaN."""
+    nan = float("nan")
+    counts, cover = np.asarray(counts, np.int64), np.asarray(cover, np.int64)
+    rows, nb = counts.shape[0] - 1, int(n_branches)
+    n_pred, n_gt, n_both = (counts[1:, c].astype(np.float64) for c in (1, 2, 3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        table = {"label": np.arange(1, rows + 1), "kind": np.array(["branch"] * nb + ["junction"] * (rows - nb), dtype=object),
+                 "n_pred": counts[1:, 1].copy(), "n_gt": counts[1:, 2].copy(), "n_both": counts[1:, 3].copy(),
+                 "dice": np.where(n_pred + n_gt > 0, 2.0 * n_both / (n_pred + n_gt), nan),
+                 "sensitivity": np.where(n_gt > 0, n_both / n_gt, nan), "precision": np.where(n_pred > 0, n_both / n_pred, nan),
+                 "coverage": np.where(cover[1:, 0] > 0, cover[1:, 1].astype(np.float64) / cover[1:, 0].astype(np.float64), nan),
+                 "length": np.concatenate([np.asarray(lengths, np.float64).reshape(-1)[:nb], np.zeros(rows - nb)])}
+    site_label = np.asarray(site_label, np.int64)
+    have_pred = site_label.size > 0 and not (np.asarray(d2_offset, np.int64) == 0xffffffff).any()
+    means = {"offset": d2_offset, "radius_true": d2_true, "radius_pred": d2_pred}
+    for key, d2 in means.items():
+        col = np.full(rows, nan)
+        if have_pred or key == "radius_true":
+            root = np.sqrt(np.asarray(d2, np.int64).astype(np.float64))
+            for l in range(1, rows + 1):
+                sel = site_label == l
+                if sel.any():
+                    col[l - 1] = float(np.mean(root[sel]))
+        table[key] = col
+    found = np.zeros(rows, bool)
+    found[:nb] = table["coverage"][:nb] >= float(found_at)
+    table["found"] = found
+    union = counts[:, 1] + counts[:, 2] - counts[:, 3]
+    length, f = table["length"][:nb], found[:nb]
+    rt, rp = table["radius_true"][:nb][f], table["radius_pred"][:nb][f]
+    ok = rt > 0
+    total = found_length = 0.0                                # added up branch after branch
+    for x, hit in zip(length.tolist(), f.tolist()):
+        total, found_length = total + x, found_length + (x if hit else 0.0)
+    scores = dict(branch_recall=float(f.sum()) / nb if nb else nan,
+                  branch_recall_length=found_length / total if nb and total > 0 else nan,
+                  worst_branch_dice=float(np.min(table["dice"][:nb])) if nb else nan,
+                  branch_radius_err=float(np.mean(np.abs(rp[ok] - rt[ok]) / rt[ok])) if ok.any() else nan,
+                  unassigned=float(union[0]) / float(union.sum()) if union.sum() > 0 else nan,
+                  n_branches=nb, n_junctions=rows - nb, n_found=int(f.sum()))
+    return scores, table
+
+
+@torch.no_grad()
+def reconstruction_branch_metrics(model, volume, outside, n, threshold=None, largest_component=False, prune_factor=1.0, max_distance=None,
+                                  found_at=0.5, grids=None):
+    """Which branch was lost, which is too thin -> (scores, table, territories).
+
+    The masks and both pruned centrelines are those of `reconstruction_graph_metrics` (same threshold, largest_component, prune_factor:
+    with `grids=` a GridAnalysis nothing is computed twice).  The voxels of the TRUE pruned centreline are the sites of a feature
+    transform (`engine.branch_territories`: branch b carries label b, junction node k label B + k); every voxel of A (the prediction's
+    mask) or B (the truth's) belongs to the territory of the site nearest to it (ties to the lowest index), a voxel farther than
+    `max_distance` voxels from the true centreline to row 0.  One counting call (afx_label_overlap_3d) gives n_pred, n_gt and n_both per
+    territory, from which the host takes dice, sensitivity and precision in fp64; a second one without an index gives coverage, the
+    share of a branch's own centreline voxels that lie in A; length is the graph's (world units; 0 for a junction row).  A second
+    feature transform, of the PREDICTED pruned centreline, read at the true centreline's voxels, gives per row offset (the mean
+    distance to the predicted centreline, voxels), radius_true (the mean sqrt(d2) of B along the row) and radius_pred (the mean sqrt(d2)
+    of A at the nearest predicted centreline voxel); NaN without a predicted centreline.  table: one entry per branch, then per junction
+    (`branch_scores`).  scores: branch_recall = the share of true branches with coverage >= found_at, branch_recall_length the same
+    weighted by length, worst_branch_dice = the minimum over the true branches, branch_radius_err = the mean over the found branches of
+    |radius_pred - radius_true| / radius_true (NaN when none is found), unassigned = row 0's share of A or B, n_branches, n_junctions,
+    n_found, threshold, voxel_size, found_at.  ValueError when the threshold leaves either mask empty."""
+    from ..engine import branch_territories, feature_transform_record, territory_overlap
+    an, thr = _analysis(model, volume, outside, n, grids, threshold)
+    a_all, b, n_pred, n_gt = an.masks(thr)
+    _refuse_empty("reconstruction_branch_metrics", n_pred, n_gt, "volume has no centreline")
+    a = an.body(thr, largest_component)
+    tree_p, tree_l = an.tree("pred", thr, largest_component, prune_factor), an.tree("gt", thr, prune_factor=prune_factor)
+    graph = tree_l["graph"]
+    terr = branch_territories(graph, max_distance)
+    counts = territory_overlap(terr, a, b)
+    cover = territory_overlap(terr, a, sites_only=True)
+    d2_off, nearest_p = feature_transform_record((tree_p["pruned"] != 0).to(torch.uint8).contiguous())
+    labels = terr["labels"].reshape(-1)
+    vox = torch.nonzero(labels, as_tuple=False).reshape(-1)                         # the true centreline's voxels in raster order
+    near = nearest_p.reshape(-1)[vox].to(torch.int64)
+    u32 = lambda t: (t.to(torch.int64) & 0xffffffff).cpu().numpy()
+    d2_pred_at = tree_p["d2"].reshape(-1)[near.clamp(min=0)]
+    scores, table = branch_scores(counts.cpu().numpy(), cover.cpu().numpy(), terr["n_branches"], graph["length"].cpu().numpy(),
+                                  labels[vox].cpu().numpy(), u32(d2_off.reshape(-1)[vox]), u32(tree_l["d2"].reshape(-1)[vox]), u32(d2_pred_at),
+                                  found_at)
+    scores.update(threshold=thr, voxel_size=an.voxel, found_at=float(found_at))
+    return scores, table, terr
 
 
 def cpr_scores(images_p, images_g):
