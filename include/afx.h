@@ -72,7 +72,11 @@ enum { AFX_ENC_NONE = 0, AFX_ENC_BARF = 1, AFX_ENC_FOURIER = 2 };
  *            stochastically: its errors are systematic otherwise), averaged over
  *            the samples: 2e-3 relative L2 of the whole gradient (F16: 5e-4).  Rays mode (with an input encoding
  *            the encoded inputs are stashed as bf8 as well); points mode
- *            (afx_mlp_backward) runs exactly as F16.                           */
+ *            (afx_mlp_backward) runs exactly as F16.
+ *            RANGE: the stashed chain is J_l = d raw / d z_l (a product of the weights alone; 1e-4 ... 1 for nn.Linear-initialised
+ *            models) times 2^10 and the sample's normalised dL/draw (<= 1), converted through f16: a |J_l| of 64 or more - an
+ *            output layer with such a weight, say - can become inf, and that neuron's row of the weight gradient NaN.  Such
+ *            a model belongs on F16 or BF16.                                                                                */
 enum { AFX_PREC_F32 = 0, AFX_PREC_BF16X3 = 1, AFX_PREC_BF16 = 2, AFX_PREC_F16 = 3, AFX_PREC_F16S8 = 4 };
 
 /* CPPN(model_definition) — model/CPPN.py:10-139.  The configuration
@@ -89,7 +93,11 @@ enum { AFX_ACT_RELU = 0, AFX_ACT_TANH = 1, AFX_ACT_SINE = 2 };
 typedef struct afx_model_desc {
   int32_t n_in;        /* num_input_channels (3)                              */
   int32_t enc;         /* AFX_ENC_*                                           */
-  int32_t n_freq;      /* pos_enc_basis L (ignored for AFX_ENC_NONE)          */
+  int32_t n_freq;      /* pos_enc_basis L (ignored for AFX_ENC_NONE).  With an encoding afx_create admits 1 <= L <= 10, i.e. K0 = 3 + 6 L =
+                        * 9 ... 63 first-layer columns, and asks that K0 rounded up to an even count (K0 + 1) fits the layer: 4 + 6 L <= width
+                        * (width 64 takes every admitted L; L = 10 fills it exactly).  At AFX_PREC_F32 the LDS a launch needs grows with L:
+                        * the backward entry points refuse an 8-hidden-layer width-256 model at L = 9 and L = 10 with AFX_E_INVALID
+                        * ("needs ... B of LDS"; its forward runs, L <= 8 trains); the 16-bit precisions' LDS does not depend on L. */
   int32_t width;       /* num_filters: 64, 128 or 256                         */
   int32_t n_hidden;    /* num_early_layers N  (Linear count = N + 2)          */
   int32_t act;         /* AFX_ACT_*                                           */

@@ -193,13 +193,15 @@ class CPPN(nn.Module):
         directions, one output channel) with any of its three activations.  tanh / sine models are evaluated by the kernels
         wherever no gradient is wanted (inference, evaluation renders, density grids: the activation is an epilogue of the same
         chain kernel); with gradients they train in the exact-fp32 kernels (precision "f32", see `fused`) and otherwise keep the
-        module's PyTorch-ROCm operators."""
+        module's PyTorch-ROCm operators.  An encoded model is taken with the band counts afx_create admits (pos_enc_basis 1 ... 10,
+        4 + 6 * pos_enc_basis <= num_filters); any other keeps the module's operators like every unsupported geometry."""
         return ((self._act_name == "relu" or (self._act_name in ("tanh", "sine") and self.use_pos_enc == "none"))
                 and self.num_late_layers == 0 and not self.use_viewdirs
                 and self.num_output_channels == 1 and self.num_input_channels == 3 and self.use_bias
                 and self.num_filters in (64, 128, 256) and 1 <= self.num_early_layers <= 16
                 and self.use_pos_enc in ("none", "barf", "fourier")
-                and (self.use_pos_enc == "none" or 2 * ((4 + 6 * self.pos_enc_basis) // 2) <= self.num_filters))
+                # afx_create's own conditions on an encoded model: 1 ... 10 bands, and the K0 + 1 = 4 + 6 L first-layer columns fit the layer
+                and (self.use_pos_enc == "none" or (1 <= self.pos_enc_basis <= 10 and 4 + 6 * self.pos_enc_basis <= self.num_filters)))
 
     def _linears(self):
         lins = [m for m in self.early_pts_layers if isinstance(m, nn.Linear)]
