@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_frangi3d.hip", "afx_kernels_lumen.hip", "afx_kernels_hull.hip", "afx_kernels_sirt.hip", "afx_kernels_tv.hip", "afx_kernels_viewmap.hip", "afx_kernels_reformat.hip", "afx_kernels_pose.hip", "afx_kernels_territory.hip", "afx_image_common.h", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
+DEPS = ["afx_api.hip", "afx_kernels_f32.hip", "afx_kernels_bf16.hip", "afx_kernels_grid.hip", "afx_kernels_image.hip", "afx_kernels_metrics.hip", "afx_kernels_mesh.hip", "afx_kernels_sdf.hip", "afx_kernels_graph.hip", "afx_kernels_frangi3d.hip", "afx_kernels_lumen.hip", "afx_kernels_hull.hip", "afx_kernels_sirt.hip", "afx_kernels_tv.hip", "afx_kernels_viewmap.hip", "afx_kernels_reformat.hip", "afx_kernels_pose.hip", "afx_kernels_territory.hip", "afx_image_common.h", "afx_geom.h", "afx_kernels_ingrad.hip", "afx_inst.h", "afx_inst_chain16.hip",
         "afx_internal.h", "afx_scan.h", os.path.join("..", "..", "include", "afx.h")]
 VARIANTS = {"": [], "safe": ["-DAFX_SAFE_WAITS"],
             "h6": ["-DAFX_H6=1"],      # the 6-bit (bf6 + block scales) H stash: 12.5 % fewer stash bytes, no faster; tests/ compare it with the default

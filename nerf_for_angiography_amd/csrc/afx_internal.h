@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <cmath>
 #include "../../include/afx.h"
 
 namespace afx {
@@ -292,6 +293,20 @@ inline int check_device_memory(const void* p, const char* what, const char* who)
   }
   (void)hipGetLastError();                            // (a failed query is check_device's to report)
   return check_device(p, what, who);
+}
+
+// Host-side checks of the lattice entry points: the n doubles at p are all finite; and a flat index of an (n0, n1, n2) lattice fits an int32
+// (the one message every such entry point gives).
+inline bool all_finite(const double* p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+inline int check_lattice_size(int32_t n0, int32_t n1, int32_t n2, const char* who) {
+  if ((int64_t)n0 * n1 >= (int64_t)1 << 31 || (int64_t)n0 * n1 * n2 >= (int64_t)1 << 31)
+    return set_error(AFX_E_INVALID, who, "n0 n1 n2 must stay below 2^31");
+  return AFX_OK;
 }
 
 inline int launched(const char* who) {

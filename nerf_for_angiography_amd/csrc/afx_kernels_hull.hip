@@ -7,6 +7,7 @@
 // back.  NOTHING CAN HANG: no lane waits for another, and the loop runs V times, a kernel argument.  The only indexed load, D[v][iw][iu],
 // is made with iu, iw clamped into the image in fp64 before they become integers.
 #include "afx_internal.h"
+#include "afx_geom.h"
 #include <cmath>
 
 // every fp64 product, quotient and sum below is rounded on its own (the definition is stated operation by operation)
@@ -17,43 +18,29 @@ namespace {
 constexpr int VH_BLOCK = 256;
 constexpr double VH_SQRT_HALF = 0x1.6a09e667f3bcdp-1;      // sqrt(0.5) rounded to fp64: how far rounding to a pixel centre moves a point
 
-struct HullView {                                     // AFX_HULL_VIEW_DOUBLES = 16
-  double R[9];                                        // cam2world's rotation, row-major: R[3 r + n] = R[r][n]
-  double c[3];                                        // the source position
-  double f;
-  double pad[3];
-};
-static_assert(sizeof(HullView) == 8 * AFX_HULL_VIEW_DOUBLES, "the view record is AFX_HULL_VIEW_DOUBLES doubles");
-
 struct HullArgs {
   double A[12];
   double rho, m, half_w, half_h, w_last, h_last;      // W / 2, H / 2, W - 1, H - 1
   int32_t P, n1, n2, V, W, H;
 };
 
-__global__ void __launch_bounds__(VH_BLOCK) k_visual_hull(const HullArgs a, const HullView* __restrict__ views, const double* __restrict__ D,
+__global__ void __launch_bounds__(VH_BLOCK) k_visual_hull(const HullArgs a, const afx::ViewRecord* __restrict__ views, const double* __restrict__ D,
                                                           uint16_t* __restrict__ seen, uint16_t* __restrict__ rejects) {
   const int64_t p64 = (int64_t)blockIdx.x * VH_BLOCK + threadIdx.x;
   if (p64 >= a.P) return;
   const int32_t p = (int32_t)p64;
-  const int32_t k = p % a.n2, ij = p / a.n2, j = ij % a.n1, i = ij / a.n1;
-  const double di = (double)i, dj = (double)j, dk = (double)k;
-  const double x0 = ((a.A[0] * di + a.A[1] * dj) + a.A[2] * dk) + a.A[3];
-  const double x1 = ((a.A[4] * di + a.A[5] * dj) + a.A[6] * dk) + a.A[7];
-  const double x2 = ((a.A[8] * di + a.A[9] * dj) + a.A[10] * dk) + a.A[11];
+  double x0, x1, x2;
+  afx::affine_apply_index(a.A, p, a.n1, a.n2, x0, x1, x2);
   const size_t image = (size_t)a.W * (size_t)a.H;
   uint32_t n_seen = 0, n_rej = 0;
   for (int32_t v = 0; v < a.V; ++v) {
-    const HullView& vw = views[v];                    // the same address in every lane
-    const double e0 = x0 - vw.c[0], e1 = x1 - vw.c[1], e2 = x2 - vw.c[2];
-    const double q0 = (vw.R[0] * e0 + vw.R[3] * e1) + vw.R[6] * e2;
-    const double q1 = (vw.R[1] * e0 + vw.R[4] * e1) + vw.R[7] * e2;
-    const double q2 = (vw.R[2] * e0 + vw.R[5] * e1) + vw.R[8] * e2;
+    const afx::ViewRecord& vw = views[v];             // the same address in every lane
+    double q0, q1, q2, u, w;
+    afx::view_camera(vw, x0, x1, x2, q0, q1, q2);
     const double d = -q2;
     const double near = d - a.rho;
     if (!(near > 0.0)) continue;                      // behind the source, or too close to it to bound the projection (a NaN ends here too)
-    const double u = a.half_w + (vw.f * q0) / d;
-    const double w = a.half_h - (vw.f * q1) / d;
+    afx::view_pixel(vw, a.half_w, a.half_h, q0, q1, d, u, w);
     const double l = sqrt(q0 * q0 + q1 * q1);
     const double r = ((vw.f * a.rho) * (d + l)) / (d * near) + a.m;
     double dx = 0.0 > -u ? 0.0 : -u, dy = 0.0 > -w ? 0.0 : -w;
@@ -93,12 +80,6 @@ __global__ void __launch_bounds__(VH_BLOCK) k_grid_apply_mask(const uint8_t* __r
   if (lane < 2 && word * 32 < n) bits[word] = (uint32_t)(vote >> (32 * lane));
 }
 
-bool vh_finite(const double* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int afx_visual_hull(int32_t n0, int32_t n1, int32_t n2, const double* index_to_world, double radius, const double* views,
@@ -112,9 +93,8 @@ extern "C" int afx_visual_hull(int32_t n0, int32_t n1, int32_t n2, const double*
   if (n_views < 1 || n_views > 65535) return afx::set_error(AFX_E_INVALID, who, "n_views must lie in 1..65535");
   if (n0 < 1 || n1 < 1 || n2 < 1) return afx::set_error(AFX_E_INVALID, who, "n0, n1, n2 must be positive");
   if (width < 1 || height < 1) return afx::set_error(AFX_E_INVALID, who, "width and height must be positive");
-  if ((int64_t)n0 * n1 >= (int64_t)1 << 31 || (int64_t)n0 * n1 * n2 >= (int64_t)1 << 31)
-    return afx::set_error(AFX_E_INVALID, who, "n0 n1 n2 must stay below 2^31");
-  if (!vh_finite(index_to_world, 12)) return afx::set_error(AFX_E_INVALID, who, "index_to_world must be finite");
+  if (int rc = afx::check_lattice_size(n0, n1, n2, who)) return rc;
+  if (!afx::all_finite(index_to_world, 12)) return afx::set_error(AFX_E_INVALID, who, "index_to_world must be finite");
   if (!(radius >= 0.0) || !std::isfinite(radius)) return afx::set_error(AFX_E_INVALID, who, "radius must be finite and >= 0");
   if (!(margin_px >= 0.0) || !std::isfinite(margin_px)) return afx::set_error(AFX_E_INVALID, who, "margin_px must be finite and >= 0");
   if (int rc = afx::check_device(views, "views", who)) return rc;
@@ -127,7 +107,7 @@ extern "C" int afx_visual_hull(int32_t n0, int32_t n1, int32_t n2, const double*
   a.half_w = (double)width / 2.0, a.half_h = (double)height / 2.0, a.w_last = (double)(width - 1), a.h_last = (double)(height - 1);
   a.P = (int32_t)((int64_t)n0 * n1 * n2), a.n1 = n1, a.n2 = n2, a.V = n_views, a.W = width, a.H = height;
   const unsigned blocks = (unsigned)(((int64_t)a.P + VH_BLOCK - 1) / VH_BLOCK);
-  hipLaunchKernelGGL(k_visual_hull, dim3(blocks), dim3(VH_BLOCK), 0, (hipStream_t)stream, a, (const HullView*)views, dist, seen, rejects);
+  hipLaunchKernelGGL(k_visual_hull, dim3(blocks), dim3(VH_BLOCK), 0, (hipStream_t)stream, a, (const afx::ViewRecord*)views, dist, seen, rejects);
   return afx::launched(who);
 }
 

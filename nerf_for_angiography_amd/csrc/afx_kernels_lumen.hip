@@ -6,6 +6,7 @@
 // lane holds before it enters the loop.  Every load is made after the index test of the definition passed; the window ends are clamped
 // into [0, P - 1] before a point is read.
 #include "afx_internal.h"
+#include "afx_geom.h"
 #include <cmath>
 
 // every fp64 product and sum below is rounded on its own (the definition is stated operation by operation); plain operators under this
@@ -30,28 +31,10 @@ struct LumenArgs {
   int32_t ppw;                                        // points per wave: 64 / R, or 1 (lanes >= R idle)
 };
 
-// step 4 of the definition: 0.0 outside, else the trilinear blend along axis 2, 1, 0
+// step 4 of the definition: afx::lattice_lookup, 0.0 outside
 template <typename T>
 __device__ __forceinline__ double lm_lookup(const LumenArgs& a, const T* __restrict__ vol, double x0, double x1, double x2) {
-  const double q0 = ((a.W[0] * x0 + a.W[1] * x1) + a.W[2] * x2) + a.W[3];
-  const double q1 = ((a.W[4] * x0 + a.W[5] * x1) + a.W[6] * x2) + a.W[7];
-  const double q2 = ((a.W[8] * x0 + a.W[9] * x1) + a.W[10] * x2) + a.W[11];
-  const bool inside = q0 >= 0.0 && q0 <= (double)(a.n0 - 1) && q1 >= 0.0 && q1 <= (double)(a.n1 - 1) && q2 >= 0.0 && q2 <= (double)(a.n2 - 1);
-  if (!inside) return 0.0;                            // NaN and huge q end here: no conversion, no load
-  const double l0 = (double)(a.n0 - 2), l1 = (double)(a.n1 - 2), l2 = (double)(a.n2 - 2);
-  double f0 = floor(q0), f1 = floor(q1), f2 = floor(q2);
-  f0 = f0 < l0 ? f0 : l0;
-  f1 = f1 < l1 ? f1 : l1;
-  f2 = f2 < l2 ? f2 : l2;
-  const double t0 = q0 - f0, t1 = q1 - f1, t2 = q2 - f2;
-  const size_t s1 = (size_t)a.n2, s0 = (size_t)a.n1 * (size_t)a.n2;
-  const T* b = vol + ((size_t)(int)f0 * s0 + (size_t)(int)f1 * s1 + (size_t)(int)f2);      // i_a <= n_a - 2: i_a + 1 is a voxel
-  const double p000 = (double)b[0], p001 = (double)b[1], p010 = (double)b[s1], p011 = (double)b[s1 + 1];
-  const double p100 = (double)b[s0], p101 = (double)b[s0 + 1], p110 = (double)b[s0 + s1], p111 = (double)b[s0 + s1 + 1];
-  const double c00 = p000 + (p001 - p000) * t2, c01 = p010 + (p011 - p010) * t2;
-  const double c10 = p100 + (p101 - p100) * t2, c11 = p110 + (p111 - p110) * t2;
-  const double c0 = c00 + (c01 - c00) * t1, c1 = c10 + (c11 - c10) * t1;
-  return c0 + (c1 - c0) * t0;
+  return afx::lattice_lookup(a, vol, x0, x1, x2, 0.0);
 }
 
 template <typename T>
@@ -150,12 +133,6 @@ __global__ void __launch_bounds__(LM_BLOCK) k_lumen_profile(const LumenArgs a, c
   }
 }
 
-bool lm_finite(const double* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int afx_lumen_profile(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t n1, int32_t n2, const double* world_to_index,
@@ -167,14 +144,13 @@ extern "C" int afx_lumen_profile(const void* vol, int32_t vol_is_f64, int32_t n0
   if (!world_to_index) return afx::set_error(AFX_E_INVALID, who, "null world_to_index");
   if (!ray_cs) return afx::set_error(AFX_E_INVALID, who, "null ray_cs");
   if (n0 < 2 || n1 < 2 || n2 < 2) return afx::set_error(AFX_E_INVALID, who, "n0, n1, n2: need at least 2 voxels along each axis");
-  if ((int64_t)n0 * n1 >= (int64_t)1 << 31 || (int64_t)n0 * n1 * n2 >= (int64_t)1 << 31)
-    return afx::set_error(AFX_E_INVALID, who, "n0 n1 n2 must stay below 2^31");
+  if (int rc = afx::check_lattice_size(n0, n1, n2, who)) return rc;
   if (n_points < 0 || n_points > 0x7fffffff) return afx::set_error(AFX_E_INVALID, who, "n_points must lie in 0..2^31 - 1");
   if (n_rays != 8 && n_rays != 16 && n_rays != 32 && n_rays != 64) return afx::set_error(AFX_E_INVALID, who, "n_rays must be 8, 16, 32 or 64");
   if (half_window < 1) return afx::set_error(AFX_E_INVALID, who, "half_window must be at least 1");
   if (!std::isfinite(iso)) return afx::set_error(AFX_E_INVALID, who, "iso must be finite");
-  if (!lm_finite(world_to_index, 12)) return afx::set_error(AFX_E_INVALID, who, "world_to_index must be finite");
-  if (!lm_finite(ray_cs, 2 * n_rays)) return afx::set_error(AFX_E_INVALID, who, "ray_cs must be finite");
+  if (!afx::all_finite(world_to_index, 12)) return afx::set_error(AFX_E_INVALID, who, "world_to_index must be finite");
+  if (!afx::all_finite(ray_cs, 2 * n_rays)) return afx::set_error(AFX_E_INVALID, who, "ray_cs must be finite");
   if (!std::isfinite(area_coef)) return afx::set_error(AFX_E_INVALID, who, "area_coef must be finite");
   if (!(step > 0.0) || !std::isfinite(step)) return afx::set_error(AFX_E_INVALID, who, "step must be finite and > 0");
   if (max_steps < 1 || max_steps > LM_MAX_STEPS) return afx::set_error(AFX_E_INVALID, who, "max_steps must lie in 1..4096");

@@ -15,6 +15,7 @@
 // BY DATA except the field, by indices that are clamped to the detector as doubles before they become integers, and the view, which is
 // range-checked first.  No atomics, no allocation, no synchronisation.
 #include "afx_internal.h"
+#include "afx_geom.h"
 #include <cmath>
 
 // every fp64 product, quotient and sum below is rounded on its own (the definition is stated operation by operation)
@@ -26,13 +27,7 @@ constexpr int POSE_BLOCK = 256;
 constexpr int POSE_WAVES = POSE_BLOCK / 64;
 constexpr int POSE_ACC = 30;                          // cost, sum r, sum w, g[6], H[21]
 
-struct PoseRecord {                                   // AFX_HULL_VIEW_DOUBLES = 16
-  double R[9];                                        // cam2world's rotation, row-major: R[3 r + n] = R[r][n]
-  double c[3];                                        // the source position
-  double f;
-  double pad[3];
-};
-static_assert(sizeof(PoseRecord) == 8 * AFX_HULL_VIEW_DOUBLES, "the view record is AFX_HULL_VIEW_DOUBLES doubles");
+using PoseRecord = afx::ViewRecord;
 
 struct PoseArgs {
   const double* field;
@@ -87,10 +82,8 @@ __global__ void __launch_bounds__(POSE_BLOCK) k_pose_chamfer(const PoseArgs a) {
     const int64_t lo = (int64_t)s * a.slice_len;
     const int64_t hi = lo + a.slice_len < (int64_t)a.N ? lo + a.slice_len : (int64_t)a.N;
     for (int64_t i = lo + tid; i < hi; i += POSE_BLOCK) {
-      const double e0 = a.points[3 * i] - rc.c[0], e1 = a.points[3 * i + 1] - rc.c[1], e2 = a.points[3 * i + 2] - rc.c[2];
-      const double q0 = (rc.R[0] * e0 + rc.R[3] * e1) + rc.R[6] * e2;
-      const double q1 = (rc.R[1] * e0 + rc.R[4] * e1) + rc.R[7] * e2;
-      const double q2 = (rc.R[2] * e0 + rc.R[5] * e1) + rc.R[8] * e2;
+      double q0, q1, q2;                              // q, su and sw enter the Jacobian below: the pixel is formed here, not by afx::view_pixel
+      afx::view_camera(rc, a.points[3 * i], a.points[3 * i + 1], a.points[3 * i + 2], q0, q1, q2);
       const double d = -q2;
       const double su = (rc.f * q0) / d, sw = (rc.f * q1) / d;
       const double u = a.half_w + su, w = a.half_h - sw;

@@ -5,6 +5,7 @@
 // NOTHING CAN HANG: no lane waits for a value that another lane or wave writes, and the slab loop runs 2 H + 1 times, a count that is a
 // kernel argument.  Every load of the volume is made after the index test of the definition passed; p < P and q < Q before a row is read.
 #include "afx_internal.h"
+#include "afx_geom.h"
 #include <cmath>
 
 // every fp64 product and sum below is rounded on its own (the definition is stated operation by operation); plain operators under this
@@ -26,28 +27,10 @@ struct ReformatArgs {
   int32_t n0, n1, n2, H, mode;
 };
 
-// step 4 of afx_lumen_profile with `fill` outside: the trilinear blend along axis 2, 1, 0
+// the lookup of afx_lumen_profile's step 4 with `fill` outside: afx::lattice_lookup
 template <typename T>
 __device__ __forceinline__ double rf_lookup(const ReformatArgs& a, const T* __restrict__ vol, double x0, double x1, double x2) {
-  const double q0 = ((a.W[0] * x0 + a.W[1] * x1) + a.W[2] * x2) + a.W[3];
-  const double q1 = ((a.W[4] * x0 + a.W[5] * x1) + a.W[6] * x2) + a.W[7];
-  const double q2 = ((a.W[8] * x0 + a.W[9] * x1) + a.W[10] * x2) + a.W[11];
-  const bool inside = q0 >= 0.0 && q0 <= (double)(a.n0 - 1) && q1 >= 0.0 && q1 <= (double)(a.n1 - 1) && q2 >= 0.0 && q2 <= (double)(a.n2 - 1);
-  if (!inside) return a.fill;                         // NaN and huge q end here: no conversion, no load
-  const double l0 = (double)(a.n0 - 2), l1 = (double)(a.n1 - 2), l2 = (double)(a.n2 - 2);
-  double f0 = floor(q0), f1 = floor(q1), f2 = floor(q2);
-  f0 = f0 < l0 ? f0 : l0;
-  f1 = f1 < l1 ? f1 : l1;
-  f2 = f2 < l2 ? f2 : l2;
-  const double t0 = q0 - f0, t1 = q1 - f1, t2 = q2 - f2;
-  const size_t s1 = (size_t)a.n2, s0 = (size_t)a.n1 * (size_t)a.n2;
-  const T* b = vol + ((size_t)(int)f0 * s0 + (size_t)(int)f1 * s1 + (size_t)(int)f2);      // i_a <= n_a - 2: i_a + 1 is a voxel
-  const double p000 = (double)b[0], p001 = (double)b[1], p010 = (double)b[s1], p011 = (double)b[s1 + 1];
-  const double p100 = (double)b[s0], p101 = (double)b[s0 + 1], p110 = (double)b[s0 + s1], p111 = (double)b[s0 + s1 + 1];
-  const double c00 = p000 + (p001 - p000) * t2, c01 = p010 + (p011 - p010) * t2;
-  const double c10 = p100 + (p101 - p100) * t2, c11 = p110 + (p111 - p110) * t2;
-  const double c0 = c00 + (c01 - c00) * t1, c1 = c10 + (c11 - c10) * t1;
-  return c0 + (c1 - c0) * t0;
+  return afx::lattice_lookup(a, vol, x0, x1, x2, a.fill);
 }
 
 template <typename T>
@@ -75,12 +58,6 @@ __global__ void __launch_bounds__(RF_BLOCK) k_reformat_planes(const ReformatArgs
   out[flat] = a.mode == 0 ? acc / a.count : acc;
 }
 
-bool rf_finite(const double* p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int afx_reformat_planes(const void* vol, int32_t vol_is_f64, int32_t n0, int32_t n1, int32_t n2, const double* world_to_index,
@@ -90,14 +67,13 @@ extern "C" int afx_reformat_planes(const void* vol, int32_t vol_is_f64, int32_t 
   if (!vol) return afx::set_error(AFX_E_INVALID, who, "null vol");
   if (!world_to_index) return afx::set_error(AFX_E_INVALID, who, "null world_to_index");
   if (n0 < 2 || n1 < 2 || n2 < 2) return afx::set_error(AFX_E_INVALID, who, "n0, n1, n2: need at least 2 voxels along each axis");
-  if ((int64_t)n0 * n1 >= (int64_t)1 << 31 || (int64_t)n0 * n1 * n2 >= (int64_t)1 << 31)
-    return afx::set_error(AFX_E_INVALID, who, "n0 n1 n2 must stay below 2^31");
+  if (int rc = afx::check_lattice_size(n0, n1, n2, who)) return rc;
   if (n_planes < 0 || n_planes > 0x7fffffff) return afx::set_error(AFX_E_INVALID, who, "n_planes must lie in 0..2^31 - 1");
   if (n_table < 0 || n_table > RF_MAX_TABLE) return afx::set_error(AFX_E_INVALID, who, "n_table must lie in 0..2^20");
   if (half_slab < 0 || half_slab > RF_MAX_HALF_SLAB) return afx::set_error(AFX_E_INVALID, who, "half_slab must lie in 0..127");
   if (mode != AFX_REFORMAT_MEAN && mode != AFX_REFORMAT_MAX) return afx::set_error(AFX_E_INVALID, who, "mode must be 0 (mean) or 1 (max)");
   if (!std::isfinite(fill)) return afx::set_error(AFX_E_INVALID, who, "fill must be finite");
-  if (!rf_finite(world_to_index, 12)) return afx::set_error(AFX_E_INVALID, who, "world_to_index must be finite");
+  if (!afx::all_finite(world_to_index, 12)) return afx::set_error(AFX_E_INVALID, who, "world_to_index must be finite");
   const int64_t blocks = (n_planes * n_table + RF_BLOCK - 1) / RF_BLOCK;      // < 2^43
   const int64_t gx = blocks < RF_GRID_X ? blocks : RF_GRID_X, gy = gx ? (blocks + gx - 1) / gx : 0;
   if (gy > RF_GRID_Y) return afx::set_error(AFX_E_INVALID, who, "n_planes n_table: more samples than one launch holds (2^46)");

@@ -19,6 +19,7 @@
 // n_segments (the searches by 32 steps); no lane waits on another outside __syncthreads.  NOTHING IS INDEXED BY DATA except area and
 // shared by the branch id, and a segment whose id lies outside 1..B is dropped before it reaches the list.
 #include "afx_internal.h"
+#include "afx_geom.h"
 #include "afx_scan.h"
 #include <cmath>
 
@@ -31,13 +32,7 @@ constexpr int VM_BLOCK = 256;
 constexpr int VM_TILE = 16;
 constexpr double VM_CULL_LIMIT = 1073741824.0;        // 2^30: the box test is trusted for coordinates below it
 
-struct VmView {                                       // AFX_HULL_VIEW_DOUBLES = 16
-  double R[9];                                        // cam2world's rotation, row-major: R[3 r + n] = R[r][n]
-  double c[3];                                        // the source position
-  double f;
-  double pad[3];
-};
-static_assert(sizeof(VmView) == 8 * AFX_HULL_VIEW_DOUBLES, "the view record is AFX_HULL_VIEW_DOUBLES doubles");
+using VmView = afx::ViewRecord;
 
 struct VmSegment {                                    // AFX_VIEWMAP_SEGMENT_DOUBLES = 8
   double p0[3], p1[3], r, pad;
@@ -71,15 +66,12 @@ __global__ void __launch_bounds__(VM_BLOCK) k_vm_check(const int32_t* __restrict
   if (bad) tree[AFX_VIEWMAP_TREE_BAD] = 1;            // every lane that writes, writes 1
 }
 
-// u, w and d of a point: the hull's operations in the hull's order
+// u, w and d of a point: afx::view_camera and afx::view_pixel, as afx_visual_hull projects
 __device__ __forceinline__ void vm_project(const VmView& vw, const double* p, double half_w, double half_h, double& u, double& w, double& d) {
-  const double e0 = p[0] - vw.c[0], e1 = p[1] - vw.c[1], e2 = p[2] - vw.c[2];
-  const double q0 = (vw.R[0] * e0 + vw.R[3] * e1) + vw.R[6] * e2;
-  const double q1 = (vw.R[1] * e0 + vw.R[4] * e1) + vw.R[7] * e2;
-  const double q2 = (vw.R[2] * e0 + vw.R[5] * e1) + vw.R[8] * e2;
+  double q0, q1, q2;
+  afx::view_camera(vw, p[0], p[1], p[2], q0, q1, q2);
   d = -q2;
-  u = half_w + (vw.f * q0) / d;
-  w = half_h - (vw.f * q1) / d;
+  afx::view_pixel(vw, half_w, half_h, q0, q1, d, u, w);
 }
 
 __global__ void __launch_bounds__(VM_BLOCK) k_vm_raster(const VmArgs a) {
