@@ -296,7 +296,7 @@ inline int check_device_memory(const void* p, const char* what, const char* who)
 }
 
 // Host-side checks of the lattice entry points: the n doubles at p are all finite; and a flat index of an (n0, n1, n2) lattice fits an int32
-// (the one message every such entry point gives).
+// (the one message every such entry point gives); and every side of a volume lies in 1..AFX_EDT3D_MAX_SIDE (the callers word the refusal).
 inline bool all_finite(const double* p, int n) {
   for (int i = 0; i < n; ++i)
     if (!std::isfinite(p[i])) return false;
@@ -307,6 +307,10 @@ inline int check_lattice_size(int32_t n0, int32_t n1, int32_t n2, const char* wh
   if ((int64_t)n0 * n1 >= (int64_t)1 << 31 || (int64_t)n0 * n1 * n2 >= (int64_t)1 << 31)
     return set_error(AFX_E_INVALID, who, "n0 n1 n2 must stay below 2^31");
   return AFX_OK;
+}
+
+inline bool volume_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
+  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
 }
 
 inline int launched(const char* who) {

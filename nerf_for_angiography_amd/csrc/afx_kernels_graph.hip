@@ -399,10 +399,6 @@ __global__ void k_pr_advance(CgState* st, unsigned long long* record) {
   st->gone = 0;
 }
 
-bool cg_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
-  return n0 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 >= 1 && n1 <= AFX_EDT3D_MAX_SIDE && n2 >= 1 && n2 <= AFX_EDT3D_MAX_SIDE;
-}
-
 // The labelling's workspace is free once the second labelling has finished: start[] and offs[] lie in it.
 struct CgBufs { uint8_t* jmask; uint8_t* pmask; uint32_t* sizes; char* shared; size_t shared_bytes; uint32_t* start; uint32_t* offs; uint32_t* chunk;
                 unsigned long long* rec_j; unsigned long long* rec_p; CgState* st; };
@@ -477,7 +473,7 @@ int graph_launch(const uint8_t* skel, const uint32_t* d2, int32_t n0, int32_t n1
 }  // namespace
 
 extern "C" size_t afx_centreline_graph_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!cg_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_graph(c, n0, n1, n2);
   return c.end;
@@ -489,7 +485,7 @@ extern "C" int afx_centreline_graph(const uint8_t* skel, const uint32_t* d2, int
   const char* who = "afx_centreline_graph";
   if (!skel || !node_labels || !branch_labels || !path_voxels || !record)
     return afx::set_error(AFX_E_INVALID, who, "null mask, node labels, branch labels, path voxels or record");
-  if (!cg_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (max_branches < 0 || max_branches > 0x7fffffff || (max_branches > 0 && !branches))
     return afx::set_error(AFX_E_INVALID, who, "max_branches must lie in 0..2^31 - 1 and be 0 when there is no branch table");
   if (step_lengths)
@@ -508,7 +504,7 @@ extern "C" int afx_centreline_graph(const uint8_t* skel, const uint32_t* d2, int
 }
 
 extern "C" size_t afx_prune_spurs_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!cg_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_prune(c, n0, n1, n2);
   return c.end;
@@ -519,7 +515,7 @@ extern "C" int afx_prune_spurs(const uint8_t* skel, const uint32_t* d2, int32_t 
                                void* stream) {
   const char* who = "afx_prune_spurs";
   if (!skel || !d2 || !out || !record) return afx::set_error(AFX_E_INVALID, who, "null mask, squared distances, output or record");
-  if (!cg_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (!(factor >= 0.0) || std::isinf(factor)) return afx::set_error(AFX_E_INVALID, who, "factor must be finite and >= 0");
   if (max_rounds < 1) return afx::set_error(AFX_E_INVALID, who, "max_rounds must be at least 1");
   if (sync_every < 0) return afx::set_error(AFX_E_INVALID, who, "sync_every must be 0 (no read-back) or the rounds between two read-backs");

@@ -37,10 +37,6 @@ struct IsoBufs {
   unsigned long long *voff, *toff;        // [chunks] vertices / triangles before the chunk (written by the scan)
 };
 
-bool iso_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
-  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
-}
-
 IsoBufs carve_iso(afx::Carve& c, int32_t n0, int32_t n1, int32_t n2) {
   const size_t total = (size_t)n0 * n1 * n2, chunks = (total + ISO_CHUNK - 1) / ISO_CHUNK;
   IsoBufs b;
@@ -356,7 +352,7 @@ __global__ void __launch_bounds__(MM_BLOCK) k_mm_finish(const double* __restrict
 }  // namespace
 
 extern "C" size_t afx_isosurface_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!iso_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_iso(c, n0, n1, n2);
   return c.end;
@@ -367,7 +363,7 @@ extern "C" int afx_isosurface_3d(const float* f, int32_t n0, int32_t n1, int32_t
                                  size_t workspace_bytes, size_t* workspace_needed, void* stream) {
   const char* who = "afx_isosurface_3d";
   if (!f || !record || !index_to_world) return afx::set_error(AFX_E_INVALID, who, "null volume, record or index_to_world");
-  if (!iso_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (iso != iso) return afx::set_error(AFX_E_INVALID, who, "iso is NaN");
   if (max_vertices < 0 || max_vertices > INT32_MAX || max_triangles < 0 || max_triangles > INT32_MAX)
     return afx::set_error(AFX_E_INVALID, who, "capacities must lie in 0..2^31 - 1");

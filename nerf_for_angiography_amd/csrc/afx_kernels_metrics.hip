@@ -147,10 +147,6 @@ constexpr int EDT3_BLOCK = 256;
 constexpr int SM_BINS = 2048;                         // 11 bits per pass of the radix select: squared distances are below 2^22
 constexpr int SM_MAX_PART = 2048;                     // workgroups of the gather = per-direction partial sums
 
-bool edt3_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
-  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
-}
-
 // First pass: g[c] = the distance from voxel c to the nearest zero voxel of its own line along axis 2 (EDT3_NONE16: the line has none).
 // A wave per line, 64 voxels at a time: the zero voxels of a chunk are one ballot, the nearest one at or below a lane the highest set
 // bit below it (or the last zero of the chunks before); the sweep back does the same from above.  Loads and stores are contiguous.
@@ -911,7 +907,7 @@ SkBufs carve_skeleton(afx::Carve& c, int32_t n0, int32_t n1, int32_t n2) {
 extern "C" int afx_simple_point_26(uint32_t nbr) { return sk_simple(nbr) ? 1 : 0; }
 
 extern "C" size_t afx_skeletonize_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_skeleton(c, n0, n1, n2);
   return c.end;
@@ -921,7 +917,7 @@ extern "C" int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int
                                   void* record, void* workspace, size_t workspace_bytes, void* stream) {
   const char* who = "afx_skeletonize_3d";
   if (!fg || !skel || !record) return afx::set_error(AFX_E_INVALID, who, "null volume, skeleton or record");
-  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (max_passes < 1) return afx::set_error(AFX_E_INVALID, who, "max_passes must be at least 1");
   if (sync_every < 0) return afx::set_error(AFX_E_INVALID, who, "sync_every must be 0 (no read-back) or the passes between two read-backs");
   const size_t need = afx_skeletonize_3d_workspace_bytes(n0, n1, n2);
@@ -959,7 +955,7 @@ extern "C" int afx_skeletonize_3d(const uint8_t* fg, int32_t n0, int32_t n1, int
 }
 
 extern "C" size_t afx_label_components_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_components(c, n0, n1, n2);
   return c.end;
@@ -970,7 +966,7 @@ extern "C" int afx_label_components_3d(const uint8_t* fg, int32_t n0, int32_t n1
                                        void* stream) {
   const char* who = "afx_label_components_3d";
   if (!fg || !labels || !record) return afx::set_error(AFX_E_INVALID, who, "null volume, labels or record");
-  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (connectivity < 1 || connectivity > 3) return afx::set_error(AFX_E_INVALID, who, "connectivity must be 1, 2 or 3 (6, 18 or 26 neighbours)");
   const size_t need = afx_label_components_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
@@ -1001,7 +997,7 @@ extern "C" int afx_filter_components_3d(const int32_t* labels, const uint32_t* s
                                         int32_t largest_only, uint32_t min_size, uint8_t* out, void* stream) {
   const char* who = "afx_filter_components_3d";
   if (!labels || !sizes || !record || !out) return afx::set_error(AFX_E_INVALID, who, "null labels, sizes, record or output");
-  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (min_size == 0) return afx::set_error(AFX_E_INVALID, who, "min_size must be at least 1");
   if (int rc = afx::check_device(labels, "labels", who)) return rc;
   if (int rc = afx::check_device(out, "the output mask", who)) return rc;
@@ -1012,7 +1008,7 @@ extern "C" int afx_filter_components_3d(const int32_t* labels, const uint32_t* s
 }
 
 extern "C" size_t afx_distance_transform_edt_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   c.take<uint16_t>((size_t)n0 * n1 * n2 * sizeof(uint16_t));
   return c.end;
@@ -1022,7 +1018,7 @@ extern "C" int afx_distance_transform_edt_3d(const uint8_t* fg, int32_t n0, int3
                                              size_t workspace_bytes, size_t* workspace_needed, void* stream) {
   const char* who = "afx_distance_transform_edt_3d";
   if (!fg || !d2) return afx::set_error(AFX_E_INVALID, who, "null volume or squared-distance output");
-  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   const size_t need = afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2);
   if (workspace_needed) *workspace_needed = need;
   if (int rc = afx::check_workspace(workspace, workspace_bytes, need, who)) return rc;
@@ -1032,7 +1028,7 @@ extern "C" int afx_distance_transform_edt_3d(const uint8_t* fg, int32_t n0, int3
 }
 
 extern "C" size_t afx_surface_metrics_3d_workspace_bytes(int32_t n0, int32_t n1, int32_t n2) {
-  if (!edt3_shape_ok(n0, n1, n2)) return 0;
+  if (!afx::volume_shape_ok(n0, n1, n2)) return 0;
   afx::Carve c;
   carve_surface(c, n0, n1, n2);
   return c.end;
@@ -1043,7 +1039,7 @@ extern "C" int afx_surface_metrics_3d(const float* pred, const float* gt, int32_
                                       void* stream) {
   const char* who = "afx_surface_metrics_3d";
   if (!pred || !gt || !record) return afx::set_error(AFX_E_INVALID, who, "null volume or record");
-  if (!edt3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need volumes of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need volumes of 1..1024 voxels along each axis");
   if (thr_pred != thr_pred || thr_gt != thr_gt) return afx::set_error(AFX_E_INVALID, who, "a threshold is NaN");
   if (!(q >= 0.0 && q <= 100.0)) return afx::set_error(AFX_E_INVALID, who, "the percentile q must lie in [0, 100]");
   const size_t need = afx_surface_metrics_3d_workspace_bytes(n0, n1, n2);

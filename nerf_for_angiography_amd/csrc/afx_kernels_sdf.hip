@@ -64,10 +64,6 @@ SdfBufs carve_sdf(afx::Carve& c, int64_t n_triangles) {
   return b;
 }
 
-bool sdf_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
-  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
-}
-
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
   return (ax * bx + ay * by) + az * bz;
 }
@@ -460,7 +456,7 @@ extern "C" int afx_mesh_sdf_3d(const float* vertices, int64_t n_vertices, const 
   const char* who = "afx_mesh_sdf_3d";
   if (!sdf_out || !record || !index_to_world) return afx::set_error(AFX_E_INVALID, who, "null sdf_out, record or index_to_world");
   if (int rc = mesh_args_ok(vertices, n_vertices, triangles, n_triangles, who)) return rc;
-  if (!sdf_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a grid of 1..1024 points along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a grid of 1..1024 points along each axis");
   if (flags & ~(uint32_t)(AFX_MESH_SDF_BRUTE | AFX_MESH_SDF_CLOSED)) return afx::set_error(AFX_E_INVALID, who, "unknown flag bits");
   SdfAffine aff;
   for (int k = 0; k < 12; ++k) {

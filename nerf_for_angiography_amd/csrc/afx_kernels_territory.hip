@@ -28,10 +28,6 @@ constexpr unsigned long long FT3_NONE64 = ~0ull;      // the packed cell of "no 
 constexpr int OV_BLOCK = 256;
 constexpr int OV_MAX_BLOCKS = 2048;
 
-bool ft3_shape_ok(int32_t n0, int32_t n1, int32_t n2) {
-  return n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= AFX_EDT3D_MAX_SIDE && n1 <= AFX_EDT3D_MAX_SIDE && n2 <= AFX_EDT3D_MAX_SIDE;
-}
-
 __global__ void __launch_bounds__(FT3_BLOCK) k_ft3_axis2(const uint8_t* __restrict__ sites, int64_t lines, int n2, uint32_t* __restrict__ d2,
                                                          int32_t* __restrict__ nearest) {
   const int lane = threadIdx.x & 63;
@@ -180,7 +176,7 @@ extern "C" int afx_feature_transform_3d(const uint8_t* sites, int32_t n0, int32_
   if (!sites) return afx::set_error(AFX_E_INVALID, who, "null sites");
   if (!d2) return afx::set_error(AFX_E_INVALID, who, "null d2");
   if (!nearest) return afx::set_error(AFX_E_INVALID, who, "null nearest");
-  if (!ft3_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
+  if (!afx::volume_shape_ok(n0, n1, n2)) return afx::set_error(AFX_E_INVALID, who, "need a volume of 1..1024 voxels along each axis");
   if (int rc = afx::check_device_memory(sites, "sites", who)) return rc;
   if (int rc = afx::check_device_memory(d2, "d2", who)) return rc;
   if (int rc = afx::check_device_memory(nearest, "nearest", who)) return rc;

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -27,6 +28,56 @@ def _f32(t: torch.Tensor, name: str, device) -> torch.Tensor:
     if t.dtype != torch.float32:
         raise ValueError(f"{name}: dtype {t.dtype}, expected float32")
     return t if t.is_contiguous() else t.contiguous()
+
+
+# ---- the buffer vocabulary of the analysis wrappers (image weights .. TV, below): every check is made on the host, before the first launch ----
+EDT3D_MAX_SIDE = 1024                 # AFX_EDT3D_MAX_SIDE
+
+
+def _on_gpu(t, name: str, who: str):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    return t
+
+
+def _buffer(t, name: str, dtype, shape, dev, who: str, exact_shape: bool = False, at_least: bool = False):
+    """A tensor the library reads or writes through its pointer: contiguous, of `dtype` (one, or a tuple of admitted ones), on `dev`, with
+    prod(shape) elements (`shape` may be the count itself; None: any number; at_least: that many or more; exact_shape: of that very
+    shape) -> t.  ValueError otherwise, in one wording."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    shape = shape if shape is None or isinstance(shape, (tuple, torch.Size)) else (int(shape),)
+    if isinstance(t, torch.Tensor) and t.dtype in dtypes and t.device == dev and t.is_contiguous():
+        if shape is None or (tuple(t.shape) == tuple(shape) if exact_shape else
+                             t.numel() >= math.prod(shape) if at_least else t.numel() == math.prod(shape)):
+            return t
+    size = "" if shape is None else f" of shape {tuple(shape)}" if exact_shape else \
+        f" of {'at least ' if at_least else ''}{math.prod(shape)} elements {tuple(shape)}"
+    got = f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous = {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
+    raise ValueError(f"{who}: {name} must be a contiguous {' or '.join(str(d) for d in dtypes)} tensor{size} on {dev}, got {got}")
+
+
+def _out(t, name: str, dtype, shape, dev, who: str, ok: bool = True, exact_shape: bool = False, at_least: bool = False):
+    """An output, record or state buffer: allocated unless the caller passed it, else checked as `_buffer` does.  ok=False: a shape the
+    library refuses gets a one-element buffer, so the call reports the limits instead of the allocator failing first (a buffer the
+    caller passed is then not held to the count: the library refuses before it writes)."""
+    if t is None:
+        return torch.empty(shape if ok else (1,), dtype=dtype, device=dev)
+    return _buffer(t, name, dtype, shape if ok else None, dev, who, exact_shape, at_least)
+
+
+def _scratch(workspace, nbytes: int, dev, who: str):
+    """-> (workspace, its size in bytes): max(nbytes, 1) fresh bytes unless the caller passed a contiguous tensor on `dev`.  Whether that one
+    is large enough is the library's to say (afx::check_workspace)."""
+    if workspace is None:
+        workspace = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace must be a contiguous tensor on {dev}")
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def _volume_side_ok(shape) -> bool:
+    """Every side of a volume within the library's 1..AFX_EDT3D_MAX_SIDE."""
+    return all(1 <= int(n) <= EDT3D_MAX_SIDE for n in shape)
 
 
 def ray_window(who: str, n_proj: int, width: int, height: int, ray_id0: int = 0, n_rays=None, ray_ids=None) -> int:
@@ -1129,9 +1180,7 @@ def topk_indices(keys: torch.Tensor, k: int) -> torch.Tensor:
 
 def _images_f64(x: torch.Tensor, who: str) -> torch.Tensor:
     """[H, W] or [N, H, W] device tensor -> contiguous float64 [N, H, W]."""
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise AfxError(f"{who}: the images must be a tensor on a GPU; there is no CPU path")
-    if x.dim() not in (2, 3):
+    if _on_gpu(x, "the images", who).dim() not in (2, 3):
         raise ValueError(f"{who}: expected [H, W] or [N, H, W], got shape {tuple(x.shape)}")
     x = x if x.dim() == 3 else x[None]
     return x.to(torch.float64).contiguous()
@@ -1150,7 +1199,7 @@ def frangi(images: torch.Tensor, sigmas=(1, 3, 5, 7, 9), beta: float = 0.5, gamm
     sg, ns = _sigma_array(sigmas)
     out = torch.empty_like(x)
     nbytes = int(lib.afx_frangi_workspace_bytes(n, h, w, ns))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _scratch(None, nbytes, x.device, "frangi")[0]
     _lib.check(lib.afx_frangi(_ptr(x), n, h, w, sg, ns, float(beta), float(gamma), int(bool(black_ridges)), _ptr(out), _ptr(ws), nbytes, None,
                               Engine._stream(x.device)), "afx_frangi")
     return out
@@ -1163,7 +1212,7 @@ def distance_transform_edt(x: torch.Tensor) -> torch.Tensor:
     n, h, w = x.shape
     out = torch.empty_like(x)
     nbytes = int(lib.afx_distance_transform_edt_workspace_bytes(n, h, w))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _scratch(None, nbytes, x.device, "distance_transform_edt")[0]
     _lib.check(lib.afx_distance_transform_edt(_ptr(x), n, h, w, _ptr(out), _ptr(ws), nbytes, None, Engine._stream(x.device)),
                "afx_distance_transform_edt")
     return out
@@ -1183,7 +1232,7 @@ def sampling_weights(images: torch.Tensor, strategy: str = "frangi", binary: boo
     out = torch.empty_like(x)
     status = torch.empty(n, dtype=torch.int32, device=x.device)
     nbytes = int(lib.afx_sampling_weights_workspace_bytes(st, n, h, w, ns))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _scratch(None, nbytes, x.device, "sampling_weights")[0]
     _lib.check(lib.afx_sampling_weights(_ptr(x), n, h, w, st, int(bool(binary)), sg, ns, float(beta), float(gamma), _ptr(out), _ptr(status),
                                         _ptr(ws), nbytes, None, Engine._stream(x.device)), "afx_sampling_weights")
     return out, status
@@ -1193,9 +1242,7 @@ def ssim(preds: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
     """afx_ssim: the SSIM (torchmetrics StructuralSimilarityIndexMeasure(data_range=1.0), computed in fp64) of every pair of two [N, H, W]
     (or [H, W]) device tensors, float64 [N].  All views in one launch sequence; nothing is read back."""
     lib = _lib.load()
-    for name, t in (("preds", preds), ("targets", targets)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"ssim: {name} must be a tensor on a GPU; there is no CPU path")
+    _on_gpu(preds, "preds", "ssim"), _on_gpu(targets, "targets", "ssim")
     if preds.shape != targets.shape or preds.dim() not in (2, 3):
         raise ValueError(f"ssim: expected two [H, W] or [N, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(targets.shape)}")
     if preds.device != targets.device:
@@ -1205,7 +1252,7 @@ def ssim(preds: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
     n, h, w = x.shape
     out = torch.empty(n, dtype=torch.float64, device=x.device)
     nbytes = int(lib.afx_ssim_workspace_bytes(n, h, w))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    ws = _scratch(None, nbytes, x.device, "ssim")[0]
     _lib.check(lib.afx_ssim(_ptr(x), _ptr(y), n, h, w, _ptr(out), _ptr(ws), nbytes, None, Engine._stream(x.device)), "afx_ssim")
     return out
 
@@ -1221,8 +1268,7 @@ def volume_grid(volume_values: torch.Tensor, origin, spacing, fill, lo: float, h
     if vol.dim() != 3:
         raise ValueError("volume: expected [nx,ny,nz]")
     n = int(n)
-    # an n the library refuses gets a one-element buffer: the call reports the range instead of the allocator failing first
-    out = torch.empty((n,) * 3 if 2 <= n <= 1 << 20 else (1,), dtype=torch.float32, device=dev)
+    out = _out(None, "out", torch.float32, (n,) * 3, dev, "volume_grid", ok=2 <= n <= 1 << 20)
     org = (C.c_double * 3)(*[float(x) for x in origin])
     spc = (C.c_double * 3)(*[float(x) for x in spacing])
     _lib.check(lib.afx_volume_grid(_ptr(vol), vol.shape[0], vol.shape[1], vol.shape[2], org, spc, float(fill), float(lo), float(hi), n,
@@ -1231,9 +1277,7 @@ def volume_grid(volume_values: torch.Tensor, origin, spacing, fill, lo: float, h
 
 
 def _volume_on_gpu(x, name: str, who: str) -> None:
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-        raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
-    if x.dim() != 3:
+    if _on_gpu(x, name, who).dim() != 3:
         raise ValueError(f"{who}: {name} must have shape [n0, n1, n2], got {tuple(x.shape)}")
 
 
@@ -1246,11 +1290,10 @@ def distance_transform_edt_3d(x: torch.Tensor, return_squared: bool = False):
     _volume_on_gpu(x, "the volume", "distance_transform_edt_3d")
     fg = (x != 0).to(torch.uint8).contiguous()
     n0, n1, n2 = fg.shape
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    nbytes = int(lib.afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2))
-    d2 = torch.empty(fg.shape if nbytes else (1,), dtype=torch.int32, device=fg.device)
-    dist = torch.empty(fg.shape if nbytes else (1,), dtype=torch.float64, device=fg.device)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=fg.device)
+    nbytes = int(lib.afx_distance_transform_edt_3d_workspace_bytes(n0, n1, n2))      # (0: a shape the library refuses)
+    d2 = _out(None, "d2", torch.int32, fg.shape, fg.device, "distance_transform_edt_3d", ok=nbytes > 0)
+    dist = _out(None, "dist", torch.float64, fg.shape, fg.device, "distance_transform_edt_3d", ok=nbytes > 0)
+    ws = _scratch(None, nbytes, fg.device, "distance_transform_edt_3d")[0]
     _lib.check(lib.afx_distance_transform_edt_3d(_ptr(fg), n0, n1, n2, _ptr(d2), _ptr(dist), _ptr(ws), nbytes, None, Engine._stream(fg.device)),
                "afx_distance_transform_edt_3d")
     if not return_squared:
@@ -1274,13 +1317,10 @@ def surface_metrics_record(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float
     dev = pred.device
     p, g = _f32(pred, "pred", dev), _f32(gt, "gt", dev)
     n0, n1, n2 = p.shape
-    nbytes = int(lib.afx_surface_metrics_3d_workspace_bytes(n0, n1, n2))
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    if record is None:
-        record = torch.empty(SURFACE_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    record = _out(record, "record", torch.int64, SURFACE_RECORD_SLOTS, dev, "surface_metrics_3d")
+    workspace, nbytes = _scratch(workspace, lib.afx_surface_metrics_3d_workspace_bytes(n0, n1, n2), dev, "surface_metrics_3d")
     _lib.check(lib.afx_surface_metrics_3d(_ptr(p), _ptr(g), n0, n1, n2, float(thr_pred), float(thr_gt), float(q), _ptr(record), _ptr(workspace),
-                                          workspace.numel(), None, Engine._stream(dev)), "afx_surface_metrics_3d")
+                                          nbytes, None, Engine._stream(dev)), "afx_surface_metrics_3d")
     return record
 
 
@@ -1330,22 +1370,16 @@ def components_record(x: torch.Tensor, connectivity: int = 1, labels=None, sizes
     bytes, to keep the capture free of allocations)."""
     lib = _lib.load()
     _volume_on_gpu(x, "the mask", "label_components_3d")
-    if x.dtype != torch.uint8 or not x.is_contiguous():
-        raise ValueError(f"components_record: the mask must be a contiguous uint8 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
-    dev = x.device
+    dev, who = x.device, "components_record"
+    _buffer(x, "the mask", torch.uint8, x.shape, dev, who)
     n0, n1, n2 = x.shape
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    nbytes = int(lib.afx_label_components_3d_workspace_bytes(n0, n1, n2))
-    if labels is None:
-        labels = torch.empty(x.shape if nbytes else (1,), dtype=torch.int32, device=dev)
-    if sizes is None:
-        sizes = torch.empty(x.numel() if nbytes else 1, dtype=torch.int32, device=dev)
-    if record is None:
-        record = torch.empty(COMPONENTS_RECORD_SLOTS, dtype=torch.int64, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.afx_label_components_3d_workspace_bytes(n0, n1, n2))      # (0: a shape the library refuses)
+    labels = _out(labels, "labels", torch.int32, x.shape, dev, who, ok=nbytes > 0)
+    sizes = _out(sizes, "sizes", torch.int32, x.numel(), dev, who, ok=nbytes > 0)
+    record = _out(record, "record", torch.int64, COMPONENTS_RECORD_SLOTS, dev, who)
+    workspace, nbytes = _scratch(workspace, nbytes, dev, who)
     _lib.check(lib.afx_label_components_3d(_ptr(x), n0, n1, n2, int(connectivity), _ptr(labels), _ptr(sizes), _ptr(record), _ptr(workspace),
-                                           workspace.numel(), None, Engine._stream(dev)), "afx_label_components_3d")
+                                           nbytes, None, Engine._stream(dev)), "afx_label_components_3d")
     return labels, sizes, record
 
 
@@ -1381,10 +1415,13 @@ def components_filter(labels: torch.Tensor, sizes: torch.Tensor, record: torch.T
     if not 1 <= int(min_size) <= 0xffffffff:
         raise ValueError(f"filter_components_3d: min_size must lie in 1..2^32 - 1, got {min_size}")
     n0, n1, n2 = labels.shape
-    if out is None:
-        out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    dev, who = labels.device, "filter_components_3d"
+    _buffer(labels, "labels", torch.int32, labels.shape, dev, who)
+    _buffer(sizes, "sizes", torch.int32, labels.numel(), dev, who)
+    _buffer(record, "record", torch.int64, COMPONENTS_RECORD_SLOTS, dev, who)
+    out = _out(out, "out", torch.uint8, labels.shape, dev, who)
     _lib.check(lib.afx_filter_components_3d(_ptr(labels), _ptr(sizes), _ptr(record), n0, n1, n2, int(bool(largest_only)), int(min_size),
-                                            _ptr(out), Engine._stream(labels.device)), "afx_filter_components_3d")
+                                            _ptr(out), Engine._stream(dev)), "afx_filter_components_3d")
     return out
 
 
@@ -1400,20 +1437,15 @@ def skeleton_record(x: torch.Tensor, max_passes: int, sync_every: int = 0, skel=
     sync_every > 0 lets the library look at the record every so many passes and stop at convergence."""
     lib = _lib.load()
     _volume_on_gpu(x, "the mask", "skeletonize_3d")
-    if x.dtype != torch.uint8 or not x.is_contiguous():
-        raise ValueError(f"skeleton_record: the mask must be a contiguous uint8 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
-    dev = x.device
+    dev, who = x.device, "skeleton_record"
+    _buffer(x, "the mask", torch.uint8, x.shape, dev, who)
     n0, n1, n2 = x.shape
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    nbytes = int(lib.afx_skeletonize_3d_workspace_bytes(n0, n1, n2))
-    if skel is None:
-        skel = torch.empty(x.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
-    if record is None:
-        record = torch.empty(SKELETON_RECORD_SLOTS, dtype=torch.int64, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.afx_skeletonize_3d_workspace_bytes(n0, n1, n2))      # (0: a shape the library refuses)
+    skel = _out(skel, "skel", torch.uint8, x.shape, dev, who, ok=nbytes > 0)
+    record = _out(record, "record", torch.int64, SKELETON_RECORD_SLOTS, dev, who)
+    workspace, nbytes = _scratch(workspace, nbytes, dev, who)
     _lib.check(lib.afx_skeletonize_3d(_ptr(x), n0, n1, n2, int(max_passes), int(sync_every), _ptr(skel), _ptr(record), _ptr(workspace),
-                                      workspace.numel(), Engine._stream(dev)), "afx_skeletonize_3d")
+                                      nbytes, Engine._stream(dev)), "afx_skeletonize_3d")
     return skel, record
 
 
@@ -1462,19 +1494,14 @@ def isosurface_record(x: torch.Tensor, iso: float, index_to_world=None, max_vert
     n0, n1, n2 = f.shape
     aff = (C.c_double * 12)(*_affine12(index_to_world, "isosurface_record"))
     max_vertices, max_triangles = int(max_vertices), int(max_triangles)
-    # a capacity the library refuses gets a one-element buffer: the call reports the range instead of the allocator failing first
-    if vertices is None:
-        vertices = torch.empty((max_vertices if 0 <= max_vertices < 2 ** 31 else 1, 3), dtype=torch.float32, device=dev)
-    if triangles is None:
-        triangles = torch.empty((max_triangles if 0 <= max_triangles < 2 ** 31 else 1, 3), dtype=torch.int32, device=dev)
-    nbytes = int(lib.afx_isosurface_3d_workspace_bytes(n0, n1, n2))
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    if record is None:
-        record = torch.empty(ISOSURFACE_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    # (the capacities are lower bounds: a longer table is the caller's to pass, nothing is written beyond max_vertices / max_triangles rows)
+    vertices = _out(vertices, "vertices", torch.float32, (max_vertices, 3), dev, "isosurface_record", ok=0 <= max_vertices < 2 ** 31, at_least=True)
+    triangles = _out(triangles, "triangles", torch.int32, (max_triangles, 3), dev, "isosurface_record", ok=0 <= max_triangles < 2 ** 31, at_least=True)
+    record = _out(record, "record", torch.int64, ISOSURFACE_RECORD_SLOTS, dev, "isosurface_record")
+    workspace, nbytes = _scratch(workspace, lib.afx_isosurface_3d_workspace_bytes(n0, n1, n2), dev, "isosurface_record")
     _lib.check(lib.afx_isosurface_3d(_ptr(f), n0, n1, n2, float(iso), aff, _ptr(vertices) if max_vertices else None, max_vertices,
                                      _ptr(triangles) if max_triangles else None, max_triangles, _ptr(record), _ptr(workspace),
-                                     workspace.numel(), None, Engine._stream(dev)), "afx_isosurface_3d")
+                                     nbytes, None, Engine._stream(dev)), "afx_isosurface_3d")
     return vertices, triangles, record
 
 
@@ -1496,8 +1523,7 @@ def extract_isosurface(x: torch.Tensor, iso: float, index_to_world=None, cap: bo
         f = torch.nn.functional.pad(f, (1, 1, 1, 1, 1, 1), value=float(fill))
         aff = aff.copy()
         aff[:, 3] = aff[:, 3] - aff[:, :3] @ [1.0, 1.0, 1.0]
-    nbytes = int(_lib.load().afx_isosurface_3d_workspace_bytes(*f.shape))
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    ws = _scratch(None, _lib.load().afx_isosurface_3d_workspace_bytes(*f.shape), dev, "extract_isosurface")[0]
     rec = isosurface_record(f, iso, aff, workspace=ws)[2].cpu().tolist()
     v, t = rec[0], rec[1]
     if v > 2 ** 31 - 1 or t > 2 ** 31 - 1:
@@ -1512,21 +1538,14 @@ def mesh_measures_record(vertices: torch.Tensor, triangles: torch.Tensor, record
     about ref_point (3 numbers; None = the origin).  V and T are read from the record on the device.  Launches only; pass `out` and
     the workspace of afx_mesh_measures_workspace_bytes bytes to keep a graph capture free of allocations."""
     lib = _lib.load()
-    for t, name in ((vertices, "vertices"), (triangles, "triangles"), (record, "the record")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"mesh_measures: {name} must be a tensor on a GPU; there is no CPU path")
-    if vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or not triangles.is_contiguous():
-        raise ValueError("mesh_measures: vertices must be contiguous float32 [V, 3], triangles contiguous int32 [T, 3]")
-    dev = vertices.device
-    nbytes = int(lib.afx_mesh_measures_workspace_bytes())
-    if workspace is None:
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty(2, dtype=torch.float64, device=dev)
+    dev, who = _mesh_on_gpu(vertices, triangles, "mesh_measures"), "mesh_measures"
+    _buffer(_on_gpu(record, "the record", who), "the record", torch.int64, ISOSURFACE_RECORD_SLOTS, dev, who)
+    out = _out(out, "out", torch.float64, 2, dev, who)
+    workspace, nbytes = _scratch(workspace, lib.afx_mesh_measures_workspace_bytes(), dev, who)
     ref = (C.c_double * 3)(*[float(r) for r in (ref_point if ref_point is not None else (0.0, 0.0, 0.0))])
     nv, nt = vertices.shape[0], triangles.shape[0]
     _lib.check(lib.afx_mesh_measures(_ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None, nt, _ptr(record), ref, _ptr(out),
-                                     _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_mesh_measures")
+                                     _ptr(workspace), nbytes, None, Engine._stream(dev)), "afx_mesh_measures")
     return out
 
 
@@ -1534,11 +1553,7 @@ def mesh_measures(vertices: torch.Tensor, triangles: torch.Tensor, ref_point=Non
     """{"area", "volume"} of an indexed triangle mesh on the device (float32 [V, 3], int32 [T, 3]): the sum of the triangles' areas and
     the enclosed volume, sum of (v0 - r) . ((v1 - r) x (v2 - r)) / 6, in fp64 in a fixed order - positive for a closed mesh whose
     normals point outwards.  ref_point r: None = the mean of the vertices' bounding box (the terms then cancel least)."""
-    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"mesh_measures: {name} must be a tensor on a GPU; there is no CPU path")
-    v = vertices.to(torch.float32).contiguous().view(-1, 3)
-    t = triangles.to(torch.int32).contiguous().view(-1, 3)
+    v, t = _as_mesh(vertices, triangles, "mesh_measures")
     if ref_point is None:
         ref_point = ((v.min(0).values.double() + v.max(0).values.double()) / 2).cpu().tolist() if v.shape[0] else (0.0, 0.0, 0.0)
     record = torch.tensor([v.shape[0], t.shape[0]] + [0] * (ISOSURFACE_RECORD_SLOTS - 2), dtype=torch.int64, device=v.device)
@@ -1553,20 +1568,16 @@ _MESH_SDF_RECORD_KEYS = ("valid_triangles", "skipped_triangles", "clear_bricks",
 
 
 def _mesh_on_gpu(vertices, triangles, who: str):
-    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
-    if vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or not triangles.is_contiguous() \
-            or vertices.dim() != 2 or vertices.shape[1] != 3 or triangles.dim() != 2 or triangles.shape[1] != 3:
-        raise ValueError(f"{who}: vertices must be contiguous float32 [V, 3], triangles contiguous int32 [T, 3]")
-    if triangles.device != vertices.device:
-        raise ValueError(f"{who}: vertices and triangles live on different devices")
+    """vertices contiguous float32 [V, 3] and triangles contiguous int32 [T, 3] on one GPU -> that device."""
+    dev = _on_gpu(vertices, "vertices", who).device
+    _on_gpu(triangles, "triangles", who)
+    _buffer(vertices, "vertices", torch.float32, vertices.shape[:1] + (3,), dev, who, exact_shape=True)
+    _buffer(triangles, "triangles", torch.int32, triangles.shape[:1] + (3,), dev, who, exact_shape=True)
+    return dev
 
 
 def _as_mesh(vertices, triangles, who: str):
-    for t, name in ((vertices, "vertices"), (triangles, "triangles")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
+    _on_gpu(vertices, "vertices", who), _on_gpu(triangles, "triangles", who)
     return vertices.to(torch.float32).contiguous().view(-1, 3), triangles.to(torch.int32).contiguous().view(-1, 3)
 
 
@@ -1579,26 +1590,21 @@ def mesh_sdf_record(vertices: torch.Tensor, triangles: torch.Tensor, shape, inde
     triangles, clear bricks, pairs the distance pass evaluated).  Launches only - nothing is read back, so the call can be captured in
     a graph (pass sdf, record and the workspace of afx_mesh_sdf_3d_workspace_bytes(T) bytes to keep the capture free of allocations)."""
     lib = _lib.load()
-    _mesh_on_gpu(vertices, triangles, "mesh_sdf_record")
-    dev = vertices.device
+    dev, who = _mesh_on_gpu(vertices, triangles, "mesh_sdf_record"), "mesh_sdf_record"
     n0, n1, n2 = (int(n) for n in shape)
-    aff = (C.c_double * 12)(*_affine12(index_to_world, "mesh_sdf_record"))
+    aff = (C.c_double * 12)(*_affine12(index_to_world, who))
     nv, nt = vertices.shape[0], triangles.shape[0]
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    ok = all(1 <= n <= 1024 for n in (n0, n1, n2))
-    if sdf is None:
-        sdf = torch.empty((n0, n1, n2) if ok else (1,), dtype=torch.float32, device=dev)
-    for t, name, dtype in ((sdf, "sdf", torch.float32), (nearest, "nearest", torch.int32), (winding, "winding", torch.float64)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or (ok and t.numel() != n0 * n1 * n2)):
-            raise ValueError(f"mesh_sdf_record: {name} must be a contiguous {dtype} tensor of {n0 * n1 * n2} elements on {dev}")
-    nbytes = int(lib.afx_mesh_sdf_3d_workspace_bytes(nt))
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    if record is None:
-        record = torch.empty(MESH_SDF_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    ok = _volume_side_ok((n0, n1, n2))
+    sdf = _out(sdf, "sdf", torch.float32, (n0, n1, n2), dev, who, ok=ok)
+    if nearest is not None:
+        _out(nearest, "nearest", torch.int32, (n0, n1, n2), dev, who, ok=ok)
+    if winding is not None:
+        _out(winding, "winding", torch.float64, (n0, n1, n2), dev, who, ok=ok)
+    record = _out(record, "record", torch.int64, MESH_SDF_RECORD_SLOTS, dev, who)
+    workspace, nbytes = _scratch(workspace, lib.afx_mesh_sdf_3d_workspace_bytes(nt), dev, who)
     _lib.check(lib.afx_mesh_sdf_3d(_ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None, nt, n0, n1, n2, aff, int(flags),
-                                   _ptr(sdf), _ptr(nearest) if nearest is not None else None, _ptr(winding) if winding is not None else None,
-                                   _ptr(record), _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_mesh_sdf_3d")
+                                   _ptr(sdf), _ptr(nearest), _ptr(winding), _ptr(record), _ptr(workspace), nbytes, None, Engine._stream(dev)),
+               "afx_mesh_sdf_3d")
     return sdf, record
 
 
@@ -1612,7 +1618,7 @@ def mesh_signed_distance(vertices: torch.Tensor, triangles: torch.Tensor, shape,
     (float64, which forces the per-point sum), record ({"valid_triangles", "skipped_triangles", "clear_bricks", "pairs_evaluated"})."""
     v, t = _as_mesh(vertices, triangles, "mesh_signed_distance")
     n0, n1, n2 = (int(n) for n in shape)
-    ok = all(1 <= n <= 1024 for n in (n0, n1, n2))
+    ok = _volume_side_ok((n0, n1, n2))
     nearest = torch.empty((n0, n1, n2), dtype=torch.int32, device=v.device) if return_nearest and ok else None
     winding = torch.empty((n0, n1, n2), dtype=torch.float64, device=v.device) if return_winding and ok else None
     flags = (MESH_SDF_BRUTE if brute else 0) | (MESH_SDF_CLOSED if closed else 0)
@@ -1628,20 +1634,13 @@ def mesh_point_distance_record(points: torch.Tensor, vertices: torch.Tensor, tri
     record); nearest (int32 [P]) is filled when given.  All pairs, one launch, no workspace; nothing is read back (pass dist and record
     to keep a graph capture free of allocations)."""
     lib = _lib.load()
-    _mesh_on_gpu(vertices, triangles, "mesh_point_distance_record")
-    if not isinstance(points, torch.Tensor) or points.device.type != "cuda":
-        raise AfxError("mesh_point_distance_record: points must be a tensor on a GPU; there is no CPU path")
-    dev = vertices.device
-    if points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.device != dev:
-        raise ValueError(f"mesh_point_distance_record: points must be contiguous float32 [P, 3] on {dev}")
+    dev, who = _mesh_on_gpu(vertices, triangles, "mesh_point_distance_record"), "mesh_point_distance_record"
+    _buffer(_on_gpu(points, "points", who), "points", torch.float32, points.shape[:1] + (3,), dev, who, exact_shape=True)
     n = points.shape[0]
-    if dist is None:
-        dist = torch.empty(n, dtype=torch.float32, device=dev)
-    for t, name, dtype in ((dist, "dist", torch.float32), (nearest, "nearest", torch.int32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != n):
-            raise ValueError(f"mesh_point_distance_record: {name} must be a contiguous {dtype} tensor of {n} elements on {dev}")
-    if record is None:
-        record = torch.empty(MESH_SDF_RECORD_SLOTS, dtype=torch.int64, device=dev)
+    dist = _out(dist, "dist", torch.float32, n, dev, who)
+    if nearest is not None:
+        _buffer(nearest, "nearest", torch.int32, n, dev, who)
+    record = _out(record, "record", torch.int64, MESH_SDF_RECORD_SLOTS, dev, who)
     nv, nt = vertices.shape[0], triangles.shape[0]
     _lib.check(lib.afx_mesh_point_distance(_ptr(points) if n else None, n, _ptr(vertices) if nv else None, nv, _ptr(triangles) if nt else None,
                                            nt, _ptr(dist) if n else None, _ptr(nearest) if nearest is not None and n else None, _ptr(record),
@@ -1652,8 +1651,7 @@ def mesh_point_distance_record(points: torch.Tensor, vertices: torch.Tensor, tri
 def mesh_point_distance(points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, return_nearest: bool = False):
     """The distance of every point ([P, 3], device) to the nearest triangle of a mesh on the device -> float32 [P] (+inf without a valid
     triangle); with return_nearest also the index of that triangle (int32, the smallest one on a tie, -1 without any)."""
-    if not isinstance(points, torch.Tensor) or points.device.type != "cuda":
-        raise AfxError("mesh_point_distance: points must be a tensor on a GPU; there is no CPU path")
+    _on_gpu(points, "points", "mesh_point_distance")
     v, t = _as_mesh(vertices, triangles, "mesh_point_distance")
     p = points.to(torch.float32).contiguous().view(-1, 3)
     nearest = torch.empty(p.shape[0], dtype=torch.int32, device=v.device) if return_nearest else None
@@ -1705,30 +1703,22 @@ def centreline_graph_record(skel: torch.Tensor, d2=None, step_lengths=None, max_
     import ctypes as C
     lib = _lib.load()
     _volume_on_gpu(skel, "the mask", "centreline_graph")
-    if skel.dtype != torch.uint8 or not skel.is_contiguous():
-        raise ValueError(f"centreline_graph_record: the mask must be a contiguous uint8 tensor, got {skel.dtype}, contiguous = {skel.is_contiguous()}")
-    if d2 is not None and (d2.dtype != torch.int32 or not d2.is_contiguous() or d2.shape != skel.shape):
-        raise ValueError("centreline_graph_record: d2 must be a contiguous int32 tensor of the mask's shape")
-    dev = skel.device
+    dev, who = skel.device, "centreline_graph_record"
+    _buffer(skel, "the mask", torch.uint8, skel.shape, dev, who)
+    if d2 is not None:
+        _buffer(d2, "d2", torch.int32, skel.shape, dev, who, exact_shape=True)
     n0, n1, n2 = skel.shape
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    nbytes = int(lib.afx_centreline_graph_workspace_bytes(n0, n1, n2))
-    if node_labels is None:
-        node_labels = torch.empty(skel.shape if nbytes else (1,), dtype=torch.int32, device=dev)
-    if branch_labels is None:
-        branch_labels = torch.empty(skel.shape if nbytes else (1,), dtype=torch.int32, device=dev)
-    if path_voxels is None:
-        path_voxels = torch.empty(skel.numel() if nbytes else 1, dtype=torch.int32, device=dev)
-    if branches is None:
-        branches = torch.empty((max(int(max_branches), 0), GRAPH_BRANCH_SLOTS), dtype=torch.int64, device=dev)
-    if record is None:
-        record = torch.empty(GRAPH_RECORD_SLOTS, dtype=torch.int64, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.afx_centreline_graph_workspace_bytes(n0, n1, n2))      # (0: a shape the library refuses)
+    node_labels = _out(node_labels, "node_labels", torch.int32, skel.shape, dev, who, ok=nbytes > 0)
+    branch_labels = _out(branch_labels, "branch_labels", torch.int32, skel.shape, dev, who, ok=nbytes > 0)
+    path_voxels = _out(path_voxels, "path_voxels", torch.int32, skel.numel(), dev, who, ok=nbytes > 0)
+    branches = _out(branches, "branches", torch.int64, (max(int(max_branches), 0), GRAPH_BRANCH_SLOTS), dev, who)
+    record = _out(record, "record", torch.int64, GRAPH_RECORD_SLOTS, dev, who)
+    workspace, nbytes = _scratch(workspace, nbytes, dev, who)
     L = None if step_lengths is None else (C.c_double * 13)(*[float(x) for x in step_lengths])
     _lib.check(lib.afx_centreline_graph(_ptr(skel), _ptr(d2), n0, n1, n2, L, _ptr(node_labels), _ptr(branch_labels), _ptr(path_voxels),
                                         _ptr(branches) if int(max_branches) > 0 else None, int(max_branches), _ptr(record), _ptr(workspace),
-                                        workspace.numel(), None, Engine._stream(dev)), "afx_centreline_graph")
+                                        nbytes, None, Engine._stream(dev)), "afx_centreline_graph")
     return node_labels, branch_labels, path_voxels, branches, record
 
 
@@ -1785,21 +1775,16 @@ def prune_record(skel: torch.Tensor, d2: torch.Tensor, factor: float, max_rounds
     pass all three buffers); sync_every > 0 lets the library look at the record every so many rounds and stop at convergence."""
     lib = _lib.load()
     _volume_on_gpu(skel, "the mask", "prune_spurs")
-    if skel.dtype != torch.uint8 or not skel.is_contiguous():
-        raise ValueError(f"prune_record: the mask must be a contiguous uint8 tensor, got {skel.dtype}, contiguous = {skel.is_contiguous()}")
-    if not isinstance(d2, torch.Tensor) or d2.dtype != torch.int32 or not d2.is_contiguous() or d2.shape != skel.shape or d2.device != skel.device:
-        raise ValueError("prune_record: d2 must be a contiguous int32 tensor of the mask's shape on its device")
-    dev = skel.device
+    dev, who = skel.device, "prune_record"
+    _buffer(skel, "the mask", torch.uint8, skel.shape, dev, who)
+    _buffer(d2, "d2", torch.int32, skel.shape, dev, who, exact_shape=True)
     n0, n1, n2 = skel.shape
-    nbytes = int(lib.afx_prune_spurs_workspace_bytes(n0, n1, n2))
-    if out is None:
-        out = torch.empty(skel.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
-    if record is None:
-        record = torch.empty(PRUNE_RECORD_SLOTS, dtype=torch.int64, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.afx_prune_spurs_workspace_bytes(n0, n1, n2))      # (0: a shape the library refuses)
+    out = _out(out, "out", torch.uint8, skel.shape, dev, who, ok=nbytes > 0)
+    record = _out(record, "record", torch.int64, PRUNE_RECORD_SLOTS, dev, who)
+    workspace, nbytes = _scratch(workspace, nbytes, dev, who)
     _lib.check(lib.afx_prune_spurs(_ptr(skel), _ptr(d2), n0, n1, n2, float(factor), int(max_rounds), int(sync_every), _ptr(out), _ptr(record),
-                                   _ptr(workspace), workspace.numel(), None, Engine._stream(dev)), "afx_prune_spurs")
+                                   _ptr(workspace), nbytes, None, Engine._stream(dev)), "afx_prune_spurs")
     return out, record
 
 
@@ -1897,19 +1882,12 @@ def lumen_profile_record(volume: torch.Tensor, points: torch.Tensor, seg_first: 
     import numpy as np
     lib = _lib.load()
     _volume_on_gpu(volume, "the volume", "lumen_profile")
-    if volume.dtype not in (torch.float32, torch.float64) or not volume.is_contiguous():
-        raise ValueError(f"lumen_profile_record: the volume must be a contiguous float32 or float64 tensor, got {volume.dtype}, "
-                         f"contiguous = {volume.is_contiguous()}")
-    dev = volume.device
-    for t, name in ((points, "points"), (seg_first, "seg_first"), (seg_last, "seg_last")):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"lumen_profile_record: {name} must be a tensor on a GPU; there is no CPU path")
-    if points.dtype != torch.float64 or not points.is_contiguous() or points.dim() != 2 or points.shape[1] != 3 or points.device != dev:
-        raise ValueError(f"lumen_profile_record: points must be contiguous float64 [P, 3] on {dev}")
+    dev, who = volume.device, "lumen_profile_record"
+    _buffer(volume, "the volume", (torch.float32, torch.float64), volume.shape, dev, who)
+    _on_gpu(points, "points", who), _on_gpu(seg_first, "seg_first", who), _on_gpu(seg_last, "seg_last", who)
+    _buffer(points, "points", torch.float64, points.shape[:1] + (3,), dev, who, exact_shape=True)
     n = points.shape[0]
-    for t, name in ((seg_first, "seg_first"), (seg_last, "seg_last")):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n or t.device != dev:
-            raise ValueError(f"lumen_profile_record: {name} must be a contiguous int32 tensor of {n} elements on {dev}")
+    _buffer(seg_first, "seg_first", torch.int32, n, dev, who), _buffer(seg_last, "seg_last", torch.int32, n, dev, who)
     r = int(n_rays)
     if ray_cs is None or area_coef is None:
         ray_cs, area_coef = lumen_ray_table(r)
@@ -1917,16 +1895,10 @@ def lumen_profile_record(volume: torch.Tensor, points: torch.Tensor, seg_first: 
     w = np.ascontiguousarray(world_to_index, np.float64).reshape(-1)
     if w.size != 12 or cs.size != 2 * max(r, 0):
         raise ValueError(f"lumen_profile_record: world_to_index must hold 12 numbers and ray_cs 2 x n_rays, got {w.size} and {cs.size}")
-    if profile is None:
-        profile = torch.empty((n, LUMEN_PROFILE_SLOTS), dtype=torch.float64, device=dev)
-    if flags is None:
-        flags = torch.empty(n, dtype=torch.int32, device=dev)
-    if radii is None and want_radii:
-        radii = torch.empty((n, max(r, 0)), dtype=torch.float64, device=dev)
-    for t, name, dtype, count in ((profile, "profile", torch.float64, n * LUMEN_PROFILE_SLOTS), (flags, "flags", torch.int32, n),
-                                  (radii, "radii", torch.float64, n * max(r, 0))):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != count):
-            raise ValueError(f"lumen_profile_record: {name} must be a contiguous {dtype} tensor of {count} elements on {dev}")
+    profile = _out(profile, "profile", torch.float64, (n, LUMEN_PROFILE_SLOTS), dev, who)
+    flags = _out(flags, "flags", torch.int32, n, dev, who)
+    if radii is not None or want_radii:
+        radii = _out(radii, "radii", torch.float64, (n, max(r, 0)), dev, who)
     n0, n1, n2 = volume.shape
     dp = lambda x: x.ctypes.data_as(C.POINTER(C.c_double))
     _lib.check(lib.afx_lumen_profile(_ptr(volume), int(volume.dtype == torch.float64), n0, n1, n2, dp(w), _ptr(points) if n else None,
@@ -2309,25 +2281,17 @@ def reformat_planes_record(volume: torch.Tensor, planes: torch.Tensor, table: to
     import numpy as np
     lib = _lib.load()
     _volume_on_gpu(volume, "the volume", "reformat_planes")
-    if volume.dtype not in (torch.float32, torch.float64) or not volume.is_contiguous():
-        raise ValueError(f"reformat_planes_record: the volume must be a contiguous float32 or float64 tensor, got {volume.dtype}, "
-                         f"contiguous = {volume.is_contiguous()}")
-    dev = volume.device
+    dev, who = volume.device, "reformat_planes_record"
+    _buffer(volume, "the volume", (torch.float32, torch.float64), volume.shape, dev, who)
     for t, name, cols in ((planes, "planes", REFORMAT_PLANE_DOUBLES), (table, "table", REFORMAT_TABLE_DOUBLES)):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise AfxError(f"reformat_planes_record: {name} must be a tensor on a GPU; there is no CPU path")
-        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != cols or t.device != dev:
-            raise ValueError(f"reformat_planes_record: {name} must be contiguous float64 [n, {cols}] on {dev}")
+        _buffer(_on_gpu(t, name, who), name, torch.float64, t.shape[:1] + (cols,), dev, who, exact_shape=True)
     if mode not in REFORMAT_MODES:
         raise ValueError(f"reformat_planes_record: mode must be one of {sorted(REFORMAT_MODES)}, got {mode!r}")
     w = np.ascontiguousarray(world_to_index, np.float64).reshape(-1)
     if w.size != 12:
         raise ValueError(f"reformat_planes_record: world_to_index must hold 12 numbers, got {w.size}")
     p, q = planes.shape[0], table.shape[0]
-    if out is None:
-        out = torch.empty((p, q), dtype=torch.float64, device=dev)
-    if out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev or out.numel() != p * q:
-        raise ValueError(f"reformat_planes_record: out must be a contiguous float64 tensor of {p * q} elements on {dev}")
+    out = _out(out, "out", torch.float64, (p, q), dev, who)
     n0, n1, n2 = volume.shape
     _lib.check(lib.afx_reformat_planes(_ptr(volume), int(volume.dtype == torch.float64), n0, n1, n2, w.ctypes.data_as(C.POINTER(C.c_double)),
                                        _ptr(planes) if p else None, p, _ptr(table) if q else None, q, int(half_slab), REFORMAT_MODES[mode],
@@ -2411,24 +2375,20 @@ def frangi_3d_record(x: torch.Tensor, sigmas=(1, 2, 3), alpha: float = 0.5, beta
     be captured in a graph.  gamma None: per scale sqrt(max S) / 2.  want_scale False (and no scale_index buffer): no index is written."""
     lib = _lib.load()
     _volume_on_gpu(x, "the volume", "frangi_3d")
-    if x.dtype not in (torch.float32, torch.float64) or not x.is_contiguous():
-        raise ValueError(f"frangi_3d_record: the volume must be a contiguous float32 or float64 tensor, got {x.dtype}, contiguous = {x.is_contiguous()}")
+    dev, who = x.device, "frangi_3d_record"
+    _buffer(x, "the volume", (torch.float32, torch.float64), x.shape, dev, who)
     if gamma is not None and not float(gamma) > 0.0:
         raise ValueError(f"frangi_3d: gamma must be None (per-scale) or > 0, got {gamma!r}")
-    dev = x.device
     n0, n1, n2 = x.shape
     sg, ns = _sigma_array(sigmas)
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    nbytes = int(lib.afx_frangi_3d_workspace_bytes(n0, n1, n2, ns))
-    if out is None:
-        out = torch.empty(x.shape if nbytes else (1,), dtype=torch.float64, device=dev)
-    if scale_index is None and want_scale:
-        scale_index = torch.empty(x.shape if nbytes else (1,), dtype=torch.uint8, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    nbytes = int(lib.afx_frangi_3d_workspace_bytes(n0, n1, n2, ns))      # (0: a shape the library refuses)
+    out = _out(out, "out", torch.float64, x.shape, dev, who, ok=nbytes > 0)
+    if scale_index is not None or want_scale:
+        scale_index = _out(scale_index, "scale_index", torch.uint8, x.shape, dev, who, ok=nbytes > 0)
+    workspace, nbytes = _scratch(workspace, nbytes, dev, who)
     _lib.check(lib.afx_frangi_3d(_ptr(x), int(x.dtype == torch.float64), n0, n1, n2, sg, ns, float(alpha), float(beta),
                                  0.0 if gamma is None else float(gamma), int(bool(black_ridges)), _ptr(out), _ptr(scale_index), _ptr(workspace),
-                                 workspace.numel(), None, Engine._stream(dev)), "afx_frangi_3d")
+                                 nbytes, None, Engine._stream(dev)), "afx_frangi_3d")
     return out, scale_index
 
 
@@ -2496,8 +2456,7 @@ def visual_hull_views(poses, masks: torch.Tensor, focal, margin_px: float = 1.0)
     empty = torch.nonzero(~on.reshape(v, -1).any(dim=1)).flatten().tolist()
     if empty:
         raise ValueError(f"visual_hull_views: the mask of view {empty[0]} is empty ({len(empty)} such view(s)): it would reject every point it sees")
-    if masks.device.type != "cuda":
-        raise AfxError("visual_hull_views: the masks must live on a GPU; there is no CPU path")
+    _on_gpu(masks, "the masks", "visual_hull_views")
     dist = distance_transform_edt((~on).to(torch.float64))
     return dict(records=torch.from_numpy(rec).to(masks.device), dist=dist, n_views=v, width=int(w), height=int(h), margin_px=float(margin_px))
 
@@ -2528,25 +2487,15 @@ def visual_hull_record(views: dict, shape, index_to_world, radius: float, seen=N
     device.  Nothing is read back and, with seen and rejects passed, nothing is allocated: the call can be captured in a graph."""
     import numpy as np
     lib = _lib.load()
-    rec, dist = views["records"], views["dist"]
-    dev = dist.device
-    if dev.type != "cuda":
-        raise AfxError("visual_hull_record: the views must live on a GPU; there is no CPU path")
+    rec, dist, who = views["records"], views["dist"], "visual_hull_record"
+    dev = _on_gpu(dist, "the views", who).device
     n0, n1, n2 = (int(s) for s in shape)
     v, w, h = int(views["n_views"]), int(views["width"]), int(views["height"])
-    if rec.dtype != torch.float64 or not rec.is_contiguous() or tuple(rec.shape) != (v, HULL_VIEW_DOUBLES) or rec.device != dev:
-        raise ValueError(f"visual_hull_record: records must be contiguous float64 [{v}, {HULL_VIEW_DOUBLES}] on {dev}")
-    if dist.dtype != torch.float64 or not dist.is_contiguous() or tuple(dist.shape) != (v, h, w):
-        raise ValueError(f"visual_hull_record: dist must be contiguous float64 [{v}, {h}, {w}]")
-    a = np.ascontiguousarray(_affine12(index_to_world, "visual_hull_record"))
-    n = max(n0, 0) * max(n1, 0) * max(n2, 0)
-    if seen is None:
-        seen = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev)
-    if rejects is None:
-        rejects = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev)
-    for t, name in ((seen, "seen"), (rejects, "rejects")):
-        if t.dtype != torch.uint16 or not t.is_contiguous() or t.device != dev or t.numel() != n:
-            raise ValueError(f"visual_hull_record: {name} must be a contiguous uint16 tensor of {n} elements on {dev}")
+    _buffer(rec, "records", torch.float64, (v, HULL_VIEW_DOUBLES), dev, who, exact_shape=True)
+    _buffer(dist, "dist", torch.float64, (v, h, w), dev, who, exact_shape=True)
+    a = np.ascontiguousarray(_affine12(index_to_world, who))
+    seen = _out(seen, "seen", torch.uint16, (n0, n1, n2), dev, who)
+    rejects = _out(rejects, "rejects", torch.uint16, (n0, n1, n2), dev, who)
     _lib.check(lib.afx_visual_hull(n0, n1, n2, a.ctypes.data_as(C.POINTER(C.c_double)), float(radius), _ptr(rec), v, w, h,
                                    float(views["margin_px"]), _ptr(dist), _ptr(seen), _ptr(rejects), Engine._stream(dev)), "afx_visual_hull")
     return seen, rejects
@@ -2575,8 +2524,8 @@ def grid_apply_mask(roi_aabb, resolution, mask_u8, occs, binary_u8, bits):
     n = g.resolution[0] * g.resolution[1] * g.resolution[2]
     for t, name, dtype, count in ((mask_u8, "mask", torch.uint8, n), (binary_u8, "binary", torch.uint8, n), (occs, "occs", torch.float32, n),
                                   (bits, "bits", torch.int32, (n + 31) // 32)):
-        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or t.numel() != count):
-            raise ValueError(f"grid_apply_mask: {name} must be a contiguous {dtype} tensor of {count} elements on {dev}")
+        if t is not None:
+            _buffer(t, name, dtype, count, dev, "grid_apply_mask")
     _lib.check(lib.afx_grid_apply_mask(C.byref(g), _ptr(mask_u8), _ptr(occs), _ptr(binary_u8), _ptr(bits), Engine._stream(dev)),
                "afx_grid_apply_mask")
 
@@ -2645,12 +2594,9 @@ def _view_map_inputs(segments, seg_branch, views, who: str):
     up = lambda x: x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
     segments, views = up(segments), up(views)
     n = seg_branch.numel()
-    if segments.dtype != torch.float64 or not segments.is_contiguous() or tuple(segments.shape) != (n, VIEWMAP_SEGMENT_DOUBLES) or segments.device != dev:
-        raise ValueError(f"{who}: segments must be contiguous float64 [{n}, {VIEWMAP_SEGMENT_DOUBLES}] on {dev}")
-    if seg_branch.dtype != torch.int32 or not seg_branch.is_contiguous() or seg_branch.dim() != 1 or seg_branch.device != dev:
-        raise ValueError(f"{who}: seg_branch must be contiguous int32 [N] on {dev}")
-    if views.dtype != torch.float64 or not views.is_contiguous() or views.dim() != 2 or views.shape[1] != HULL_VIEW_DOUBLES or views.device != dev:
-        raise ValueError(f"{who}: views must be contiguous float64 [V, {HULL_VIEW_DOUBLES}] on {dev}")
+    _buffer(segments, "segments", torch.float64, (n, VIEWMAP_SEGMENT_DOUBLES), dev, who, exact_shape=True)
+    _buffer(seg_branch, "seg_branch", torch.int32, (n,), dev, who, exact_shape=True)
+    _buffer(views, "views", torch.float64, views.shape[:1] + (HULL_VIEW_DOUBLES,), dev, who, exact_shape=True)
     return segments, seg_branch, views
 
 
@@ -2673,21 +2619,15 @@ def view_map_record(segments, seg_branch, views, width: int, height: int, brute:
     n, v, b, w, h = seg_branch.numel(), views.shape[0], int(n_branches), int(width), int(height)
     if not (counts or foreshortening):
         raise ValueError("view_map_record: counts and foreshortening are both off: nothing to compute")
-    ok = 1 <= b <= 65535 and 1 <= v <= 65535 and 1 <= w <= 16384 and 1 <= h <= 16384      # else one-element buffers: the library names the offender
+    ok = 1 <= b <= 65535 and 1 <= v <= 65535 and 1 <= w <= 16384 and 1 <= h <= 16384      # (else the library names the offender)
     want = {}
     if counts:
         want.update(count=((v, h, w), torch.uint16), area=((v, b), torch.int32), shared=((v, b), torch.int32),
                     tree=((v, VIEWMAP_TREE_SLOTS), torch.int32))
     if foreshortening:
         want.update(proj=((v, b), torch.float64), length=((b,), torch.float64))
-    res = {}
-    for name, (shape, dtype) in want.items():
-        t = None if out is None else out.get(name)
-        if t is None:
-            t = torch.empty(shape if ok else (1,), dtype=dtype, device=dev)
-        elif t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
-            raise ValueError(f"view_map_record: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
-        res[name] = t
+    res = {name: _out(None if out is None else out.get(name), name, dtype, shape, dev, "view_map_record", ok=ok, exact_shape=True)
+           for name, (shape, dtype) in want.items()}
     _lib.check(lib.afx_view_map(_ptr(segments), _ptr(seg_branch), n, b, _ptr(views), v, w, h, VIEWMAP_BRUTE if brute else 0, _ptr(res.get("count")),
                                 _ptr(res.get("area")), _ptr(res.get("shared")), _ptr(res.get("tree")), _ptr(res.get("proj")), _ptr(res.get("length")),
                                 Engine._stream(dev)), "afx_view_map")
@@ -2836,26 +2776,11 @@ def _pose_f64(x, shape, name, dev, who):
     if x is None:
         return None
     t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64)))
-    if t.device != dev:
-        t = t.to(dev)
-    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must be contiguous float64 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    return t
-
-
-def _pose_out(t, shape, dtype, name, dev, who):
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
-    return t
+    return _buffer(t.to(dev), name, torch.float64, shape, dev, who, exact_shape=True)
 
 
 def _pose_device(views: dict, who: str):
-    dev = views["field"].device
-    if dev.type != "cuda":
-        raise AfxError(f"{who}: the views must live on a GPU; there is no CPU path")
-    return dev
+    return _on_gpu(views["field"], "the views", who).device
 
 
 def pose_compose(records, xi, outer: bool = False, out=None) -> torch.Tensor:
@@ -2863,14 +2788,12 @@ def pose_compose(records, xi, outer: bool = False, out=None) -> torch.Tensor:
     rotation, q' = C(a) q + t) -> [R, 16] with xi [R, 6], or with outer=True and xi [M, 6] every pair, [R, M, 16].  Device tensors in,
     a device tensor out; nothing is read back."""
     lib = _lib.load()
-    if not isinstance(records, torch.Tensor) or records.device.type != "cuda":
-        raise AfxError("pose_compose: the records must be a tensor on a GPU; there is no CPU path")
-    dev = records.device
+    dev = _on_gpu(records, "the records", "pose_compose").device
     r = records.shape[0]
     records = _pose_f64(records, (r, HULL_VIEW_DOUBLES), "records", dev, "pose_compose")
     m = int(xi.shape[0]) if outer else r
     xi = _pose_f64(xi, (m, 6), "xi", dev, "pose_compose")
-    out = _pose_out(out, (r, m, HULL_VIEW_DOUBLES) if outer else (r, HULL_VIEW_DOUBLES), torch.float64, "out", dev, "pose_compose")
+    out = _out(out, "out", torch.float64, (r, m, HULL_VIEW_DOUBLES) if outer else (r, HULL_VIEW_DOUBLES), dev, "pose_compose", exact_shape=True)
     _lib.check(lib.afx_pose_compose(_ptr(records), r, _ptr(xi), m if outer else 0, _ptr(out), Engine._stream(dev)), "afx_pose_compose")
     return out
 
@@ -2896,12 +2819,10 @@ def pose_chamfer_record(views: dict, points, radius, weight, records, rec_view, 
     radius = _pose_f64(radius, (n,), "radius", dev, "pose_chamfer_record")
     weight = _pose_f64(weight, (n,), "weight", dev, "pose_chamfer_record")
     records = _pose_f64(records, (k, HULL_VIEW_DOUBLES), "records", dev, "pose_chamfer_record")
-    if not isinstance(rec_view, torch.Tensor) or rec_view.dtype != torch.int32 or not rec_view.is_contiguous() or rec_view.device != dev or \
-            tuple(rec_view.shape) != (k,):
-        raise ValueError(f"pose_chamfer_record: rec_view must be contiguous int32 [{k}] on {dev}")
+    _buffer(rec_view, "rec_view", torch.int32, (k,), dev, "pose_chamfer_record", exact_shape=True)
     ok = k >= 1 and s >= 1
-    sums = _pose_out(sums, (k, s, POSE_SUM_DOUBLES) if ok else (1,), torch.float64, "sums", dev, "pose_chamfer_record")
-    counts = _pose_out(counts, (k, s, 4) if ok else (1,), torch.int32, "counts", dev, "pose_chamfer_record")
+    sums = _out(sums, "sums", torch.float64, (k, s, POSE_SUM_DOUBLES), dev, "pose_chamfer_record", ok=ok, exact_shape=True)
+    counts = _out(counts, "counts", torch.int32, (k, s, 4), dev, "pose_chamfer_record", ok=ok, exact_shape=True)
     _lib.check(lib.afx_pose_chamfer(_ptr(field), v, w, h, _ptr(points), _ptr(radius), _ptr(weight), n, _ptr(records), _ptr(rec_view), k,
                                     float(trunc), s, POSE_COST_ONLY if cost_only else 0, _ptr(sums), _ptr(counts), Engine._stream(dev)),
                "afx_pose_chamfer")
@@ -3081,16 +3002,6 @@ def centreline_register_poses(graph: dict, views: dict, index_to_world=None, rad
 
 LABEL_OVERLAP_MAX_LABELS = 4095       # AFX_LABEL_OVERLAP_MAX_LABELS
 EDT3D_NONE = 0xffffffff               # AFX_EDT3D_NONE
-EDT3D_MAX_SIDE = 1024                 # AFX_EDT3D_MAX_SIDE
-
-
-def _territory_tensor(t, shape, dtype, name, dev, who):
-    """A caller's buffer of the territory entry points: contiguous, of that dtype and shape, on that GPU."""
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-        raise AfxError(f"{who}: {name} must be a tensor on a GPU; there is no CPU path")
-    if t.dtype != dtype or not t.is_contiguous() or t.device != dev or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}, got {t.dtype} {tuple(t.shape)}")
-    return t
 
 
 def feature_transform_record(sites: torch.Tensor, d2=None, nearest=None):
@@ -3100,16 +3011,13 @@ def feature_transform_record(sites: torch.Tensor, d2=None, nearest=None):
     back: the call can be captured in a graph.  There is no workspace: the two outputs are the passes' own storage."""
     lib = _lib.load()
     _volume_on_gpu(sites, "the sites", "feature_transform_3d")
-    if sites.dtype != torch.uint8 or not sites.is_contiguous():
-        raise ValueError(f"feature_transform_record: the sites must be a contiguous uint8 tensor, got {sites.dtype}, contiguous = {sites.is_contiguous()}")
-    dev = sites.device
+    dev, who = sites.device, "feature_transform_record"
+    _buffer(sites, "the sites", torch.uint8, sites.shape, dev, who)
     n0, n1, n2 = sites.shape
-    # a shape the library refuses gets one-element buffers: the call reports the limits instead of the allocator failing first
-    ok = all(1 <= s <= EDT3D_MAX_SIDE for s in sites.shape)
-    shape = tuple(sites.shape) if ok else (1,)
-    d2 = torch.empty(shape, dtype=torch.int32, device=dev) if d2 is None else _territory_tensor(d2, shape, torch.int32, "d2", dev, "feature_transform_record")
-    nearest = torch.empty(shape, dtype=torch.int32, device=dev) if nearest is None else \
-        _territory_tensor(nearest, shape, torch.int32, "nearest", dev, "feature_transform_record")
+    ok = _volume_side_ok(sites.shape)
+    d2 = _out(d2 if d2 is None else _on_gpu(d2, "d2", who), "d2", torch.int32, sites.shape, dev, who, ok=ok, exact_shape=True)
+    nearest = _out(nearest if nearest is None else _on_gpu(nearest, "nearest", who), "nearest", torch.int32, sites.shape, dev, who, ok=ok,
+                   exact_shape=True)
     _lib.check(lib.afx_feature_transform_3d(_ptr(sites), n0, n1, n2, _ptr(d2), _ptr(nearest), Engine._stream(dev)), "afx_feature_transform_3d")
     return d2, nearest
 
@@ -3133,19 +3041,16 @@ def label_overlap_record(labels: torch.Tensor, a: torch.Tensor, n_labels: int, b
     call zeroes counts itself.  With counts passed nothing is allocated or read back: the call can be captured in a graph."""
     lib = _lib.load()
     who = "label_overlap_record"
-    if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
-        raise AfxError("label_overlap_3d: the labels must be a tensor on a GPU; there is no CPU path")
-    dev, shape, n = labels.device, tuple(labels.shape), labels.numel()
-    labels = _territory_tensor(labels, shape, torch.int32, "labels", dev, who)
-    a = _territory_tensor(a, shape, torch.uint8, "a", dev, who)
-    b = None if b is None else _territory_tensor(b, shape, torch.uint8, "b", dev, who)
-    index = None if index is None else _territory_tensor(index, shape, torch.int32, "index", dev, who)
-    d2 = None if d2 is None else _territory_tensor(d2, shape, torch.int32, "d2", dev, who)
-    territory = None if territory is None else _territory_tensor(territory, shape, torch.int32, "territory", dev, who)
+    dev, shape, n = _on_gpu(labels, "the labels", "label_overlap_3d").device, tuple(labels.shape), labels.numel()
+    for t, name, dtype in ((labels, "labels", torch.int32), (a, "a", torch.uint8), (b, "b", torch.uint8), (index, "index", torch.int32),
+                           (d2, "d2", torch.int32), (territory, "territory", torch.int32)):
+        if t is not None or name == "a":                  # (a is required: None is refused like any other non-tensor)
+            _buffer(_on_gpu(t, name, who), name, dtype, shape, dev, who, exact_shape=True)
     if not 0 <= int(max_d2) <= EDT3D_NONE:
         raise ValueError(f"{who}: max_d2 = {max_d2} must lie in 0..0xffffffff")
-    rows = int(n_labels) + 1 if 0 <= int(n_labels) <= LABEL_OVERLAP_MAX_LABELS else 1      # a refused n_labels: the call reports the limits
-    counts = torch.empty((rows, 4), dtype=torch.int64, device=dev) if counts is None else _territory_tensor(counts, (rows, 4), torch.int64, "counts", dev, who)
+    if counts is not None:
+        _on_gpu(counts, "counts", who)
+    counts = _out(counts, "counts", torch.int64, (int(n_labels) + 1, 4), dev, who, ok=0 <= int(n_labels) <= LABEL_OVERLAP_MAX_LABELS, exact_shape=True)
     _lib.check(lib.afx_label_overlap_3d(_ptr(labels), _ptr(index), _ptr(d2), int(max_d2), _ptr(a), _ptr(b), n, int(n_labels), _ptr(counts),
                                         _ptr(territory), Engine._stream(dev)), "afx_label_overlap_3d")
     return counts, territory
@@ -3165,8 +3070,7 @@ def label_overlap_3d(labels: torch.Tensor, a: torch.Tensor, b=None, index=None, 
     = in; b may be None); index: integer tensor of the same shape (e.g. `feature_transform_3d`'s nearest; None: every voxel speaks for
     itself); d2 with max_d2: voxels whose d2 lies above max_d2 go to row 0 (both or neither).  n_labels=None: max(labels), read back.
     counts[l] = (voxels, voxels of a, of b, of both) with label l; row 0 collects what belongs to no label."""
-    if not isinstance(labels, torch.Tensor) or labels.device.type != "cuda":
-        raise AfxError("label_overlap_3d: the labels must be a tensor on a GPU; there is no CPU path")
+    _on_gpu(labels, "the labels", "label_overlap_3d")
     if (d2 is None) != (max_d2 is None):
         raise ValueError("label_overlap_3d: d2 and max_d2 go together")
     shape, dev = tuple(labels.shape), labels.device
@@ -3251,19 +3155,9 @@ def xray_views(poses, focal, width: int, height: int, near: float, far: float, n
 
 def _xray_views_checked(views: dict, who: str):
     rec = views["records"]
-    dev = rec.device
-    if dev.type != "cuda":
-        raise AfxError(f"{who}: the views must live on a GPU; there is no CPU path")
-    v = int(views["n_views"])
-    if rec.dtype != torch.float64 or not rec.is_contiguous() or tuple(rec.shape) != (v, HULL_VIEW_DOUBLES):
-        raise ValueError(f"{who}: records must be contiguous float64 [{v}, {HULL_VIEW_DOUBLES}]")
+    dev, v = _on_gpu(rec, "the views", who).device, int(views["n_views"])
+    _buffer(rec, "records", torch.float64, (v, HULL_VIEW_DOUBLES), dev, who, exact_shape=True)
     return rec, dev, v, int(views["width"]), int(views["height"])
-
-
-def _xray_f64(t, name, count, dev, who):
-    if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != dev
-                          or t.numel() != count):
-        raise ValueError(f"{who}: {name} must be a contiguous float64 tensor of {count} elements on {dev}")
 
 
 def xray_project(volume: torch.Tensor, views: dict, index_to_world=None, target=None, weight=None, out=None) -> torch.Tensor:
@@ -3276,14 +3170,13 @@ def xray_project(volume: torch.Tensor, views: dict, index_to_world=None, target=
     rec, dev, v, w, h = _xray_views_checked(views, "xray_project")
     if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
         raise ValueError("xray_project: the volume must be a [n0, n1, n2] tensor")
-    _xray_f64(volume, "the volume", volume.numel(), dev, "xray_project")
+    _buffer(volume, "the volume", torch.float64, volume.shape, dev, "xray_project")
     if (target is None) != (weight is None):
         raise ValueError("xray_project: target and weight are given together or not at all")
     b = np.ascontiguousarray(lumen_world_to_index(_affine12(index_to_world, "xray_project")))
-    if out is None:
-        out = torch.empty((v, h, w), dtype=torch.float64, device=dev)
-    for t, name in ((target, "target"), (weight, "weight"), (out, "out")):
-        _xray_f64(t, name, v * h * w, dev, "xray_project")
+    if target is not None:
+        _buffer(target, "target", torch.float64, (v, h, w), dev, "xray_project"), _buffer(weight, "weight", torch.float64, (v, h, w), dev, "xray_project")
+    out = _out(out, "out", torch.float64, (v, h, w), dev, "xray_project")
     n0, n1, n2 = volume.shape
     _lib.check(lib.afx_xray_project(_ptr(volume), n0, n1, n2, b.ctypes.data_as(C.POINTER(C.c_double)), _ptr(rec), v, w, h, float(views["near"]),
                                     float(views["far"]), int(views["n_samples"]), _ptr(target), _ptr(weight), _ptr(out), Engine._stream(dev)),
@@ -3305,19 +3198,16 @@ def xray_backproject(images: torch.Tensor, views: dict, shape, index_to_world=No
     n = max(n0, 0) * max(n1, 0) * max(n2, 0)
     if images is None:
         raise ValueError("xray_backproject: images must be a float64 [V, H, W] tensor")
-    _xray_f64(images, "images", v * h * w, dev, "xray_backproject")
+    _buffer(images, "images", torch.float64, (v, h, w), dev, "xray_backproject")
     a = np.ascontiguousarray(_affine12(index_to_world, "xray_backproject"))
     if x_inout is None:
         if mask is not None:
             raise ValueError("xray_backproject: mask belongs to the fused update (x_inout)")
         acc = torch.empty((n0, n1, n2), dtype=torch.float64, device=dev) if acc is None else acc
         seen = torch.empty((n0, n1, n2), dtype=torch.uint16, device=dev) if seen is None else seen
-    _xray_f64(acc, "acc", n, dev, "xray_backproject")
-    _xray_f64(x_inout, "x_inout", n, dev, "xray_backproject")
-    if seen is not None and (seen.dtype != torch.uint16 or not seen.is_contiguous() or seen.device != dev or seen.numel() != n):
-        raise ValueError(f"xray_backproject: seen must be a contiguous uint16 tensor of {n} elements on {dev}")
-    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev or mask.numel() != n):
-        raise ValueError(f"xray_backproject: mask must be a contiguous uint8 tensor of {n} elements on {dev}")
+    for t, name, dtype in ((acc, "acc", torch.float64), (x_inout, "x_inout", torch.float64), (seen, "seen", torch.uint16), (mask, "mask", torch.uint8)):
+        if t is not None:
+            _buffer(t, name, dtype, n, dev, "xray_backproject")
     _lib.check(lib.afx_xray_backproject(_ptr(images), _ptr(rec), v, w, h, n0, n1, n2, a.ctypes.data_as(C.POINTER(C.c_double)), _ptr(acc),
                                         _ptr(seen), _ptr(x_inout), float(relax), int(bool(nonneg)), _ptr(mask), Engine._stream(dev)),
                "afx_xray_backproject")
@@ -3345,27 +3235,15 @@ def tv_denoise_3d(x: torch.Tensor, weight: float, iterations: int = 50, tau: flo
     lib = _lib.load()
     if not isinstance(x, torch.Tensor) or x.dim() != 3:
         raise ValueError("tv_denoise_3d: x must be a [n0, n1, n2] tensor")
-    dev = x.device
-    if dev.type != "cuda":
-        raise AfxError("tv_denoise_3d: the volume must live on a GPU; there is no CPU path")
-    n = x.numel()
-    _xray_f64(x, "x", n, dev, "tv_denoise_3d")
-    if out is None:
-        out = torch.empty_like(x)
-    _xray_f64(out, "out", n, dev, "tv_denoise_3d")
+    dev, who = _on_gpu(x, "the volume", "tv_denoise_3d").device, "tv_denoise_3d"
+    _buffer(x, "x", torch.float64, x.shape, dev, who)
+    out = _out(out, "out", torch.float64, x.shape, dev, who)
     if mask is not None:
-        if tuple(mask.shape) != tuple(x.shape):
-            raise ValueError(f"tv_denoise_3d: mask must have the shape {tuple(x.shape)}, got {tuple(mask.shape)}")
-        if mask.dtype == torch.bool and mask.is_contiguous() and mask.device == dev:
-            mask = mask.view(torch.uint8)                 # (the same bytes)
-        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev:
-            raise ValueError(f"tv_denoise_3d: mask must be a contiguous uint8 or bool tensor on {dev}")
+        mask = _buffer(mask, "mask", (torch.uint8, torch.bool), x.shape, dev, who, exact_shape=True).view(torch.uint8)      # (bool: the same bytes)
     n0, n1, n2 = x.shape
-    if workspace is None and int(iterations) > 0:
-        workspace = tv_denoise_3d_workspace(x.shape, dev)
-    if workspace is not None and (workspace.device != dev or not workspace.is_contiguous()):
-        raise ValueError(f"tv_denoise_3d: workspace must be a contiguous tensor on {dev}")
-    nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    nbytes = 0
+    if workspace is not None or int(iterations) > 0:
+        workspace, nbytes = _scratch(workspace, lib.afx_tv_denoise_3d_workspace_bytes(n0, n1, n2), dev, who)
     _lib.check(lib.afx_tv_denoise_3d(_ptr(x), n0, n1, n2, float(weight), float(tau), int(iterations), int(bool(nonneg)), _ptr(mask), _ptr(out),
                                      _ptr(workspace), nbytes, Engine._stream(dev)), "afx_tv_denoise_3d")
     return out
