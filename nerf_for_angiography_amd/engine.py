@@ -20,17 +20,8 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _f32(t: torch.Tensor, name: str, device) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name}: expected a tensor")
-    if t.device != device:
-        raise ValueError(f"{name}: on {t.device}, expected {device}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected float32")
-    return t if t.is_contiguous() else t.contiguous()
-
-
-# ---- the buffer vocabulary of the analysis wrappers (image weights .. TV, below): every check is made on the host, before the first launch ----
+# ---- the buffer vocabulary of every wrapper: each tensor whose pointer goes to the library passes _buffer, _out or _scratch on the host, before the
+# first launch - dtype, count and contiguity against the device of the wrapper's first tensor, then _on_gpu; nothing is converted but a strided input ----
 EDT3D_MAX_SIDE = 1024                 # AFX_EDT3D_MAX_SIDE
 
 
@@ -40,20 +31,21 @@ def _on_gpu(t, name: str, who: str):
     return t
 
 
-def _buffer(t, name: str, dtype, shape, dev, who: str, exact_shape: bool = False, at_least: bool = False):
+def _buffer(t, name: str, dtype, shape, dev, who: str, exact_shape: bool = False, at_least: bool = False, copy: bool = False):
     """A tensor the library reads or writes through its pointer: contiguous, of `dtype` (one, or a tuple of admitted ones), on `dev`, with
     prod(shape) elements (`shape` may be the count itself; None: any number; at_least: that many or more; exact_shape: of that very
-    shape) -> t.  ValueError otherwise, in one wording."""
+    shape) -> t.  copy: an input the library only reads may be strided (a column-major ray table, a [:, None] view) and comes back as a
+    contiguous copy.  ValueError otherwise, in one wording."""
     dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
     shape = shape if shape is None or isinstance(shape, (tuple, torch.Size)) else (int(shape),)
-    if isinstance(t, torch.Tensor) and t.dtype in dtypes and t.device == dev and t.is_contiguous():
+    if isinstance(t, torch.Tensor) and t.dtype in dtypes and t.device == dev and (copy or t.is_contiguous()):
         if shape is None or (tuple(t.shape) == tuple(shape) if exact_shape else
                              t.numel() >= math.prod(shape) if at_least else t.numel() == math.prod(shape)):
-            return t
+            return t.contiguous() if copy else t
     size = "" if shape is None else f" of shape {tuple(shape)}" if exact_shape else \
         f" of {'at least ' if at_least else ''}{math.prod(shape)} elements {tuple(shape)}"
     got = f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous = {t.is_contiguous()}" if isinstance(t, torch.Tensor) else type(t).__name__
-    raise ValueError(f"{who}: {name} must be a contiguous {' or '.join(str(d) for d in dtypes)} tensor{size} on {dev}, got {got}")
+    raise ValueError(f"{who}: {name} must be a {'' if copy else 'contiguous '}{' or '.join(str(d) for d in dtypes)} tensor{size} on {dev}, got {got}")
 
 
 def _out(t, name: str, dtype, shape, dev, who: str, ok: bool = True, exact_shape: bool = False, at_least: bool = False):
@@ -145,7 +137,8 @@ class Engine:
         h = C.c_void_p()
         self._check(self.lib.afx_create(C.byref(self.desc), C.byref(h)), "afx_create")
         self.h = h
-        self.width, self.n_hidden, self.enc = width, n_hidden, enc
+        self.width, self.n_hidden, self.enc, self.n_freq = width, n_hidden, enc, int(n_freq)
+        self._prepared_bytes = {}      # prec -> the size of its prepared buffer
         self.param_count = int(self.lib.afx_query(h, _lib.Q_PARAM_COUNT, 0, 0, 0))
         self.k0 = int(self.lib.afx_query(h, _lib.Q_K0, 0, 0, 0))
         self.max_workspace_bytes = int(max_workspace_bytes)
@@ -216,13 +209,22 @@ class Engine:
         return self._ws
 
     # ---- weights -----------------------------------------------------------------------------
+    def _model(self, who: str, prepared, prec: str, grad_flat=None):
+        """-> prepared's device.  `prepared` holds at least the bytes prepare() allocates at `prec` (asked of the library once per
+        precision), `grad_flat` (None: not given) is float32 [param_count] on that device: the kernels add param_count floats to it."""
+        if prec not in self._prepared_bytes:
+            self._prepared_bytes[prec] = int(self.lib.afx_query(self.h, _lib.Q_PREPARED_BYTES, _lib.PREC[prec], 0, 0))
+        dev = prepared.device
+        _buffer(prepared, "prepared", torch.uint8, self._prepared_bytes[prec], dev, who, at_least=True)
+        if grad_flat is not None:
+            _buffer(grad_flat, "grad_flat", torch.float32, self.param_count, dev, who)
+        return dev
+
     def prepare(self, flat: torch.Tensor, enc_aux: Optional[torch.Tensor], prec: str, key=None):
         """Re-tile the flat parameters for `prec` unless `key` says the cached copy is current."""
-        if not flat.is_cuda:
-            raise AfxError("the fused MI355X path needs parameters on a GPU; there is no CPU fallback")
-        flat = _f32(flat, "flat parameters", flat.device)
-        if flat.numel() != self.param_count:
-            raise ValueError(f"flat parameters: {flat.numel()} floats, expected {self.param_count}")
+        dev = flat.device
+        flat = _buffer(flat, "flat parameters", torch.float32, self.param_count, dev, "prepare", copy=True)
+        _on_gpu(flat, "flat parameters", "prepare")
         p = _lib.PREC[prec]
         cached = self._prepared.get(prec)
         if cached is not None and key is not None and cached[1] == key and cached[0].device == flat.device:
@@ -231,7 +233,7 @@ class Engine:
         buf = cached[0] if cached is not None and cached[0].device == flat.device else torch.empty(
             nbytes, dtype=torch.uint8, device=flat.device)
         if enc_aux is not None:
-            enc_aux = _f32(enc_aux, "enc_aux", flat.device)
+            enc_aux = _buffer(enc_aux, "enc_aux", torch.float32, None, dev, "prepare", copy=True)
         self._check(self.lib.afx_prepare_weights(self.h, p, _ptr(flat), _ptr(enc_aux), _ptr(buf), nbytes,
                                                 self._stream(flat.device)), "afx_prepare_weights")
         self._prepared[prec] = (buf, key)
@@ -239,10 +241,11 @@ class Engine:
 
     # ---- MLP on explicit points --------------------------------------------------------------
     def infer(self, prepared: torch.Tensor, pts: torch.Tensor, prec: str, apply_sigmoid: bool = False):
-        dev = prepared.device
-        pts = _f32(pts, "points", dev)
+        dev = self._model("infer", prepared, prec)
+        pts = _buffer(pts, "points", torch.float32, None, dev, "infer", copy=True)
         if pts.dim() != 2 or pts.shape[1] != 3:
             raise ValueError(f"points: shape {tuple(pts.shape)}, expected [P,3]")
+        _on_gpu(prepared, "prepared", "infer")
         out = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
         self._check(self.lib.afx_mlp_infer(self.h, _lib.PREC[prec], _ptr(prepared), _ptr(pts), pts.shape[0], _ptr(out),
                                           int(apply_sigmoid), self._stream(dev)), "afx_mlp_infer")
@@ -255,6 +258,10 @@ class Engine:
         if d_aux is None:
             yield
             return
+        _buffer(flat, "flat", torch.float32, self.param_count, flat.device, "encoding_grad")
+        # (only the fourier encoding has coefficients, 3 n_freq of them; which encodings train is the library's to say)
+        _buffer(d_aux, "d_aux", torch.float32, 3 * self.n_freq if self.enc == "fourier" else None, flat.device, "encoding_grad")
+        _on_gpu(flat, "flat", "encoding_grad")
         self._check(self.lib.afx_set_encoding_grad(self.h, _ptr(flat), _ptr(d_aux)), "afx_set_encoding_grad")
         try:
             yield
@@ -262,12 +269,11 @@ class Engine:
             self.lib.afx_set_encoding_grad(self.h, None, None)
 
     def mlp_backward(self, prepared, pts, d_out, grad_flat, prec: str):
-        dev = prepared.device
-        pts = _f32(pts, "points", dev)
-        d_out = _f32(d_out, "d_out", dev)
+        dev = self._model("mlp_backward", prepared, prec, grad_flat)
+        pts = _buffer(pts, "points", torch.float32, None, dev, "mlp_backward", copy=True)
         n = pts.shape[0]
-        if d_out.numel() != n:
-            raise ValueError("d_out: one value per point expected")
+        d_out = _buffer(d_out, "d_out", torch.float32, n, dev, "mlp_backward", copy=True)
+        _on_gpu(prepared, "prepared", "mlp_backward")
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_WORKSPACE_FULL, 0, n, _lib.PREC[prec]))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         self._check(self.lib.afx_mlp_backward(self.h, _lib.PREC[prec], _ptr(prepared), _ptr(pts), n, _ptr(d_out),
@@ -276,14 +282,12 @@ class Engine:
 
     def mlp_backward_inputs(self, prepared, pts, d_out, grad_flat, d_pts, prec: str):
         """afx_mlp_backward_inputs: d_pts [P,3] = dL/dpts (written); grad_flat += dL/dparams unless it is None."""
-        dev = prepared.device
-        pts = _f32(pts, "points", dev)
-        d_out = _f32(d_out, "d_out", dev)
+        dev = self._model("mlp_backward_inputs", prepared, prec, grad_flat)
+        pts = _buffer(pts, "points", torch.float32, None, dev, "mlp_backward_inputs", copy=True)
         n = pts.shape[0]
-        if d_out.numel() != n:
-            raise ValueError("d_out: one value per point expected")
-        if tuple(d_pts.shape) != (n, 3) or d_pts.dtype != torch.float32 or not d_pts.is_contiguous():
-            raise ValueError("d_pts: expected a contiguous float32 [P,3] tensor")
+        d_out = _buffer(d_out, "d_out", torch.float32, n, dev, "mlp_backward_inputs", copy=True)
+        _buffer(d_pts, "d_pts", torch.float32, (n, 3), dev, "mlp_backward_inputs", exact_shape=True)
+        _on_gpu(prepared, "prepared", "mlp_backward_inputs")
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_INPUTS_WORKSPACE_FULL, 0, n, _lib.PREC[prec]))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         self._check(self.lib.afx_mlp_backward_inputs(self.h, _lib.PREC[prec], _ptr(prepared), _ptr(pts), n, _ptr(d_out), _ptr(grad_flat),
@@ -295,30 +299,23 @@ class Engine:
         keep = []
         a.n_rays, a.n_samples = int(spec.n_rays), int(spec.n_samples)
         if spec.poses is not None:
-            poses = spec.poses
-            if poses.device != dev or poses.dtype != torch.float64:
-                raise ValueError("poses: expected a float64 tensor on the model's device")
-            poses = poses.contiguous().reshape(-1, 12)
+            poses = _buffer(spec.poses, "poses", torch.float64, None, dev, "render", copy=True).reshape(-1, 12)
             keep.append(poses)
             a.ray_mode, a.poses = _lib.RAYS_POSE, poses.data_ptr()
             if spec.ray_ids is not None:
-                ids = spec.ray_ids
-                if ids.device != dev or ids.dtype != torch.int32 or ids.numel() != spec.n_rays:
-                    raise ValueError("ray_ids: expected int32 [n_rays] on the model's device")
-                ids = ids.contiguous()
+                ids = _buffer(spec.ray_ids, "ray_ids", torch.int32, spec.n_rays, dev, "render", copy=True)
                 keep.append(ids)
                 a.ray_ids = ids.data_ptr()
             a.ray_id0, a.width, a.height, a.focal = int(spec.ray_id0), int(spec.width), int(spec.height), float(spec.focal)
         else:
-            o, d = _f32(spec.origins, "origins", dev), _f32(spec.dirs, "dirs", dev)
-            if tuple(o.shape) != (spec.n_rays, 3) or tuple(d.shape) != (spec.n_rays, 3):
-                raise ValueError("origins/dirs: expected [n_rays,3]")
+            o = _buffer(spec.origins, "origins", torch.float32, (spec.n_rays, 3), dev, "render", exact_shape=True, copy=True)
+            d = _buffer(spec.dirs, "dirs", torch.float32, (spec.n_rays, 3), dev, "render", exact_shape=True, copy=True)
             keep += [o, d]
             a.ray_mode, a.origins, a.dirs = _lib.RAYS_ARRAYS, o.data_ptr(), d.data_ptr()
         if spec.mode == "acc":
             a.depth_mode, a.t_near, a.t_far = _lib.DEPTH_UNIFORM_MID, float(spec.t_near), float(spec.t_far)
         elif spec.mode == "dense":
-            z = _f32(spec.z, "z", dev)
+            z = _buffer(spec.z, "z", torch.float32, None, dev, "render", copy=True)
             if z.dim() == 1 and z.shape[0] == spec.n_samples:
                 a.depth_mode = _lib.DEPTH_SHARED_Z
             elif tuple(z.shape) == (spec.n_rays, spec.n_samples):
@@ -340,11 +337,12 @@ class Engine:
         return a, keep
 
     def render_forward(self, prepared, spec: RenderSpec, prec: str, want_sigma=False, want_tau=False):
-        dev = prepared.device
+        dev = self._model("render_forward", prepared, prec)
         pixel = torch.empty(spec.n_rays, dtype=torch.float32, device=dev)
         sigma = torch.empty(spec.n_rays, spec.n_samples, dtype=torch.float32, device=dev) if want_sigma else None
         tau = torch.empty(spec.n_rays, spec.n_samples, dtype=torch.float32, device=dev) if want_tau else None
         a, keep = self._render_args(spec, dev, pixel, sigma, tau)
+        _on_gpu(prepared, "prepared", "render_forward")
         ws = self._workspace(int(self.lib.afx_query(self.h, _lib.Q_FWD_WORKSPACE, spec.n_rays, spec.n_samples, 0)), dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
         self._check(self.lib.afx_render_forward(self.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), self._stream(dev)),
@@ -353,10 +351,11 @@ class Engine:
         return pixel, sigma, tau
 
     def render_backward(self, prepared, spec: RenderSpec, pixel, d_pixel, grad_flat, prec: str):
-        dev = prepared.device
-        pixel = _f32(pixel, "pixel", dev)
-        d_pixel = _f32(d_pixel, "d_pixel", dev)
+        dev = self._model("render_backward", prepared, prec, grad_flat)
+        pixel = _buffer(pixel, "pixel", torch.float32, spec.n_rays, dev, "render_backward", copy=True)
+        d_pixel = _buffer(d_pixel, "d_pixel", torch.float32, spec.n_rays, dev, "render_backward", copy=True)
         a, keep = self._render_args(spec, dev, pixel)
+        _on_gpu(prepared, "prepared", "render_backward")
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_WORKSPACE_FULL, spec.n_rays, spec.n_samples, _lib.PREC[prec]))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -364,17 +363,18 @@ class Engine:
                                                 _ptr(grad_flat), self._stream(dev)), "afx_render_backward")
         del keep
 
-
     def render_backward_inputs(self, prepared, spec: RenderSpec, pixel, d_pixel, grad_flat, d_origins, d_dirs, prec: str):
         """afx_render_backward_inputs: d_origins / d_dirs [R,3] (either None) = dL/d(ray origins / directions), written;
         grad_flat += dL/dparams unless it is None."""
-        dev = prepared.device
-        pixel = _f32(pixel, "pixel", dev)
-        d_pixel = _f32(d_pixel, "d_pixel", dev)
+        who = "render_backward_inputs"
+        dev = self._model(who, prepared, prec, grad_flat)
+        pixel = _buffer(pixel, "pixel", torch.float32, spec.n_rays, dev, who, copy=True)
+        d_pixel = _buffer(d_pixel, "d_pixel", torch.float32, spec.n_rays, dev, who, copy=True)
         for t, name in ((d_origins, "d_origins"), (d_dirs, "d_dirs")):
-            if t is not None and (tuple(t.shape) != (spec.n_rays, 3) or t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError(f"{name}: expected a contiguous float32 [n_rays,3] tensor")
+            if t is not None:
+                _buffer(t, name, torch.float32, (spec.n_rays, 3), dev, who, exact_shape=True)
         a, keep = self._render_args(spec, dev, pixel)
+        _on_gpu(prepared, "prepared", who)
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_INPUTS_WORKSPACE_FULL, spec.n_rays, spec.n_samples, _lib.PREC[prec]))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -384,11 +384,16 @@ class Engine:
 
     def train_step_packed_mse(self, prepared, origins, dirs, packed: "PackedGroups", target, inv_n: float, grad_flat, prec: str):
         """afx_train_step_packed_mse: the reference's iteration body on the march's packed samples; returns the pixels [n_rays]."""
-        dev = prepared.device
-        o, d, target = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(target, "target", dev)
-        n_rays = packed.n_rays
-        if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3) or target.numel() != n_rays:
-            raise ValueError("train_step_packed_mse: origins/dirs [n_rays,3] and target [n_rays] expected")
+        who, n_rays, n_groups = "train_step_packed_mse", packed.n_rays, packed.n_groups
+        dev = self._model(who, prepared, prec, grad_flat)
+        o = _buffer(origins, "origins", torch.float32, (n_rays, 3), dev, who, exact_shape=True, copy=True)
+        d = _buffer(dirs, "dirs", torch.float32, (n_rays, 3), dev, who, exact_shape=True, copy=True)
+        target = _buffer(target, "target", torch.float32, n_rays, dev, who, copy=True)
+        _buffer(packed.group_offsets, "group_offsets", torch.int64, n_rays + 1, dev, who)
+        _buffer(packed.group_ray, "group_ray", torch.int32, n_groups, dev, who)
+        _buffer(packed.ts_pad, "ts_pad", torch.float32, 32 * n_groups, dev, who)
+        _buffer(packed.te_pad, "te_pad", torch.float32, 32 * n_groups, dev, who)
+        _on_gpu(prepared, "prepared", who)
         pixel = torch.empty(n_rays, dtype=torch.float32, device=dev)
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_WORKSPACE_FULL, 0, max(packed.n_groups, 1) * 32, _lib.PREC[prec]))
         full += 4 * (n_rays + packed.n_groups) + 1024
@@ -406,14 +411,16 @@ class Engine:
                              step: float, early_stop_eps: float, alpha_thre: float, grid_bits=None, grid_aabb=None, grid_res=None):
         """afx_march_train_step_mse: the reference's grid iteration (march, alpha pass, visibility, packed training step) in one call.
         Returns (pixels [n_rays], n_candidates, n_kept); n_kept == 0: nothing survived, pixels / grad_flat untouched."""
-        dev = prepared.device
-        o, d, target = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(target, "target", dev)
+        who = "march_train_step_mse"
+        dev = self._model(who, prepared, prec, grad_flat)
+        o, d, target = (_buffer(t, name, torch.float32, None, dev, who, copy=True) for t, name in ((origins, "origins"), (dirs, "dirs"), (target, "target")))
         n_rays = o.shape[0]
         if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3) or target.numel() != n_rays:
             raise ValueError("march_train_step_mse: origins/dirs [n_rays,3] and target [n_rays] expected")
         pixel = torch.empty(n_rays, dtype=torch.float32, device=dev)
         a = _lib.MarchTrainArgs()
-        _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+        _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res, dev, who)
+        _on_gpu(prepared, "prepared", who)
         a.early_stop_eps, a.alpha_thre, a.inv_n = float(early_stop_eps), float(alpha_thre), float(inv_n)
         a.target, a.pixel, a.grad_flat = target.data_ptr(), pixel.data_ptr(), grad_flat.data_ptr()
         need = max(64 << 20, self._ws.numel() if self._ws is not None and self._ws.device == dev else 0)
@@ -471,21 +478,19 @@ class Engine:
     def _march_step_device_sizes(self, fn: str, ws_fn: str, prepared, origins, dirs, target, inv_n, grad_flat, prec, scene_aabb, near_plane,
                                  far_plane, step, early_stop_eps, alpha_thre, grid_bits, grid_aabb, grid_res, pixel, counts, skip):
         who = fn[4:]
-        dev = prepared.device
-        o, d, target = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(target, "target", dev)
+        dev = self._model(who, prepared, prec, grad_flat)
+        o, d, target = (_buffer(t, name, torch.float32, None, dev, who, copy=True) for t, name in ((origins, "origins"), (dirs, "dirs"), (target, "target")))
         n_rays = o.shape[0]
         if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3) or target.numel() != n_rays:
             raise ValueError(f"{who}: origins/dirs [n_rays,3] and target [n_rays] expected")
         if far_plane is None:
             raise ValueError(f"{who}: the workspace bound needs a far plane")
-        pixel = torch.empty(n_rays, dtype=torch.float32, device=dev) if pixel is None else pixel
-        counts = torch.empty(3, dtype=torch.int64, device=dev) if counts is None else counts
-        skip = torch.empty(1, dtype=torch.float32, device=dev) if skip is None else skip
-        for t, dt, n, name in ((pixel, torch.float32, n_rays, "pixel"), (counts, torch.int64, 3, "counts"), (skip, torch.float32, 1, "skip")):
-            if t.device != dev or t.dtype != dt or t.numel() != n or not t.is_contiguous():
-                raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+        pixel = _out(pixel, "pixel", torch.float32, n_rays, dev, who)
+        counts = _out(counts, "counts", torch.int64, 3, dev, who)
+        skip = _out(skip, "skip", torch.float32, 1, dev, who)
         a = _lib.MarchTrainArgs()
-        _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+        _fill_march_args(a.march, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res, dev, who)
+        _on_gpu(prepared, "prepared", who)
         a.early_stop_eps, a.alpha_thre, a.inv_n = float(early_stop_eps), float(alpha_thre), float(inv_n)
         a.target, a.pixel, a.grad_flat = target.data_ptr(), pixel.data_ptr(), grad_flat.data_ptr()
         max_steps = int(self.lib.afx_march_max_steps(C.byref(a.march)))
@@ -511,16 +516,15 @@ class Engine:
         (every step of every ray a candidate) fits max_workspace_bytes and afx_mlp_infer's 2^31 - 256 points; each ray's result depends on
         that ray alone, so the split changes nothing.  One host read-back per call.
         Returns (pixel [R], binary_pixel [R] or None, kept_counts int32 [R], n_candidates)."""
-        dev = prepared.device
+        dev = self._model("march_render", prepared, prec)
         pose = poses is not None
         if pose:
-            if poses.device != dev or poses.dtype != torch.float64:
-                raise ValueError(f"march_render: poses must be float64 on {dev}")
-            poses = poses[:, :3, :].contiguous()
+            poses = _buffer(poses[:, :3, :], "poses", torch.float64, None, dev, "march_render", copy=True)
             n_rays = ray_window("march_render", poses.shape[0], width, height, ray_id0, n_rays)
             o = d = None
         else:
-            o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
+            o = _buffer(origins, "origins", torch.float32, None, dev, "march_render", copy=True)
+            d = _buffer(dirs, "dirs", torch.float32, None, dev, "march_render", copy=True)
             n_rays = o.shape[0]
             if tuple(o.shape) != (n_rays, 3) or tuple(d.shape) != (n_rays, 3):
                 raise ValueError("march_render: origins/dirs [n_rays,3] expected")
@@ -528,7 +532,8 @@ class Engine:
         if far_plane is None:
             raise ValueError("march_render: the workspace bound needs a far plane")
         a = _lib.MarchRenderArgs()
-        _fill_march_args(a.march, None, None, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+        _fill_march_args(a.march, None, None, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res, dev, "march_render")
+        _on_gpu(prepared, "prepared", "march_render")
         mode = _lib.RAYS_POSE if pose else _lib.RAYS_ARRAYS
         a.ray_mode = mode
         if pose:
@@ -573,13 +578,14 @@ class Engine:
     def hier_train_step_mse(self, prepared, spec: RenderSpec, n_fine: int, u, target, inv_n: float, grad_flat, prec: str, want_z_all=True):
         """afx_hier_train_step_mse: hierarchical step with coarse re-use; `spec` carries the rays and the COARSE depths (mode 'dense').
         Returns (pixels [R], merged depths [R, S + n_fine] | None)."""
-        dev = prepared.device
-        target, u = _f32(target, "target", dev), _f32(u, "u", dev)
-        if target.numel() != spec.n_rays or tuple(u.shape) != (spec.n_rays, int(n_fine)):
-            raise ValueError("hier_train_step_mse: target [n_rays] and u [n_rays, n_fine] expected")
+        who = "hier_train_step_mse"
+        dev = self._model(who, prepared, prec, grad_flat)
+        target = _buffer(target, "target", torch.float32, spec.n_rays, dev, who, copy=True)
+        u = _buffer(u, "u", torch.float32, (spec.n_rays, int(n_fine)), dev, who, exact_shape=True, copy=True)
         pixel = torch.empty(spec.n_rays, dtype=torch.float32, device=dev)
         z_all = torch.empty(spec.n_rays, spec.n_samples + int(n_fine), dtype=torch.float32, device=dev) if want_z_all else None
         a, keep = self._render_args(spec, dev, pixel)
+        _on_gpu(prepared, "prepared", who)
         full = int(self.lib.afx_hier_workspace_bytes(self.h, spec.n_rays, spec.n_samples, int(n_fine)))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -598,12 +604,11 @@ class Engine:
 
     def train_step_mse(self, prepared, spec: RenderSpec, target, inv_n: float, grad_flat, prec: str):
         """Fused forward + MSE + backward (afx_train_step_mse); returns the rendered pixels."""
-        dev = prepared.device
-        target = _f32(target, "target", dev)
-        if target.numel() != spec.n_rays:
-            raise ValueError("target: one value per ray expected")
+        dev = self._model("train_step_mse", prepared, prec, grad_flat)
+        target = _buffer(target, "target", torch.float32, spec.n_rays, dev, "train_step_mse", copy=True)
         pixel = torch.empty(spec.n_rays, dtype=torch.float32, device=dev)
         a, keep = self._render_args(spec, dev, pixel)
+        _on_gpu(prepared, "prepared", "train_step_mse")
         full = int(self.lib.afx_query(self.h, _lib.Q_BWD_WORKSPACE_FULL, spec.n_rays, spec.n_samples, _lib.PREC[prec]))
         ws = self._workspace(min(full, self.max_workspace_bytes), dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -627,9 +632,12 @@ def pack_groups(offsets, t_starts, t_ends, n_groups=None, group_offsets=None) ->
     """offsets int64 [R+1] (exclusive scan of the per-ray sample counts), t_starts / t_ends [n] -> PackedGroups."""
     lib = _lib.load()
     dev = offsets.device
-    if dev.type != "cuda":
-        raise AfxError("pack_groups: the sample list must live on a GPU; there is no CPU fallback")
-    n_rays = offsets.numel() - 1
+    n_rays = _buffer(offsets, "offsets", torch.int64, None, dev, "pack_groups").numel() - 1
+    if group_offsets is not None:
+        _buffer(group_offsets, "group_offsets", torch.int64, n_rays + 1, dev, "pack_groups")
+    ts = _buffer(t_starts.reshape(-1), "t_starts", torch.float32, None, dev, "pack_groups", copy=True)
+    te = _buffer(t_ends.reshape(-1), "t_ends", torch.float32, ts.numel(), dev, "pack_groups", copy=True)
+    _on_gpu(offsets, "offsets", "pack_groups")
     if group_offsets is None:
         cnt = offsets[1:] - offsets[:-1]
         group_offsets = torch.zeros(n_rays + 1, dtype=torch.int64, device=dev)
@@ -640,7 +648,6 @@ def pack_groups(offsets, t_starts, t_ends, n_groups=None, group_offsets=None) ->
     te_pad = torch.empty(n_groups * 32, device=dev)
     group_ray = torch.empty(n_groups, dtype=torch.int32, device=dev)
     if n_groups:
-        ts, te = _f32(t_starts.reshape(-1), "t_starts", dev), _f32(t_ends.reshape(-1), "t_ends", dev)
         _lib.check(lib.afx_pack_groups(_ptr(offsets), _ptr(group_offsets), n_rays, _ptr(ts), _ptr(te), _ptr(ts_pad), _ptr(te_pad),
                                        _ptr(group_ray), Engine._stream(dev)), "afx_pack_groups")
     return PackedGroups(n_rays, n_groups, group_offsets, group_ray, ts_pad, te_pad)
@@ -648,10 +655,14 @@ def pack_groups(offsets, t_starts, t_ends, n_groups=None, group_offsets=None) ->
 
 # ---- stand-alone compositing / sampling kernels (no model) -----------------------------------
 def composite_dense(raw, dirs, z, want_aux=True):
+    """afx_composite_dense: raw [R,S], dirs [R,3], z [S] or [R,S] -> (rgb [R], depth [R], weights [R,S], entropy [R], sigma [R,S])."""
     lib = _lib.load()
-    dev = raw.device
-    raw, dirs, z = _f32(raw, "raw", dev), _f32(dirs, "dirs", dev), _f32(z, "z", dev)
+    dev, who = raw.device, "composite_dense"
+    raw = _buffer(raw, "raw", torch.float32, None, dev, who, copy=True)
     r, s = raw.shape
+    dirs = _buffer(dirs, "dirs", torch.float32, (r, 3), dev, who, exact_shape=True, copy=True)
+    z = _buffer(z, "z", torch.float32, (r, s) if z.dim() == 2 else (s,), dev, who, exact_shape=True, copy=True)
+    _on_gpu(raw, "raw", who)
     rgb = torch.empty(r, device=dev)
     depth = torch.empty(r, device=dev) if want_aux else None
     w = torch.empty(r, s, device=dev) if want_aux else None
@@ -664,48 +675,29 @@ def composite_dense(raw, dirs, z, want_aux=True):
 
 def composite_dense_backward(raw, dirs, z, rgb, d_rgb):
     lib = _lib.load()
-    dev = raw.device
-    d_raw = torch.empty_like(raw)
+    dev, who = raw.device, "composite_dense_backward"
+    raw = _buffer(raw, "raw", torch.float32, None, dev, who, copy=True)
     r, s = raw.shape
-    _lib.check(lib.afx_composite_dense_backward(_ptr(raw), _ptr(dirs), _ptr(z), int(z.dim() == 2), r, s, _ptr(rgb),
-                                                _ptr(_f32(d_rgb, "d_rgb", dev)), _ptr(d_raw), Engine._stream(dev)),
-               "afx_composite_dense_backward")
+    dirs = _buffer(dirs, "dirs", torch.float32, (r, 3), dev, who, exact_shape=True, copy=True)
+    z = _buffer(z, "z", torch.float32, (r, s) if z.dim() == 2 else (s,), dev, who, exact_shape=True, copy=True)
+    rgb, d_rgb = _buffer(rgb, "rgb", torch.float32, r, dev, who, copy=True), _buffer(d_rgb, "d_rgb", torch.float32, r, dev, who, copy=True)
+    _on_gpu(raw, "raw", who)
+    d_raw = torch.empty_like(raw)
+    _lib.check(lib.afx_composite_dense_backward(_ptr(raw), _ptr(dirs), _ptr(z), int(z.dim() == 2), r, s, _ptr(rgb), _ptr(d_rgb), _ptr(d_raw),
+                                                Engine._stream(dev)), "afx_composite_dense_backward")
     return d_raw
 
 
-def _packed_args(fn, floats, ints):
-    """What the packed-sample wrappers hand to the library by pointer: `floats` {name: (tensor, entries)} must be float32 and come back
-    flattened and contiguous (_f32); `ints` {name: (tensor, dtype, entries)} must have exactly that dtype and be contiguous already; every
-    tensor on the one GPU of the first.  Nothing is converted: a violation raises AfxError naming the argument, before the library is
-    called (an int64 ray_indices or a float64 t_starts would otherwise be read as something else).  Types and sizes are checked before
-    the devices.  -> the float tensors in order."""
-    named = [(k, t, torch.float32, n) for k, (t, n) in floats.items()] + [(k, t, dt, n) for k, (t, dt, n) in ints.items()]
-    for name, t, dtype, n in named:
-        if not isinstance(t, torch.Tensor):
-            raise AfxError(f"{fn}: {name}: expected a tensor")
-        if t.dtype != dtype:
-            raise AfxError(f"{fn}: {name}: dtype {t.dtype}, expected {dtype}")
-        if n is not None and t.numel() != n:
-            raise AfxError(f"{fn}: {name}: {t.numel()} entries, expected {n}")
-    dev = named[0][1].device
-    for name, t, _, _ in named:
-        if not t.is_cuda:
-            raise AfxError(f"{fn}: {name} must live on the GPU; there is no CPU fallback")
-        if t.device != dev:
-            raise AfxError(f"{fn}: {name}: on {t.device}, expected {dev}")
-    for name, (t, _, _) in ints.items():
-        if not t.is_contiguous():
-            raise AfxError(f"{fn}: {name}: expected a contiguous tensor")
-    return [_f32(t.reshape(-1), name, dev) for name, (t, _) in floats.items()]
-
-
 def composite_packed(pred, ray_indices, t_starts, t_ends, n_rays):
-    """afx_composite_packed: pred[n] (before the sigmoid), ray_indices[n] int32 ascending, t_starts / t_ends [n] -> rgb_map[n_rays]."""
+    """afx_composite_packed: pred[n] (before the sigmoid), ray_indices[n] int32 ascending, t_starts / t_ends [n] -> rgb_map[n_rays].
+    Nothing is converted: an int64 ray_indices or a float64 t_starts would otherwise be read as something else."""
     lib = _lib.load()
-    n, n_rays = (pred.numel() if isinstance(pred, torch.Tensor) else None), int(n_rays)
-    pred, ts, te = _packed_args("composite_packed", {"pred": (pred, None), "t_starts": (t_starts, n), "t_ends": (t_ends, n)},
-                                {"ray_indices": (ray_indices, torch.int32, n)})
-    dev = pred.device
+    dev, who, n_rays = getattr(pred, "device", None), "composite_packed", int(n_rays)
+    pred = _buffer(pred, "pred", torch.float32, None, dev, who, copy=True)
+    n = pred.numel()
+    ts, te = _buffer(t_starts, "t_starts", torch.float32, n, dev, who, copy=True), _buffer(t_ends, "t_ends", torch.float32, n, dev, who, copy=True)
+    _buffer(ray_indices, "ray_indices", torch.int32, n, dev, who)
+    _on_gpu(pred, "pred", who)
     rgb = torch.empty(n_rays, device=dev)
     _lib.check(lib.afx_composite_packed(_ptr(pred), _ptr(ray_indices), _ptr(ts), _ptr(te), n, n_rays,
                                         _ptr(rgb), Engine._stream(dev)), "afx_composite_packed")
@@ -715,11 +707,13 @@ def composite_packed(pred, ray_indices, t_starts, t_ends, n_rays):
 def composite_packed_backward(pred, ray_indices, t_starts, t_ends, n_rays, rgb, d_rgb):
     """afx_composite_packed_backward: rgb = composite_packed's result, d_rgb[n_rays] -> d_pred, in pred's shape."""
     lib = _lib.load()
-    n, n_rays = (pred.numel() if isinstance(pred, torch.Tensor) else None), int(n_rays)
-    flat, ts, te, rgb, d_rgb = _packed_args("composite_packed_backward",
-                                            {"pred": (pred, None), "t_starts": (t_starts, n), "t_ends": (t_ends, n), "rgb": (rgb, n_rays),
-                                             "d_rgb": (d_rgb, n_rays)}, {"ray_indices": (ray_indices, torch.int32, n)})
-    dev = flat.device
+    dev, who, n_rays = getattr(pred, "device", None), "composite_packed_backward", int(n_rays)
+    flat = _buffer(pred, "pred", torch.float32, None, dev, who, copy=True)
+    n = flat.numel()
+    ts, te = _buffer(t_starts, "t_starts", torch.float32, n, dev, who, copy=True), _buffer(t_ends, "t_ends", torch.float32, n, dev, who, copy=True)
+    rgb, d_rgb = _buffer(rgb, "rgb", torch.float32, n_rays, dev, who, copy=True), _buffer(d_rgb, "d_rgb", torch.float32, n_rays, dev, who, copy=True)
+    _buffer(ray_indices, "ray_indices", torch.int32, n, dev, who)
+    _on_gpu(flat, "pred", who)
     d_pred = torch.empty(pred.shape, device=dev)
     _lib.check(lib.afx_composite_packed_backward(_ptr(flat), _ptr(ray_indices), _ptr(ts), _ptr(te), n,
                                                  n_rays, _ptr(rgb), _ptr(d_rgb), _ptr(d_pred),
@@ -728,25 +722,15 @@ def composite_packed_backward(pred, ray_indices, t_starts, t_ends, n_rays, rgb, 
 
 
 # ---- per-ray entropy of the density profile (get_ray_entropy) with its gradient ---------------
-def _entropy_ray_indices(ray_indices, n, dev):
-    if not isinstance(ray_indices, torch.Tensor) or ray_indices.device != dev or ray_indices.dtype != torch.int32:
-        raise ValueError(f"ray_indices: expected an int32 tensor on {dev}")
-    if ray_indices.numel() != n:
-        raise ValueError(f"ray_indices: {ray_indices.numel()} entries for {n} samples")
-    return ray_indices if ray_indices.is_contiguous() else ray_indices.contiguous()
-
-
 def ray_entropy_packed(pred, ray_indices, rgb_map, n_rays, threshold=0.4):
     """afx_ray_entropy_packed: pred[n] (before the sigmoid), ray_indices[n] int32 ascending, rgb_map[n_rays] -> (entropy[n_rays],
     ray_sums[n_rays,2] for ray_entropy_packed_backward)."""
     lib = _lib.load()
-    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-        raise AfxError("ray_entropy_packed: tensors must live on the GPU; there is no CPU fallback")
-    dev, n_rays = pred.device, int(n_rays)
-    pred, rgb_map = _f32(pred.reshape(-1), "pred", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
-    ri = _entropy_ray_indices(ray_indices, pred.numel(), dev)
-    if rgb_map.numel() != n_rays:
-        raise ValueError(f"rgb_map: {rgb_map.numel()} entries for {n_rays} rays")
+    dev, who, n_rays = getattr(pred, "device", None), "ray_entropy_packed", int(n_rays)
+    pred = _buffer(pred, "pred", torch.float32, None, dev, who, copy=True)
+    ri = _buffer(ray_indices, "ray_indices", torch.int32, pred.numel(), dev, who, copy=True)
+    rgb_map = _buffer(rgb_map, "rgb_map", torch.float32, n_rays, dev, who, copy=True)
+    _on_gpu(pred, "pred", who)
     ent = torch.empty(n_rays, device=dev)
     sums = torch.empty(n_rays, 2, device=dev)
     _lib.check(lib.afx_ray_entropy_packed(_ptr(pred), _ptr(ri), pred.numel(), _ptr(rgb_map), n_rays, float(threshold), _ptr(ent), _ptr(sums),
@@ -758,16 +742,15 @@ def ray_entropy_packed_backward(pred, ray_indices, rgb_map, ray_sums, d_entropy,
     """afx_ray_entropy_packed_backward -> d_pred[n].  `out`: a gradient buffer the result is ADDED to (the accumulate flag), e.g. the one
     composite_packed_backward returned; without it a new tensor is written."""
     lib = _lib.load()
-    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
-        raise AfxError("ray_entropy_packed_backward: tensors must live on the GPU; there is no CPU fallback")
-    dev = pred.device
-    pred, rgb_map = _f32(pred.reshape(-1), "pred", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
-    ri = _entropy_ray_indices(ray_indices, pred.numel(), dev)
-    ray_sums, d_entropy = _f32(ray_sums, "ray_sums", dev), _f32(d_entropy.reshape(-1), "d_entropy", dev)
-    if ray_sums.shape != (rgb_map.numel(), 2) or d_entropy.numel() != rgb_map.numel():
-        raise ValueError("ray_sums / d_entropy: expected [n_rays,2] and [n_rays]")
-    if out is not None and (_f32(out, "out", dev) is not out or out.numel() != pred.numel()):
-        raise ValueError("out: expected a contiguous tensor with one entry per sample")
+    dev, who = getattr(pred, "device", None), "ray_entropy_packed_backward"
+    pred = _buffer(pred, "pred", torch.float32, None, dev, who, copy=True).reshape(-1)
+    ri = _buffer(ray_indices, "ray_indices", torch.int32, pred.numel(), dev, who, copy=True)
+    rgb_map = _buffer(rgb_map, "rgb_map", torch.float32, None, dev, who, copy=True)
+    ray_sums = _buffer(ray_sums, "ray_sums", torch.float32, (rgb_map.numel(), 2), dev, who, exact_shape=True, copy=True)
+    d_entropy = _buffer(d_entropy, "d_entropy", torch.float32, rgb_map.numel(), dev, who, copy=True)
+    if out is not None:
+        _buffer(out, "out", torch.float32, pred.numel(), dev, who)
+    _on_gpu(pred, "pred", who)
     d_pred = torch.empty_like(pred) if out is None else out
     _lib.check(lib.afx_ray_entropy_packed_backward(_ptr(pred), _ptr(ri), pred.numel(), _ptr(rgb_map), float(threshold), _ptr(ray_sums),
                                                    _ptr(d_entropy), int(out is not None), _ptr(d_pred), Engine._stream(dev)),
@@ -778,13 +761,13 @@ def ray_entropy_packed_backward(pred, ray_indices, rgb_map, ray_sums, d_entropy,
 def ray_entropy_dense(raw, rgb_map, threshold=0.4):
     """afx_ray_entropy_dense: raw[R,S] (before the sigmoid), rgb_map[R] -> (entropy[R], ray_sums[R,2])."""
     lib = _lib.load()
-    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
-        raise AfxError("ray_entropy_dense: tensors must live on the GPU; there is no CPU fallback")
-    dev = raw.device
-    raw, rgb_map = _f32(raw, "raw", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
-    if raw.dim() != 2 or raw.shape[1] < 1 or rgb_map.numel() != raw.shape[0]:
+    dev, who = getattr(raw, "device", None), "ray_entropy_dense"
+    raw = _buffer(raw, "raw", torch.float32, None, dev, who, copy=True)
+    if raw.dim() != 2 or raw.shape[1] < 1:
         raise ValueError("ray_entropy_dense: expected raw[R,S] with S >= 1 and rgb_map[R]")
     r, s = raw.shape
+    rgb_map = _buffer(rgb_map, "rgb_map", torch.float32, r, dev, who, copy=True)
+    _on_gpu(raw, "raw", who)
     ent = torch.empty(r, device=dev)
     sums = torch.empty(r, 2, device=dev)
     _lib.check(lib.afx_ray_entropy_dense(_ptr(raw), r, s, _ptr(rgb_map), float(threshold), _ptr(ent), _ptr(sums), Engine._stream(dev)),
@@ -795,18 +778,16 @@ def ray_entropy_dense(raw, rgb_map, threshold=0.4):
 def ray_entropy_dense_backward(raw, rgb_map, ray_sums, d_entropy, threshold=0.4, out=None):
     """afx_ray_entropy_dense_backward -> d_raw[R,S]; `out` as in ray_entropy_packed_backward."""
     lib = _lib.load()
-    if not isinstance(raw, torch.Tensor) or not raw.is_cuda:
-        raise AfxError("ray_entropy_dense_backward: tensors must live on the GPU; there is no CPU fallback")
-    dev = raw.device
-    raw, rgb_map = _f32(raw, "raw", dev), _f32(rgb_map.reshape(-1), "rgb_map", dev)
-    ray_sums, d_entropy = _f32(ray_sums, "ray_sums", dev), _f32(d_entropy.reshape(-1), "d_entropy", dev)
-    if raw.dim() != 2 or raw.shape[1] < 1 or rgb_map.numel() != raw.shape[0] or ray_sums.shape != (raw.shape[0], 2) \
-            or d_entropy.numel() != raw.shape[0]:
+    dev, who = getattr(raw, "device", None), "ray_entropy_dense_backward"
+    raw = _buffer(raw, "raw", torch.float32, None, dev, who, copy=True)
+    if raw.dim() != 2 or raw.shape[1] < 1:
         raise ValueError("ray_entropy_dense_backward: expected raw[R,S], rgb_map[R], ray_sums[R,2], d_entropy[R]")
-    if out is not None and (_f32(out, "out", dev) is not out or out.shape != raw.shape):
-        raise ValueError("out: expected a contiguous [R,S] tensor")
-    d_raw = torch.empty_like(raw) if out is None else out
     r, s = raw.shape
+    rgb_map = _buffer(rgb_map, "rgb_map", torch.float32, r, dev, who, copy=True)
+    ray_sums = _buffer(ray_sums, "ray_sums", torch.float32, (r, 2), dev, who, exact_shape=True, copy=True)
+    d_entropy = _buffer(d_entropy, "d_entropy", torch.float32, r, dev, who, copy=True)
+    d_raw = _out(out, "out", torch.float32, (r, s), dev, who, exact_shape=True)
+    _on_gpu(raw, "raw", who)
     _lib.check(lib.afx_ray_entropy_dense_backward(_ptr(raw), r, s, _ptr(rgb_map), float(threshold), _ptr(ray_sums), _ptr(d_entropy),
                                                   int(out is not None), _ptr(d_raw), Engine._stream(dev)), "afx_ray_entropy_dense_backward")
     return d_raw
@@ -818,13 +799,11 @@ def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None,
     float32, or poses [n_proj,3 or 4,4] + width / height / focal, generated in fp64 in the kernel: the rays `ray_ids` (any integer tensor)
     of the [n_proj, H, W] table, or ray_id0 .. ray_id0 + n_rays of it (n_rays defaults to the rest).  Rays outside the table raise."""
     lib = _lib.load()
-    dev = vol.device
-    if not vol.is_cuda:
-        raise AfxError("project_volume: the volume must live on a GPU; there is no CPU fallback")
-    vol = _f32(vol, "volume", dev)
+    dev, who = vol.device, "project_volume"
+    vol = _buffer(vol, "volume", torch.float32, None, dev, who, copy=True)
     if vol.dim() != 3:
         raise ValueError("volume: expected [nx,ny,nz]")
-    z = _f32(depth_values, "depth_values", dev)
+    z = _buffer(depth_values, "depth_values", torch.float32, None, dev, who, copy=True)
     a = RenderArgs()
     keep = [vol, z]
     if poses is not None:
@@ -842,12 +821,13 @@ def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None,
             a.ray_ids = ray_ids.data_ptr()
         a.ray_id0, a.width, a.height, a.focal = int(ray_id0), int(width), int(height), float(focal)
     else:
-        o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
+        o, d = _buffer(origins, "origins", torch.float32, None, dev, who, copy=True), _buffer(dirs, "dirs", torch.float32, None, dev, who, copy=True)
         keep += [o, d]
         n = o.shape[0]
         if tuple(o.shape) != (n, 3) or tuple(d.shape) != (n, 3):
             raise ValueError(f"project_volume: origins/dirs: expected two [n_rays, 3] tensors, got {tuple(o.shape)} and {tuple(d.shape)}")
         a.ray_mode, a.origins, a.dirs = _lib.RAYS_ARRAYS, o.data_ptr(), d.data_ptr()
+    _on_gpu(vol, "volume", who)
     pixel = torch.empty(int(n), dtype=torch.float32, device=dev)
     a.n_rays, a.n_samples, a.depth_mode, a.z, a.pixel = int(n), int(z.numel()), _lib.DEPTH_SHARED_Z, z.data_ptr(), pixel.data_ptr()
     org = (C.c_double * 3)(*[float(x) for x in origin])
@@ -858,29 +838,26 @@ def project_volume(vol, origin, spacing, fill_value, depth_values, origins=None,
     return pixel
 
 
-def fine_depths(z_coarse, w_coarse, u):
+def fine_depths(z_coarse, w_coarse, u, fn: str = "afx_fine_depths", name: str = "w_coarse"):
+    """afx_fine_depths: z_coarse [S] or [R,S], the coarse pass's weights w_coarse [R,S], the draw u [R,n_fine] -> merged depths [R, S + n_fine]."""
     lib = _lib.load()
-    dev = w_coarse.device
-    z_coarse, w_coarse, u = _f32(z_coarse, "z_coarse", dev), _f32(w_coarse, "w_coarse", dev), _f32(u, "u", dev)
+    dev, who = w_coarse.device, fn[4:]
+    w_coarse = _buffer(w_coarse, name, torch.float32, None, dev, who, copy=True)
     r, s = w_coarse.shape
+    z_coarse = _buffer(z_coarse, "z_coarse", torch.float32, (r, s) if z_coarse.dim() == 2 else (s,), dev, who, exact_shape=True, copy=True)
+    u = _buffer(u, "u", torch.float32, None, dev, who, copy=True)
+    if u.dim() != 2 or u.shape[0] != r:
+        raise ValueError(f"{who}: u must have shape [{r}, n_fine], got {tuple(u.shape)}")
     nf = u.shape[1]
+    _on_gpu(w_coarse, name, who)
     out = torch.empty(r, s + nf, device=dev)
-    _lib.check(lib.afx_fine_depths(_ptr(z_coarse), int(z_coarse.dim() == 2), _ptr(w_coarse), _ptr(u), r, s, nf, _ptr(out),
-                                   Engine._stream(dev)), "afx_fine_depths")
+    _lib.check(getattr(lib, fn)(_ptr(z_coarse), int(z_coarse.dim() == 2), _ptr(w_coarse), _ptr(u), r, s, nf, _ptr(out), Engine._stream(dev)), fn)
     return out
 
 
 def fine_depths_from_tau(z_coarse, tau_coarse, u):
     """afx_fine_depths_from_tau: merged coarse + fine depths from the coarse pass's per-sample optical depths [R,S]."""
-    lib = _lib.load()
-    dev = tau_coarse.device
-    z_coarse, tau_coarse, u = _f32(z_coarse, "z_coarse", dev), _f32(tau_coarse, "tau_coarse", dev), _f32(u, "u", dev)
-    r, s = tau_coarse.shape
-    nf = u.shape[1]
-    out = torch.empty(r, s + nf, device=dev)
-    _lib.check(lib.afx_fine_depths_from_tau(_ptr(z_coarse), int(z_coarse.dim() == 2), _ptr(tau_coarse), _ptr(u), r, s, nf, _ptr(out),
-                                            Engine._stream(dev)), "afx_fine_depths_from_tau")
-    return out
+    return fine_depths(z_coarse, tau_coarse, u, "afx_fine_depths_from_tau", "tau_coarse")
 
 
 # ---- occupancy grid / ray marching / device ray sampler (no model) ---------------------------------------------
@@ -901,33 +878,6 @@ def philox_uniform(seed: int, stream_id: int, n: int, device) -> torch.Tensor:
     return out
 
 
-def _grid_args(fn, resolution, named):
-    """What the occupancy-grid wrappers hand to the library by pointer, in the style of grid_apply_mask and _packed_args: `named`
-    [(name, tensor or None, dtype, entries, at_least)] - every tensor that is given must have exactly that dtype, be contiguous and hold
-    `entries` elements (at_least: that many or more), all of them on the one GPU of the first.  Nothing is converted: a violation is a
-    ValueError naming the argument, raised before the library is called (an int64 cell_idx or a short bits tensor would otherwise go
-    straight to a kernel).  Types and sizes are checked before the devices.  The VALUES of cell_idx are not checked - that would need a
-    device read -: every index must lie in [0, num_cells) (include/afx.h).  -> the device."""
-    given = [e for e in named if e[1] is not None]
-    for name, t, dtype, count, at_least in given:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{fn}: {name}: expected a tensor")
-        if t.dtype != dtype:
-            raise ValueError(f"{fn}: {name}: dtype {t.dtype}, expected {dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{fn}: {name}: expected a contiguous tensor")
-        if t.numel() < count if at_least else t.numel() != count:
-            raise ValueError(f"{fn}: {name}: {t.numel()} entries, expected {'at least ' if at_least else ''}{count} "
-                             f"(resolution {list(resolution)})")
-    dev = given[0][1].device
-    for name, t, _, _, _ in given:
-        if t.device.type != "cuda":
-            raise ValueError(f"{fn}: {name} must live on the GPU; there is no CPU fallback")
-        if t.device != dev:
-            raise ValueError(f"{fn}: {name}: on {t.device}, expected {dev}")
-    return dev
-
-
 def _num_cells(resolution) -> int:
     r = [int(x) for x in resolution]
     return r[0] * r[1] * r[2]
@@ -935,20 +885,21 @@ def _num_cells(resolution) -> int:
 
 def grid_points(roi_aabb, resolution, cell_idx, n, jitter=None, seed=0, stream_id=0, device=None):
     """afx_grid_points: one jittered world point per selected cell -> [n, 3].  cell_idx: None (cells 0 .. n-1) or int32 [n], every index in
-    [0, num_cells), unchecked; jitter: None (the Philox stream (seed, stream_id)) or float32 [n, 3]."""
+    [0, num_cells), unchecked (that would need a device read); jitter: None (the Philox stream (seed, stream_id)) or float32 [n, 3]."""
     lib = _lib.load()
-    n = int(n)
-    if cell_idx is not None and (not isinstance(cell_idx, torch.Tensor) or cell_idx.dim() != 1):
-        raise ValueError("grid_points: cell_idx: expected a 1-D tensor")
-    if jitter is not None and (not isinstance(jitter, torch.Tensor) or tuple(jitter.shape) != (n, 3)):
-        raise ValueError(f"grid_points: jitter: expected a tensor of shape [{n}, 3]")
-    named = [("cell_idx", cell_idx, torch.int32, n, False), ("jitter", jitter, torch.float32, 3 * n, False)]
+    n, who = int(n), "grid_points"
     if cell_idx is None and jitter is None:
         dev = torch.device(device) if device is not None else None
         if dev is None or dev.type != "cuda":
-            raise AfxError("grid_points: the occupancy grid lives on a GPU; there is no CPU fallback")
+            raise AfxError("grid_points: the occupancy grid lives on a GPU; there is no CPU path")
     else:
-        dev = _grid_args("grid_points", resolution, named)
+        first = cell_idx if cell_idx is not None else jitter
+        dev = getattr(first, "device", None)
+        if cell_idx is not None:
+            _buffer(cell_idx, "cell_idx", torch.int32, (n,), dev, who, exact_shape=True)
+        if jitter is not None:
+            _buffer(jitter, "jitter", torch.float32, (n, 3), dev, who, exact_shape=True)
+        _on_gpu(first, "cell_idx" if cell_idx is not None else "jitter", who)
         if device is not None and torch.device(device).index not in (None, dev.index):
             raise ValueError(f"grid_points: device {device}, but the tensors are on {dev}")
     g = _grid_desc(roi_aabb, resolution)
@@ -962,17 +913,16 @@ def grid_update(roi_aabb, resolution, occs, cell_idx, occ_new, ema_decay, scratc
     """afx_grid_update, in place: occs[c] = max(occs[c] * ema_decay, occ_new) over the selected cells.  occs, scratch: float32 [num_cells];
     cell_idx: None (cells 0 .. n-1) or int32 [n], every index in [0, num_cells), unchecked; occ_new: float32, n entries."""
     lib = _lib.load()
-    if not isinstance(occ_new, torch.Tensor):
-        raise ValueError("grid_update: occ_new: expected a tensor")
-    if cell_idx is not None and (not isinstance(cell_idx, torch.Tensor) or cell_idx.dim() != 1):
-        raise ValueError("grid_update: cell_idx: expected a 1-D tensor")
-    nc, n = _num_cells(resolution), occ_new.numel()
+    dev, who, nc = getattr(occs, "device", None), "grid_update", _num_cells(resolution)
+    _buffer(occs, "occs", torch.float32, nc, dev, who)
+    _buffer(scratch, "scratch", torch.float32, nc, dev, who)
+    occ_new = _buffer(occ_new, "occ_new", torch.float32, None, dev, who, copy=True)
+    n = occ_new.numel()
     if cell_idx is None and n > nc:
         raise ValueError(f"grid_update: occ_new: {n} entries for the first cells of a grid of {nc}")
-    occ_new = occ_new.reshape(-1)
-    occ_new = occ_new if occ_new.is_contiguous() else occ_new.contiguous()
-    dev = _grid_args("grid_update", resolution, [("occs", occs, torch.float32, nc, False), ("scratch", scratch, torch.float32, nc, False),
-                                                 ("cell_idx", cell_idx, torch.int32, n, False), ("occ_new", occ_new, torch.float32, n, False)])
+    if cell_idx is not None:
+        _buffer(cell_idx, "cell_idx", torch.int32, (n,), dev, who, exact_shape=True)
+    _on_gpu(occs, "occs", who)
     g = _grid_desc(roi_aabb, resolution)
     _lib.check(lib.afx_grid_update(C.byref(g), _ptr(occs), _ptr(scratch), _ptr(cell_idx), n, _ptr(occ_new),
                                    float(ema_decay), Engine._stream(dev)), "afx_grid_update")
@@ -982,10 +932,12 @@ def grid_binarize(roi_aabb, resolution, occs, occ_thre, binary_u8, bits, partial
     """afx_grid_binarize: binary_u8[c] = occs[c] > min(mean(occs), occ_thre) and the march's bitfield.  occs float32 and binary_u8 uint8
     [num_cells], bits int32 [(num_cells + 31) // 32], partial_ws float64, at least 256 entries."""
     lib = _lib.load()
-    nc = _num_cells(resolution)
-    dev = _grid_args("grid_binarize", resolution, [("occs", occs, torch.float32, nc, False), ("binary_u8", binary_u8, torch.uint8, nc, False),
-                                                   ("bits", bits, torch.int32, (nc + 31) // 32, False),
-                                                   ("partial_ws", partial_ws, torch.float64, 256, True)])
+    dev, who, nc = getattr(occs, "device", None), "grid_binarize", _num_cells(resolution)
+    _buffer(occs, "occs", torch.float32, nc, dev, who)
+    _buffer(binary_u8, "binary_u8", torch.uint8, nc, dev, who)
+    _buffer(bits, "bits", torch.int32, (nc + 31) // 32, dev, who)
+    _buffer(partial_ws, "partial_ws", torch.float64, 256, dev, who, at_least=True)
+    _on_gpu(occs, "occs", who)
     g = _grid_desc(roi_aabb, resolution)
     _lib.check(lib.afx_grid_binarize(C.byref(g), _ptr(occs), float(occ_thre), _ptr(binary_u8), _ptr(bits), _ptr(partial_ws),
                                      Engine._stream(dev)), "afx_grid_binarize")
@@ -995,10 +947,10 @@ def grid_pack(roi_aabb, resolution, binary_u8, bits):
     """afx_grid_pack: the march's bitfield from a byte mask (a restored grid).  binary_u8 uint8 [num_cells], bits int32
     [(num_cells + 31) // 32]."""
     lib = _lib.load()
-    if isinstance(binary_u8, torch.Tensor) and binary_u8.device.type != "cuda":
-        raise AfxError("grid_pack: the occupancy grid lives on a GPU; there is no CPU fallback")
-    nc = _num_cells(resolution)
-    dev = _grid_args("grid_pack", resolution, [("binary_u8", binary_u8, torch.uint8, nc, False), ("bits", bits, torch.int32, (nc + 31) // 32, False)])
+    dev, who, nc = getattr(binary_u8, "device", None), "grid_pack", _num_cells(resolution)
+    _buffer(binary_u8, "binary_u8", torch.uint8, nc, dev, who)
+    _buffer(bits, "bits", torch.int32, (nc + 31) // 32, dev, who)
+    _on_gpu(binary_u8, "binary_u8", who)
     g = _grid_desc(roi_aabb, resolution)
     _lib.check(lib.afx_grid_pack(C.byref(g), _ptr(binary_u8), _ptr(bits), Engine._stream(dev)), "afx_grid_pack")
 
@@ -1020,17 +972,16 @@ def grid_select_cells(roi_aabb, resolution, bits, n_draw, seed, step, cells=None
     """afx_grid_select_cells: the post-warm-up cells of a refresh drawn on the device from the march's bitfield (draw rule: include/afx.h).
     `step`: int or 0-dim int64 device tensor.  Returns (cells [2 n_draw] int32 - valid up to count -, count [1] int64), device tensors."""
     lib = _lib.load()
-    if bits.device.type != "cuda":
-        raise AfxError("grid_select_cells: the occupancy grid lives on a GPU; there is no CPU fallback")
-    dev = bits.device
+    dev, who, n_draw = bits.device, "grid_select_cells", int(n_draw)
     g = _grid_desc(roi_aabb, resolution)
-    cells = torch.empty(2 * int(n_draw), dtype=torch.int32, device=dev) if cells is None else cells
-    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
-    if workspace is None:
-        workspace = torch.empty(max(int(lib.afx_grid_select_workspace_bytes(C.byref(g))), 1), dtype=torch.uint8, device=dev)
-    step_h, step_d = _step_args(step, dev, "grid_select_cells")
-    _lib.check(lib.afx_grid_select_cells(C.byref(g), _ptr(bits), int(n_draw), int(seed), step_h, step_d, _ptr(cells), _ptr(count), _ptr(workspace),
-                                         workspace.numel(), Engine._stream(dev)), "afx_grid_select_cells")
+    _buffer(bits, "bits", torch.int32, (_num_cells(resolution) + 31) // 32, dev, who)
+    cells = _out(cells, "cells", torch.int32, 2 * n_draw, dev, who, ok=n_draw >= 0, at_least=True)
+    count = _out(count, "count", torch.int64, 1, dev, who)
+    step_h, step_d = _step_args(step, dev, who)
+    _on_gpu(bits, "bits", who)
+    workspace, nbytes = _scratch(workspace, lib.afx_grid_select_workspace_bytes(C.byref(g)), dev, who)
+    _lib.check(lib.afx_grid_select_cells(C.byref(g), _ptr(bits), n_draw, int(seed), step_h, step_d, _ptr(cells), _ptr(count), _ptr(workspace),
+                                         nbytes, Engine._stream(dev)), "afx_grid_select_cells")
     return cells, count
 
 
@@ -1047,24 +998,26 @@ def grid_refresh(eng: Engine, prepared, prec: str, roi_aabb, resolution, occs, b
     """afx_grid_refresh: one refresh of one grid in place (occs, binary_u8, bits) - cells (all, or the device draw), jittered points,
     sigmoid(MLP) at `prec` on `prepared`, decay / EMA, threshold - with no host synchronisation.  `step`: int or 0-dim int64 device tensor
     (read when the kernels run: a captured call follows it)."""
-    dev = occs.device
-    if dev.type != "cuda":
-        raise AfxError("grid_refresh: the occupancy grid lives on a GPU; there is no CPU fallback")
+    dev, who, nc = occs.device, "grid_refresh", _num_cells(resolution)
+    _buffer(occs, "occs", torch.float32, nc, dev, who)
+    _buffer(binary_u8, "binary_u8", torch.uint8, nc, dev, who)
+    _buffer(bits, "bits", torch.int32, (nc + 31) // 32, dev, who)
+    eng._model(who, prepared, prec)
+    if prepared.device != dev:
+        raise ValueError(f"grid_refresh: prepared on {prepared.device}, expected {dev}")
+    workspace, nbytes = _scratch(workspace, 0, dev, who)
+    _on_gpu(occs, "occs", who)
     a = _lib.GridRefreshArgs()
     a.grid = _grid_desc(roi_aabb, resolution)
-    for t, name in ((binary_u8, "binary"), (bits, "bits"), (workspace, "workspace"), (prepared, "prepared")):
-        if t.device != dev:
-            raise ValueError(f"grid_refresh: {name} on {t.device}, expected {dev}")
     a.occs, a.binary, a.bits = occs.data_ptr(), binary_u8.data_ptr(), bits.data_ptr()
     a.all_cells, a.n_draw, a.seed = int(bool(all_cells)), int(n_draw), int(seed)
-    step_h, step_d = _step_args(step, dev, "grid_refresh")
-    a.step, a.step_dev = step_h, step_d
+    a.step, a.step_dev = _step_args(step, dev, who)
     a.occ_thre, a.ema_decay = float(occ_thre), float(ema_decay)
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
     eng._check(eng.lib.afx_grid_refresh(eng.h, _lib.PREC[prec], _ptr(prepared), C.byref(a), Engine._stream(dev)), "afx_grid_refresh")
 
 
-def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res):
+def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res, dev=None, who="march"):
     if o is not None:      # (None: the rays come from elsewhere - afx_march_render's pose mode)
         m.origins, m.dirs, m.n_rays = o.data_ptr(), d.data_ptr(), o.shape[0]
     if scene_aabb is not None:
@@ -1080,16 +1033,10 @@ def _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits
         # k_march_count / k_march_write read grid_bits[cell >> 5] without a check of their own
         if grid_aabb is None or grid_res is None:
             raise ValueError("march: grid_bits needs grid_aabb and grid_res")
-        if not isinstance(grid_bits, torch.Tensor) or grid_bits.dtype != torch.int32 or not grid_bits.is_contiguous():
-            raise ValueError("march: grid_bits: expected a contiguous int32 tensor (32 cells per word)")
-        if o is not None and grid_bits.device != o.device:
-            raise ValueError(f"march: grid_bits on {grid_bits.device}, expected {o.device}")
         res = [int(x) for x in grid_res]
         if len(res) != 3 or min(res) <= 0 or len(list(grid_aabb)) != 6:
             raise ValueError("march: grid_res must be three positive sizes and grid_aabb six numbers")
-        words = (res[0] * res[1] * res[2] + 31) // 32
-        if grid_bits.numel() < words:
-            raise ValueError(f"march: grid_bits has {grid_bits.numel()} words, the {res[0]} x {res[1]} x {res[2]} grid needs {words}")
+        _buffer(grid_bits, "grid_bits", torch.int32, (_num_cells(res) + 31) // 32, dev if dev is not None else o.device, who, at_least=True)
         m.grid_bits = grid_bits.data_ptr()
         m.grid = _grid_desc(grid_aabb, grid_res)
 
@@ -1100,9 +1047,7 @@ def march(origins, dirs, scene_aabb, near_plane, far_plane, step, grid_bits=None
     box nor a far plane bounds, and a grid_bits that is not int32, on another device, without box and resolution, or shorter than the grid."""
     lib = _lib.load()
     dev = origins.device
-    if dev.type != "cuda":
-        raise AfxError("march: rays must live on a GPU; there is no CPU fallback")
-    o, d = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev)
+    o, d = _buffer(origins, "origins", torch.float32, None, dev, "march", copy=True), _buffer(dirs, "dirs", torch.float32, None, dev, "march", copy=True)
     if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape:
         raise ValueError(f"march: origins {tuple(o.shape)} and dirs {tuple(d.shape)}: expected [R, 3] both")
     if not float(step) > 0:
@@ -1110,7 +1055,8 @@ def march(origins, dirs, scene_aabb, near_plane, far_plane, step, grid_bits=None
     if scene_aabb is None and far_plane is None:
         raise ValueError("march: neither a scene box nor a far plane bounds the rays")
     m = _lib.MarchArgs()
-    _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res)
+    _fill_march_args(m, o, d, scene_aabb, near_plane, far_plane, step, grid_bits, grid_aabb, grid_res, dev)
+    _on_gpu(origins, "origins", "march")
     st = Engine._stream(dev)
     counts = torch.empty(o.shape[0], dtype=torch.int32, device=dev)
     _lib.check(lib.afx_march_count(C.byref(m), _ptr(counts), st), "afx_march_count")
@@ -1132,10 +1078,11 @@ def march_visibility(raw, ts, te, offsets, early_stop_eps, alpha_thre, is_alpha=
     ascending with offsets[-1] == n is the caller's to keep (the march's own output does): checking it would cost a host read per call,
     and the kernels index the samples by it."""
     lib = _lib.load()
-    n = raw.numel() if isinstance(raw, torch.Tensor) else None
-    raw, ts, te = _packed_args("march_visibility", {"raw": (raw, None), "ts": (ts, n), "te": (te, n)}, {"offsets": (offsets, torch.int64, None)})
-    dev = raw.device
-    n_rays = offsets.numel() - 1
+    dev, who = getattr(raw, "device", None), "march_visibility"
+    raw = _buffer(raw, "raw", torch.float32, None, dev, who, copy=True)
+    ts, te = _buffer(ts, "ts", torch.float32, raw.numel(), dev, who, copy=True), _buffer(te, "te", torch.float32, raw.numel(), dev, who, copy=True)
+    n_rays = _buffer(offsets, "offsets", torch.int64, None, dev, who).numel() - 1
+    _on_gpu(raw, "raw", who)
     if n_rays < 0:
         raise AfxError("march_visibility: offsets: expected [n_rays + 1] entries")
     keep = torch.empty(ts.numel(), dtype=torch.uint8, device=dev)
@@ -1163,17 +1110,15 @@ def march_visibility(raw, ts, te, offsets, early_stop_eps, alpha_thre, is_alpha=
 def topk_indices(keys: torch.Tensor, k: int) -> torch.Tensor:
     """Indices (int64, ascending) of the k largest keys - afx_topk_indices: radix select, deterministic, no full sort."""
     lib = _lib.load()
-    if keys.device.type != "cuda":
-        raise AfxError("topk_indices: keys must live on a GPU; there is no CPU fallback")
-    keys = keys.contiguous()
+    keys = _buffer(keys, "keys", torch.float32, None, keys.device, "topk_indices", copy=True)
     n = keys.numel()
     if not 0 <= k <= n:
         raise ValueError(f"topk_indices: k = {k} outside [0, {n}]")
+    _on_gpu(keys, "keys", "topk_indices")
     out = torch.empty(int(k), dtype=torch.int64, device=keys.device)
     if k == 0:
         return out
-    nbytes = int(lib.afx_topk_workspace_bytes(n))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    ws, nbytes = _scratch(None, lib.afx_topk_workspace_bytes(n), keys.device, "topk_indices")
     _lib.check(lib.afx_topk_indices(_ptr(keys), n, int(k), _ptr(out), _ptr(ws), nbytes, Engine._stream(keys.device)), "afx_topk_indices")
     return out
 
@@ -1261,10 +1206,8 @@ def volume_grid(volume_values: torch.Tensor, origin, spacing, fill, lo: float, h
     """afx_volume_grid: a voxel volume [nx, ny, nz] (trilinear, `fill` outside; what VoxelVolume stands for) sampled at
     np.meshgrid(t, t, t), t = np.linspace(lo, hi, n) rounded to fp32 - float32 [n, n, n], grid[i, j, k] = mu(t[j], t[i], t[k])."""
     lib = _lib.load()
-    if not isinstance(volume_values, torch.Tensor) or volume_values.device.type != "cuda":
-        raise AfxError("volume_grid: the volume must be a tensor on a GPU; there is no CPU fallback")
-    dev = volume_values.device
-    vol = _f32(volume_values, "volume", dev)
+    dev = _on_gpu(volume_values, "the volume", "volume_grid").device
+    vol = _buffer(volume_values, "volume", torch.float32, None, dev, "volume_grid", copy=True)
     if vol.dim() != 3:
         raise ValueError("volume: expected [nx,ny,nz]")
     n = int(n)
@@ -1315,7 +1258,7 @@ def surface_metrics_record(pred: torch.Tensor, gt: torch.Tensor, thr_pred: float
     if pred.shape != gt.shape or pred.device != gt.device:
         raise ValueError(f"surface_metrics_3d: pred {tuple(pred.shape)} on {pred.device}, gt {tuple(gt.shape)} on {gt.device}")
     dev = pred.device
-    p, g = _f32(pred, "pred", dev), _f32(gt, "gt", dev)
+    p, g = (_buffer(t, name, torch.float32, None, dev, "surface_metrics_3d", copy=True) for t, name in ((pred, "pred"), (gt, "gt")))
     n0, n1, n2 = p.shape
     record = _out(record, "record", torch.int64, SURFACE_RECORD_SLOTS, dev, "surface_metrics_3d")
     workspace, nbytes = _scratch(workspace, lib.afx_surface_metrics_3d_workspace_bytes(n0, n1, n2), dev, "surface_metrics_3d")
@@ -1490,7 +1433,7 @@ def isosurface_record(x: torch.Tensor, iso: float, index_to_world=None, max_vert
     lib = _lib.load()
     _volume_on_gpu(x, "the volume", "isosurface_record")
     dev = x.device
-    f = _f32(x, "the volume", dev)
+    f = _buffer(x, "the volume", torch.float32, None, dev, "isosurface_record", copy=True)
     n0, n1, n2 = f.shape
     aff = (C.c_double * 12)(*_affine12(index_to_world, "isosurface_record"))
     max_vertices, max_triangles = int(max_vertices), int(max_triangles)
@@ -1515,7 +1458,7 @@ def extract_isosurface(x: torch.Tensor, iso: float, index_to_world=None, cap: bo
     surface where the vessel leaves the grid: B = 0.  ValueError when fill >= iso (the cap would be inside)."""
     _volume_on_gpu(x, "the volume", "extract_isosurface")
     dev = x.device
-    f = _f32(x, "the volume", dev)
+    f = _buffer(x, "the volume", torch.float32, None, dev, "extract_isosurface", copy=True)
     aff = _affine12(index_to_world, "extract_isosurface").reshape(3, 4)
     if cap:
         if not float(fill) < float(iso):
@@ -3324,20 +3267,19 @@ class RayBatchSampler:
     are expected to advance by one per iteration (any other id starts a new block of `prefetch` draws at that id)."""
 
     def __init__(self, origins, dirs, pixels, weights, k, seed=0, prefetch=16):
-        dev = origins.device
-        if dev.type != "cuda":
-            raise AfxError("RayBatchSampler: the ray table must live on a GPU; there is no CPU fallback")
         self.lib = _lib.load()
-        self.origins, self.dirs, self.weights = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(weights, "weights", dev)
-        self.pixels = _f32(pixels, "pixels", dev) if pixels is not None else None
+        dev, who = origins.device, "RayBatchSampler"
+        self.origins, self.dirs, self.weights, self.pixels = (t if t is None else _buffer(t, name, torch.float32, None, dev, who, copy=True) for t, name in
+                                                              ((origins, "origins"), (dirs, "dirs"), (weights, "weights"), (pixels, "pixels")))
         n = self.origins.shape[0]
         if tuple(self.origins.shape) != (n, 3) or tuple(self.dirs.shape) != (n, 3) or self.weights.numel() != n \
                 or (self.pixels is not None and self.pixels.numel() != n):
             raise ValueError("RayBatchSampler: expected origins/dirs [n,3], pixels/weights [n]")
+        _on_gpu(origins, "origins", who)
         if not 0 < int(k) <= n or not 1 <= int(prefetch) <= 65535:
             raise ValueError("RayBatchSampler: need 0 < k <= n and 1 <= prefetch <= 65535")
         self.n, self.k, self.seed, self.prefetch, self.dev = n, int(k), int(seed), int(prefetch), dev
-        self._ws = torch.empty(int(self.lib.afx_sample_batches_workspace_bytes(n, self.prefetch)), dtype=torch.uint8, device=dev)
+        self._ws, self._ws_bytes = _scratch(None, self.lib.afx_sample_batches_workspace_bytes(n, self.prefetch), dev, "RayBatchSampler")
         self._idx = torch.empty(self.prefetch, self.k, dtype=torch.int64, device=dev)
         self._first = None      # stream id of row 0 of _idx
 
@@ -3346,7 +3288,7 @@ class RayBatchSampler:
         st = Engine._stream(self.dev)
         if self._first is None or not self._first <= stream_id < self._first + self.prefetch:
             _lib.check(self.lib.afx_sample_batches(_ptr(self.weights), self.n, self.seed, stream_id, self.prefetch, self.k, _ptr(self._idx),
-                                                   _ptr(self._ws), self._ws.numel(), st), "afx_sample_batches")
+                                                   _ptr(self._ws), self._ws_bytes, st), "afx_sample_batches")
             self._first = stream_id
         idx = self._idx[stream_id - self._first]
         o, d = torch.empty(self.k, 3, device=self.dev), torch.empty(self.k, 3, device=self.dev)
@@ -3366,55 +3308,55 @@ def sample_batches_dev(weights, seed: int, stream_id0_dev, n_batches: int, k: in
     when the kernels run.  Launches only: a graph captured over the call follows the counter.  Pass out_idx [n_batches, k] (int64) and a
     workspace of sample_batches_workspace_bytes(n, n_batches) bytes to reuse static buffers.  Returns out_idx."""
     lib = _lib.load()
-    dev = weights.device
-    if dev.type != "cuda":
-        raise AfxError("sample_batches_dev: the ray table must live on a GPU; there is no CPU fallback")
-    weights = _f32(weights, "weights", dev)
+    dev, who = weights.device, "sample_batches_dev"
+    weights = _buffer(weights, "weights", torch.float32, None, dev, who, copy=True)
     n, n_batches, k = weights.numel(), int(n_batches), int(k)
     if not torch.is_tensor(stream_id0_dev):
         raise ValueError("sample_batches_dev: the first stream id must be a 0-dim int64 device tensor (RayBatchSampler takes host ids)")
-    _, step_d = _step_args(stream_id0_dev, dev, "sample_batches_dev")
-    if out_idx is None:
-        out_idx = torch.empty(max(n_batches, 0), max(k, 0), dtype=torch.int64, device=dev)
-    elif out_idx.device != dev or out_idx.dtype != torch.int64 or out_idx.numel() != n_batches * k or not out_idx.is_contiguous():
-        raise ValueError(f"sample_batches_dev: out_idx must be a contiguous int64 tensor of {n_batches} x {k} elements on {dev}")
-    if workspace is None:
-        workspace = torch.empty(max(int(lib.afx_sample_batches_workspace_bytes(n, max(n_batches, 1))), 1), dtype=torch.uint8, device=dev)
-    elif workspace.device != dev:
-        raise ValueError(f"sample_batches_dev: workspace on {workspace.device}, expected {dev}")
-    _lib.check(lib.afx_sample_batches_dev(_ptr(weights), n, int(seed), step_d, n_batches, k, _ptr(out_idx), _ptr(workspace), workspace.numel(),
+    _, step_d = _step_args(stream_id0_dev, dev, who)
+    out_idx = _out(out_idx, "out_idx", torch.int64, (max(n_batches, 0), max(k, 0)), dev, who)
+    _on_gpu(weights, "weights", who)
+    workspace, nbytes = _scratch(workspace, 0 if workspace is not None else lib.afx_sample_batches_workspace_bytes(n, max(n_batches, 1)), dev, who)
+    _lib.check(lib.afx_sample_batches_dev(_ptr(weights), n, int(seed), step_d, n_batches, k, _ptr(out_idx), _ptr(workspace), nbytes,
                                           Engine._stream(dev)), "afx_sample_batches_dev")
     return out_idx
 
 
 def gather_rays(origins, dirs, pixels, idx, origins_out, dirs_out, pixels_out):
-    """afx_gather_rays into the caller's buffers: rows idx [k] (int64) of a float32 ray table [n,3], [n,3], [n]."""
+    """afx_gather_rays into the caller's buffers: rows idx [k] (int64) of a float32 ray table [n,3], [n,3], [n].  The VALUES of idx are
+    not checked (that would need a device read): every index must lie in [0, n)."""
     lib = _lib.load()
-    _lib.check(lib.afx_gather_rays(_ptr(origins), _ptr(dirs), _ptr(pixels), _ptr(idx), idx.numel(), _ptr(origins_out), _ptr(dirs_out),
-                                   _ptr(pixels_out), Engine._stream(origins.device)), "afx_gather_rays")
+    dev, who, n = origins.device, "gather_rays", origins.shape[0]
+    _buffer(origins, "origins", torch.float32, (n, 3), dev, who, exact_shape=True)
+    _buffer(dirs, "dirs", torch.float32, (n, 3), dev, who, exact_shape=True)
+    k = _buffer(idx, "idx", torch.int64, None, dev, who).numel()
+    _buffer(origins_out, "origins_out", torch.float32, (k, 3), dev, who)
+    _buffer(dirs_out, "dirs_out", torch.float32, (k, 3), dev, who)
+    if pixels is not None:      # (either may be None: the kernel copies the pixels when it has both)
+        _buffer(pixels, "pixels", torch.float32, n, dev, who)
+    if pixels_out is not None:
+        _buffer(pixels_out, "pixels_out", torch.float32, k, dev, who)
+    _on_gpu(origins, "origins", who)
+    _lib.check(lib.afx_gather_rays(_ptr(origins), _ptr(dirs), _ptr(pixels), _ptr(idx), k, _ptr(origins_out), _ptr(dirs_out),
+                                   _ptr(pixels_out), Engine._stream(dev)), "afx_gather_rays")
 
 
 def train_round_advance(step_dev, lr_table, lr_dev, skip, loss, counts, loss_hist, counts_hist, skip_hist, last_loss, n_marched):
     """afx_train_round_advance: the bookkeeping behind one captured grid iteration, on the device (include/afx.h) - the next learning rate
     from `lr_table`, the step's loss / counts / skip flag into slot step % round_len of the history (round_len = loss_hist.numel()),
     last_loss, n_marched, step + 1.  Every argument is a device tensor: int64 step_dev [1], counts [3], counts_hist [round_len, 3],
-    n_marched [1]; float32 the rest."""
+    n_marched [1]; float32 the rest (lr_table of any length)."""
     lib = _lib.load()
-    dev = step_dev.device
-    if dev.type != "cuda":
-        raise AfxError("train_round_advance: the counters live on a GPU; there is no CPU fallback")
-    L = loss_hist.numel()
+    dev, L = step_dev.device, loss_hist.numel()
     spec = (("step_dev", step_dev, torch.int64, 1), ("lr_table", lr_table, torch.float32, None), ("lr_dev", lr_dev, torch.float32, 1),
             ("skip", skip, torch.float32, 1), ("loss", loss, torch.float32, 1), ("counts", counts, torch.int64, 3),
             ("loss_hist", loss_hist, torch.float32, L), ("counts_hist", counts_hist, torch.int64, 3 * L), ("skip_hist", skip_hist, torch.float32, L),
             ("last_loss", last_loss, torch.float32, 1), ("n_marched", n_marched, torch.int64, 1))
-    for name, t, dt, n in spec:
-        if t.device != dev or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_contiguous():
-            raise ValueError(f"train_round_advance: {name} must be a contiguous {dt} tensor of {n if n is not None else 'n_table'} elements on {dev}")
     a = _lib.TrainRoundArgs()
     a.n_table, a.round_len = lr_table.numel(), L
-    for name, t, _, _ in spec:
-        setattr(a, name, t.data_ptr())
+    for name, t, dt, n in spec:
+        setattr(a, name, _buffer(t, name, dt, n, dev, "train_round_advance").data_ptr())
+    _on_gpu(step_dev, "step_dev", "train_round_advance")
     _lib.check(lib.afx_train_round_advance(C.byref(a), Engine._stream(dev)), "afx_train_round_advance")
 
 
@@ -3422,19 +3364,15 @@ def sample_rays(origins, dirs, pixels, weights, k, u=None, seed=0, stream_id=0):
     """Weighted sample WITHOUT replacement of k rows of a device-resident ray table (sample_pixel_rays, nerf_helpers.py:137-150):
     Efraimidis-Spirakis keys log(u)/w, radix-select top-k on the device (afx_topk_indices), gather.  Returns (origins[k,3], dirs[k,3], pixels[k] | None, idx)."""
     lib = _lib.load()
-    dev = origins.device
-    if dev.type != "cuda":
-        raise AfxError("sample_rays: the ray table must live on a GPU; there is no CPU fallback")
+    dev, who = origins.device, "sample_rays"
     # (row-major [n,3] tables: a frame's `df[[x, y, z]].to_numpy()` is usually column-major, and .float().to(device) keeps those strides)
-    origins, dirs, weights = _f32(origins, "origins", dev), _f32(dirs, "dirs", dev), _f32(weights, "weights", dev)
-    if pixels is not None:
-        pixels = _f32(pixels, "pixels", dev)
-    if u is not None:
-        u = _f32(u, "u", dev)
+    origins, dirs, weights, pixels, u = (t if t is None else _buffer(t, name, torch.float32, None, dev, who, copy=True) for t, name in
+                                         ((origins, "origins"), (dirs, "dirs"), (weights, "weights"), (pixels, "pixels"), (u, "u")))
     n = origins.shape[0]
     if tuple(origins.shape) != (n, 3) or tuple(dirs.shape) != (n, 3) or weights.numel() != n or (pixels is not None and pixels.numel() != n) \
             or (u is not None and u.numel() != n):
         raise ValueError("sample_rays: expected origins/dirs [n,3], pixels/weights/u [n]")
+    _on_gpu(origins, "origins", who)
     keys = torch.empty(n, device=dev)
     st = Engine._stream(dev)
     _lib.check(lib.afx_sample_keys(_ptr(weights), n, _ptr(u), int(seed), int(stream_id), _ptr(keys), st), "afx_sample_keys")

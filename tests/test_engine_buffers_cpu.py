@@ -1,6 +1,9 @@
-"""The host side of the analysis wrappers of nerf_for_angiography_amd/engine.py, without a device: the buffer vocabulary (_on_gpu, _buffer,
-_out, _scratch, _volume_side_ok) on CPU tensors, and one table over every public analysis wrapper that takes a tensor - called with CPU
-tensors of otherwise valid dtype and shape, each refuses with AfxError "... there is no CPU path" before anything else happens."""
+"""The host side of the wrappers of nerf_for_angiography_amd/engine.py, without a device: the buffer vocabulary (_on_gpu, _buffer, _out,
+_scratch, _volume_side_ok) on CPU tensors, and one table over every public wrapper that takes a tensor - the analysis wrappers and the
+training, grid, march and sampler wrappers (Engine's methods on the smallest model the library admits) - called with CPU tensors of
+otherwise valid dtype and shape, each refuses with AfxError "... there is no CPU path" before anything else happens."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -102,6 +105,95 @@ NO_CPU_PATH = {
 }
 
 
+# ---- the training, grid, march and sampler wrappers: 9 rays of 6 samples, 3 groups, a 5 x 3 x 7 grid (105 cells, 4 words), n_draw 4, 2 batches of 3 ----
+R, S, G, NF, RES, NC, BOX = 9, 6, 3, 2, (5, 3, 7), 105, [0.0, 0.0, 0.0, 5.0, 3.0, 7.0]
+F32, I32, I64, U8 = torch.float32, torch.int32, torch.int64, torch.uint8
+
+
+@functools.lru_cache(maxsize=None)
+def _model():
+    """The smallest model the library admits, with CPU stand-ins for its buffers."""
+    eng = e.Engine(64, 1)
+    return eng, torch.zeros(eng.param_count), torch.zeros(eng.param_count)
+
+
+def _prep(prec):
+    """CPU bytes of the size Engine.prepare allocates at `prec`."""
+    from nerf_for_angiography_amd import _lib
+    eng = _model()[0]
+    return torch.zeros(int(eng.lib.afx_query(eng.h, _lib.Q_PREPARED_BYTES, _lib.PREC[prec], 0, 0)), dtype=U8)
+
+
+def _t():
+    o, d = torch.zeros(R, 3), torch.ones(R, 3)
+    return dict(o=o, d=d, tgt=torch.zeros(R), pix=torch.zeros(R), pts=torch.zeros(R, 3), z=torch.linspace(0.1, 0.9, S), u=torch.rand(R, NF),
+                raw=torch.zeros(R, S), bits=torch.zeros(4, dtype=I32), occs=torch.zeros(NC), b8=torch.zeros(NC, dtype=U8),
+                acc=e.RenderSpec(R, S, origins=o, dirs=d, mode="acc", t_near=0.0, t_far=1.0),
+                dense=e.RenderSpec(R, S, origins=o, dirs=d, mode="dense", z=torch.linspace(0.1, 0.9, S)),
+                packed=e.PackedGroups(R, G, torch.zeros(R + 1, dtype=I64), torch.zeros(G, dtype=I32), torch.zeros(32 * G), torch.zeros(32 * G)),
+                march=dict(grid_bits=torch.zeros(4, dtype=I32), grid_aabb=BOX, grid_res=RES),
+                ri=torch.zeros(R * S, dtype=I32), n=torch.zeros(R * S), off=torch.arange(R + 1) * S, step=torch.zeros((), dtype=I64),
+                one=torch.zeros(1), one64=torch.zeros(1, dtype=I64), three64=torch.zeros(3, dtype=I64))
+
+
+T = _t()
+NO_CPU_PATH.update({
+    "Engine.prepare": lambda: _model()[0].prepare(_model()[1], None, "f32"),
+    "Engine.infer": lambda: _model()[0].infer(_prep("f32"), T["pts"], "f32"),
+    "Engine.encoding_grad": lambda: _model()[0].encoding_grad(_model()[1], torch.zeros(3)).__enter__(),
+    "Engine.mlp_backward": lambda: _model()[0].mlp_backward(_prep("f32"), T["pts"], T["tgt"], _model()[2], "f32"),
+    "Engine.mlp_backward_inputs": lambda: _model()[0].mlp_backward_inputs(_prep("f32"), T["pts"], T["tgt"], None, torch.zeros(R, 3), "f32"),
+    "Engine.render_forward": lambda: _model()[0].render_forward(_prep("f32"), T["acc"], "f32"),
+    "Engine.render_backward": lambda: _model()[0].render_backward(_prep("f32"), T["acc"], T["pix"], T["tgt"], _model()[2], "f32"),
+    "Engine.render_backward_inputs": lambda: _model()[0].render_backward_inputs(_prep("f32"), T["acc"], T["pix"], T["tgt"], None, torch.zeros(R, 3),
+                                                                               torch.zeros(R, 3), "f32"),
+    "Engine.train_step_mse": lambda: _model()[0].train_step_mse(_prep("f16s8"), T["acc"], T["tgt"], 1.0 / R, _model()[2], "f16s8"),
+    "Engine.hier_train_step_mse": lambda: _model()[0].hier_train_step_mse(_prep("f16s8"), T["dense"], NF, T["u"], T["tgt"], 1.0 / R, _model()[2], "f16s8"),
+    "Engine.train_step_packed_mse": lambda: _model()[0].train_step_packed_mse(_prep("f16s8"), T["o"], T["d"], T["packed"], T["tgt"], 1.0 / R, _model()[2],
+                                                                             "f16s8"),
+    "Engine.march_train_step_mse": lambda: _model()[0].march_train_step_mse(_prep("f16s8"), T["o"], T["d"], T["tgt"], 1.0 / R, _model()[2], "f16s8", BOX,
+                                                                           0.0, 9.0, 0.5, 1e-4, 1e-2, **T["march"]),
+    "Engine.march_train_step_mse_capturable": lambda: _model()[0].march_train_step_mse_capturable(
+        _prep("f16s8"), T["o"], T["d"], T["tgt"], 1.0 / R, _model()[2], "f16s8", BOX, 0.0, 9.0, 0.5, 1e-4, 1e-2, pixel=torch.zeros(R),
+        counts=torch.zeros(3, dtype=I64), skip=torch.zeros(1), **T["march"]),
+    "Engine.march_train_step_mse_single_eval": lambda: _model()[0].march_train_step_mse_single_eval(
+        _prep("f16s8"), T["o"], T["d"], T["tgt"], 1.0 / R, _model()[2], "f16s8", BOX, 0.0, 9.0, 0.5, 1e-4, 1e-2, **T["march"]),
+    "Engine.march_render": lambda: _model()[0].march_render(_prep("f16s8"), "f16s8", BOX, 0.0, 9.0, 0.5, 1e-4, 1e-2, origins=T["o"], dirs=T["d"],
+                                                           **T["march"]),
+    "pack_groups": lambda: e.pack_groups(T["off"], T["n"], T["n"]),
+    "composite_dense": lambda: e.composite_dense(T["raw"], T["d"], T["z"]),
+    "composite_dense_backward": lambda: e.composite_dense_backward(T["raw"], T["d"], T["z"], T["pix"], T["tgt"]),
+    "composite_packed": lambda: e.composite_packed(T["n"], T["ri"], T["n"], T["n"], R),
+    "composite_packed_backward": lambda: e.composite_packed_backward(T["n"], T["ri"], T["n"], T["n"], R, T["pix"], T["tgt"]),
+    "ray_entropy_packed": lambda: e.ray_entropy_packed(T["n"], T["ri"], T["pix"], R),
+    "ray_entropy_packed_backward": lambda: e.ray_entropy_packed_backward(T["n"], T["ri"], T["pix"], torch.ones(R, 2), T["tgt"], out=torch.zeros(R * S)),
+    "ray_entropy_dense": lambda: e.ray_entropy_dense(T["raw"], T["pix"]),
+    "ray_entropy_dense_backward": lambda: e.ray_entropy_dense_backward(T["raw"], T["pix"], torch.ones(R, 2), T["tgt"], out=torch.zeros(R, S)),
+    "project_volume": lambda: e.project_volume(I["vol"], (0, 0, 0), (1, 1, 1), 0.0, T["z"], origins=T["o"], dirs=T["d"]),
+    "fine_depths": lambda: e.fine_depths(T["z"], T["raw"], T["u"]),
+    "fine_depths_from_tau": lambda: e.fine_depths_from_tau(T["raw"], T["raw"], T["u"]),
+    "volume_grid": lambda: e.volume_grid(I["vol"], (0, 0, 0), (1, 1, 1), 0.0, -1.0, 1.0, 4),
+    "grid_points": lambda: e.grid_points(BOX, RES, torch.zeros(4, dtype=I32), 4, jitter=torch.zeros(4, 3)),
+    "grid_update": lambda: e.grid_update(BOX, RES, T["occs"], torch.zeros(4, dtype=I32), torch.zeros(4), 0.95, torch.zeros(NC)),
+    "grid_binarize": lambda: e.grid_binarize(BOX, RES, T["occs"], 1e-2, T["b8"], T["bits"], torch.zeros(256, dtype=torch.float64)),
+    "grid_pack": lambda: e.grid_pack(BOX, RES, T["b8"], T["bits"]),
+    "grid_select_cells": lambda: e.grid_select_cells(BOX, RES, T["bits"], 4, 1, T["step"], cells=torch.zeros(8, dtype=I32), count=T["one64"],
+                                                     workspace=torch.zeros(64, dtype=U8)),
+    "grid_refresh": lambda: e.grid_refresh(_model()[0], _prep("f16s8"), "f16s8", BOX, RES, T["occs"], T["b8"], T["bits"], 4, False, 1, T["step"], 1e-2, 0.95,
+                                           torch.zeros(64, dtype=U8)),
+    "march": lambda: e.march(T["o"], T["d"], BOX, 0.0, 9.0, 0.5, **T["march"]),
+    "march_visibility": lambda: e.march_visibility(T["n"], T["n"], T["n"], T["off"], 1e-4, 1e-2),
+    "topk_indices": lambda: e.topk_indices(T["n"], 3),
+    "RayBatchSampler": lambda: e.RayBatchSampler(T["o"], T["d"], T["pix"], torch.ones(R), 3),
+    "sample_batches_dev": lambda: e.sample_batches_dev(torch.ones(R), 1, T["step"], 2, 3, out_idx=torch.zeros(2, 3, dtype=I64),
+                                                       workspace=torch.zeros(64, dtype=U8)),
+    "gather_rays": lambda: e.gather_rays(T["o"], T["d"], T["pix"], torch.zeros(3, dtype=I64), torch.zeros(3, 3), torch.zeros(3, 3), torch.zeros(3)),
+    "train_round_advance": lambda: e.train_round_advance(T["one64"], torch.zeros(5), T["one"], T["one"], T["one"], T["three64"], torch.zeros(2),
+                                                         torch.zeros(2, 3, dtype=I64), torch.zeros(2), T["one"], T["one64"]),
+    "sample_rays": lambda: e.sample_rays(T["o"], T["d"], T["pix"], torch.ones(R), 3, u=torch.rand(R)),
+})
+
+
 @pytest.mark.parametrize("name", sorted(NO_CPU_PATH))
 def test_analysis_wrappers_have_no_cpu_path(name):
     with pytest.raises(AfxError, match="no CPU path"):
@@ -141,6 +233,27 @@ def test_buffer_accepts_the_right_tensor_and_names_every_violation():
     assert engine._buffer(good, "buf", torch.float32, SHAPE, CPU, "unit", exact_shape=True) is good
     with pytest.raises(ValueError, match="buf"):                                                          # another device
         engine._buffer(good, "buf", torch.float32, SHAPE, torch.device("meta"), "unit")
+
+
+def test_buffer_copy_makes_a_strided_input_contiguous_and_converts_nothing_else():
+    table = torch.arange(15, dtype=torch.float32).reshape(3, 5).t()                 # a column-major [5, 3] table
+    assert not table.is_contiguous()
+    with pytest.raises(ValueError, match="unit: rays must be a contiguous"):       # without the keyword a strided tensor is refused
+        engine._buffer(table, "rays", torch.float32, (5, 3), CPU, "unit")
+    got = engine._buffer(table, "rays", torch.float32, (5, 3), CPU, "unit", exact_shape=True, copy=True)
+    assert got.is_contiguous() and got.shape == table.shape and torch.equal(got, table) and got.data_ptr() != table.data_ptr()
+    view = torch.arange(4.0)[:, None].expand(4, 3)                                  # a broadcast view
+    assert torch.equal(engine._buffer(view, "rays", torch.float32, 12, CPU, "unit", copy=True), view.contiguous())
+    good = torch.zeros(5, 3)
+    assert engine._buffer(good, "rays", torch.float32, (5, 3), CPU, "unit", copy=True) is good      # a contiguous one is not copied
+    for what, bad in _violations((5, 3)).items():
+        if what != "transposed":
+            with pytest.raises(ValueError, match=r"^unit: rays must be a torch\.float32 tensor of 15 elements"):
+                engine._buffer(bad, "rays", torch.float32, (5, 3), CPU, "unit", copy=True)
+    with pytest.raises(ValueError, match="unit: rays"):                            # another device: refused, not moved
+        engine._buffer(good, "rays", torch.float32, (5, 3), torch.device("meta"), "unit", copy=True)
+    with pytest.raises(ValueError, match=r"rays .*shape \(5, 3\)"):                # the count but not the shape
+        engine._buffer(table.t(), "rays", torch.float32, (5, 3), CPU, "unit", exact_shape=True, copy=True)
 
 
 def test_buffer_at_least_admits_a_longer_buffer_only():

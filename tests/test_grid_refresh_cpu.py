@@ -191,8 +191,9 @@ def test_refusals():
     host_grid = OccupancyGrid(roi_aabb=[-1.0, -1, -1, 1, 1, 1], resolution=16)
     with pytest.raises(AfxError):
         host_grid.refresh(None, 300)
-    with pytest.raises(AfxError):
-        engine.grid_refresh(eng, torch.zeros(8, dtype=torch.uint8), "f16s8", [-1.0, -1, -1, 1, 1, 1], (16, 16, 16), host_grid.occs,
+    prepared = torch.zeros(int(lib.afx_query(eng.h, _lib.Q_PREPARED_BYTES, p, 0, 0)), dtype=torch.uint8)      # (well-formed but for the device)
+    with pytest.raises(AfxError, match="no CPU path"):
+        engine.grid_refresh(eng, prepared, "f16s8", [-1.0, -1, -1, 1, 1, 1], (16, 16, 16), host_grid.occs,
                             host_grid._binary_u8, host_grid._bits, nc // 4, False, 0, 300, 0.01, 0.95, torch.zeros(need, dtype=torch.uint8))
 
 

@@ -201,6 +201,7 @@ def test_wrappers_refuse_by_type_and_size_before_the_device():
     """The checks that need no GPU: a wrong dtype, size or layout is a ValueError naming the argument, raised before the device is looked at
     and before the library is called (host tensors of the right type and size are refused for living on the host)."""
     from nerf_for_angiography_amd import engine
+    from nerf_for_angiography_amd._lib import AfxError
     box, res, n = gr.BOXES[0], (5, 3, 7), 105
     occs, scratch, b8 = torch.zeros(n), torch.zeros(n), torch.zeros(n, dtype=torch.uint8)
     bits, part = torch.zeros(4, dtype=torch.int32), torch.zeros(256, dtype=torch.float64)
@@ -239,9 +240,9 @@ def test_wrappers_refuse_by_type_and_size_before_the_device():
         engine.grid_points(box, res, cells.long(), 9)
     with pytest.raises(ValueError, match="cell_idx"):
         engine.grid_points(box, res, cells, 10)
-    with pytest.raises(ValueError, match="GPU"):
+    with pytest.raises(AfxError, match="occs must be a tensor on a GPU; there is no CPU path"):
         engine.grid_update(box, res, occs, cells, new, 0.95, scratch)
-    with pytest.raises(ValueError, match="GPU"):
+    with pytest.raises(AfxError, match="occs must be a tensor on a GPU; there is no CPU path"):
         engine.grid_binarize(box, res, occs, 1e-2, b8, bits, part)
-    with pytest.raises(ValueError, match="GPU"):
+    with pytest.raises(AfxError, match="cell_idx must be a tensor on a GPU; there is no CPU path"):
         engine.grid_points(box, res, cells, 9, jitter=torch.zeros(9, 3))

@@ -58,13 +58,13 @@ def test_wrappers_refuse_host_tensors():
     from nerf_for_angiography_amd.nerf.nerf_helpers_acc import acc_ray_entropy
     pred, ri, rgb = torch.zeros(6), torch.tensor([0, 0, 1, 1, 1, 2], dtype=torch.int32), torch.full((3,), 0.2)
     sums, d_ent = torch.ones(3, 2), torch.ones(3)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.ray_entropy_packed(pred, ri, rgb, 3)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.ray_entropy_packed_backward(pred, ri, rgb, sums, d_ent)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.ray_entropy_dense(pred.reshape(3, 2), rgb)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.ray_entropy_dense_backward(pred.reshape(3, 2), rgb, sums, d_ent)
     with pytest.raises(AfxError, match="no CPU fallback"):
         acc_ray_entropy(pred, ri, rgb, 3)

@@ -88,11 +88,11 @@ def test_refusals_before_any_launch():
     assert lib.afx_topk_indices(FAKE, n, -1, FAKE, FAKE, 1 << 20, None) == -1
     assert lib.afx_topk_indices(FAKE, n, 5, FAKE, FAKE, int(lib.afx_topk_workspace_bytes(n)) - 1, None) == -2
     o, d, p, w = torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n), torch.ones(n)                     # host tensors
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.sample_rays(o, d, p, w, 10, seed=1, stream_id=2)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.topk_indices(w, 10)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.RayBatchSampler(o, d, p, w, 10)
-    with pytest.raises(AfxError, match="no CPU fallback"):
+    with pytest.raises(AfxError, match="no CPU path"):
         engine.sample_batches_dev(w, 0, torch.zeros((), dtype=torch.int64), 4, 10)
